@@ -15,17 +15,27 @@ timed region), the clock and the JSON line. value = world_size * rays_per_batch 
 definition (engine/trainer.py:276-284) with a device sync around the timed region.
 
 The timed region — K steps after W warm-up steps, barrier + device sync on both sides, max over ranks — is run `--windows`
-times (default 7) ON THE SAME K ITERATIONS: the training state at the start of the window (parameters, Adam moments, step
-counters, sampler state) is restored before every repeat, so every repeat measures the same work in the same phase of the
-proposal-update schedule; `ms_per_step` is the MEDIAN repeat, config.window_ms holds min / max / n. A single 15 ms window
-moved by +-5 % from run to run. `long_run` continues from there for `--long-steps` iterations (default 300).
+times ON THE SAME K ITERATIONS: the training state at the start of the window (parameters, Adam moments, step counters,
+sampler state) is restored before every repeat, so every repeat measures the same work in the same phase of the
+proposal-update schedule; `ms_per_step` is the MEDIAN repeat, config.window_ms holds min / max / n. A plain run times one
+window (exactly K steps); `--full` repeats it 7 times (a single 15 ms window moved by +-5 % from run to run).
 
-Extra objects on the JSON line:
+A plain run sets up, warms up, times the K steps, writes `--dump-outputs` if asked and prints the JSON line. `--full` adds
+what takes runs of its own (each also available through its own option):
+  long_run      — `--long-steps` further iterations after the window (default 300 with --full, 0 otherwise).
   roofline      — the kernel with the largest share of the step (runner-up riding along), timed live with HIP events on the
-                  launch stream (separate, untimed profiling steps after the timed region), against its algorithmic work.
-  roofline_step — SURVEY.md §8(d) whole-step algorithmic HBM bytes / ms_per_step against the 8 TB/s peak.
+                  launch stream (separate, untimed profiling steps after the timed region), against its algorithmic work
+                  (also with --kernel-table).
   cpu_baseline  — the CPU oracle (oracle/nerfacto_oracle.py, kind "port") running the same training step on one full
                   batch on this box's host cores (rank 0, N = 1 only).
+  secondary     — the other workloads' windows, each in a process of its own (see secondary_lines).
+Always on the line: roofline_step — SURVEY.md §8(d) whole-step algorithmic HBM bytes / ms_per_step against the 8 TB/s peak
+(arithmetic on the measured window, no run of its own).
+
+--dump-outputs DIR writes, after the timed steps, what the last timed step handed its caller as float32 .npy files: the
+model outputs (rgb, accumulation, depths, weights of every sampler level) and the loss values of the explicit schedule, and a
+fixed seeded sample of the updated parameters (see dump_outputs). Inputs are seeded, so two builds can be compared file by
+file.
 """
 import argparse
 import json
@@ -44,6 +54,7 @@ if ROOT not in sys.path:
 RAYS_PER_GPU = 4096
 BATCH_SLOTS = 8  # pre-generated ray batches resident in HBM; the timed loop takes a different one every step
 NGP_DENSITY = 60.0  # --workload ngp (scripts/bench_ngp.py): the synthetic field's density
+DUMP_PARAM_SAMPLE = 1 << 20  # --dump-outputs: parameters written (seeded sample of the 19.4 M, 4 MB)
 
 
 def build_model(device, seed, camera_optimizer="off"):
@@ -121,6 +132,31 @@ class TrainingState:
         t._true_steps = dict(self.counts)
         ps = m.proposal_sampler
         t.step, t.opt_step, ps._step, ps._steps_since_update, ps._anneal, m.step = self.scalars
+
+
+def dump_outputs(directory, trainer, arena):
+    """--dump-outputs: what the last timed step handed its caller, one float32 .npy file per array in `directory` (~19 MB):
+    the explicit schedule's model outputs (train_step.NerfactoTrainStep.outputs: rgb, accumulation, expected / median depths,
+    weights_<level> of every sampler level) and loss_<name> values — through the autograd modules only the summed `loss` —
+    and `params_sample`: the parameters after the step's update at DUMP_PARAM_SAMPLE sorted indices drawn with a fixed seed
+    (`params_sample_index`, float64). Called after a timed window, whose `finish()` has applied the last step's update."""
+    arrays = {}
+    if trainer.runner is not None:
+        for name, t in trainer.runner.outputs().items():
+            if name == "weights_list":
+                arrays.update((f"weights_{i}", w) for i, w in enumerate(t))
+            else:
+                arrays[name] = t
+        arrays.update((f"loss_{name}", t) for name, t in trainer.loss_dict().items())
+    else:
+        arrays["loss"] = trainer.loss_buf
+    flat = arena.flat.detach()
+    idx = np.sort(np.random.RandomState(0).randint(0, flat.numel(), size=min(DUMP_PARAM_SAMPLE, flat.numel())))
+    arrays["params_sample"] = flat.reshape(-1)[torch.from_numpy(idx).to(flat.device)]
+    os.makedirs(directory, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), t.detach().float().cpu().numpy())
+    np.save(os.path.join(directory, "params_sample_index.npy"), idx.astype(np.float64))
 
 
 def cpu_baseline(n_rays=RAYS_PER_GPU, steps=3, threads=None, workload="bounded"):
@@ -208,7 +244,7 @@ def cpu_baseline_ngp(o, d, cam, tgt, binaries, cfg, n_rays=256, steps=2):
 
 
 def secondary_lines(steps, warmup, headline_ms):
-    """The lines of the other workloads this repository covers, timed in the DEFAULT run so that the driver's one JSON line
+    """The lines of the other workloads this repository covers, timed in the --full run so that its one JSON line
     carries them: one window of `steps` iterations each, measured by this same script (or scripts/bench_seam.py)
     in a process of its own on the same GPU right after the headline — the reference's nerfacto default with the camera
     optimiser on (models/nerfacto.py:131 SO3xR3), BASELINE configs[4] (unbounded / contraction), configs[3] (instant-ngp incl.
@@ -254,8 +290,14 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--windows", type=int, default=7, help="repeats of the timed K-step window on the same iterations (median)")
-    ap.add_argument("--long-steps", type=int, default=300, help="secondary figure: this many further iterations (0: skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: 7 windows, long run, roofline, CPU baseline, secondary workloads")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32; see dump_outputs)")
+    ap.add_argument("--windows", type=int, default=None,
+                    help="repeats of the timed K-step window on the same iterations (median; default 1, 7 with --full)")
+    ap.add_argument("--long-steps", type=int, default=None,
+                    help="secondary figure: this many further iterations (default 0 = skip, 300 with --full)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-graph", action="store_true", help="launch every kernel eagerly instead of replaying hipGraphs")
     ap.add_argument("--autograd", action="store_true",
@@ -283,8 +325,15 @@ def main():
     ap.add_argument("--param-checksum", action="store_true", help="add sha256 digests of the arenas after the FIRST window to config")
     ap.add_argument("--dry-run", action="store_true", help="no GPU: rehearse the multi-GPU launch plumbing over gloo")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the `secondary` object of the default N = 1 run (the other workloads' 20-step windows, see secondary_lines)")
+                    help="skip the `secondary` object of the --full N = 1 run (the other workloads' 20-step windows, see secondary_lines)")
     args = ap.parse_args()
+    if args.windows is None:
+        args.windows = 7 if args.full else 1
+    if args.long_steps is None:
+        args.long_steps = 300 if args.full else 0
+    profile = args.full or args.kernel_table  # the per-kernel table / roofline: untimed profiling steps of their own
+    if args.dump_outputs and args.workload == "ngp":
+        ap.error("--dump-outputs covers the nerfacto workloads (bounded, unbounded)")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -370,7 +419,7 @@ def main():
             sec = float(t.item())
         return sec, updates
 
-    state = TrainingState(trainer, arena, model) if args.windows > 1 else None
+    state = TrainingState(trainer, arena, model) if (args.windows > 1 or profile) else None
     windows, checksum, updates = [], None, 0
     for w in range(max(1, args.windows)):
         if w > 0:
@@ -386,6 +435,8 @@ def main():
                 checksum = {name: hashlib.sha256(t.detach().cpu().numpy().tobytes()).hexdigest()[:32]
                             for name, t in (("params", arena.flat), ("exp_avg", arena.exp_avg), ("exp_avg_sq", arena.exp_avg_sq))}
     elapsed = float(np.median(windows))
+    if args.dump_outputs and rank == 0:  # before anything else moves the state: the last window's last step
+        dump_outputs(args.dump_outputs, trainer, arena)
     long_run = None
     if args.long_steps > 0:
         sec, upd = timed_window(args.long_steps)
@@ -398,11 +449,11 @@ def main():
 
     main_points = RAYS_PER_GPU * model.config.num_nerf_samples_per_ray
     roof, table = (None, [])
-    if rank == 0:
+    if profile and rank == 0:
         if state is not None:
             state.restore()  # the per-kernel table is taken on the window's own iterations
         roof, table = RL.measure_roofline(trainer, arena, max(1, args.profile_steps), main_points)
-    elif world > 1:  # keep the collective pattern identical on every rank during the profiling steps
+    elif profile and world > 1:  # keep the collective pattern identical on every rank during the profiling steps
         if state is not None:
             state.restore()
         for _ in range(max(1, args.profile_steps) + RL.ROOFLINE_WARMUP_ITERS):  # (+ measure_roofline's untimed warm-up on rank 0)
@@ -442,13 +493,14 @@ def main():
                        "driver": ("Model API over the explicit kernel schedule (fused_step.py)" if args.fused_model_api else
                                   "autograd modules") if args.autograd else
                                  "nerfstudio_amd.trainer.HipTrainer over the explicit kernel schedule (train_step.py)"},
-            "roofline": roof,
             "roofline_step": {"bound": "hbm", "achieved": round(step_bytes / (ms * 1e-3) / 1e9, 1), "peak": RL.HBM_PEAK_GBS,
                               "unit": "GB/s", "frac": round(step_bytes / (ms * 1e-3) / 1e9 / RL.HBM_PEAK_GBS, 4),
                               "algorithmic_bytes_per_step": int(step_bytes),
                               "note": "SURVEY.md 8(d): hash gathers of all levels + main-table scatter + Adam (28 B/param) + the "
                                       "proposal tables' scatter on the window's update steps"},
         }
+        if profile:
+            out["roofline"] = roof
         if long_run is not None:
             out["long_run"] = long_run
         if args.start_step:
@@ -459,9 +511,9 @@ def main():
             out["config"].update(dp_mode=args.dp_mode, rccl_ranks=dist.get_world_size(), dist_backend=dist.get_backend())
         if args.force_dp:
             out["config"]["force_dp"] = "data-parallel schedule over a one-rank RCCL communicator (rehearsal of the N > 1 path)"
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(workload=args.workload)
-        if (world == 1 and not args.no_secondary and not args.force_dp and args.workload == "bounded" and args.camera_optimizer == "off"
+        if (args.full and world == 1 and not args.no_secondary and not args.force_dp and args.workload == "bounded" and args.camera_optimizer == "off"
                 and not (args.autograd or args.no_graph or args.start_step or args.kernel_table or args.param_checksum)):
             out["secondary"] = secondary_lines(args.steps, args.warmup, float(out["ms_per_step"]))
         if args.kernel_table:

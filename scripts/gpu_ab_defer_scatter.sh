@@ -7,22 +7,22 @@ mkdir -p $out
 {
 for arm in 1 0 1 0; do
   echo "== NSAMD_DEFER_SCATTER=$arm  --steps 20 --warmup 5"
-  NSAMD_DEFER_SCATTER=$arm timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --param-checksum 2>/dev/null | grep '^{' | python -c "
+  NSAMD_DEFER_SCATTER=$arm timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --param-checksum 2>/dev/null | grep '^{' | python -c "
 import json,sys
 j=json.loads(sys.stdin.read()); print(j['ms_per_step'], j['value'], j['config'].get('param_checksum',{}).get('params'), j['config']['launch'][:70])"
 done
 for arm in 1 0; do
   echo "== NSAMD_DEFER_SCATTER=$arm  --steps 300"
-  NSAMD_DEFER_SCATTER=$arm timeout 300 python bench.py --steps 300 --warmup 5 --no-cpu-baseline --param-checksum 2>/dev/null | grep '^{' | python -c "
+  NSAMD_DEFER_SCATTER=$arm timeout 300 python bench.py --full --steps 300 --warmup 5 --no-cpu-baseline --param-checksum 2>/dev/null | grep '^{' | python -c "
 import json,sys
 j=json.loads(sys.stdin.read()); print(j['ms_per_step'], j['value'], j['config'].get('param_checksum',{}).get('params'))"
   echo "== NSAMD_DEFER_SCATTER=$arm  --start-step 5000 --steps 120"
-  NSAMD_DEFER_SCATTER=$arm timeout 300 python bench.py --start-step 5000 --steps 120 --warmup 6 --no-cpu-baseline --param-checksum 2>/dev/null | grep '^{' | python -c "
+  NSAMD_DEFER_SCATTER=$arm timeout 300 python bench.py --full --start-step 5000 --steps 120 --warmup 6 --no-cpu-baseline --param-checksum 2>/dev/null | grep '^{' | python -c "
 import json,sys
 j=json.loads(sys.stdin.read()); print(j['ms_per_step'], j['value'], j['config'].get('param_checksum',{}).get('params'))"
 done
 echo "== eager N=1 (no graph) checksum, 20 steps"
-timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --param-checksum --no-graph 2>/dev/null | grep '^{' | python -c "
+timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --param-checksum --no-graph 2>/dev/null | grep '^{' | python -c "
 import json,sys
 j=json.loads(sys.stdin.read()); print(j['ms_per_step'], j['value'], j['config'].get('param_checksum',{}).get('params'))"
 echo "== graph-vs-eager bit tests"

@@ -14,7 +14,7 @@ for i in 1 2; do
   for arm in prev new; do
     if [ $arm = prev ]; then export NSAMD_LIB=$P; else unset NSAMD_LIB; fi
     echo "== driver window, $arm"
-    timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --param-checksum 2>/dev/null | grep '^{' | python -c "
+    timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --param-checksum 2>/dev/null | grep '^{' | python -c "
 import json,sys
 j=json.loads(sys.stdin.read()); print(j['ms_per_step'], j['value'], j['config'].get('param_checksum',{}).get('params'))"
   done

@@ -5,7 +5,7 @@ cd ${GRAFT_REPO_ROOT:-/root/repo}
 O=gpurun_out/${1:-ab_schedule}; mkdir -p $O
 run() {  # label, env...
   echo "== $*" | tee -a $O/ab.log
-  env "${@:2}" timeout 300 python bench.py --steps 100 --warmup 10 --no-cpu-baseline $FLAGS 2>>$O/ab.err | \
+  env "${@:2}" timeout 300 python bench.py --full --steps 100 --warmup 10 --no-cpu-baseline $FLAGS 2>>$O/ab.err | \
     python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['ms_per_step'], d['value'], d['config']['final_loss'], d['config']['launch'][:60])" | tee -a $O/ab.log
 }
 for FLAGS in "" "--no-graph"; do for d in 1 0; do for s in 0 1; do

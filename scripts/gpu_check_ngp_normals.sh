@@ -9,10 +9,10 @@ export HSA_ENABLE_IPC_MODE_LEGACY=0
 echo "== pytest (normals, packed)"
 timeout 900 python -m pytest tests/test_normals.py tests/test_gpu_packed.py -m gpu -q 2>&1 | tail -25
 echo "== bench --workload ngp (explicit schedule)"
-timeout 600 python bench.py --workload ngp --steps 30 --warmup 10 --kernel-table 2> $out/bench_ngp_kernel_table.log | grep '^{' | tee $out/bench_ngp.json | cut -c1-1500
+timeout 600 python bench.py --full --workload ngp --steps 30 --warmup 10 --kernel-table 2> $out/bench_ngp_kernel_table.log | grep '^{' | tee $out/bench_ngp.json | cut -c1-1500
 head -45 $out/bench_ngp_kernel_table.log | cut -c1-140
 echo "== bench --workload ngp --ngp-module-path"
-timeout 600 python bench.py --workload ngp --steps 30 --warmup 10 --no-cpu-baseline --ngp-module-path 2> $out/bench_ngp_module.err | grep '^{' | tee $out/bench_ngp_module.json | cut -c1-400
+timeout 600 python bench.py --full --workload ngp --steps 30 --warmup 10 --no-cpu-baseline --ngp-module-path 2> $out/bench_ngp_module.err | grep '^{' | tee $out/bench_ngp_module.json | cut -c1-400
 tail -3 $out/bench_ngp_module.err
 } > $out/summary.txt 2>&1
 tail -60 $out/summary.txt

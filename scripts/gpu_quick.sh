@@ -11,7 +11,7 @@ echo "== gated chains alone (sparse phase)"
 (timeout 200 python scripts/probe_gated_scatter_clocks.py 0; timeout 200 python scripts/probe_gated_scatter_clocks.py 1) 2>&1 | grep -v amdgpu.ids | grep "marked\|chain of\|lifetime\|->"
 for i in 1 2; do
 echo "== driver window"
-timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --param-checksum --kernel-table 2> $out/table.log | grep '^{' | python -c "
+timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --param-checksum --kernel-table 2> $out/table.log | grep '^{' | python -c "
 import json,sys
 j=json.loads(sys.stdin.read()); print(j['ms_per_step'], j['value'], j['config'].get('param_checksum',{}).get('params'))"
 done

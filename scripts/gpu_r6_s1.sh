@@ -17,7 +17,7 @@ for i in 1 2; do
   for arm in dw0 new dw2; do
     if [ $arm = new ]; then unset NSAMD_LIB; else export NSAMD_LIB=$R/nerfstudio_amd/libnsamd_$arm.so; fi
     echo "== $arm"
-    timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --long-steps 0 --param-checksum --kernel-table --profile-steps 10 2> $out/table_${arm}_$i.log | grep '^{' | python -c "
+    timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --long-steps 0 --param-checksum --kernel-table --profile-steps 10 2> $out/table_${arm}_$i.log | grep '^{' | python -c "
 import json,sys
 j=json.loads(sys.stdin.read()); print(j['ms_per_step'], j['value'], j['roofline'], j['config'].get('param_checksum',{}).get('params'))"
     grep "field_mlp_bwd\|field_mlp_fwd\|scatter_apply" $out/table_${arm}_$i.log | cut -c1-150

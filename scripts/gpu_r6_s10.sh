@@ -8,7 +8,7 @@ mkdir -p $out
 export TMPDIR=/tmp
 cd $R
 echo "== default bench" > $out/summary.txt
-( time timeout 600 python bench.py ) > $out/bench_default.json 2> $out/bench_default.err
+( time timeout 600 python bench.py --full ) > $out/bench_default.json 2> $out/bench_default.err
 tail -3 $out/bench_default.err >> $out/summary.txt
 python - >> $out/summary.txt <<'PY'
 import json

@@ -20,7 +20,7 @@ for i in 1 2; do
   for res in 0 300; do
     export NSAMD_SCATTER_COMBINE_RES=$res
     echo "-- NSAMD_SCATTER_COMBINE_RES=$res"
-    timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --long-steps 300 --start-step 40 2>/dev/null | grep '^{' | python -c "
+    timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --long-steps 300 --start-step 40 2>/dev/null | grep '^{' | python -c "
 import json,sys
 j=json.loads(sys.stdin.read()); print(j['ms_per_step'], j['value'], j.get('long_run'), j['config']['final_loss'])"
   done

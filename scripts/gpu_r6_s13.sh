@@ -13,7 +13,7 @@ for i in 1 2 3; do
     if [ $arm = prev ]; then export NSAMD_LIB=$R/nerfstudio_amd/libnsamd_prev.so NSAMD_LIB_OLDER_ABI=1 NSAMD_DENSITY_REDUCE_RIDER=0; else unset NSAMD_LIB NSAMD_LIB_OLDER_ABI NSAMD_DENSITY_REDUCE_RIDER; fi
     echo "== $arm"
     PROBE_STEPS=200 timeout 200 python scripts/probe_iteration_times.py 2>/dev/null | tail -1
-    timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --long-steps 300 2>/dev/null | grep '^{' | python -c "
+    timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --long-steps 300 2>/dev/null | grep '^{' | python -c "
 import json,sys
 j=json.loads(sys.stdin.read()); print('window', j['ms_per_step'], j['value'], 'long', j['long_run']['ms_per_step'], j['config']['final_loss'])"
   done

@@ -18,7 +18,7 @@ done
 unset NSAMD_LIB
 for arm in prev new; do
   if [ $arm = prev ]; then export NSAMD_LIB=$R/nerfstudio_amd/libnsamd_prev.so; else unset NSAMD_LIB; fi
-  timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --long-steps 0 --param-checksum 2>/dev/null | grep '^{' | python -c "
+  timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --long-steps 0 --param-checksum 2>/dev/null | grep '^{' | python -c "
 import json,sys
 j=json.loads(sys.stdin.read()); print('$arm window', j['ms_per_step'], j['value'], j['config']['param_checksum']['params'])"
 done

@@ -10,7 +10,7 @@ cd $R
 for i in 1 2 3; do
   for n in 4 3 2 1; do
     echo "== NSAMD_ADAM_BLOCKS_PER_CU=$n"
-    NSAMD_ADAM_BLOCKS_PER_CU=$n timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --long-steps 300 2>/dev/null | grep '^{' | python -c "
+    NSAMD_ADAM_BLOCKS_PER_CU=$n timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --long-steps 300 2>/dev/null | grep '^{' | python -c "
 import json,sys
 j=json.loads(sys.stdin.read()); print('window', j['ms_per_step'], j['value'], 'long', j['long_run']['ms_per_step'])"
   done

@@ -12,7 +12,7 @@ for i in 1 2 3; do
   for arm in "default:" "reserve36:NSAMD_BWD_RESERVE_CUS=36" "reserve64:NSAMD_BWD_RESERVE_CUS=64" "reserve16:NSAMD_BWD_RESERVE_CUS=16"; do
     name=${arm%%:*}; envs=${arm#*:}
     echo "== $name"
-    env $envs timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --long-steps 300 --param-checksum 2>/dev/null | grep '^{' | python -c "
+    env $envs timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --long-steps 300 --param-checksum 2>/dev/null | grep '^{' | python -c "
 import json,sys
 j=json.loads(sys.stdin.read()); print('window', j['ms_per_step'], j['value'], 'long', j['long_run']['ms_per_step'], 'loss', j['config']['final_loss'], j['config']['param_checksum']['params'][:12])"
   done
@@ -20,7 +20,7 @@ done
 for arm in "default:" "reserve36:NSAMD_BWD_RESERVE_CUS=36"; do
   name=${arm%%:*}; envs=${arm#*:}
   echo "== $name: --start-step 5000"
-  env $envs timeout 300 python bench.py --steps 120 --warmup 12 --start-step 5000 --no-cpu-baseline --no-secondary --long-steps 0 2>/dev/null | grep '^{' | python -c "
+  env $envs timeout 300 python bench.py --full --steps 120 --warmup 12 --start-step 5000 --no-cpu-baseline --no-secondary --long-steps 0 2>/dev/null | grep '^{' | python -c "
 import json,sys
 j=json.loads(sys.stdin.read()); print('late', j['ms_per_step'], j['value'])"
   echo "== $name: per-kind iteration times"

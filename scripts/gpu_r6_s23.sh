@@ -11,7 +11,7 @@ for i in 1 2 3; do
   for arm in "default:" "no_reduce:NSAMD_DIAG_SKIP_DW_REDUCE=1" "own_launch:NSAMD_REDUCE_RIDER=0"; do
     name=${arm%%:*}; envs=${arm#*:}
     echo "== $name"
-    env $envs timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --long-steps 100 --start-step 5000 2>/dev/null | grep '^{' | python -c "
+    env $envs timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --long-steps 100 --start-step 5000 2>/dev/null | grep '^{' | python -c "
 import json,sys
 j=json.loads(sys.stdin.read()); print('window', j['ms_per_step'], j['value'], 'long', j['long_run']['ms_per_step'], 'loss', j['config']['final_loss'])"
   done

@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 for arm in "in_line:NSAMD_SIDE_STREAM=0" "default:"; do
   name=${arm%%:*}; envs=${arm#*:}
   cd /tmp; rm -rf /tmp/ktl
-  env $envs timeout 600 rocprofv3 --kernel-trace -d /tmp/ktl -o k -- python $R/bench.py --steps 12 --warmup 150 --windows 1 --long-steps 0 --no-cpu-baseline --no-secondary > $out/rocprof_$name.log 2>&1
+  env $envs timeout 600 rocprofv3 --kernel-trace -d /tmp/ktl -o k -- python $R/bench.py --full --steps 12 --warmup 150 --windows 1 --long-steps 0 --no-cpu-baseline --no-secondary > $out/rocprof_$name.log 2>&1
   cd $R
   NAME=$name OUT=$out python - <<'PY'
 import glob, os, sqlite3

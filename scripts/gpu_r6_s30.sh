@@ -12,7 +12,7 @@ for arm in "eager:--no-graph" "force_dp:--force-dp"; do
   echo "== $name"
   timeout 600 python -c "
 import cProfile, pstats, sys, io
-sys.argv = ['bench.py', '--steps', '200', '--warmup', '20', '--windows', '1', '--long-steps', '0', '--no-cpu-baseline', '--no-secondary'] + '$flags'.split()
+sys.argv = ['bench.py', '--full', '--steps', '200', '--warmup', '20', '--windows', '1', '--long-steps', '0', '--no-cpu-baseline', '--no-secondary'] + '$flags'.split()
 import bench
 pr = cProfile.Profile()
 pr.enable()

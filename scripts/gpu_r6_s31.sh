@@ -5,7 +5,7 @@ out=$R/gpurun_out/r6_s31
 mkdir -p $out
 export TMPDIR=/tmp
 cd /tmp; rm -rf /tmp/ktl
-timeout 600 rocprofv3 --kernel-trace -d /tmp/ktl -o k -- python $R/bench.py --steps 12 --warmup 150 --windows 1 --long-steps 0 --no-cpu-baseline --no-secondary --camera-optimizer SO3xR3 > $out/rocprof.log 2>&1
+timeout 600 rocprofv3 --kernel-trace -d /tmp/ktl -o k -- python $R/bench.py --full --steps 12 --warmup 150 --windows 1 --long-steps 0 --no-cpu-baseline --no-secondary --camera-optimizer SO3xR3 > $out/rocprof.log 2>&1
 cd $R
 OUT=$out python - <<'PY'
 import glob, os, sqlite3

@@ -7,7 +7,7 @@ export TMPDIR=/tmp
 for arm in "ray_terms:NSAMD_RAY_TERMS=1" "plain:NSAMD_RAY_TERMS=0"; do
   name=${arm%%:*}; envs=${arm#*:}
   cd /tmp; rm -rf /tmp/ktl
-  env $envs timeout 600 rocprofv3 --kernel-trace -d /tmp/ktl -o k -- python $R/bench.py --steps 8 --warmup 40 --windows 1 --long-steps 0 --no-cpu-baseline --no-secondary > $out/rocprof_$name.log 2>&1
+  env $envs timeout 600 rocprofv3 --kernel-trace -d /tmp/ktl -o k -- python $R/bench.py --full --steps 8 --warmup 40 --windows 1 --long-steps 0 --no-cpu-baseline --no-secondary > $out/rocprof_$name.log 2>&1
   cd $R
   OUT=$out NAME=$name python - <<'PY'
 import glob, os, sqlite3

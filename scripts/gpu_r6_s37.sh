@@ -10,7 +10,7 @@ cd $R
 for arm in "default:" "long0:--long-steps 0"; do
   name=${arm%%:*}; flags=${arm#*:}
   echo "== $name"
-  NSAMD_ROOFLINE_SAMPLES=1 timeout 300 python bench.py --no-cpu-baseline --no-secondary $flags 2>&1 | grep "samples\|^{" | cut -c1-600
+  NSAMD_ROOFLINE_SAMPLES=1 timeout 300 python bench.py --full --no-cpu-baseline --no-secondary $flags 2>&1 | grep "samples\|^{" | cut -c1-600
 done
 } > $out/summary.txt 2>&1
 cat $out/summary.txt

@@ -11,7 +11,7 @@ for i in 1 2 3; do
   for arm in "default:" "defer_apply:NSAMD_DEFER_APPLY=1"; do
     name=${arm%%:*}; envs=${arm#*:}
     echo "== $name"
-    env $envs timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --long-steps 300 --param-checksum 2>&1 | grep '^{\|Error\|error' | python -c "
+    env $envs timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --long-steps 300 --param-checksum 2>&1 | grep '^{\|Error\|error' | python -c "
 import json,sys
 t=sys.stdin.read()
 try:

@@ -12,7 +12,7 @@ for i in 1 2 3; do
   for arm in "fused:" "two_launches:NSAMD_NGP_FUSE_ROUTE=0"; do
     name=${arm%%:*}; envs=${arm#*:}
     echo "== $name"
-    env $envs timeout 300 python bench.py --workload ngp --steps 32 --warmup 10 --no-cpu-baseline 2>/dev/null | grep '^{' | python -c "
+    env $envs timeout 300 python bench.py --full --workload ngp --steps 32 --warmup 10 --no-cpu-baseline 2>/dev/null | grep '^{' | python -c "
 import json,sys
 j=json.loads(sys.stdin.read()); print('ms', j['ms_per_step'], j['value'], 'loss', j['config'].get('final_loss'))"
   done

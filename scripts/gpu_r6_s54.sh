@@ -11,7 +11,7 @@ for i in 1 2 3; do
   for arm in "default:" "select_root:NSAMD_SELECT_ROOT=1"; do
     name=${arm%%:*}; envs=${arm#*:}
     echo "== $name"
-    env $envs timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --long-steps 300 --param-checksum 2>&1 | grep '^{\|Error' | python -c "
+    env $envs timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --long-steps 300 --param-checksum 2>&1 | grep '^{\|Error' | python -c "
 import json,sys
 t=sys.stdin.read()
 try:
@@ -22,7 +22,7 @@ done
 echo "== eager arms (bits)"
 for arm in "default:" "select_root:NSAMD_SELECT_ROOT=1"; do
   name=${arm%%:*}; envs=${arm#*:}
-  env $envs timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --long-steps 0 --param-checksum --no-graph 2>/dev/null | grep '^{' | python -c "
+  env $envs timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --long-steps 0 --param-checksum --no-graph 2>/dev/null | grep '^{' | python -c "
 import json,sys
 j=json.loads(sys.stdin.read()); print('$name eager window', j['ms_per_step'], 'loss', j['config']['final_loss'], j['config']['param_checksum']['params'][:12])"
 done

@@ -6,7 +6,7 @@ OUT=$R/gpurun_out/r6_s7
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/ktl
-timeout 600 rocprofv3 --kernel-trace -d /tmp/ktl -o k -- python $R/bench.py --steps 12 --warmup 10 --start-step 40 --long-steps 0 --windows 1 --no-cpu-baseline > $OUT/rocprof.log 2>&1
+timeout 600 rocprofv3 --kernel-trace -d /tmp/ktl -o k -- python $R/bench.py --full --steps 12 --warmup 10 --start-step 40 --long-steps 0 --windows 1 --no-cpu-baseline > $OUT/rocprof.log 2>&1
 cd $R
 TAG=r6_s7 python - <<'PY'
 import glob, os, sqlite3

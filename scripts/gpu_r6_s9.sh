@@ -12,7 +12,7 @@ for i in 1 2 3; do
     export NSAMD_FUSE_TABLE_ADAM=$arm
     echo "== NSAMD_FUSE_TABLE_ADAM=$arm"
     PROBE_STEPS=200 timeout 200 python scripts/probe_iteration_times.py 2>/dev/null | tail -1
-    timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --long-steps 0 --start-step 40 2>/dev/null | grep '^{' | python -c "
+    timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --long-steps 0 --start-step 40 2>/dev/null | grep '^{' | python -c "
 import json,sys
 j=json.loads(sys.stdin.read()); print('window from step 40:', j['ms_per_step'], j['value'])"
   done

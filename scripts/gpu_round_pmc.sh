@@ -9,5 +9,5 @@ export TMPDIR=/tmp
 bash scripts/collect_pmc.sh $TAG > $OUT/collect_pmc.log 2>&1
 cp $OUT/pmc_traffic.json $R/profiles/pmc_traffic.json 2>/dev/null
 head -n 45 $OUT/kernel_stats.csv 2>/dev/null | cut -c1-200
-timeout 600 python bench.py --kernel-table > $OUT/bench_default.json 2> $OUT/bench_default_kernel_table.log
+timeout 600 python bench.py --full --kernel-table > $OUT/bench_default.json 2> $OUT/bench_default_kernel_table.log
 cat $OUT/bench_default.json
