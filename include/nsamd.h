@@ -296,14 +296,6 @@ int nsamd_field_mlp_bwd(const float* enc, const float* selector, const float* di
  * scatter_workspace: nsamd_field_mlp_bwd_scatter_workspace(grid, M, &state) floats, the first `state` of them zero
  * before the first call (the kernels leave them zero). Returns NSAMD_ERR_UNSUPPORTED for other level counts. */
 int64_t nsamd_field_mlp_bwd_scatter_workspace(nsamd_grid grid, int64_t M, int64_t* state_words);
-/* Leave `cus` compute units out of the persistent workgroups of the NEXT launches of the field backward (all four entry
- * points; 0 = none, the default; -1 = as many as ONE more sweep over the tiles frees — the workgroups take
- * ceil(tile groups / workgroups) sweeps whatever their number, so that is the cheapest reservation: 6 sweeps on 256 CUs
- * become 7 on 220 for 196 608 points) and return the previous setting. The backward's workgroups own a CU's LDS and registers
- * for the whole launch; on the iterations whose proposal networks receive gradient (model_components/ray_samplers.py:
- * 590-609) their latency-bound backward chains, queued on another stream, otherwise wait for its end. Process-wide,
- * read when a launch is issued (or captured). Results are the same gradients summed in another fixed order. */
-int nsamd_field_mlp_bwd_reserve_cus(int cus);
 int nsamd_field_mlp_bwd_scatter(nsamd_points pts, int transform, nsamd_aabb aabb, nsamd_grid grid, const float* enc,
                                 const float* selector, const float* directions, const int64_t* camera_indices,
                                 const float* appearance_const, int64_t dir_group, int64_t M, nsamd_field_mlp mlp,

@@ -23,7 +23,6 @@
 // Head input slots (internal K order of head layer 0): [0,16) SH, 16 = density pre-activation (zero weight),
 // [17,32) geo features = base outputs 1..15 in place, [32,64) appearance embedding. Logical column = slot for
 // slot < 16, slot - 1 for slot >= 17.
-#include <stdlib.h>
 
 #include "common.h"
 #include "field_reduce.h"
@@ -411,14 +410,6 @@ __global__ void probe_mfma_bf16_kernel(const float* __restrict__ A, const float*
 }
 
 // ---- backward -------------------------------------------------------------------------------------------------
-// Attribution builds (scripts/build_variant.sh x "-DNSAMD_FIELD_BWD_SKIP_CONST=n", timing only, results are wrong): the bits of
-// NSAMD_FIELD_BWD_SKIP as a compile-time constant in the PRODUCT kernel (the instrumented build's run-time switches cost
-// registers and scalar spills of their own), plus 64 = no scratch stores (and splits), 128 = no forward GEMMs.
-#ifndef NSAMD_FIELD_BWD_SKIP_CONST
-#define NSAMD_FIELD_BWD_SKIP_CONST 0
-#endif
-constexpr int kSkipConst = NSAMD_FIELD_BWD_SKIP_CONST;
-
 // store a chain-layout vector (T tiles of 16 features) as S[feature][point]: lane (j, g) register (t, r) is feature
 // 16t + 4g + r of point j. Feature-major, so that a weight-gradient MFMA operand — 4 consecutive POINTS of one feature —
 // is one ds_read_b128 (the point-major layout of round 1 cost one ds_read_b32 per MFMA operand, 2-3 LDS round trips per
@@ -522,7 +513,6 @@ template <int NT, int KT, int LD>
 __device__ __forceinline__ void rows_gemm_fwd(const float* Wrows, const v4f* in, v4f* out, int j, int g) {
 #pragma unroll
   for (int t = 0; t < KT; ++t) {
-    if (kSkipConst & 128) continue;
     v4f a[NT];
 #pragma unroll
     for (int n = 0; n < NT; ++n) a[n] = *reinterpret_cast<const v4f*>(Wrows + (16 * n + j) * LD + 16 * t + 4 * g);
@@ -673,7 +663,6 @@ __device__ __forceinline__ void coop_dw_pk(v4f* acc, float* dbacc, bool want_db,
 #endif
 template <int T, bool HEAD0 = false>
 __device__ __forceinline__ void store_rows(float* S, const v4f* x, int j, int g) {
-  if (kSkipConst & 64) return;
   if (NSAMD_DW_BF16 == 0 || (NSAMD_DW_BF16 == 1 && HEAD0)) store_rows_f32<T>(S, x, j, g);
   else store_rows_pk<T>(S, x, j, g);
 }
@@ -844,7 +833,7 @@ __device__ __noinline__ void route_record_slow(RouteLds* L, float x, float y, fl
 // kept apart —; as global stores they are fire-and-forget, and what is left of a record is its chain of ~6 dependent LDS
 // round trips, which four records now share.)
 template <int K>
-__device__ __forceinline__ void route_level(RouteLds* L, const float (*stash)[64], int lane, int probe_skip) {
+__device__ __forceinline__ void route_level(RouteLds* L, const float (*stash)[64], int lane) {
   constexpr int t = K >> 1, rr = K & 1;
   const int g = lane >> 4;
   const int level = 8 * t + 2 * g + rr;
@@ -867,7 +856,7 @@ __device__ __forceinline__ void route_level(RouteLds* L, const float (*stash)[64
   for (int q = 0; q < 4; ++q) h[q] = pair_hash(c, q, mask);
 #pragma unroll
   for (int q = 0; q < 4; ++q)
-    rank[q] = (probe_skip & 16) ? (uint32_t)(threadIdx.x & 127) : atomicAdd(cnt + (h[q].ia >> sl), 1u);  // ds_add_rtn_u32
+    rank[q] = atomicAdd(cnt + (h[q].ia >> sl), 1u);  // ds_add_rtn_u32
   uint4* const base = L->queues + (L->lv[level].loff + blockIdx.x * C);
   const uint32_t level_cap = L->level_cap;
   bool slow[4], full[4];
@@ -886,7 +875,7 @@ __device__ __forceinline__ void route_level(RouteLds* L, const float (*stash)[64
     full[q] = rank[q] >= C;
     slow[q] = straddle || full[q];
     // (record indices fit 32 bits: the plan checks queue_records < 2^31)
-    if (!full[q] && !(probe_skip & 8)) rec_store(base + (bin * level_cap + rank[q]), rec);
+    if (!full[q]) rec_store(base + (bin * level_cap + rank[q]), rec);
     full[q] = full[q] && !straddle;
   }
 #pragma unroll
@@ -895,11 +884,11 @@ __device__ __forceinline__ void route_level(RouteLds* L, const float (*stash)[64
 }
 
 // every record of the stashed tile at once (after the last tile of a workgroup; emission of a tile normally rides on the next one)
-__device__ __forceinline__ void route_flush(RouteLds* L, const float (*stash)[64], int lane, int probe_skip) {
-  route_level<0>(L, stash, lane, probe_skip);
-  route_level<1>(L, stash, lane, probe_skip);
-  route_level<2>(L, stash, lane, probe_skip);
-  route_level<3>(L, stash, lane, probe_skip);
+__device__ __forceinline__ void route_flush(RouteLds* L, const float (*stash)[64], int lane) {
+  route_level<0>(L, stash, lane);
+  route_level<1>(L, stash, lane);
+  route_level<2>(L, stash, lane);
+  route_level<3>(L, stash, lane);
 }
 
 // Raw position of this lane's point of a tile, in two halves: `route_issue_position` puts the loads out (one phase ahead of
@@ -1026,13 +1015,13 @@ __device__ __forceinline__ void fetch_tile(TileFetch& f, int64_t tile, int64_t t
 struct RouteBetween {
   RouteLds* L;
   const float (*stash)[64];
-  int lane, probe_skip;
+  int lane;
   bool on;
   template <int I>
   __device__ __forceinline__ void at() const {
     if (!on) return;
-    if (I == 0) route_level<0>(L, stash, lane, probe_skip);
-    if (I == 2) route_level<1>(L, stash, lane, probe_skip);
+    if (I == 0) route_level<0>(L, stash, lane);
+    if (I == 2) route_level<1>(L, stash, lane);
   }
 };
 
@@ -1050,17 +1039,7 @@ __global__ __launch_bounds__(kCoopThreads) void field_mlp_bwd_kernel(
     const int64_t* __restrict__ cams, const float* __restrict__ app_const, int64_t dir_group, int64_t M,
     nsamd_field_mlp mlp, int app_dim, const float* __restrict__ ddensity, const float* __restrict__ drgb,
     float* __restrict__ denc, nsamd_field_mlp_grads grads, float* __restrict__ partials,
-    float* __restrict__ app_partials, int app_rows_per_point, int probe_skip_arg, RouteArgs R) {
-  // probe_skip (NSAMD_FIELD_BWD_SKIP, timing experiments only — results are wrong when set): 1 = no weight-gradient
-  // MFMAs, 2 = no workgroup barriers inside the tile loop, 4 = no data-gradient GEMMs. A run-time value only in the
-  // instrumented build (`make probe`): the product kernel folds the switches away (a dozen scalar conditions and their
-  // registers in a kernel whose scalar registers spill).
-#ifdef NSAMD_PROBE_CLOCKS
-  const int probe_skip = probe_skip_arg;
-#else
-  constexpr int probe_skip = kSkipConst;  // 0 in the product; -DNSAMD_FIELD_BWD_SKIP_CONST=n: attribution builds (wrong results)
-  (void)probe_skip_arg;
-#endif
+    float* __restrict__ app_partials, int app_rows_per_point, RouteArgs R) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   float* W = lds;                     // kRowTotal
   float* bias = lds + kRowTotal;      // 256
@@ -1154,7 +1133,7 @@ __global__ __launch_bounds__(kCoopThreads) void field_mlp_bwd_kernel(
       nxt_xin = nxt.xin;
       if (ROUTE) {
         // records 0..6 of the PREVIOUS tile leave between this tile's forward GEMMs, the other nine between the phases below
-        const RouteBetween rb{RL, RL->stash[wave], lane, probe_skip, it > 0 && !(probe_skip & 32)};
+        const RouteBetween rb{RL, RL->stash[wave], lane, it > 0};
         coop_forward_tile<RouteBetween, RAYC>(W, bias, dir, app_table, app_const, app_dim, ti, lane, A, app, rb, cterm);
       } else {
         coop_forward_tile<NoBetween, RAYC>(W, bias, dir, app_table, app_const, app_dim, ti, lane, A, app, NoBetween{}, cterm);
@@ -1175,11 +1154,11 @@ __global__ __launch_bounds__(kCoopThreads) void field_mlp_bwd_kernel(
       coop_forward_tile(W, bias, dir, app_table, app_const, app_dim, ti, lane, A);
     }
     PROBE_STAMP(kCoopWaves, 3 + 10 * (int)it);
-    const bool emit = ROUTE && it > 0 && !(probe_skip & 32);  // the previous tile's records are still going out
+    const bool emit = ROUTE && it > 0;  // the previous tile's records are still going out
 #define NSAMD_ROUTE_LEVEL(K)                                                      \
   do {                                                                           \
     if (ROUTE) {                                                                 \
-      if (emit) route_level<K>(RL, RL->stash[wave], lane, probe_skip);           \
+      if (emit) route_level<K>(RL, RL->stash[wave], lane);           \
     }                                                                            \
   } while (0)
 
@@ -1193,7 +1172,7 @@ __global__ __launch_bounds__(kCoopThreads) void field_mlp_bwd_kernel(
         g_rgbp[0][c] = up_rgb[c] * (sg * (1.0f - sg));
       }
     }
-    if (!(probe_skip & 2)) __syncthreads();  // the previous iteration's last weight-gradient reads of the scratch are done
+    __syncthreads();  // the previous iteration's last weight-gradient reads of the scratch are done
     // Every layer: the wave stores its (Dout, X) tiles, runs its own data-gradient GEMM (registers + weights only) while
     // the stores drain, THEN meets the workgroup and takes its share of the weight gradient — so both barrier intervals
     // of a layer hold MFMA work (the store -> barrier interval used to hold none).
@@ -1201,11 +1180,11 @@ __global__ __launch_bounds__(kCoopThreads) void field_mlp_bwd_kernel(
     store_rows<4>(Sx, A.hb, j, g);
     v4f g_hb[4];
     zero_tiles<4>(g_hb);
-    if (!(probe_skip & 4)) rows_gemm_bwd<4, 1, kLd64>(W + kRowHead2, g_rgbp, g_hb, j, g);
+    rows_gemm_bwd<4, 1, kLd64>(W + kRowHead2, g_rgbp, g_hb, j, g);
     relu_mask<4>(g_hb, A.hb);
-    if (!(probe_skip & 2)) __syncthreads();
-    if (!(probe_skip & 1)) coop_dw<1>(dW_h2, &db_h2, bias_owner14, scratch, 4 * own_half, 4, 0, own_q, j, g);
-    if (!(probe_skip & 2)) __syncthreads();
+    __syncthreads();
+    coop_dw<1>(dW_h2, &db_h2, bias_owner14, scratch, 4 * own_half, 4, 0, own_q, j, g);
+    __syncthreads();
     PROBE_STAMP(kCoopWaves, 4 + 10 * (int)it);
 
     // ---- head layer 1 (64 -> 64) ----
@@ -1213,12 +1192,12 @@ __global__ __launch_bounds__(kCoopThreads) void field_mlp_bwd_kernel(
     store_rows<4>(Sx, A.ha, j, g);
     v4f g_ha[4];
     zero_tiles<4>(g_ha);
-    if (!(probe_skip & 4)) rows_gemm_bwd<4, 4, kLd64>(W + kRowHead1, g_hb, g_ha, j, g);
+    rows_gemm_bwd<4, 4, kLd64>(W + kRowHead1, g_hb, g_ha, j, g);
     relu_mask<4>(g_ha, A.ha);
     NSAMD_ROUTE_LEVEL(2);
-    if (!(probe_skip & 2)) __syncthreads();
-    if (!(probe_skip & 1)) coop_dw<2>(dW_h1, &db_h1, bias_owner44, scratch, 0, kCoopWaves, own_n, own_m2, j, g);
-    if (!(probe_skip & 2)) __syncthreads();
+    __syncthreads();
+    coop_dw<2>(dW_h1, &db_h1, bias_owner44, scratch, 0, kCoopWaves, own_n, own_m2, j, g);
+    __syncthreads();
     PROBE_STAMP(kCoopWaves, 5 + 10 * (int)it);
 
     // ---- head layer 0 (slots 64 -> 64) ----
@@ -1229,7 +1208,7 @@ __global__ __launch_bounds__(kCoopThreads) void field_mlp_bwd_kernel(
       // partial row is dropped by the reduce), data gradient for that tile alone
       store_rows<4>(Sd, g_ha, j, g);
       store_rows<1>(Sx, A.o16, j, g);
-      if (!(probe_skip & 4)) rows_gemm_bwd<1, 4, kLd64>(W + kRowHead0 + 16, g_ha, g_hin + 1, j, g);
+      rows_gemm_bwd<1, 4, kLd64>(W + kRowHead0 + 16, g_ha, g_hin + 1, j, g);
       // S_tile: the tile's 64 sums of dL/d(pre-activation) over its 16 points (DPP butterfly, lane j == 0 of every row), and the
       // ray's inputs, into the free rows of the wave's X area (the geo tile takes 16 of its 64 rows)
       float* Ss = Sx + kRayS;
@@ -1241,8 +1220,8 @@ __global__ __launch_bounds__(kCoopThreads) void field_mlp_bwd_kernel(
         if (j == 0) *reinterpret_cast<v4f*>(Ss + 16 * n + 4 * g) = v;
       }
       if (lane < 48) Sx[kRayX + lane] = lane < 16 + app_dim ? nxt_xin : 0.0f;
-      if (!(probe_skip & 2)) __syncthreads();
-      if (!(probe_skip & 1)) {
+      __syncthreads();
+      {
         coop_dw<1>(dW_h0, &db_h0, true, scratch, 4 * own_half, 4, own_q, 0, j, g);
         // per-ray columns: k = the workgroup's 8 tiles (two instructions of 4), A = S (row 16 a + j), B = the tiles' inputs
         const int a = wave & 3, b0 = wave >> 2;  // b: 0 = SH, 1 / 2 = appearance 0..15 / 16..31
@@ -1266,15 +1245,15 @@ __global__ __launch_bounds__(kCoopThreads) void field_mlp_bwd_kernel(
             *reinterpret_cast<v4f*>(app_partials + ((uint32_t)tj * 32u + (uint32_t)(16 * wave + 4 * g))) = o;
         }
       }
-      if (!(probe_skip & 2)) __syncthreads();
+      __syncthreads();
     } else {
     store_rows<4, true>(Sd, g_ha, j, g);
     store_rows<4, true>(Sx, A.hin, j, g);
     // input tile 0 is the SH block: it carries no gradient, so only columns 16..63 (tiles 1..3) are formed
-    if (!(probe_skip & 4)) rows_gemm_bwd<3, 4, kLd64>(W + kRowHead0 + 16, g_ha, g_hin + 1, j, g);
-    if (!(probe_skip & 2)) __syncthreads();
-    if (!(probe_skip & 1)) coop_dw<2, true>(dW_h0, &db_h0, bias_owner44, scratch, 0, kCoopWaves, own_n, own_m2, j, g);
-    if (!(probe_skip & 2)) __syncthreads();
+    rows_gemm_bwd<3, 4, kLd64>(W + kRowHead0 + 16, g_ha, g_hin + 1, j, g);
+    __syncthreads();
+    coop_dw<2, true>(dW_h0, &db_h0, bias_owner44, scratch, 0, kCoopWaves, own_n, own_m2, j, g);
+    __syncthreads();
     }
     PROBE_STAMP(kCoopWaves, 6 + 10 * (int)it);
 
@@ -1339,12 +1318,12 @@ __global__ __launch_bounds__(kCoopThreads) void field_mlp_bwd_kernel(
     store_rows<4>(Sx, A.h1, j, g);
     v4f g_h1[4];
     zero_tiles<4>(g_h1);
-    if (!(probe_skip & 4)) rows_gemm_bwd<4, 1, kLd64>(W + kRowBase1, g_o16, g_h1, j, g);
+    rows_gemm_bwd<4, 1, kLd64>(W + kRowBase1, g_o16, g_h1, j, g);
     relu_mask<4>(g_h1, A.h1);
     NSAMD_ROUTE_LEVEL(3);
-    if (!(probe_skip & 2)) __syncthreads();
-    if (!(probe_skip & 1)) coop_dw<1>(dW_b1, &db_b1, bias_owner14, scratch, 4 * own_half, 4, 0, own_q, j, g);
-    if (!(probe_skip & 2)) __syncthreads();
+    __syncthreads();
+    coop_dw<1>(dW_b1, &db_b1, bias_owner14, scratch, 4 * own_half, 4, 0, own_q, j, g);
+    __syncthreads();
     PROBE_STAMP(kCoopWaves, 7 + 10 * (int)it);
 
     // ---- base layer 0 (32 -> 64) ----
@@ -1354,7 +1333,7 @@ __global__ __launch_bounds__(kCoopThreads) void field_mlp_bwd_kernel(
     store_rows<2>(Sx, A.enc, j, g);
     v4f g_enc[2];
     zero_tiles<2>(g_enc);
-    if (!(probe_skip & 4)) rows_gemm_bwd<2, 4, kLd32>(W + kRowBase0, g_h1, g_enc, j, g);
+    rows_gemm_bwd<2, 4, kLd32>(W + kRowBase0, g_h1, g_enc, j, g);
     if (ti.live && denc != nullptr) {
 #pragma unroll
       for (int t = 0; t < 2; ++t)
@@ -1376,17 +1355,17 @@ __global__ __launch_bounds__(kCoopThreads) void field_mlp_bwd_kernel(
       RL->stash[wave][9][lane] = py;
       RL->stash[wave][10][lane] = pz;
     }
-    if (!(probe_skip & 2)) __syncthreads();
+    __syncthreads();
     if (AHEAD && it + 1 < iters)  // the next tile's inputs (see TileFetch)
       fetch_tile<RAYC>(nxt, tile + per_iter, tiles, lane, M, enc, selector, directions, cams, app_table, app_const, app_dim,
                        dir_group, ddensity, drgb, mlp.ray_terms, mlp.ray_inputs);
     PROBE_STAMP(kCoopWaves, 9 + 10 * (int)it);
-    if (!(probe_skip & 1)) coop_dw<1>(dW_b0, &db_b0, own_m1 == 0, scratch, 0, kCoopWaves, own_n, own_m1, j, g);
+    coop_dw<1>(dW_b0, &db_b0, own_m1 == 0, scratch, 0, kCoopWaves, own_n, own_m1, j, g);
     // no barrier here: the next writer of the scratch is the next iteration's head layer 2, behind its own barrier
     PROBE_STAMP(kCoopWaves, 8 + 10 * (int)it);
 #undef NSAMD_ROUTE_LEVEL
   }
-  if (ROUTE && iters > 0 && !(probe_skip & 32)) route_flush(RL, RL->stash[wave], lane, probe_skip);  // the last tile's records
+  if (ROUTE && iters > 0) route_flush(RL, RL->stash[wave], lane);  // the last tile's records
   PROBE_STAMP(kCoopWaves, 62);
 
   // ---- the two point-halves of the 1 x 4 layers meet in LDS (scratch is free now) ---------------------------------
@@ -1514,34 +1493,15 @@ static int num_cus() {
   return cached;
 }
 
-// Compute units the persistent backward leaves to other streams' launches (nsamd_field_mlp_bwd_reserve_cus): its workgroups
-// own a CU's LDS and registers for the whole launch, so whatever is queued beside it otherwise waits for its end.
-static int g_bwd_reserved_cus = 0;
-
-// workgroups of a backward launch over `groups` tile groups (kCoopWaves tiles each). Reservation -1 = "one more sweep": the
-// persistent workgroups take ceil(groups / workgroups) sweeps whatever the count, so a few CUs cannot be left out for free —
-// the cheapest reservation is the one that adds exactly one sweep and spreads it evenly (1536 groups on 256 CUs: 6 sweeps of
-// 256 -> 7 sweeps of 220, 36 CUs free); only where that costs <= 25 % (>= 4 sweeps).
-static int field_bwd_workgroups(int64_t groups) {
-  const int cus = num_cus();
-  if (g_bwd_reserved_cus > 0) return cus - g_bwd_reserved_cus > 1 ? cus - g_bwd_reserved_cus : 1;
-  if (g_bwd_reserved_cus < 0) {
-    const int64_t sweeps = (groups + cus - 1) / cus;
-    if (sweeps >= 4) return (int)((groups + sweeps) / (sweeps + 1));
-  }
-  return cus;
-}
-
-extern "C" int nsamd_field_mlp_bwd_reserve_cus(int cus) {
-  const int prev = g_bwd_reserved_cus;
-  g_bwd_reserved_cus = cus < 0 ? -1 : cus;
-  return prev;
+// workgroups of a backward launch over M points: one per CU, at most one per group of kCoopWaves 16-point tiles
+static unsigned field_bwd_blocks(int64_t M) {
+  const int64_t tiles = (M + 15) / 16;
+  return (unsigned)min((int64_t)num_cus(), (tiles + kCoopWaves - 1) / kCoopWaves);
 }
 
 // the RAYC kernels apply: terms given and every 16-point tile inside one ray
 static bool field_ray_terms_apply(const nsamd_field_mlp& mlp, int64_t dir_group, int64_t M) {
-  static const bool on = getenv("NSAMD_RAY_TERMS") == nullptr || atoi(getenv("NSAMD_RAY_TERMS")) != 0;  // =0: A/B, the plain kernels
-  return on && mlp.ray_terms != nullptr && dir_group % 16 == 0 && M % dir_group == 0;
+  return mlp.ray_terms != nullptr && dir_group % 16 == 0 && M % dir_group == 0;
 }
 
 extern "C" int nsamd_field_ray_terms(const float* directions, const int64_t* camera_indices, const float* appearance_const,
@@ -1575,26 +1535,15 @@ static int field_mlp_fwd_impl(const float* enc, const float* selector, const flo
   NSAMD_REQUIRE(density != nullptr);  // rgb NULL: density only
   const size_t lds = sizeof(float) * (kFragTotal + 256);
   const int64_t tiles = (M + 15) / 16;
-  // One 16-wave workgroup per CU by default (4 waves per SIMD, the weights staged once per CU): 57 us on the bench shape
-  // against 59.5 (8 waves x 2 workgroups) and 65 (4 waves x 3) on the same box — NSAMD_FIELD_FWD_WAVES=8|4 selects those.
-  static const int waves = getenv("NSAMD_FIELD_FWD_WAVES") ? atoi(getenv("NSAMD_FIELD_FWD_WAVES")) : 16;
-  if (field_ray_terms_apply(mlp, dir_group, M) && rgb != nullptr) {
-    const unsigned blocks = (unsigned)min((int64_t)num_cus(), (tiles + 15) / 16);
+  // One 16-wave workgroup per CU (4 waves per SIMD, the weights staged once per CU): 57 us on the bench shape against 59.5
+  // (8 waves x 2 workgroups) and 65 (4 waves x 3) on the same box.
+  const unsigned blocks = (unsigned)min((int64_t)num_cus(), (tiles + 15) / 16);
+  if (field_ray_terms_apply(mlp, dir_group, M) && rgb != nullptr)
     field_mlp_fwd_kernel<16, true><<<blocks, 1024, lds, (hipStream_t)stream>>>(
         enc, selector, directions, camera_indices, appearance_const, dir_group, M, mlp, app_dim, density, rgb);
-  } else if (waves == 16) {
-    const unsigned blocks = (unsigned)min((int64_t)num_cus(), (tiles + 15) / 16);
+  else
     field_mlp_fwd_kernel<16><<<blocks, 1024, lds, (hipStream_t)stream>>>(
         enc, selector, directions, camera_indices, appearance_const, dir_group, M, mlp, app_dim, density, rgb);
-  } else if (waves == 8) {
-    const unsigned blocks = (unsigned)min((int64_t)num_cus() * 2, (tiles + 7) / 8);
-    field_mlp_fwd_kernel<8><<<blocks, 512, lds, (hipStream_t)stream>>>(
-        enc, selector, directions, camera_indices, appearance_const, dir_group, M, mlp, app_dim, density, rgb);
-  } else {
-    const unsigned blocks = (unsigned)min((int64_t)num_cus() * 3, (tiles + kWaves - 1) / kWaves);
-    field_mlp_fwd_kernel<kWaves><<<blocks, kFieldThreads, lds, (hipStream_t)stream>>>(
-        enc, selector, directions, camera_indices, appearance_const, dir_group, M, mlp, app_dim, density, rgb);
-  }
   NSAMD_CHECK_LAUNCH();
   return NSAMD_OK;
 }
@@ -1636,9 +1585,7 @@ static int field_mlp_bwd_impl(const float* enc, const float* selector, const flo
       return NSAMD_ERR_LAUNCH;
     if (dev >= 0 && dev < 64) attr_set[dev] = true;
   }
-  static const int probe_skip = getenv("NSAMD_FIELD_BWD_SKIP") ? atoi(getenv("NSAMD_FIELD_BWD_SKIP")) : 0;
-  const int64_t groups = (tiles + kCoopWaves - 1) / kCoopWaves;
-  const unsigned blocks = (unsigned)min((int64_t)field_bwd_workgroups(groups), groups);
+  const unsigned blocks = field_bwd_blocks(M);
   float* partials = (workspace != nullptr && workspace_floats >= (int64_t)blocks * kPartialStride) ? workspace : nullptr;
   // per-tile rows of the appearance-embedding gradient (fixed-order reduction per camera): needs every 16-point tile
   // inside one ray and room behind the weight-gradient partials; otherwise float atomics (sums in no fixed order)
@@ -1673,22 +1620,22 @@ static int field_mlp_bwd_impl(const float* enc, const float* selector, const flo
       if (rayc)
         field_mlp_bwd_kernel<true, true><<<blocks, kCoopThreads, lds + sizeof(uint32_t) * kRouteLdsWords, (hipStream_t)stream>>>(
             enc, selector, directions, camera_indices, appearance_const, dir_group, M, mlp, app_dim, ddensity, drgb, denc,
-            grads, partials, app_partials, app_rows_per_point, probe_skip, R);
+            grads, partials, app_partials, app_rows_per_point, R);
       else
         field_mlp_bwd_kernel<true, false><<<blocks, kCoopThreads, lds + sizeof(uint32_t) * kRouteLdsWords, (hipStream_t)stream>>>(
             enc, selector, directions, camera_indices, appearance_const, dir_group, M, mlp, app_dim, ddensity, drgb, denc,
-            grads, partials, app_partials, app_rows_per_point, probe_skip, R);
+            grads, partials, app_partials, app_rows_per_point, R);
       NSAMD_CHECK_LAUNCH();
     }
   } else if (phases & 1) {
     if (rayc)
       field_mlp_bwd_kernel<false, true><<<blocks, kCoopThreads, lds, (hipStream_t)stream>>>(
           enc, selector, directions, camera_indices, appearance_const, dir_group, M, mlp, app_dim, ddensity, drgb, denc,
-          grads, partials, app_partials, app_rows_per_point, probe_skip, RouteArgs{});
+          grads, partials, app_partials, app_rows_per_point, RouteArgs{});
     else
       field_mlp_bwd_kernel<false, false><<<blocks, kCoopThreads, lds, (hipStream_t)stream>>>(
           enc, selector, directions, camera_indices, appearance_const, dir_group, M, mlp, app_dim, ddensity, drgb, denc,
-          grads, partials, app_partials, app_rows_per_point, probe_skip, RouteArgs{});
+          grads, partials, app_partials, app_rows_per_point, RouteArgs{});
     NSAMD_CHECK_LAUNCH();
   }
   // weight-gradient partials -> gradients, and (extra blocks, one per camera) the appearance rows -> embedding gradient
@@ -1697,9 +1644,7 @@ static int field_mlp_bwd_impl(const float* enc, const float* selector, const flo
   const bool apply = route_in != nullptr && (phases & 4);
   // Both asked for in one call: the reduce RIDES the apply pass as extra workgroups (field_reduce.h; the two are independent)
   // — one launch and one dependent-launch gap fewer on the critical path, same sums in the same order.
-  // NSAMD_REDUCE_RIDER=0: the reduce as a launch of its own (A/B).
-  static const bool rider_on = getenv("NSAMD_REDUCE_RIDER") == nullptr || atoi(getenv("NSAMD_REDUCE_RIDER")) != 0;
-  const bool ride = reduce && apply && rider_on && scatter_apply_takes_rider(plan);
+  const bool ride = reduce && apply && scatter_apply_takes_rider(plan);
   if (reduce && !ride) {
     const size_t red_lds = sizeof(float) * kReduceGroups * 64;
     field_dw_reduce_kernel<<<kDwBlocks + app_blocks, kReduceThreads, red_lds, (hipStream_t)stream>>>(
@@ -1719,11 +1664,6 @@ static int field_mlp_bwd_impl(const float* enc, const float* selector, const flo
                                 ride ? &rd : nullptr);
   }
   return NSAMD_OK;
-}
-
-static unsigned field_bwd_blocks(int64_t M) {
-  const int64_t tiles = (M + 15) / 16;
-  return (unsigned)min((int64_t)num_cus(), (tiles + kCoopWaves - 1) / kCoopWaves);
 }
 
 extern "C" int64_t nsamd_field_mlp_bwd_scatter_workspace(nsamd_grid grid, int64_t M, int64_t* state_words) {

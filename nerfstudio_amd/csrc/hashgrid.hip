@@ -28,7 +28,6 @@
 // list applied after pass 2 (write-only call), so the result never depends on sizing. Fallbacks: without scratch one
 // workgroup OWNS a tile and scans all sample points (hash_encode_bwd_sliced_kernel, 32x redundant hashing, 0.70 ms for
 // the main table); tiny problems keep the direct-atomic kernel. DESIGN.md 4.1 has the measurements behind each choice.
-#include <stdlib.h>
 
 #include "common.h"
 #include "scatter.h"
@@ -92,97 +91,21 @@ __global__ __launch_bounds__(kHashBlock) void hash_encode_fwd_kernel(nsamd_point
   }
 }
 
-// One level per thread, two switches measured against the kernel above (NSAMD_HASH_FWD_MODE bits 1 / 2):
-//  kPair: the two x-neighbours of a cell edge differ by lo ^ hi in their hashed index whatever y and z are; when that is 1
-//         (lo even) or 0 (the point sits on a lattice plane) both entries lie in one aligned 16-B chunk, so ONE dwordx4 gather
-//         serves the pair and the second, lane-masked gather only runs for odd lo — 6 instead of 8 L1 accesses per (point,
-//         level) on average. The gathers are bound by L1 tag lookups (r02: 23.9 M accesses, 0.53 per clock per CU), not bytes.
-//  kXcd:  1-D grid, block b runs on XCD b % 8 (observed placement, speed only): XCD x sweeps levels x, 15 - x, 16 + x, ... so a
-//         level slice is filled into ONE L2 instead of all eight.
-template <bool kPair, bool kXcd>
-__global__ __launch_bounds__(kHashBlock) void hash_encode_fwd_v2_kernel(nsamd_points P, int64_t M, int transform,
-                                                                        nsamd_aabb box, const float2* __restrict__ table,
-                                                                        nsamd_grid grid, float* __restrict__ enc,
-                                                                        int64_t stride_p, int64_t stride_k,
-                                                                        float* __restrict__ selector, unsigned nb) {
-  int level;
-  int64_t pb;
-  if (kXcd) {
-    const unsigned xcd = blockIdx.x & 7u, q = blockIdx.x >> 3;
-    const unsigned li = q / nb;
-    pb = q - li * nb;
-    level = (li & 1u) ? (int)(8u * li + 7u - xcd) : (int)(8u * li + xcd);
-    if (level >= grid.num_levels) return;
-  } else {
-    level = blockIdx.y;
-    pb = blockIdx.x;
-  }
-  const int64_t p = pb * kHashBlock + threadIdx.x;
-  if (p >= M) return;
-  float x, y, z;
-  load_position_burst(P, p, x, y, z);
-  const float sel = normalise_position(transform, box, x, y, z);
-  const uint32_t mask = (1u << grid.log2_table_size) - 1u;
-  const Cell c = locate_cell(x, y, z, grid.scalings[level]);
-  const float2* __restrict__ tl = table + ((size_t)level << grid.log2_table_size);
-  float2 v0, v1, v2, v3, v4, v5, v6, v7;
-  if (kPair) {
-    const float4* __restrict__ tl4 = reinterpret_cast<const float4*>(tl);
-    const uint32_t hy0 = (uint32_t)c.lo[1] * kPrimeY, hy1 = (uint32_t)c.hi[1] * kPrimeY;
-    const uint32_t hz0 = (uint32_t)c.lo[2] * kPrimeZ, hz1 = (uint32_t)c.hi[2] * kPrimeZ;
-    const uint32_t xl = (uint32_t)c.lo[0], xh = (uint32_t)c.hi[0];
-    const uint32_t a0 = (xl ^ hy0 ^ hz0) & mask, a1 = (xl ^ hy1 ^ hz0) & mask, a2 = (xl ^ hy0 ^ hz1) & mask,
-                   a3 = (xl ^ hy1 ^ hz1) & mask;
-    const uint32_t b0 = (xh ^ hy0 ^ hz0) & mask, b1 = (xh ^ hy1 ^ hz0) & mask, b2 = (xh ^ hy0 ^ hz1) & mask,
-                   b3 = (xh ^ hy1 ^ hz1) & mask;
-    const float4 q0 = tl4[a0 >> 1], q1 = tl4[a1 >> 1], q2 = tl4[a2 >> 1], q3 = tl4[a3 >> 1];
-    auto half = [](const float4& q, uint32_t i) { return (i & 1u) ? make_float2(q.z, q.w) : make_float2(q.x, q.y); };
-    v0 = half(q0, a0); v2 = half(q1, a1); v4 = half(q2, a2); v6 = half(q3, a3);
-    if ((((xl ^ xh) & mask) >> 1) == 0u) {
-      v1 = half(q0, b0); v3 = half(q1, b1); v5 = half(q2, b2); v7 = half(q3, b3);
-    } else {
-      v1 = tl[b0]; v3 = tl[b1]; v5 = tl[b2]; v7 = tl[b3];
-    }
-  } else {
-    v0 = tl[corner_index(c, 0, mask)]; v1 = tl[corner_index(c, 1, mask)]; v2 = tl[corner_index(c, 2, mask)];
-    v3 = tl[corner_index(c, 3, mask)]; v4 = tl[corner_index(c, 4, mask)]; v5 = tl[corner_index(c, 5, mask)];
-    v6 = tl[corner_index(c, 6, mask)]; v7 = tl[corner_index(c, 7, mask)];
-  }
-  const float wx = c.w[0], wy = c.w[1], wz = c.w[2];
-  const float ux = 1.0f - wx, uy = 1.0f - wy, uz = 1.0f - wz;
-  float r[2];
-#pragma unroll
-  for (int f = 0; f < 2; ++f) {
-    auto g = [&](const float2& a) { return f == 0 ? a.x : a.y; };
-    const float yc_zc = g(v7) * wx + g(v6) * ux;  // blend order x, y, z exactly as encodings.py:446-456
-    const float yf_zc = g(v5) * wx + g(v4) * ux;
-    const float yf_zf = g(v1) * wx + g(v0) * ux;
-    const float yc_zf = g(v3) * wx + g(v2) * ux;
-    const float zc = yc_zc * wy + yf_zc * uy;
-    const float zf = yc_zf * wy + yf_zf * uy;
-    r[f] = zc * wz + zf * uz;
-  }
-  float* o = enc + p * stride_p + (int64_t)(2 * level) * stride_k;
-  o[0] = r[0];
-  o[stride_k] = r[1];
-  // (behind the gathers: vector memory operations retire in order and stores count — in front of them the selector store
-  //  would have to complete before the first gathered value may be used)
-  if (level == 0 && selector != nullptr) selector[p] = sel;
-}
-
-// kLanePair (NSAMD_HASH_FWD_MODE bit 4; round 5). What a divergent gather costs on this part is the number of distinct 128-B
+// One level per thread, lanes in pairs (round 5). What a divergent gather costs on this part is the number of distinct 128-B
 // LINES a wave instruction touches — ~0.47 lines per clock and CU whatever the access width, and lanes that share a line are
 // free (scripts/probe_gather.hip, profiles/r05_s14_probe_gather.txt: pairs of lanes on one line 2 x, quads 4 x the lane rate;
 // the forward at fine levels runs the address unit 91 % busy, profiles/r05_s13_hash_fwd_cache_counters.txt). The two
 // x-neighbours of a cell edge sit in ONE line 15 times out of 16 (their indices differ by lo ^ hi = 2^(k+1) - 1, k = trailing
 // ones of lo; a line holds 16 entries) but, fetched by the same lane in two instructions, the second fetch pays for the line
-// again (6 lines per point and level with the pair gathers above). Here lanes 2i and 2i + 1 work on ONE point at a time — the
+// again (6 lines per point and level with one lane gathering both, 16-B pair loads). Here lanes 2i and 2i + 1 work on ONE point at a time — the
 // even lane fetches the four lo-x corners, the odd lane the four hi-x corners, in the same four instructions — first on the even
 // lane's point, then on the odd lane's: 8 gather instructions of 32 points x ~1.06 lines instead of 4 x 64 + 4 x 32, i.e.
 // 4.25 lines per point and level. The neighbour's cell hashes and the fetched values cross the lane pair as DPP quad_perm
 // moves (VALU rate, no LDS); every lane then blends its own point exactly as before: same operations, same bits.
 // (Two points per lane on top of it — twice the gathers in flight, half the waves — changes nothing: 63.0 against 63.1 us,
 // profiles/r05_s17_*. What is left of a coarse level, 1.5 us, is the ~300 vector instructions of a (point, level) thread.)
+// kXcd: 1-D grid, block b runs on XCD b % 8 (observed placement, speed only): XCD x sweeps levels x, 15 - x, 16 + x, ... so a
+// level slice is filled into ONE L2 instead of all eight.
 template <bool kXcd>
 __global__ __launch_bounds__(kHashBlock) void hash_encode_fwd_v3_kernel(nsamd_points P, int64_t M, int transform,
                                                                         nsamd_aabb box, const float2* __restrict__ table,
@@ -221,7 +144,7 @@ __global__ __launch_bounds__(kHashBlock) void hash_encode_fwd_v3_kernel(nsamd_po
   // round E: the even lane's point (own for even lanes, the neighbour's for odd ones); round O: the odd lane's point
   const uint32_t ex = odd ? nx : own_x, ey0 = odd ? ny0 : hy0, ey1 = odd ? ny1 : hy1, ez0 = odd ? nz0 : hz0, ez1 = odd ? nz1 : hz1;
   const uint32_t ox = odd ? own_x : nx, oy0 = odd ? hy0 : ny0, oy1 = odd ? hy1 : ny1, oz0 = odd ? hz0 : nz0, oz1 = odd ? hz1 : nz1;
-  // corner pair q: (y, z) = (lo, lo), (hi, lo), (lo, hi), (hi, hi) — v0/v1, v2/v3, v4/v5, v6/v7 of the kernels above
+  // corner pair q: (y, z) = (lo, lo), (hi, lo), (lo, hi), (hi, hi) — v0/v1, v2/v3, v4/v5, v6/v7 of the kernel above
   const float2 e0 = tl[(ex ^ ey0 ^ ez0) & mask], e1 = tl[(ex ^ ey1 ^ ez0) & mask], e2 = tl[(ex ^ ey0 ^ ez1) & mask],
                e3 = tl[(ex ^ ey1 ^ ez1) & mask];
   const float2 o0 = tl[(ox ^ oy0 ^ oz0) & mask], o1 = tl[(ox ^ oy1 ^ oz0) & mask], o2 = tl[(ox ^ oy0 ^ oz1) & mask],
@@ -539,11 +462,6 @@ static int check_grid(const nsamd_grid& g) {
 
 using namespace nsamd;
 
-static int env_int(const char* name, int dflt) {
-  const char* e = getenv(name);
-  return e != nullptr ? atoi(e) : dflt;
-}
-
 extern "C" int nsamd_hashgrid_encode_fwd(nsamd_points pts, int64_t M, int transform, nsamd_aabb aabb,
                                          const float* table, nsamd_grid grid, float* enc, int64_t stride_p,
                                          int64_t stride_k, float* selector, nsamd_stream_t stream) {
@@ -560,44 +478,21 @@ extern "C" int nsamd_hashgrid_encode_fwd(nsamd_points pts, int64_t M, int transf
   // Levels per thread: small tables (all levels of a proposal grid sit in one XCD's L2 together) gain from sharing the
   // position and having 32 gathers in flight (44.5 -> 38.8 us, 27.9 -> 24.6 us); for the main grid one level already
   // fills an L2 and sweeping several at once thrashes it (80 -> 97 us). Measured, profiles/r01_negative_results.txt.
-  static const int lv_force = env_int("NSAMD_HASH_FWD_LEVELS", 0);
-  const int lv_env = lv_force ? lv_force : (((int64_t)8 << grid.log2_table_size) >= (2 << 20) ? 1 : 4);
-  if (lv_env >= 4) {
+  if (((int64_t)8 << grid.log2_table_size) < (2 << 20)) {
     dim3 g((unsigned)nb, (unsigned)((grid.num_levels + 3) / 4));
     hash_encode_fwd_kernel<4><<<g, kHashBlock, 0, (hipStream_t)stream>>>(
         pts, M, transform, aabb, reinterpret_cast<const float2*>(table), grid, enc, stride_p, stride_k, selector);
-  } else if (lv_env >= 2) {
-    dim3 g((unsigned)nb, (unsigned)((grid.num_levels + 1) / 2));
-    hash_encode_fwd_kernel<2><<<g, kHashBlock, 0, (hipStream_t)stream>>>(
-        pts, M, transform, aabb, reinterpret_cast<const float2*>(table), grid, enc, stride_p, stride_k, selector);
   } else {
-    // pair gathers + XCD-aware level sweep (mode 3): 83.8 -> 78.8 us on the main grid (81.5 with either alone); lane pairs on
-    // one line + the XCD-aware sweep (mode 7, round 5): 76.1 -> 63.3 us on one box, a fine level 5.5 -> 4.4 us
-    // (profiles/r05_s15_*). Same arithmetic in every mode.
-    static const int mode = env_int("NSAMD_HASH_FWD_MODE", 7);
+    // lane pairs on one line + the XCD-aware level sweep (round 5): 76.1 -> 63.3 us on one box, a fine level 5.5 -> 4.4 us
+    // (profiles/r05_s15_*); pair gathers + the sweep alone had taken 83.8 -> 78.8 us. Same arithmetic either way.
     const float2* t2 = reinterpret_cast<const float2*>(table);
-    const dim3 g2((unsigned)nb, (unsigned)grid.num_levels);
     const int64_t xcd_blocks = 8 * nb * ((grid.num_levels + 7) / 8);
-    const bool xcd = (mode & 2) && grid.num_levels % 8 == 0 && xcd_blocks <= 0x7fffffffLL;
-    const dim3 g1((unsigned)xcd_blocks);
-    if ((mode & 4) && xcd)
-      hash_encode_fwd_v3_kernel<true><<<g1, kHashBlock, 0, (hipStream_t)stream>>>(
-          pts, M, transform, aabb, t2, grid, enc, stride_p, stride_k, selector, (unsigned)nb);
-    else if (mode & 4)
-      hash_encode_fwd_v3_kernel<false><<<g2, kHashBlock, 0, (hipStream_t)stream>>>(
-          pts, M, transform, aabb, t2, grid, enc, stride_p, stride_k, selector, (unsigned)nb);
-    else if ((mode & 1) && xcd)
-      hash_encode_fwd_v2_kernel<true, true><<<g1, kHashBlock, 0, (hipStream_t)stream>>>(
-          pts, M, transform, aabb, t2, grid, enc, stride_p, stride_k, selector, (unsigned)nb);
-    else if (mode & 1)
-      hash_encode_fwd_v2_kernel<true, false><<<g2, kHashBlock, 0, (hipStream_t)stream>>>(
-          pts, M, transform, aabb, t2, grid, enc, stride_p, stride_k, selector, (unsigned)nb);
-    else if (xcd)
-      hash_encode_fwd_v2_kernel<false, true><<<g1, kHashBlock, 0, (hipStream_t)stream>>>(
+    if (grid.num_levels % 8 == 0 && xcd_blocks <= 0x7fffffffLL)
+      hash_encode_fwd_v3_kernel<true><<<dim3((unsigned)xcd_blocks), kHashBlock, 0, (hipStream_t)stream>>>(
           pts, M, transform, aabb, t2, grid, enc, stride_p, stride_k, selector, (unsigned)nb);
     else
-      hash_encode_fwd_kernel<1><<<g2, kHashBlock, 0, (hipStream_t)stream>>>(pts, M, transform, aabb, t2, grid, enc, stride_p,
-                                                                          stride_k, selector);
+      hash_encode_fwd_v3_kernel<false><<<dim3((unsigned)nb, (unsigned)grid.num_levels), kHashBlock, 0, (hipStream_t)stream>>>(
+          pts, M, transform, aabb, t2, grid, enc, stride_p, stride_k, selector, (unsigned)nb);
   }
   NSAMD_CHECK_LAUNCH();
   return NSAMD_OK;

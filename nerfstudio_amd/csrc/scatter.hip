@@ -24,7 +24,6 @@
 // routing and the atomics' order do not reach the result: two runs on the same inputs give the same bits. Records that
 // find no room in their tile go to a spill list; pass 2 folds the first kSpillFold of them into their tiles (still
 // exact and order-free), the finish kernel applies any rest with float atomics and counts them (hdr[kHdrEvtUnordered]).
-#include <stdlib.h>
 
 #include <type_traits>
 
@@ -741,31 +740,13 @@ __global__ void scatter_finish_pair_kernel(ApplyCall a, ApplyCall b) {  // (same
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------
-static int env_int(const char* name, int dflt) {
-  const char* e = getenv(name);
-  return e != nullptr ? atoi(e) : dflt;
-}
 static unsigned apply_threads(int slice_log2);
 
-// fine-kernel shape (threads, points per thread, levels per thread); NSAMD_SCATTER_SHAPE = "TPL" digits (experiments; read
-// once). Measured on MI355X (profiles/r02_scatter_variants.txt): 1024 x 1 x 4 is the fastest or within noise of it; two
-// points per thread, two levels per thread and an LDS-staged coalescing variant were slower and are gone.
-struct FineShape {
-  int threads, pts, levels;
-};
-static FineShape fine_shape() {
-  static const int code = env_int("NSAMD_SCATTER_SHAPE", 114);
-  switch (code) {
-    case 514: return FineShape{512, 1, 4};
-    case 112: return FineShape{1024, 1, 2};
-    default: return FineShape{1024, 1, 4};
-  }
-}
-
-static int scatter_target_tiles() {
-  static const int v = env_int("NSAMD_SCATTER_TILES", 512);
-  return v >= 64 ? v : 512;
-}
+// fine-kernel shape: threads and levels per thread (one point per thread). Measured on MI355X
+// (profiles/r02_scatter_variants.txt): 1024 x 1 x 4 is the fastest or within noise of it; 512 threads, two points per thread,
+// two levels per thread and an LDS-staged coalescing variant were slower and are gone.
+constexpr int kFineThreads = 1024, kFineLevels = 4;
+constexpr int kScatterTargetTiles = 512;
 
 constexpr int kSliceLog2Max = 13;  // 8192 entries x 2 x int64 = 128 KiB of the 160 KiB LDS
 
@@ -773,7 +754,7 @@ ScatterPlan scatter_plan(const nsamd_grid& grid, int64_t M, bool max_spill) {
   ScatterPlan p{};
   if (M <= 0 || grid.num_levels <= 0 || grid.num_levels > NSAMD_MAX_LEVELS) return p;
   int bits = 0;
-  while ((grid.num_levels << bits) < scatter_target_tiles()) ++bits;
+  while ((grid.num_levels << bits) < kScatterTargetTiles) ++bits;
   int sl = grid.log2_table_size - bits;
   // a tile at least as wide as the finest resolution keeps every x-pair inside one tile (no straddling pairs)
   float res_max = 0.0f;
@@ -785,12 +766,11 @@ ScatterPlan scatter_plan(const nsamd_grid& grid, int64_t M, bool max_spill) {
   if (sl > grid.log2_table_size) sl = grid.log2_table_size;
   const int log2_bins = grid.log2_table_size - sl;
   if (log2_bins > kMaxLog2Bins) return p;
-  const FineShape fsx = fine_shape();
   ScatterGeom& g = p.geom;
   g.slice_log2 = sl;
   g.log2_bins = log2_bins;
   g.num_levels = grid.num_levels;
-  g.block_points = (uint32_t)(fsx.threads * fsx.pts);
+  g.block_points = (uint32_t)kFineThreads;
   const int64_t bins = (int64_t)1 << log2_bins;
   const int64_t segs = (M + g.block_points - 1) / g.block_points;
   // static segment: 2x the uniform-hash expectation of 4 pair records per point and level
@@ -848,7 +828,7 @@ ScatterPlan scatter_plan_producers(const nsamd_grid& grid, int64_t M, int workgr
   if (M <= 0 || workgroups <= 0 || seg_cap < 16 || grid.num_levels <= 0 || grid.num_levels > NSAMD_MAX_LEVELS) return p;
   // tiles as scatter_plan chooses them: wide enough for every x-pair to stay inside one tile, 128 KiB of LDS at most
   int bits = 0;
-  while ((grid.num_levels << bits) < scatter_target_tiles()) ++bits;
+  while ((grid.num_levels << bits) < kScatterTargetTiles) ++bits;
   int sl = grid.log2_table_size - bits;
   float res_max = 0.0f;
   for (int l = 0; l < grid.num_levels; ++l) res_max = grid.scalings[l] > res_max ? grid.scalings[l] : res_max;
@@ -941,11 +921,8 @@ int scatter_apply_launch(const nsamd_grid& grid, const ScatterPlan& plan, float*
   return NSAMD_OK;
 }
 
-// threads of an apply-pass workgroup for tiles of 2^slice_log2 entries. NSAMD_APPLY_THREADS_12 (experiments): the count for
-// 4096-entry tiles (64 KiB of LDS: 512 threads let two workgroups share a compute unit, NSAMD_SCATTER_TILES=2048).
+// threads of an apply-pass workgroup for tiles of 2^slice_log2 entries
 static unsigned apply_threads(int slice_log2) {
-  static const int t12 = env_int("NSAMD_APPLY_THREADS_12", 1024);
-  if (slice_log2 == 12 && (t12 == 256 || t12 == 512 || t12 == 1024)) return (unsigned)t12;
   return slice_log2 > 11 ? 1024u : (slice_log2 > 9 ? 512u : 256u);
 }
 
@@ -969,30 +946,16 @@ ScatterBufs scatter_bufs(float* workspace, const ScatterPlan& p) {
   return b;
 }
 
-template <int kThreads, int kPts, int kLevels>
-static void launch_fine(const nsamd_points& pts, int64_t M, int transform, const nsamd_aabb& aabb, const nsamd_grid& grid,
-                        const float* denc, int64_t stride_p, int64_t stride_k, const ScatterGeom& G,
-                        const LevelList& fine, const ScatterBufs& buf, const uint32_t* gate, const uint8_t* ray_mask,
-                        hipStream_t st) {
-  const size_t lds = sizeof(uint32_t) * (3 * (size_t)kLevels * ((size_t)1 << G.log2_bins) + kLevels);
-  dim3 g1(G.segs, (unsigned)((fine.count + kLevels - 1) / kLevels));
-  scatter_route_fine_kernel<kThreads, kPts, kLevels><<<g1, kThreads, lds, st>>>(pts, M, transform, aabb, grid, denc,
-                                                                                 stride_p, stride_k, G, fine, buf, gate, ray_mask);
-}
-
 // Which levels of a call go through the run-merging kernel (coarse) and which through the plain route (fine); sets G.coarse_mask.
 static void classify_levels(const nsamd_points& pts, const nsamd_grid& grid, ScatterGeom& G, LevelList& coarse,
                             LevelList& fine) {
-  static const int combine_env = env_int("NSAMD_SCATTER_COMBINE_RES", 0);
   float coarse_below = 0.0f;
   // Round 6 (profiles/r06_s12_*, r06_s14_*): since the run kernel and the apply pass on non-empty segments (rounds 3 - 5) the
   // 96-sample level is cheaper merged as well — its route + apply read 40 + 37 us plain against 35 + 9 us for the 2.7 x larger
   // 256-sample level merged; all five of its levels through the run kernel: long run 0.6919 / 0.6883 against 0.6971 / 0.6959 ms
-  // from step 40, window 0.657 / 0.658 against 0.667 / 0.667 from step 0 (NSAMD_SCATTER_MERGE_96=0: the plain route, A/B).
-  static const int merge96 = env_int("NSAMD_SCATTER_MERGE_96", 1);
-  if (pts.positions == nullptr && pts.samples_per_ray >= (merge96 ? 96 : 192))
+  // from step 40, window 0.657 / 0.658 against 0.667 / 0.667 from step 0.
+  if (pts.positions == nullptr && pts.samples_per_ray >= 96)
     coarse_below = pts.samples_per_ray >= 192 ? (float)pts.samples_per_ray : 1e30f;
-  if (combine_env > 0) coarse_below = (float)combine_env;
   for (int l = 0; l < grid.num_levels; ++l) {
     if (grid.scalings[l] < coarse_below) {
       G.coarse_mask |= 1u << l;
@@ -1003,13 +966,10 @@ static void classify_levels(const nsamd_points& pts, const nsamd_grid& grid, Sca
   }
 }
 
-// levels per thread of the run kernel (NSAMD_RUNS_LEVELS = 1 / 2 / 4, read once): fewer levels per thread = more, shorter
-// workgroups — its time is the latency of one workgroup's two sweeps (profiles/r03_sparse_regime_kernel_stats.csv)
+// levels per thread of the run kernel: fewer levels per thread = more, shorter workgroups — its time is the latency of one
+// workgroup's two sweeps (profiles/r03_sparse_regime_kernel_stats.csv)
 // (MI355X, driver window of the bench: 4 -> 75 us, 2 -> 54, 1 -> 54 per launch of the 256-sample level's scatter)
-static int runs_levels_setting() {
-  static const int runs_levels = env_int("NSAMD_RUNS_LEVELS", 2);
-  return runs_levels == 1 || runs_levels == 2 ? runs_levels : 4;
-}
+constexpr int kRunLevels = 2;
 
 int scatter_launch(const nsamd_points& pts, int64_t M, int transform, const nsamd_aabb& aabb, const nsamd_grid& grid,
                    const float* denc, int64_t stride_p, int64_t stride_k, float* dtable, float* workspace,
@@ -1023,8 +983,7 @@ int scatter_launch(const nsamd_points& pts, int64_t M, int transform, const nsam
   // Levels whose cells are wide against the sample spacing go through the run-merging kernel: with >= 192 samples per
   // ray (the first proposal level) consecutive samples share cells on every level of the small proposal grids and
   // merging pays (75 vs 107 us at M = 1 M); with 96 or 48 samples per ray the plain route is faster on every level
-  // (65 vs 88 us, 178 vs 197 us for the main table; profiles/r02a_*). NSAMD_SCATTER_COMBINE_RES > 0 overrides the
-  // threshold: levels with resolution below it are merged (1 = none).
+  // (65 vs 88 us, 178 vs 197 us for the main table; profiles/r02a_*).
   LevelList coarse{}, fine{};
   classify_levels(pts, grid, G, coarse, fine);
   {
@@ -1032,28 +991,19 @@ int scatter_launch(const nsamd_points& pts, int64_t M, int transform, const nsam
     if (rc) return rc;
   }
   if (fine.count > 0) {
-    const FineShape s = fine_shape();
-    const int code = s.threads * 100 + s.pts * 10 + s.levels;
-    switch (code) {
-      case 51214: launch_fine<512, 1, 4>(pts, M, transform, aabb, grid, denc, stride_p, stride_k, G, fine, buf, gate, ray_mask, st); break;
-      case 102412: launch_fine<1024, 1, 2>(pts, M, transform, aabb, grid, denc, stride_p, stride_k, G, fine, buf, gate, ray_mask, st); break;
-      default: launch_fine<1024, 1, 4>(pts, M, transform, aabb, grid, denc, stride_p, stride_k, G, fine, buf, gate, ray_mask, st); break;
-    }
+    const size_t lds = sizeof(uint32_t) * (3 * (size_t)kFineLevels * ((size_t)1 << G.log2_bins) + kFineLevels);
+    dim3 g1(G.segs, (unsigned)((fine.count + kFineLevels - 1) / kFineLevels));
+    scatter_route_fine_kernel<kFineThreads, 1, kFineLevels><<<g1, kFineThreads, lds, st>>>(
+        pts, M, transform, aabb, grid, denc, stride_p, stride_k, G, fine, buf, gate, ray_mask);
     NSAMD_CHECK_LAUNCH();
   }
   if (coarse.count > 0) {
-    const int runs_levels = runs_levels_setting();
+    constexpr int kL = kRunLevels;
     const int64_t per_block = (int64_t)kRunThreads * kRunLen;
-    auto launch_runs = [&](auto tag) {
-      constexpr int kL = decltype(tag)::value;
-      const size_t lds = sizeof(uint32_t) * (3 * (size_t)kL * ((size_t)1 << G.log2_bins) + kL);
-      dim3 g1((unsigned)((M + per_block - 1) / per_block), (unsigned)((coarse.count + kL - 1) / kL));
-      scatter_route_runs_kernel<kL><<<g1, kRunThreads, lds, st>>>(pts, M, transform, aabb, grid, denc, stride_p, stride_k, G,
-                                                                coarse, buf, gate, ray_mask);
-    };
-    if (runs_levels == 1) launch_runs(std::integral_constant<int, 1>{});
-    else if (runs_levels == 2) launch_runs(std::integral_constant<int, 2>{});
-    else launch_runs(std::integral_constant<int, 4>{});
+    const size_t lds = sizeof(uint32_t) * (3 * (size_t)kL * ((size_t)1 << G.log2_bins) + kL);
+    dim3 g1((unsigned)((M + per_block - 1) / per_block), (unsigned)((coarse.count + kL - 1) / kL));
+    scatter_route_runs_kernel<kL><<<g1, kRunThreads, lds, st>>>(pts, M, transform, aabb, grid, denc, stride_p, stride_k, G,
+                                                              coarse, buf, gate, ray_mask);
     NSAMD_CHECK_LAUNCH();
   }
   const unsigned threads = apply_threads(G.slice_log2);
@@ -1093,27 +1043,21 @@ int scatter_launch_pair(const ScatterCall& a, const ScatterCall& b, hipStream_t 
     const int rc = apply_lds_attribute();
     if (rc) return rc;
   }
+  constexpr int kL = kRunLevels;
   const int64_t per_block = (int64_t)kRunThreads * kRunLen;
-  auto launch_runs = [&](auto tag) {
-    constexpr int kL = decltype(tag)::value;
-    RunsCall rc[2];
-    size_t lds = 0;
-    unsigned gx = 0, gy = 0;
-    for (int i = 0; i < 2; ++i) {
-      rc[i] = RunsCall{c[i]->pts, c[i]->M, c[i]->transform, c[i]->aabb, c[i]->grid, c[i]->denc, c[i]->stride_p, c[i]->stride_k,
-                       G[i], coarse[i], buf[i], c[i]->gate, c[i]->ray_mask,
-                       (uint32_t)((c[i]->M + per_block - 1) / per_block), (uint32_t)((coarse[i].count + kL - 1) / kL)};
-      const size_t l = sizeof(uint32_t) * (3 * (size_t)kL * ((size_t)1 << G[i].log2_bins) + kL);
-      lds = l > lds ? l : lds;
-      gx = rc[i].grid_x > gx ? rc[i].grid_x : gx;
-      gy = rc[i].grid_y > gy ? rc[i].grid_y : gy;
-    }
-    scatter_route_runs_pair_kernel<kL><<<dim3(gx, gy, 2u), kRunThreads, lds, st>>>(rc[0], rc[1]);
-  };
-  const int runs_levels = runs_levels_setting();
-  if (runs_levels == 1) launch_runs(std::integral_constant<int, 1>{});
-  else if (runs_levels == 2) launch_runs(std::integral_constant<int, 2>{});
-  else launch_runs(std::integral_constant<int, 4>{});
+  RunsCall rc[2];
+  size_t run_lds = 0;
+  unsigned gx = 0, gy = 0;
+  for (int i = 0; i < 2; ++i) {
+    rc[i] = RunsCall{c[i]->pts, c[i]->M, c[i]->transform, c[i]->aabb, c[i]->grid, c[i]->denc, c[i]->stride_p, c[i]->stride_k,
+                     G[i], coarse[i], buf[i], c[i]->gate, c[i]->ray_mask,
+                     (uint32_t)((c[i]->M + per_block - 1) / per_block), (uint32_t)((coarse[i].count + kL - 1) / kL)};
+    const size_t l = sizeof(uint32_t) * (3 * (size_t)kL * ((size_t)1 << G[i].log2_bins) + kL);
+    run_lds = l > run_lds ? l : run_lds;
+    gx = rc[i].grid_x > gx ? rc[i].grid_x : gx;
+    gy = rc[i].grid_y > gy ? rc[i].grid_y : gy;
+  }
+  scatter_route_runs_pair_kernel<kL><<<dim3(gx, gy, 2u), kRunThreads, run_lds, st>>>(rc[0], rc[1]);
   NSAMD_CHECK_LAUNCH();
   ApplyCall ac[2];
   unsigned bins = 0, levels = 0;

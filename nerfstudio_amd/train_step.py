@@ -138,12 +138,6 @@ class NerfactoTrainStep:
         # round trip, no route launch); NSAMD_FUSE_ROUTE=0: the two entry points (A/B).
         self.fuse_route = os.environ.get("NSAMD_FUSE_ROUTE", "1") == "1"
         self.keep_denc = False  # True: the fused launch also stores the encoded-feature gradient in `f_denc` (tests read it)
-        self.prop_mlp_inline = os.environ.get("NSAMD_PROP_MLP_INLINE", "0") == "1"
-        # compute units the persistent main backward leaves to the proposal chains on the iterations that run them
-        # (0, the default: none; -1: one more sweep of the persistent workgroups, 36 of 256 CUs at 196 608 points; n: n CUs.
-        #  Measured round 6, profiles/r06_s22_*, r06_s27_*: -0.5 % window / -0.7 % long run for a field backward that is 16 %
-        #  longer on those iterations — opt-in)
-        self.bwd_reserve_cus = int(os.environ.get("NSAMD_BWD_RESERVE_CUS", "0"))
         # the same stage of the proposal levels' backward chains as one launch across the levels (0: level by level, A/B)
         self.merge_prop_levels = os.environ.get("NSAMD_MERGE_PROP_LEVELS", "1") == "1"
         # the iteration's loss values and training metrics, written by the losses launch's finishing pass (nsamd.h):
@@ -161,27 +155,15 @@ class NerfactoTrainStep:
         # scatter kernels were reworked (latency-bound phases, small workgroups) they overlap: 3.87 -> 4.02 M rays/s on
         # MI355X (profiles/). `side_stream = None` runs them back to back (the data-parallel path does: its proposal
         # chain is the cover for the main-field all-reduce).
-        self.side_stream = torch.cuda.Stream(device=device)
-        # ... and the proposal levels are independent of each other too: level i > 0 gets its own stream
-        self.level_streams = [torch.cuda.Stream(device=device) for _ in range(max(self.n_prop - 1, 0))]
-        self._fork, self._join = torch.cuda.Event(), torch.cuda.Event()
-        # the field backward's weight-gradient reduce on its own stream, beside the table scatter (opt-in: NSAMD_SPLIT_REDUCE=1; measured neutral)
-        self.split_reduce = os.environ.get("NSAMD_SPLIT_REDUCE", "0") == "1"
-        self.reduce_stream = torch.cuda.Stream(device=device)
-        self.rays_beside_apply = os.environ.get("NSAMD_RAYS_BESIDE_APPLY", "1") == "1"  # (camera optimiser, see backward_field_and_table)
-        self._red_fork, self._red_join = torch.cuda.Event(), torch.cuda.Event()
-        self._level_join = [torch.cuda.Event() for _ in self.level_streams]
-        # Proposal levels may run their backward chains on separate streams only when they share nothing: a shared
-        # network (use_same_proposal_network) means one gradient buffer, and equal (grid, sample count) means one
-        # scatter workspace — concurrent launches would race on either.
-        keys = [(id(self.props[lvl]), self.props[lvl].encoding.spec, n * self.counts[lvl]) for lvl in range(self.n_prop)]
-        self.levels_independent = (len({k[0] for k in keys}) == self.n_prop and
-                                   len({(k[1], k[2]) for k in keys}) == self.n_prop)
-        # Every level's chain on the ONE side stream by default (round 6, profiles/r06_s19_*: three alternating repeats, window
+        # Every level's chain on this ONE side stream (round 6, profiles/r06_s19_*: three alternating repeats, window
         # 0.6265 / 0.6304 / 0.6275 against 0.6494 / 0.6512 / 0.6278 ms with a stream per level, long run 0.689 against 0.695; the
-        # chains in line on the main stream 0.674 / 0.736 — same bits in all three). NSAMD_LEVEL_STREAMS=1: a stream per level.
-        if os.environ.get("NSAMD_LEVEL_STREAMS", "0") != "1":
-            self.levels_independent = False
+        # chains in line on the main stream 0.674 / 0.736 — same bits in all three).
+        self.side_stream = torch.cuda.Stream(device=device)
+        self._fork, self._join = torch.cuda.Event(), torch.cuda.Event()
+        # camera optimiser: the rays' gradient through the main grid on its own stream, beside the table scatter's apply pass
+        # (see backward_field_and_table)
+        self.reduce_stream = torch.cuda.Stream(device=device)
+        self._red_fork, self._red_join = torch.cuda.Event(), torch.cuda.Event()
         # ---- camera optimiser (nerfstudio's nerfacto default is SO3xR3, the benchmark recipe is "off") ----
         # Host-side torch computes the corrected rays from `pose_adjustment` (a [num_cameras, 6] parameter); the kernels
         # return dL/d(origins, directions) per ray (nsamd_hashgrid_encode_bwd_rays, one buffer per sampling level so that
@@ -212,10 +194,6 @@ class NerfactoTrainStep:
         self.cameras_outside = False
         self.grad_lookup = None  # {id(parameter): gradient buffer} of an arena that does not bind `param.grad`
         self.main_table_write_only = True  # the main table's gradient is written, not accumulated (written_params)
-        # True: backward_field_and_table leaves the table scatter to the caller (`backward_table`): bench.py's deferred
-        # schedule runs it beside the NEXT iteration's proposal forward, from the copies `shadow_points` took
-        self.defer_table = False
-        self.sh_origins = self.sh_directions = self.sh_t_bins = None
         self.spacing = int(getattr(model.proposal_sampler.initial_sampler, "spacing", 0))
         # host-evaluated tables (bit-identical to the reference's CPU linspace)
         self.edges = F._linspace("edges", self.counts[0], device)
@@ -291,14 +269,9 @@ class NerfactoTrainStep:
         self.backward_all(updated)
 
     def proposal_branches(self):
-        """[(stream, join event, proposal levels)]: how the proposal backward splits over streams. Levels that share a
-        network or a scatter workspace stay on one stream; [] without a side stream."""
-        if self.side_stream is None:
-            return []
-        if not self.levels_independent:
-            return [(self.side_stream, self._join, None)]
-        return [(self.side_stream, self._join, [0])] + [(ls, ev, [i + 1]) for i, (ls, ev) in
-                                                         enumerate(zip(self.level_streams, self._level_join))]
+        """[(stream, join event, proposal levels)]: how the proposal backward splits over streams — every level on the one
+        side stream, or [] without a side stream."""
+        return [] if self.side_stream is None else [(self.side_stream, self._join, None)]
 
     def backward_all(self, updated: bool) -> None:
         """Everything after the losses: the main backward chain, the proposal chains on the steps that update them
@@ -312,34 +285,20 @@ class NerfactoTrainStep:
         on the current stream. A data-parallel caller starts the main-field gradient exchange between this and
         backward_join — the proposal chains then run beside the main chain AND beside the collective."""
         branches = self.proposal_branches() if updated else []
-        if updated and os.environ.get("NSAMD_DIAG_SKIP_PROP_BWD") == "1":
-            # timing diagnostic only (wrong training): update iterations without the proposal networks' backward chains — what
-            # an update iteration would cost if those chains hid completely behind the main backward
-            self._open_branches = []
-            self.backward_main()
-            return
         self._open_branches = branches
         if branches:
             # The backward chains are independent (disjoint gradients, separate scratch): fork the proposal chains onto
             # their own streams so that these latency-bound kernels overlap with the main chain.
             main = N.current_stream()
-            side_stage = "all"
-            if self.prop_mlp_inline:
-                # NSAMD_PROP_MLP_INLINE=1 (experiment): the levels' weights + density-MLP backward run IN LINE ahead of the main
-                # backward — beside it their 44-KiB workgroups delay the persistent main-backward workgroups at its start, and
-                # what follows them starves until it ends — and only the table scatters are forked
-                self.backward_proposals(stage="mlp")
-                side_stage = "scatter"
             self._fork.record(main)
             for stream, join, levels in branches:
                 stream.wait_event(self._fork)
                 with N.on_stream(stream):
-                    self.backward_proposals(levels=levels, stage=side_stage)
+                    self.backward_proposals(levels=levels)
                     join.record(stream)
-            self.backward_main(reserve=True)
+            self.backward_main()
         else:
-            # (the reservation follows the KIND of iteration, not the streams: every schedule sums the same partials)
-            self.backward_main(reserve=updated)
+            self.backward_main()
             if updated:
                 self.backward_proposals()
 
@@ -356,7 +315,7 @@ class NerfactoTrainStep:
         parallelism the all-reduce of the main-field gradients can start right after this while `backward_proposals`
         (interlevel-loss gradients of the proposal networks) still runs."""
         self.forward_and_losses(updated, draw_jitter)
-        self.backward_main(reserve=updated)
+        self.backward_main()
 
     def written_params(self):
         """Parameters whose gradient this runner WRITES (hash tables, nsamd_hashgrid_encode_bwd_set): callers need not
@@ -489,7 +448,7 @@ class NerfactoTrainStep:
             ck(lib.nsamd_piecewise_bins(N.ptr(self.nears), N.ptr(self.fars), N.ptr(self.edges), N.ptr(jit0), int(per_edge), n,
                                         S0, self.spacing, N.ptr(self.s_bins[0]), N.ptr(self.t_bins[0]), st), "piecewise_bins")
         hook, self.after_bins = getattr(self, "after_bins", None), None
-        if hook is not None:  # (trainer.HipTrainer: the point where the pending main-field Adam is forked off, NSAMD_FORK_AFTER_BINS)
+        if hook is not None:  # (trainer.HipTrainer: the ray terms, behind the batch selection)
             hook()
         # ---- proposal levels ----
         for lvl in range(self.n_prop):
@@ -611,18 +570,9 @@ class NerfactoTrainStep:
             self._loss_vals_fresh = True
 
     @profiler.time_function
-    def backward_main(self, field: bool = True, reserve: bool = False) -> None:
+    def backward_main(self, field: bool = True) -> None:
         """composite -> weights -> field MLPs -> main hash table (MSE + distortion gradients). `field=False`: stop before
-        the field's MLPs (the caller runs `backward_field_and_table`). `reserve`: an iteration that also runs the proposal
-        levels' backward chains — the persistent field backward leaves `bwd_reserve_cus` compute units to them."""
-        if reserve and field and self.bwd_reserve_cus != 0:
-            lib = N.load()
-            prev = lib.nsamd_field_mlp_bwd_reserve_cus(self.bwd_reserve_cus)
-            try:
-                self.backward_main(field=True)
-            finally:
-                lib.nsamd_field_mlp_bwd_reserve_cus(prev)
-            return
+        the field's MLPs (the caller runs `backward_field_and_table`)."""
         lib, st, n = N.load(), N.stream(), self.n
         ck = N.check
         L = self.n_prop
@@ -654,9 +604,7 @@ class NerfactoTrainStep:
         if self.ray_terms_on:  # (what forward_main computed for this batch and these parameters)
             fm.ray_terms, fm.ray_inputs = N.ptr(self.ray_terms), N.ptr(self.ray_inputs)
         grads = N.FieldMlpGrads(*(N.ptr(self._grad(p)) for p in params), N.ptr(self._grad(emb)) if emb is not None else None)
-        split = self.split_reduce and self.side_stream is not None
-        if (self.fuse_route and self.main_table_write_only and not self.defer_table
-                and enc.spec.num_levels == 16):
+        if self.fuse_route and self.main_table_write_only and enc.spec.num_levels == 16:
             sws, sws_n = F._producer_scatter_workspace(enc.spec, self.f_enc.device, mm)
             if sws is not None:
                 want_denc = self.cam_opt is not None or self.keep_denc  # the camera optimiser's share needs the feature gradient as well
@@ -667,27 +615,10 @@ class NerfactoTrainStep:
                 if N.PROFILE is not None:  # the per-kernel table (utils/roofline.py): one launch group at a time, same bits
                     for phase in (1, 2, 4):
                         ck(lib.nsamd_field_mlp_bwd_scatter_phase(*args, phase, st), "field_mlp_bwd_scatter_phase")
-                elif split:
-                    # the weight-gradient reduce (12.8 MB of partial rows, latency-bound) needs nothing the apply pass produces
-                    # and vice versa: the reduce on its own stream BESIDE the apply pass (NSAMD_SPLIT_REDUCE=1; same bits)
-                    ck(lib.nsamd_field_mlp_bwd_scatter_phase(*args, 1, st), "field_mlp_bwd_scatter_phase")
-                    main = N.current_stream()
-                    self._red_fork.record(main)
-                    self.reduce_stream.wait_event(self._red_fork)
-                    with N.on_stream(self.reduce_stream):
-                        ck(lib.nsamd_field_mlp_bwd_scatter_phase(*args, 2, N.stream()), "field_mlp_bwd_scatter_phase")
-                        self._red_join.record(self.reduce_stream)
-                    ck(lib.nsamd_field_mlp_bwd_scatter_phase(*args, 4, st), "field_mlp_bwd_scatter_phase")
-                    main.wait_event(self._red_join)
-                elif os.environ.get("NSAMD_DIAG_SKIP_DW_REDUCE") == "1":
-                    # timing diagnostic only (wrong training): no weight-gradient reduce at all — what the iteration would cost
-                    # if the reduce were free
-                    for phase in (1, 4):
-                        ck(lib.nsamd_field_mlp_bwd_scatter_phase(*args, phase, st), "field_mlp_bwd_scatter_phase")
-                elif self.cam_opt is not None and self.rays_beside_apply:
+                elif self.cam_opt is not None:
                     # camera optimiser: the rays' gradient through the main grid (a gather pass over the table, 96 us) needs the
                     # encoded-feature gradient the kernel has just written and nothing of the table scatter's apply pass (LDS
-                    # atomics, latency-bound): beside it on the second stream instead of behind it (NSAMD_RAYS_BESIDE_APPLY=0: A/B)
+                    # atomics, latency-bound): beside it on the second stream instead of behind it
                     ck(lib.nsamd_field_mlp_bwd_scatter_phase(*args, 1, st), "field_mlp_bwd_scatter_phase")
                     main = N.current_stream()
                     self._red_fork.record(main)
@@ -703,40 +634,22 @@ class NerfactoTrainStep:
                 if self.cam_opt is not None:
                     self._rays_backward(L, fld, self.f_denc)
                 return
-        if split:
-            # The sum of the per-workgroup weight-gradient partials needs nothing the table scatter produces and vice
-            # versa: the gradient kernel here, the reduce on its own stream beside the scatter (joined at the end).
-            args = (N.ptr(self.f_enc), N.ptr(self.f_sel), N.ptr(self.directions), cams, None, S, mm, fm,
-                    N.ptr(self.d_dens_main), N.ptr(self.d_rgb_s), N.ptr(self.f_denc), grads, N.ptr(self.field_ws),
-                    self.field_ws.numel())
-            ck(lib.nsamd_field_mlp_bwd_phase(*args, 1, st), "field_mlp_bwd_phase")
-            main = N.current_stream()
-            self._red_fork.record(main)
-            self.reduce_stream.wait_event(self._red_fork)
-            with N.on_stream(self.reduce_stream):
-                ck(lib.nsamd_field_mlp_bwd_phase(*args, 2, N.stream()), "field_mlp_bwd_phase")
-                self._red_join.record(self.reduce_stream)
-        else:
-            ck(lib.nsamd_field_mlp_bwd(N.ptr(self.f_enc), N.ptr(self.f_sel), N.ptr(self.directions), cams, None, S, mm, fm,
-                                       N.ptr(self.d_dens_main), N.ptr(self.d_rgb_s), N.ptr(self.f_denc), grads,
-                                       N.ptr(self.field_ws), self.field_ws.numel(), st), "field_mlp_bwd")
+        ck(lib.nsamd_field_mlp_bwd(N.ptr(self.f_enc), N.ptr(self.f_sel), N.ptr(self.directions), cams, None, S, mm, fm,
+                                   N.ptr(self.d_dens_main), N.ptr(self.d_rgb_s), N.ptr(self.f_denc), grads,
+                                   N.ptr(self.field_ws), self.field_ws.numel(), st), "field_mlp_bwd")
         if self.cam_opt is not None:
             self._rays_backward(L, fld, self.f_denc)
-        if not self.defer_table:
-            self.backward_table()
-        if split:
-            N.current_stream().wait_event(self._red_join)
+        self.backward_table()
 
-    def backward_table(self, shadow: bool = False) -> None:
-        """The main table's gradient scatter from `f_denc`. `shadow`: the sample points come from the copies `shadow_points`
-        took (a caller that runs this scatter AFTER the next batch has been selected: bench.py's deferred schedule)."""
+    def backward_table(self) -> None:
+        """The main table's gradient scatter from `f_denc`."""
         lib, st = N.load(), N.stream()
         ck = N.check
         fld = self.model.field
         L = self.n_prop
         mm = self.m_main
         enc = fld.mlp_base.encoding
-        pts = N.make_points(None, self.sh_origins, self.sh_directions, self.sh_t_bins, self.counts[L]) if shadow else self._points(L)
+        pts = self._points(L)
         if self.main_table_write_only:
             ws, ws_n = F._scatter_workspace(enc.spec, self.f_enc.device, mm, write_only=True)
             ck(lib.nsamd_hashgrid_encode_bwd_set(pts, mm, fld._transform, fld._box, N.ptr(enc.hash_table),
@@ -750,80 +663,62 @@ class NerfactoTrainStep:
                                              N.ptr(self._grad(enc.hash_table)), None, N.ptr(ws), ws_n, st),
                "hashgrid_encode_bwd")
 
-    def shadow_points(self) -> None:
-        """Copies of what defines the final samples (ray origins, directions, bin edges: 0.9 MB) for a table scatter that
-        runs after the next batch has overwritten them (`backward_table(shadow=True)`)."""
-        L = self.n_prop
-        if self.sh_origins is None:
-            self.sh_origins, self.sh_directions = torch.empty_like(self.origins), torch.empty_like(self.directions)
-            self.sh_t_bins = torch.empty_like(self.t_bins[L])
-        self.sh_origins.copy_(self.origins)
-        self.sh_directions.copy_(self.directions)
-        self.sh_t_bins.copy_(self.t_bins[L])
-
     @profiler.time_function
-    def backward_proposals(self, levels=None, stage: str = "all") -> None:
+    def backward_proposals(self, levels=None) -> None:
         """Backward of the proposal networks (interlevel loss only; main-level weights are detached, losses.py:119-120).
         Needs the dw_prop written by forward_backward_main(updated=True). `levels`: subset of proposal levels (their
-        chains share nothing, so they may run on different streams). `stage`: "mlp" = weights backward + density-MLP backward
-        (its weight-gradient reduce included), "scatter" = ray gradients + table scatter, "all" = both in order."""
+        chains share nothing, so they may run on different streams)."""
         lib, st, n = N.load(), N.stream(), self.n
         ck = N.check
-        do_mlp, do_scatter = stage in ("all", "mlp"), stage in ("all", "scatter")
         lvls = list(range(self.n_prop) if levels is None else levels)
-        if (self.merge_prop_levels and stage == "all" and len(lvls) >= 2 and self.gate_proposals and self.cam_opt is None
+        if (self.merge_prop_levels and len(lvls) >= 2 and self.gate_proposals and self.cam_opt is None
                 and N.PROFILE is None):
             # every stage of the levels' chains as ONE launch across the levels (nsamd_proposal_levels_bwd; same bits)
             arr = self._proposal_level_structs(lvls)
             if arr is not None:
                 ck(lib.nsamd_proposal_levels_bwd(arr, len(lvls), int(self.gates_precleared), st), "proposal_levels_bwd")
                 return
-        for _ in (0,):
-            for lvl in lvls:
-                net = self.props[lvl]
-                S, m = self.counts[lvl], n * self.counts[lvl]
-                mlp = net.mlp_base[1]
-                W0, b0, W1, b1 = mlp.param_tensors()
-                dm = N.DensityMlp(N.ptr(W0), N.ptr(b0), N.ptr(W1), N.ptr(b1), W0.shape[1], W0.shape[0],
-                                  float(net.average_init_density))
-                gate = self._gate(lvl)
-                dws = self.density_ws[lvl]
-                spec = net.encoding.spec
-                ws, ws_n = F._scatter_workspace(spec, self.f_enc.device, m)
-                grads = (N.ptr(self._grad(W0)), N.ptr(self._grad(b0)), N.ptr(self._grad(W1)), N.ptr(self._grad(b1)))
-                if gate is None or ws is None:  # ungated chain (A/B switch, or no binned-scatter workspace for this shape)
-                    if do_mlp:
-                        ck(lib.nsamd_weights_bwd(N.ptr(self.t_bins[lvl]), N.ptr(self.p_dens[lvl]), N.ptr(self.dw_prop[lvl]),
-                                                 n, S, N.ptr(self.p_ddens[lvl]), st), "weights_bwd")
-                        ck(lib.nsamd_density_mlp_bwd(N.ptr(self.p_enc[lvl]), N.ptr(self.p_sel[lvl]), N.ptr(self.p_pre[lvl]),
-                                                     N.ptr(self.p_ddens[lvl]), m, dm, N.ptr(self.p_denc[lvl]), *grads,
-                                                     N.ptr(dws), dws.numel(), st), "density_mlp_bwd")
-                    if do_scatter:
-                        if self.cam_opt is not None:
-                            self._rays_backward(lvl, net, self.p_denc[lvl])
-                        ck(lib.nsamd_hashgrid_encode_bwd(self._points(lvl), m, net._transform, net._box,
-                                                         N.ptr(net.encoding.hash_table), spec.native(), N.ptr(self.p_denc[lvl]),
-                                                         1, m, N.ptr(self._grad(net.encoding.hash_table)), None, N.ptr(ws), ws_n,
-                                                         st), "hashgrid_encode_bwd")
-                    continue
-                # the weights backward raises the level's flag when any ray carries interlevel gradient; the rest of the
-                # chain returns at once while it is clear (the zero-filled gradients are then already the result)
-                mask = N.ptr(self.prop_ray_masks[lvl])
-                if do_mlp:
-                    ck(lib.nsamd_weights_bwd_gate(N.ptr(self.t_bins[lvl]), N.ptr(self.p_dens[lvl]), N.ptr(self.dw_prop[lvl]),
-                                                  n, S, N.ptr(self.p_ddens[lvl]), gate, mask, int(self.gates_precleared), st),
-                       "weights_bwd_gate")
-                    ck(lib.nsamd_density_mlp_bwd_gated(N.ptr(self.p_enc[lvl]), N.ptr(self.p_sel[lvl]), N.ptr(self.p_pre[lvl]),
-                                                       N.ptr(self.p_ddens[lvl]), m, dm, N.ptr(self.p_denc[lvl]), *grads,
-                                                       N.ptr(dws), dws.numel(), gate, mask, S, st), "density_mlp_bwd_gated")
-                if do_scatter:
-                    if self.cam_opt is not None:
-                        self._rays_backward(lvl, net, self.p_denc[lvl], gate, mask)
-                    ck(lib.nsamd_hashgrid_encode_bwd_gated(self._points(lvl), m, net._transform, net._box,
-                                                           N.ptr(net.encoding.hash_table), spec.native(),
-                                                           N.ptr(self.p_denc[lvl]), 1, m,
-                                                           N.ptr(self._grad(net.encoding.hash_table)), N.ptr(ws), ws_n, gate,
-                                                           mask, st), "hashgrid_encode_bwd_gated")
+        for lvl in lvls:
+            net = self.props[lvl]
+            S, m = self.counts[lvl], n * self.counts[lvl]
+            mlp = net.mlp_base[1]
+            W0, b0, W1, b1 = mlp.param_tensors()
+            dm = N.DensityMlp(N.ptr(W0), N.ptr(b0), N.ptr(W1), N.ptr(b1), W0.shape[1], W0.shape[0],
+                              float(net.average_init_density))
+            gate = self._gate(lvl)
+            dws = self.density_ws[lvl]
+            spec = net.encoding.spec
+            ws, ws_n = F._scatter_workspace(spec, self.f_enc.device, m)
+            grads = (N.ptr(self._grad(W0)), N.ptr(self._grad(b0)), N.ptr(self._grad(W1)), N.ptr(self._grad(b1)))
+            if gate is None or ws is None:  # ungated chain (A/B switch, or no binned-scatter workspace for this shape)
+                ck(lib.nsamd_weights_bwd(N.ptr(self.t_bins[lvl]), N.ptr(self.p_dens[lvl]), N.ptr(self.dw_prop[lvl]),
+                                         n, S, N.ptr(self.p_ddens[lvl]), st), "weights_bwd")
+                ck(lib.nsamd_density_mlp_bwd(N.ptr(self.p_enc[lvl]), N.ptr(self.p_sel[lvl]), N.ptr(self.p_pre[lvl]),
+                                             N.ptr(self.p_ddens[lvl]), m, dm, N.ptr(self.p_denc[lvl]), *grads,
+                                             N.ptr(dws), dws.numel(), st), "density_mlp_bwd")
+                if self.cam_opt is not None:
+                    self._rays_backward(lvl, net, self.p_denc[lvl])
+                ck(lib.nsamd_hashgrid_encode_bwd(self._points(lvl), m, net._transform, net._box,
+                                                 N.ptr(net.encoding.hash_table), spec.native(), N.ptr(self.p_denc[lvl]),
+                                                 1, m, N.ptr(self._grad(net.encoding.hash_table)), None, N.ptr(ws), ws_n,
+                                                 st), "hashgrid_encode_bwd")
+                continue
+            # the weights backward raises the level's flag when any ray carries interlevel gradient; the rest of the
+            # chain returns at once while it is clear (the zero-filled gradients are then already the result)
+            mask = N.ptr(self.prop_ray_masks[lvl])
+            ck(lib.nsamd_weights_bwd_gate(N.ptr(self.t_bins[lvl]), N.ptr(self.p_dens[lvl]), N.ptr(self.dw_prop[lvl]),
+                                          n, S, N.ptr(self.p_ddens[lvl]), gate, mask, int(self.gates_precleared), st),
+               "weights_bwd_gate")
+            ck(lib.nsamd_density_mlp_bwd_gated(N.ptr(self.p_enc[lvl]), N.ptr(self.p_sel[lvl]), N.ptr(self.p_pre[lvl]),
+                                               N.ptr(self.p_ddens[lvl]), m, dm, N.ptr(self.p_denc[lvl]), *grads,
+                                               N.ptr(dws), dws.numel(), gate, mask, S, st), "density_mlp_bwd_gated")
+            if self.cam_opt is not None:
+                self._rays_backward(lvl, net, self.p_denc[lvl], gate, mask)
+            ck(lib.nsamd_hashgrid_encode_bwd_gated(self._points(lvl), m, net._transform, net._box,
+                                                   N.ptr(net.encoding.hash_table), spec.native(),
+                                                   N.ptr(self.p_denc[lvl]), 1, m,
+                                                   N.ptr(self._grad(net.encoding.hash_table)), N.ptr(ws), ws_n, gate,
+                                                   mask, st), "hashgrid_encode_bwd_gated")
 
     def _proposal_level_structs(self, lvls):
         """ctypes array of nsamd_proposal_level_bwd for `lvls` (None: a level without a binned-scatter workspace). The structs

@@ -130,7 +130,7 @@ class HipTrainer:
         self.use_graph = use_graph and self.on_gpu
         self.runner = runner
         self.defer = False
-        self.defer_scatter = False
+        self.defer_scatter = False  # read by bench.py: the main table scatter is never deferred to the next iteration
         self.opt_parallel = True  # False: the deferred Adam runs on the main stream (per-kernel timing)
         # False: the jitter buffer of the runner is filled by the caller before every iteration (parity tests inject the
         # draws the CPU oracle uses; the default draws them on the device inside the iteration, graph-safe Philox)
@@ -161,16 +161,10 @@ class HipTrainer:
             # from hipGraphs, neutral with eager launches — so it is the default with graphs. NSAMD_DEFER_MAIN_ADAM=0/1: A/B.
             self.defer = (not self.dp and self.on_gpu and
                           os.environ.get("NSAMD_DEFER_MAIN_ADAM", "1" if self.use_graph else "0") == "1")
-            # NSAMD_DEFER_SCATTER=1 (opt-in, measured and NOT adopted: profiles/r03_negative_results.txt item 8) defers the
-            # main TABLE SCATTER of iteration k as well, beside [select batch, proposal forward k+1]; same bits, 1-2 % slower.
-            self.defer_scatter = self.defer and os.environ.get("NSAMD_DEFER_SCATTER", "0") == "1"
-            self.fork_after_bins = os.environ.get("NSAMD_FORK_AFTER_BINS", "0") == "1"
             if self.defer:
                 self.opt_stream = torch.cuda.Stream(device=dev)
                 self._opt_fork, self._opt_join = torch.cuda.Event(), torch.cuda.Event()
-                self._sh_fork, self._sh_join = torch.cuda.Event(), torch.cuda.Event()
                 self._batch_ready = torch.cuda.Event()
-            self.terms_on_branch = os.environ.get("NSAMD_TERMS_ON_BRANCH", "1") == "1"  # (=0: in line, A/B)
             mode = os.environ.get("NSAMD_STEP_PROLOGUE", "ring")
             mode = "ring" if mode == "1" else mode
             if (mode in ("ring", "table") and self.on_gpu and runner is None
@@ -217,12 +211,8 @@ class HipTrainer:
             if self.dp:
                 from .dp_schedule import PipelinedExchange
 
-                # the pending main-field Adam waits for its exchange on its own stream, beside the next proposal forward
-                # (NSAMD_DP_UPDATE_STREAM=1; measured on a one-rank communicator, profiles/r03_dp_rehearsal.txt: 0.992 vs
-                # 0.969 ms — off by default)
-                upd = torch.cuda.Stream(device=dev) if (self.on_gpu and os.environ.get("NSAMD_DP_UPDATE_STREAM", "0") == "1") else None
                 self.exchange = PipelinedExchange(arena, self._run, before_main_update=self._push_hyper,
-                                                  sharded=self.dp_sharded, update_stream=upd)
+                                                  sharded=self.dp_sharded)
                 # eager segments only (a captured segment must end with its streams joined); NSAMD_DP_FORK=0: round-2 order
                 self.dp_fork = os.environ.get("NSAMD_DP_FORK", "1") == "1" and getattr(r, "side_stream", None) is not None
                 # the coarse levels of the main table can only ever touch 288 k of their 2.6 M rows: exchange those
@@ -445,9 +435,7 @@ class HipTrainer:
         self._step_prologue()  # the step's scalars and draws: first node, every branch below depends on it
         draw = self.draw_jitter and not self.prologue
 
-        def pending_update():  # what iteration k-1 left behind: [its table scatter ->] its main-field Adam
-            if self.defer_scatter:
-                r.backward_table(shadow=True)
+        def pending_update():  # what iteration k-1 left behind: its main-field Adam
             a.step(grad_scale=1.0, groups=["fields"], hyper_dev=self.hyper_views)
             if beside:
                 # ... and, off the critical path, this iteration's zero-fills: the Adam above was the last reader of the
@@ -458,7 +446,7 @@ class HipTrainer:
         # The ray terms of this iteration's main-field forward (train_step.ray_terms_launch) need the updated head weights and
         # the selected batch, nothing else: they go on the Adam branch, behind an event the main branch records once the batch
         # is in place — off the critical path instead of a launch (and a dependent-launch gap) in front of the hash forward.
-        terms_beside = beside and getattr(r, "ray_terms_on", False) and self.terms_on_branch
+        terms_beside = beside and getattr(r, "ray_terms_on", False)
 
         def fork():
             self._opt_fork.record(main)
@@ -475,44 +463,22 @@ class HipTrainer:
                 r.ray_terms_launch()
                 self._opt_join.record(self.opt_stream)
 
-        # NSAMD_FORK_AFTER_BINS=1: the branch starts BEHIND the launch that selects the batch and writes the initial bins (8 MB of
-        # stores that read 45 us beside the HBM-saturating Adam and 14 us alone) instead of in front of it
-        late_fork = beside and self.fork_after_bins and not r.cameras_outside and getattr(r, "fuse_select", False) \
-            and getattr(r, "cam_opt", None) is None
-        terms_beside = terms_beside and not late_fork
-        if beside and not late_fork:
+        if beside:
             fork()
-        elif pending and not beside:
+        elif pending:
             pending_update()
         if not r.cameras_outside:
             self._select_batch()
             r.apply_camera_corrections()
-        if late_fork:
-            r.after_bins = fork
-        elif terms_beside:
+        if terms_beside:
             r.after_bins = terms_behind_batch
         r.forward_proposals(draw, need_enc=updated)
         if beside:
             main.wait_event(self._opt_join)
-        if self.defer_scatter:  # the final samples are known: copy what defines them, beside the main forward
-            if self.opt_parallel:
-                self._sh_fork.record(main)
-                self.opt_stream.wait_event(self._sh_fork)
-                with N.on_stream(self.opt_stream):
-                    r.shadow_points()
-                    self._sh_join.record(self.opt_stream)
-            else:
-                r.shadow_points()
         if not beside:
             self._zero(updated)
         r.forward_main_and_losses(updated)
-        r.defer_table = self.defer_scatter
-        try:
-            r.backward_all(updated)
-        finally:
-            r.defer_table = False
-        if self.defer_scatter and self.opt_parallel:
-            main.wait_event(self._sh_join)
+        r.backward_all(updated)
         late = (["proposal_networks"] if updated else []) + ([self.cam_group] if self.cam_inside else [])
         if late:
             a.step(grad_scale=1.0, groups=late, hyper_dev=self.hyper_views)
@@ -595,7 +561,7 @@ class HipTrainer:
                 if name[1]:
                     self._clear_gates()
                 r.forward_main_and_losses(name[1])
-                r.backward_main(reserve=name[1])
+                r.backward_main()
         elif name == "pbwd":
             if self.dp_fork:
                 r.backward_join(True)
@@ -637,10 +603,8 @@ class HipTrainer:
         region, evaluation, checkpointing)."""
         if self.exchange is not None:
             self.exchange.finish()
-        if self._pending_main:  # deferred schedule: the last iteration's [table scatter and] main-field update
+        if self._pending_main:  # deferred schedule: the last iteration's main-field update
             self._push_hyper(direct=True)  # (the table's rows stay valid: see `_push_hyper`)
-            if self.defer_scatter:
-                self.runner.backward_table(shadow=True)
             self.arena.step(grad_scale=1.0, groups=["fields"], hyper_dev=self.hyper_views)
             self._pending_main = False
             self._true_steps = dict(self.arena.step_counts)

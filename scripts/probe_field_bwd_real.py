@@ -1,9 +1,8 @@
 #!/usr/bin/env python3
 """Time the main field's backward launch (phase 1 of nsamd_field_mlp_bwd_scatter_phase: gradients + the scatter's records) ALONE
 on the buffers of a real training iteration at the benchmark's size — the bench's model and rays, one forward + losses, then the
-launch repeated with HIP events around each repetition. The library comes from NSAMD_LIB, so attribution builds
-(scripts/build_variant.sh x "-DNSAMD_FIELD_BWD_SKIP_CONST=n") can be timed on the same inputs: their results are wrong, their
-time is what the product kernel costs without the part they leave out. GPU box only:
+launch repeated with HIP events around each repetition. The library comes from NSAMD_LIB, so variant builds
+(scripts/build_variant.sh) can be timed on the same inputs. GPU box only:
     [NSAMD_LIB=...] python scripts/probe_field_bwd_real.py [reps]"""
 import os
 import sys

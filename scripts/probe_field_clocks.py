@@ -124,10 +124,9 @@ def report(name, t, labels):
 
 
 print(f"fwd {timed(fwd):.1f} us   bwd {timed(bwd):.1f} us   (no clock buffer set)")
-W = int(os.environ.get("NSAMD_FIELD_FWD_WAVES", "16"))
-f = stamps(fwd, {4: 768 * 4, 8: 512 * 8, 16: 256 * 16}[W])
+f = stamps(fwd, 256 * 16)
 labels = [(1, "stage weights + barrier")]
-for it in range(4 if W == 4 else 3):
+for it in range(3):
     labels += [(2 + 4 * it, f"tile {it}: inputs issued"), (3 + 4 * it, f"tile {it}: base layers"),
                (4 + 4 * it, f"tile {it}: SH + head layers"), (5 + 4 * it, f"tile {it}: outputs stored")]
 labels += [(63, "end")]

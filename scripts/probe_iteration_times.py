@@ -2,7 +2,7 @@
 """GPU box: wall time per training iteration INSIDE the real loop of bench.py (alternating update / non-update iterations
 from step 10 on), split by kind: HIP events on the launch stream around every Trainer.train_iteration(), median per kind, and
 the host-clock average over the whole loop. PROBE_EAGER=1: eager launches instead of hipGraph replay.
-Environment: NSAMD_DEFER_MAIN_ADAM, NSAMD_SPLIT_REDUCE, NSAMD_SIDE_STREAM."""
+Environment: NSAMD_DEFER_MAIN_ADAM, NSAMD_SIDE_STREAM."""
 import os
 import sys
 import time
@@ -44,7 +44,7 @@ for _ in range(n):
 tr.finish()
 torch.cuda.synchronize()
 wall = (time.perf_counter() - t0) / n * 1e6
-tag = (f"{'eager' if eager else 'graph'} defer={int(tr.defer)} split={int(tr.runner.split_reduce)} "
+tag = (f"{'eager' if eager else 'graph'} defer={int(tr.defer)} "
        f"side={int(tr.runner.side_stream is not None)}")
 out = [f"{tag}: loop {wall:7.1f} us/iteration, loss {float(tr.last_loss()):.6f}"]
 for kind in (False, True):

@@ -1,8 +1,7 @@
 #!/usr/bin/env python3
 """GPU box: the main-table gradient scatter (nsamd_hashgrid_encode_bwd_set, L=16, T=2^19, M=196608) in isolation, on the
 gradients of a real training state: 20 eager training steps of the bench workload, then the scatter call alone, timed with
-HIP events (median of 50). Environment switches (NSAMD_SCATTER_SHAPE, NSAMD_SCATTER_COMBINE_RES, ...) are read once per
-process by the library, so run one process per variant."""
+HIP events (median of 50). Compare library builds through NSAMD_LIB (scripts/build_variant.sh), one process per build."""
 import os
 import sys
 

@@ -412,3 +412,24 @@ def test_pinhole_camera_args_picks_only_cameras_the_grid_generator_covers():
     assert pinhole_camera_args(cam(camera_to_worlds=torch.eye(4)[None, :3].repeat(2, 1, 1))) is None  # two cameras
     assert pinhole_camera_args(cam(fx=torch.tensor([[100.0], [101.0]]))) is None
     assert pinhole_camera_args(types.SimpleNamespace(camera_to_worlds=torch.eye(4)[None, :3])) is None  # no intrinsics
+
+
+def test_environment_switches_match_the_design_table():
+    """The kernel library reads no environment, and DESIGN §9 lists exactly the NSAMD_* switches the package reads (the
+    build-time row aside): a switch that is added or removed without its row fails here."""
+    import glob
+    import os
+    import re
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    pkg = os.path.join(root, "nerfstudio_amd")
+    native = glob.glob(os.path.join(pkg, "csrc", "*.hip")) + glob.glob(os.path.join(pkg, "csrc", "*.h"))
+    assert native and not [p for p in native if "getenv" in open(p).read()]
+    read = set()
+    for p in glob.glob(os.path.join(pkg, "**", "*.py"), recursive=True):
+        read |= set(re.findall(r'os\.environ(?:\.get|\.setdefault)?[\[(]\s*"(NSAMD_\w+)"', open(p).read()))
+    design = open(os.path.join(root, "DESIGN.md")).read()
+    section = design.split("\n## 9.", 1)[1].split("\n## ", 1)[0]
+    rows = [ln for ln in section.splitlines() if ln.startswith("| `NSAMD_")]
+    listed = set(re.findall(r"`(NSAMD_\w+)`", "\n".join(rows)))
+    assert read == listed, (sorted(read - listed), sorted(listed - read))
