@@ -116,7 +116,6 @@ class NerfactoTrainStep:
         # direction, appearance row) once per ray instead of once per sample. NSAMD_RAY_TERMS=0: the plain kernels (A/B).
         self.ray_terms_on = os.environ.get("NSAMD_RAY_TERMS", "1") == "1" and self.counts[-1] % 16 == 0
         self.ray_terms = e(n, 64) if self.ray_terms_on else None
-        self._ray_terms_ready = False
         self.ray_inputs = e(n, 16 + (32 if fld.embedding_appearance is not None else 0)) \
             if (self.ray_terms_on and not forward_only) else None  # (the backward's: weight gradient of the 48 per-ray columns)
         self.f_denc = t(*self.f_enc.shape)
@@ -415,12 +414,13 @@ class NerfactoTrainStep:
         self._corrected = None
 
     @profiler.time_function
-    def forward_proposals(self, draw_jitter: bool = True, need_enc: bool = True) -> None:
+    def forward_proposals(self, draw_jitter: bool = True, need_enc: bool = True, after_bins=None) -> None:
         """Initial bins and the proposal levels (density fields + resampling): reads only the proposal networks'
         parameters, so with data parallelism it can run while the main-field gradients of the previous step are still
         being all-reduced (bench.py). need_enc: keep the levels' encoded features / selector / pre-activation for
         backward_proposals (False on the steps where the proposal networks get no gradient, ray_samplers.py:590: the
-        fused forward then writes nothing but the densities)."""
+        fused forward then writes nothing but the densities). after_bins: called right behind the launch that writes the
+        initial bins (and selects the batch), before the proposal levels."""
         lib, st, n = N.load(), N.stream(), self.n
         ck = N.check
         per_edge = not self.single_jitter
@@ -447,9 +447,8 @@ class NerfactoTrainStep:
         else:
             ck(lib.nsamd_piecewise_bins(N.ptr(self.nears), N.ptr(self.fars), N.ptr(self.edges), N.ptr(jit0), int(per_edge), n,
                                         S0, self.spacing, N.ptr(self.s_bins[0]), N.ptr(self.t_bins[0]), st), "piecewise_bins")
-        hook, self.after_bins = getattr(self, "after_bins", None), None
-        if hook is not None:  # (trainer.HipTrainer: the ray terms, behind the batch selection)
-            hook()
+        if after_bins is not None:  # (trainer.HipTrainer: the ray terms, behind the batch selection)
+            after_bins()
         # ---- proposal levels ----
         for lvl in range(self.n_prop):
             net = self.props[lvl]
@@ -495,9 +494,9 @@ class NerfactoTrainStep:
                                            N.ptr(self.s_bins[lvl + 1]), N.ptr(self.t_bins[lvl + 1]), st),
                "proposal_resample")
 
-    def forward_main_and_losses(self, updated: bool) -> None:
+    def forward_main_and_losses(self, updated: bool, terms_ready: bool = False) -> None:
         """Main field on the final samples, compositing, and the three losses with their gradients."""
-        self.forward_main()
+        self.forward_main(terms_ready)
         self.losses(updated)
 
     def ray_terms_launch(self) -> None:
@@ -513,11 +512,11 @@ class NerfactoTrainStep:
         cams = N.ptr(self.camera_indices) if emb is not None else None
         N.check(lib.nsamd_field_ray_terms(N.ptr(self.directions), cams, None, n, fm, N.ptr(self.ray_terms), N.ptr(self.ray_inputs),
                                           st), "field_ray_terms")
-        self._ray_terms_ready = True
 
     @profiler.time_function
-    def forward_main(self) -> None:
-        """Hash grid + MLPs of the main field on the final samples -> per-sample density and rgb."""
+    def forward_main(self, terms_ready: bool = False) -> None:
+        """Hash grid + MLPs of the main field on the final samples -> per-sample density and rgb. terms_ready: the caller has
+        launched `ray_terms_launch` for this batch and these parameters itself (trainer.HipTrainer: off the critical path)."""
         lib, st, n, cfg = N.load(), N.stream(), self.n, self.cfg
         ck = N.check
         fld = self.model.field
@@ -530,9 +529,8 @@ class NerfactoTrainStep:
                         float(fld.average_init_density))
         cams = N.ptr(self.camera_indices) if emb is not None else None
         if self.ray_terms_on:
-            if not self._ray_terms_ready:  # (a caller may have launched them already, off the critical path: trainer.HipTrainer)
+            if not terms_ready:
                 self.ray_terms_launch()
-            self._ray_terms_ready = False
             fm.ray_terms, fm.ray_inputs = N.ptr(self.ray_terms), N.ptr(self.ray_inputs)
         ck(lib.nsamd_hashgrid_encode_fwd(self._points(L), mm, fld._transform, fld._box, N.ptr(enc.hash_table),
                                          enc.spec.native(), N.ptr(self.f_enc), 1, mm, N.ptr(self.f_sel), st),

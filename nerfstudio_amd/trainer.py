@@ -12,14 +12,17 @@ Reference seam: `Trainer.train_iteration` (engine/trainer.py:487-531) -> `Vanill
 Eager mode runs the Python body every step. Graph mode captures that same body ONCE per schedule variant (proposal networks
 updated this step / not, ray_samplers.py:590) into a hipGraph and replays it: ~60 kernel launches become one graph launch,
 which is what a sub-millisecond step needs (MI355X_MICROARCH.md price list: eager goes host-bound below ~3 us per kernel).
-Everything that changes from step to step lives in device memory: the ray batch, the jitter draws (graph-safe Philox), the
-anneal exponent and Adam's bias-corrected step sizes (`hyper`, refreshed by a 32-byte async copy from a ring of pinned host
-slots before each replay).
+Everything that changes from step to step lives in device memory: the ray batch, the jitter draws (counter-based Philox),
+the anneal exponent and Adam's bias-corrected step sizes (`hyper`). The first node of the body (nsamd_step_prologue) draws
+the step's uniforms and reads the step's scalars out of a ring of rows in pinned host memory that the host writes before
+each launch. Where the body does not select the batch itself (the data-parallel segments, the camera parts outside the
+body) or there is no prologue (the module path), the scalars arrive by a 32-byte async copy instead.
 
-N = 1 with graphs (default): the main-field Adam of iteration k is the first node of iteration k+1's graph, on a branch
-beside select-batch / jitter / the proposal forward (`_deferred_iteration_body`; four captured variants: proposal update x
-pending Adam). Same dependencies as Adam at the end of the iteration, hence the same bits; `finish()` runs the last pending
-update (a caller that reads the parameters — evaluation, checkpoint — calls it first).
+N = 1: one body (`_body`) serves every schedule, eager or captured. With graphs (default) the main-field Adam of iteration k
+runs at the head of iteration k+1's graph, on a branch beside select-batch / jitter / the proposal forward (four captured
+variants: proposal update x pending Adam). Same dependencies as Adam at the end of the iteration, hence the same bits;
+`finish()` runs the last pending update (a caller that reads the parameters — evaluation, checkpoint — calls it first).
+Without graphs the iteration runs in order, Adam at its end.
 
 N > 1 (data parallel): the iteration runs as segments (eager launches by default, captured hipGraphs on request) and the
 main-field gradient exchange (RCCL, its own stream) is PIPELINED across steps (dp_schedule.PipelinedExchange). The proposal
@@ -92,7 +95,6 @@ class HipTrainer:
         self.hyper_ring_np = [h.numpy() for h in self.hyper_ring]
         self.hyper_events = [None] * 64
         self.hyper_slot = 0
-        lr_source_is_default = lr_source is None
         if lr_source is None:
             from .schedulers import ExponentialDecayScheduler, ExponentialDecaySchedulerConfig, nerfacto_schedulers
 
@@ -103,25 +105,18 @@ class HipTrainer:
             lr_source = lambda group, it: sched[group].get_lr(max(it, 0), base[group])  # noqa: E731
         self.lr_source = lr_source
         self.exchange = None  # dp_schedule.PipelinedExchange (N > 1 with the runner)
-        # ---- device-side head of the iteration (nsamd_step_prologue), N = 1 with the runner on the GPU ----
+        # ---- device-side head of the iteration (nsamd_step_prologue), on the GPU with the trainer's own runner ----
         # A replayed graph had two host-issued operations in front of it every iteration — the 32-byte upload of `hyper` and the
         # offset fill of torch's graph-safe generator (for the jitter's uniform_) — and each eager -> graph hand-over leaves the
-        # stream idle for ~8 us (profiles/r05_s9_seam_trace_gaps.txt). With the prologue the first node of the graph fetches the
-        # step's scalars itself and draws the step's uniforms with a counter-based generator. NSAMD_STEP_PROLOGUE selects where
-        # the scalars come from:
-        #   "ring" (default)  a ring of rows in pinned HOST memory the device reads directly: the host writes row i % rows for
-        #                     iteration i (exact host arithmetic, at the time it would have issued the upload) and launches; the
-        #                     device's own row counter picks it up. Nothing is predicted, so it serves a trainer whose learning
-        #                     rates come from outside (pipeline.TrainEngine) as well. An event every 64 rows keeps the host from
-        #                     lapping the device.
-        #   "table"           a table of rows in DEVICE memory the host computes AHEAD by running its own bookkeeping forward
-        #                     (re-uploaded when the rows run out or a row differs from what the host computes for the iteration at
-        #                     hand); needs iterations whose scalars are a function of the step (this trainer's own schedulers).
-        #   "0"               the per-iteration upload and torch's generator (A/B; other draws, same distribution).
+        # stream idle for ~8 us (profiles/r05_s9_seam_trace_gaps.txt). With the prologue the first node of the graph draws the
+        # step's uniforms with a counter-based generator and fetches the step's scalars itself, from a ring of rows in pinned
+        # HOST memory the device reads directly: the host writes row i % rows for iteration i (exact host arithmetic, at the
+        # time it would have issued the upload) and launches; the device's own row counter picks it up. Nothing is predicted, so
+        # it serves a trainer whose learning rates come from outside (pipeline.TrainEngine) as well. An event every 64 rows
+        # keeps the host from lapping the device. (A table of rows predicted ahead in device memory measured the same, the
+        # per-iteration upload 3 % slower: profiles/r05_s11_ab_step_prologue.txt.)
         self.prologue = False          # set below
-        self.prologue_table = False    # the scalars come from the predicted table
-        self.prologue_ring = False     # the scalars come from the ring in host memory
-        self.table_rows = 128
+        self.prologue_ring = False     # the scalars come from the ring in host memory (else: the upload)
         self.ring_rows = 256
         self.hyper_views = {g: self.hyper[o:o + 2] for g, o in _HYPER.items()}
         self.loss_buf = torch.zeros((), device=dev)
@@ -165,10 +160,7 @@ class HipTrainer:
                 self.opt_stream = torch.cuda.Stream(device=dev)
                 self._opt_fork, self._opt_join = torch.cuda.Event(), torch.cuda.Event()
                 self._batch_ready = torch.cuda.Event()
-            mode = os.environ.get("NSAMD_STEP_PROLOGUE", "ring")
-            mode = "ring" if mode == "1" else mode
-            if (mode in ("ring", "table") and self.on_gpu and runner is None
-                    and getattr(r, "single_jitter", False) and hasattr(r, "jitter")):
+            if self.on_gpu and runner is None and getattr(r, "single_jitter", False) and hasattr(r, "jitter"):
                 self.prologue = True
                 self.step_counter = torch.zeros(2, device=dev, dtype=torch.int64)  # [row, draw]
                 # The draws are keyed by (seed, draw counter). The counter starts at the model's training step, so that a trainer
@@ -189,25 +181,12 @@ class HipTrainer:
                 # (the data-parallel segments keep the upload as well — their Adam launches are segments of their own, ordered by
                 #  the exchange — and take the DRAWS from the prologue: one generator for every schedule, so that a one-rank
                 #  data-parallel run trains through the bits of the single-GPU one)
-                inside = not r.cameras_outside and not self.dp
-                if mode == "ring" and inside:
+                if not r.cameras_outside and not self.dp:
                     self.prologue_ring = True
                     self.ring_host = torch.zeros(self.ring_rows, _HYPER_FLOATS).pin_memory()  # (device-visible: hipHostMalloc)
                     self.ring_np = self.ring_host.numpy()
                     self._ring_pos = 0                 # rows written so far == the device's row counter at the next launch
                     self._ring_events = [None] * 4     # recorded every 64 rows
-                elif mode == "table" and inside and bool(drive_callbacks) and lr_source_is_default:
-                    # (this trainer drives the model's callbacks itself and the learning rates are a function of the iteration)
-                    self.prologue_table = True
-                    self.hyper_table = torch.zeros(self.table_rows * _HYPER_FLOATS, device=dev)
-                    self.table_host = torch.zeros(self.table_rows, _HYPER_FLOATS).pin_memory()
-                    self.table_host_np = self.table_host.numpy()
-                    self._table_pos, self._table_valid, self._table_event, self._table_base = 0, False, None, 0
-                    import numpy as np
-
-                    self._row_scratch = np.zeros(_HYPER_FLOATS, dtype=np.float32)
-                    self._row_unread = np.zeros(_HYPER_FLOATS, dtype=bool)  # (entries an iteration without a pending update skips)
-                    self._row_unread[_HYPER["fields"]:_HYPER["fields"] + 2] = True
             if self.dp:
                 from .dp_schedule import PipelinedExchange
 
@@ -236,11 +215,6 @@ class HipTrainer:
             self.rb, self.batch = ray_bundle, batch
 
     # -- pieces of one iteration ---------------------------------------------------------------------------------------
-    def _prologue(self, updated):
-        if self.drive_callbacks:
-            self.model.set_step(self.step)  # BEFORE_TRAIN_ITERATION callback: proposal weight anneal
-        self._push_hyper()
-
     def _hyper_row(self, out, step, counts, have_pending):
         """The step-dependent scalars of iteration `step` into `out` (8 floats, numpy): Adam step sizes of the NEXT update of
         each group (`counts`: the groups' step counters before the iteration) + the anneal exponent + the batch slot."""
@@ -257,39 +231,6 @@ class HipTrainer:
             out[off], out[off + 1] = F.adam_hyper(counts[group] + 1, lr, a.betas)
         out[_HYPER_ANNEAL] = self.model.proposal_sampler._anneal
         out[_HYPER_SLOT] = float(step % self.slots)
-
-    def _predict_rows(self):
-        """Rows 1 .. of the table: the scalars of the iterations AFTER the one at hand, by running the host-side bookkeeping of
-        those iterations (the model's step callbacks, the sampler's update rule, the optimiser groups' step counters) ahead on
-        its own scalar state, which is put back afterwards. Row 0 (the iteration at hand) is already in place."""
-        m, ps = self.model, self.model.proposal_sampler
-        saved = (ps._step, ps._steps_since_update, ps._anneal, getattr(m, "step", None))
-        counts, pending, step = dict(self.arena.step_counts), self._have_pending, self.step
-        rows = self.table_host_np
-        try:
-            for r in range(self.table_rows):
-                if r > 0:
-                    m.set_step(step)  # BEFORE_TRAIN_ITERATION: the anneal exponent of that iteration
-                    self._hyper_row(rows[r], step, counts, pending)
-                updated = ps.updated_this_step()
-                # what the iteration does to the counters (train_iteration's `stepped`)
-                if self.defer:
-                    if pending:
-                        counts["fields"] += 1
-                    pending = True
-                else:
-                    counts["fields"] += 1
-                if updated:
-                    counts["proposal_networks"] += 1
-                    ps.mark_updated()
-                if self.cam_inside:
-                    counts[self.cam_group] += 1
-                m.after_step(step)  # AFTER_TRAIN_ITERATION: the sampler's step counter
-                step += 1
-        finally:
-            ps._step, ps._steps_since_update, ps._anneal = saved[:3]
-            if saved[3] is not None:
-                m.step = saved[3]
 
     def _push_hyper(self, direct: bool = False):
         """Adam step sizes of the NEXT update of each group + the anneal exponent -> device (async, race-free). `direct`: into
@@ -309,42 +250,6 @@ class HipTrainer:
             self._hyper_row(self.ring_np[i % self.ring_rows], self.step, a.step_counts, self._have_pending)
             self._ring_pos = i + 1
             return
-        if self.prologue_table and not direct:
-            # the graph's first node copies row `counter % rows` of the table into `hyper`: nothing to upload while the row the
-            # host computes for THIS iteration is the one the device is about to read
-            row = self._row_scratch
-            self._hyper_row(row, self.step, a.step_counts, self._have_pending)
-            pos = self._table_pos
-            unread = self.defer and not self._have_pending
-
-            def serves(r):
-                # an iteration of the deferred schedule WITHOUT a pending main-field update (the first one, and the one after
-                # every `finish`) launches no main-field Adam: its two scalars are not read, so the row predicted for an
-                # iteration with a pending update serves it as well — a `finish` does not cost a new table
-                want = self.table_host_np[r]
-                return bool(((want == row) | self._row_unread).all() if unread else (want == row).all())
-
-            if self._table_valid:
-                if pos < self.table_rows and serves(pos):
-                    self._table_pos = pos + 1
-                    return
-                # a caller that rewound the training state (bench.py repeats its window on the same iterations; a checkpoint
-                # restore): the rows of those iterations are still in the table — move the device's row counter, nothing else
-                back = self.step - self._table_base
-                if 0 <= back < self.table_rows and serves(back):
-                    self.step_counter[0:1].fill_(back)
-                    self._table_pos = back + 1
-                    return
-            if self._table_event is not None:
-                self._table_event.synchronize()  # the previous upload has read the pinned table
-            self.table_host_np[0] = row
-            self._predict_rows()
-            self.hyper_table.copy_(self.table_host.reshape(-1), non_blocking=True)
-            self.step_counter[0:1].zero_()
-            self._table_event = torch.cuda.Event()
-            self._table_event.record(N.current_stream())
-            self._table_pos, self._table_valid, self._table_base = 1, True, self.step
-            return
         slot = self.hyper_slot
         self.hyper_slot = (slot + 1) % len(self.hyper_ring)
         if self.hyper_events[slot] is not None:
@@ -358,52 +263,17 @@ class HipTrainer:
             self.hyper_events[slot] = ev
 
     def _step_prologue(self):
-        """First launch of an iteration body (captured with it): the step's scalars out of the table, the step's draws."""
+        """First launch of an iteration body (captured with it): the step's draws and, with the ring, the step's scalars."""
         if not self.prologue:
             return
-        from . import _native as N
-
         r = self.runner
         draw = self.draw_jitter
         j = r.jitter if draw else None
         bg = r.bg_rays if (draw and r.bg_rays is not None) else None
-        if self.prologue_ring:
-            rows_ptr, rows = self.ring_host.data_ptr(), self.ring_rows
-        elif self.prologue_table:
-            rows_ptr, rows = N.ptr(self.hyper_table), self.table_rows
-        else:
-            rows_ptr, rows = None, 0
+        rows_ptr, rows = (self.ring_host.data_ptr(), self.ring_rows) if self.prologue_ring else (None, 0)
         N.check(N.load().nsamd_step_prologue(
             N.ptr(self.step_counter), rows_ptr, rows, N.ptr(self.hyper), N.ptr(j), j.numel() if j is not None else 0,
             N.ptr(bg), bg.numel() if bg is not None else 0, self.rng_seed, N.stream()), "step_prologue")
-
-    def _fwd_bwd(self, updated):
-        """Single-process path: forward, losses and the main backward (runner: also the proposal backward)."""
-        from .cameras.rays import RayBundle
-
-        if self.runner is not None:
-            self._step_prologue()
-            self._select_batch()
-            self.runner.apply_camera_corrections()
-            # the main table's gradient is written, not accumulated; the proposal group's gradients are neither produced nor
-            # consumed on a step that does not update it (ray_samplers.py:590-599), so its 10 MB need no zero-fill then
-            self._zero(updated)
-            self.runner.forward_proposals(self.draw_jitter and not self.prologue, need_enc=updated)
-            self.runner.forward_main_and_losses(updated)
-            self.runner.backward_all(updated)  # the backward chains run as parallel branches
-            return
-        self._select_batch()
-        self.arena.zero_grad()
-        m = self.model
-        m.proposal_sampler.force_updated = updated
-        rb = RayBundle(origins=self.rb.origins, directions=self.rb.directions, pixel_area=self.rb.pixel_area,
-                       camera_indices=self.rb.camera_indices)
-        out = m(rb)
-        metrics = m.get_metrics_dict(out, self.batch)
-        loss_dict = m.get_loss_dict(out, self.batch, metrics)
-        loss = sum(loss_dict.values())
-        loss.backward()
-        self.loss_buf.copy_(loss.detach())
 
     def _zero(self, updated, groups=None):
         """Zero-fills ahead of an iteration's forward; `groups`: only these gradient slices (a later segment of the same
@@ -423,38 +293,29 @@ class HipTrainer:
         if getattr(self.runner, "gates_precleared", False):
             self.runner.prop_gates.zero_()
 
-    def _deferred_iteration_body(self, updated, pending):
-        """One iteration of the deferred schedule (N = 1, runner):
-            [Adam main k-1  ||  select batch, proposal forward k] -> main forward, losses, backward chains k
-            -> [Adam proposals k]                                                            (update steps)
-        Inside a captured hipGraph the two halves of the first line are parallel branches. With the camera optimiser on,
-        batch selection and the pose corrections have already run (eagerly, `_cameras_before`)."""
+    def _stepped(self, updated, pending):
+        """The optimiser groups whose Adam launches one iteration issues — the reference steps a group only when it received
+        gradients (engine/optimizers.py:160-172): the main field's (deferred schedule: the previous iteration's, when one is
+        pending), the proposal networks' on update steps, the camera optimiser's when it is part of the body."""
+        return ((["fields"] if pending or not self.defer else []) + (["proposal_networks"] if updated else [])
+                + ([self.cam_group] if self.cam_inside else []))
+
+    def _body(self, updated, pending):
+        """One N = 1 iteration over the runner, eager or captured as the graph ("all", updated, pending):
+            in order:  select batch -> zero-fills -> proposal forward -> main forward, losses, backward chains -> Adam
+            deferred:  [Adam main k-1, zero-fills  ||  select batch, proposal forward k] -> main forward, losses,
+                       backward chains k -> [Adam proposals k]                                          (update steps)
+        Inside a captured hipGraph the two halves of the deferred first line are parallel branches. With the camera parts
+        outside, batch selection and the pose corrections have already run (eagerly, `_cameras_before`)."""
         r, a = self.runner, self.arena
-        main = N.current_stream()
+        assert self.defer or not pending
         beside = pending and self.opt_parallel
-        self._step_prologue()  # the step's scalars and draws: first node, every branch below depends on it
-        draw = self.draw_jitter and not self.prologue
-
-        def pending_update():  # what iteration k-1 left behind: its main-field Adam
-            a.step(grad_scale=1.0, groups=["fields"], hyper_dev=self.hyper_views)
-            if beside:
-                # ... and, off the critical path, this iteration's zero-fills: the Adam above was the last reader of the
-                # field gradients, the proposal / camera groups were consumed at the end of their last update iteration, and
-                # nothing before the join below writes a gradient
-                self._zero(updated)
-
+        main = N.current_stream() if beside else None  # (the stream the Adam branch forks from and joins)
         # The ray terms of this iteration's main-field forward (train_step.ray_terms_launch) need the updated head weights and
-        # the selected batch, nothing else: they go on the Adam branch, behind an event the main branch records once the batch
-        # is in place — off the critical path instead of a launch (and a dependent-launch gap) in front of the hash forward.
+        # the selected batch, nothing else: beside a pending Adam they go on its branch, behind an event the main branch
+        # records once the batch is in place — off the critical path instead of a launch (and a dependent-launch gap) in
+        # front of the hash forward.
         terms_beside = beside and getattr(r, "ray_terms_on", False)
-
-        def fork():
-            self._opt_fork.record(main)
-            self.opt_stream.wait_event(self._opt_fork)
-            with N.on_stream(self.opt_stream):
-                pending_update()
-                if not terms_beside:
-                    self._opt_join.record(self.opt_stream)
 
         def terms_behind_batch():  # (runs inside forward_proposals, right behind the launch that selects the batch)
             self._batch_ready.record(main)
@@ -463,25 +324,66 @@ class HipTrainer:
                 r.ray_terms_launch()
                 self._opt_join.record(self.opt_stream)
 
+        self._step_prologue()  # the step's scalars and draws: first node, every branch below depends on it
         if beside:
-            fork()
+            self._opt_fork.record(main)
+            self.opt_stream.wait_event(self._opt_fork)
+            with N.on_stream(self.opt_stream):
+                a.step(grad_scale=1.0, groups=["fields"], hyper_dev=self.hyper_views)  # what iteration k-1 left behind
+                # ... and, off the critical path, this iteration's zero-fills: the Adam above was the last reader of the field
+                # gradients, the proposal / camera groups were consumed at the end of their last update iteration, and
+                # nothing before the join below writes a gradient
+                self._zero(updated)
+                if not terms_beside:
+                    self._opt_join.record(self.opt_stream)
         elif pending:
-            pending_update()
+            a.step(grad_scale=1.0, groups=["fields"], hyper_dev=self.hyper_views)
         if not r.cameras_outside:
             self._select_batch()
             r.apply_camera_corrections()
+        if not self.defer:
+            # the main table's gradient is written, not accumulated; the proposal group's gradients are neither produced nor
+            # consumed on a step that does not update it (ray_samplers.py:590-599), so its 10 MB need no zero-fill then
+            self._zero(updated)
+        # (the ray-terms keywords only when the terms ride the Adam branch: a runner without ray terms keeps the plain calls)
+        draw = self.draw_jitter and not self.prologue
         if terms_beside:
-            r.after_bins = terms_behind_batch
-        r.forward_proposals(draw, need_enc=updated)
+            r.forward_proposals(draw, need_enc=updated, after_bins=terms_behind_batch)
+        else:
+            r.forward_proposals(draw, need_enc=updated)
         if beside:
             main.wait_event(self._opt_join)
-        if not beside:
+        elif self.defer:
             self._zero(updated)
-        r.forward_main_and_losses(updated)
-        r.backward_all(updated)
-        late = (["proposal_networks"] if updated else []) + ([self.cam_group] if self.cam_inside else [])
+        if terms_beside:
+            r.forward_main_and_losses(updated, terms_ready=True)
+        else:
+            r.forward_main_and_losses(updated)
+        r.backward_all(updated)  # the backward chains run as parallel branches
+        late = self._stepped(updated, pending=False)  # (a pending main-field update has run at the head)
         if late:
             a.step(grad_scale=1.0, groups=late, hyper_dev=self.hyper_views)
+
+    def _module_body(self, updated):
+        """use_runner=False: forward, losses and backward through the nn.Modules and autograd, then — N > 1 — one blocking
+        all-reduce of the whole arena (not pipelined), then Adam."""
+        from .cameras.rays import RayBundle
+
+        self._select_batch()
+        self.arena.zero_grad()
+        m = self.model
+        m.proposal_sampler.force_updated = updated
+        rb = RayBundle(origins=self.rb.origins, directions=self.rb.directions, pixel_area=self.rb.pixel_area,
+                       camera_indices=self.rb.camera_indices)
+        out = m(rb)
+        metrics = m.get_metrics_dict(out, self.batch)
+        loss_dict = m.get_loss_dict(out, self.batch, metrics)
+        loss = sum(loss_dict.values())
+        loss.backward()
+        self.loss_buf.copy_(loss.detach())
+        if self.dp:
+            self.arena.all_reduce()
+        self.arena.step(grad_scale=1.0 / self.world, groups=self._stepped(updated, pending=False), hyper_dev=self.hyper_views)
 
     def _select_batch(self):
         """This step's rays out of the HBM-resident pool (slot index in device memory: replayable) — the hand-over the
@@ -505,11 +407,6 @@ class HipTrainer:
         N.check(N.load().nsamd_select_batch(N.ptr(self.hyper[_HYPER_SLOT:_HYPER_SLOT + 1]), self.slots, o.shape[0],
                                             N.ptr(p["origins"]), N.ptr(p["directions"]), N.ptr(p["cameras"]), N.ptr(p["target"]),
                                             N.ptr(o), N.ptr(d), N.ptr(c), N.ptr(t), N.stream()), "select_batch")
-
-    def _optimise(self, updated):
-        # the reference steps an optimiser group only when it received gradients (engine/optimizers.py:160-172)
-        groups = (["fields", "proposal_networks"] if updated else ["fields"]) + ([self.cam_group] if self.cam_inside else [])
-        self.arena.step(grad_scale=1.0 / self.world, groups=groups, hyper_dev=self.hyper_views)
 
     # -- camera optimiser: the host-side halves around the captured part ---------------------------------------------------
     @property
@@ -543,7 +440,7 @@ class HipTrainer:
         """The body of one captured segment (also what the eager path runs)."""
         r, a = self.runner, self.arena
         if name == "pfwd":
-            self._step_prologue()  # (the step's draws; the scalars were uploaded by `_prologue`)
+            self._step_prologue()  # (the step's draws; the scalars were uploaded by `_push_hyper`)
             if not self._cams_outside:
                 self._select_batch()
                 r.apply_camera_corrections()
@@ -604,7 +501,7 @@ class HipTrainer:
         if self.exchange is not None:
             self.exchange.finish()
         if self._pending_main:  # deferred schedule: the last iteration's main-field update
-            self._push_hyper(direct=True)  # (the table's rows stay valid: see `_push_hyper`)
+            self._push_hyper(direct=True)
             self.arena.step(grad_scale=1.0, groups=["fields"], hyper_dev=self.hyper_views)
             self._pending_main = False
             self._true_steps = dict(self.arena.step_counts)
@@ -612,21 +509,6 @@ class HipTrainer:
     @property
     def _have_pending(self):
         return self._pending_main or (self.exchange is not None and self.exchange.pending)
-
-    def _pipelined_iteration(self, updated):
-        self._prologue(updated)
-        if self._cams_outside:
-            self._cameras_before()
-        self.exchange.iteration(updated)
-        if self._cams_outside:
-            self._cameras_after(updated)
-
-    def _plain_dp_iteration(self, updated):
-        """N > 1 through the autograd modules: one blocking all-reduce of the whole arena (not pipelined)."""
-        self._prologue(updated)
-        self._fwd_bwd(updated)
-        self.arena.all_reduce()
-        self._optimise(updated)
 
     # -- graph capture ---------------------------------------------------------------------------------------------
     def warm_variants(self):
@@ -641,7 +523,7 @@ class HipTrainer:
         with N.on_stream(side):
             defer, self.defer = self.defer, False  # (in order, so that every schedule trains through the same states)
             for upd in (True, False):
-                self._eager_iteration(upd)
+                self._iteration(upd, replay=False)
             self.finish()
             self.defer = defer
         N.current_stream().wait_stream(side)
@@ -665,53 +547,19 @@ class HipTrainer:
                 with torch.cuda.graph(g):
                     self._seg(name)
                 graphs[name] = g
-        elif self.defer:
-            for upd in (True, False):
-                for pend in (True, False):
-                    g = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g):  # the whole iteration is one graph
-                        self._deferred_iteration_body(upd, pend)
-                    graphs[("all", upd, pend)] = g
         else:
             for upd in (True, False):
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):  # the whole iteration is one graph
-                    self._plain_body(upd)
-                graphs[("all", upd)] = g
+                for pend in ((True, False) if self.defer else (False,)):
+                    g = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(g):  # the whole iteration is one graph
+                        if self.runner is not None:
+                            self._body(upd, pend)
+                        else:
+                            self._module_body(upd)
+                    graphs[("all", upd, pend)] = g
         for name in self.arena.step_counts:  # captures executed nothing; undo the host-side counters they bumped
             self.arena.step_counts[name] = self._true_steps[name]
         self.graphs = graphs
-
-    def _plain_body(self, updated):
-        """[select batch] -> forward -> losses -> backward -> Adam, in order (what a captured ("all", updated) graph holds)."""
-        r = self.runner
-        if r is not None and r.cameras_outside:
-            self._step_prologue()
-            self._zero(updated)
-            r.forward_proposals(self.draw_jitter and not self.prologue, need_enc=updated)
-            r.forward_main_and_losses(updated)
-            r.backward_all(updated)
-        else:
-            self._fwd_bwd(updated)
-        self._optimise(updated)
-
-    def _eager_iteration(self, updated):
-        if self.pipelined:
-            self._pipelined_iteration(updated)
-        elif self.dp:
-            self._plain_dp_iteration(updated)
-        else:
-            self._prologue(updated)
-            if self._cams_outside:
-                self._cameras_before()
-            if self.defer:
-                self._deferred_iteration_body(updated, self._pending_main)
-                self._pending_main = True
-            else:
-                self._plain_body(updated)
-            if self._cams_outside:
-                self._cameras_after(updated)
-        self._true_steps = dict(self.arena.step_counts)
 
     def try_capture(self, warm: bool = True):
         if not self.use_graph or (self.dp and not self.pipelined):
@@ -729,29 +577,36 @@ class HipTrainer:
             return False
 
     # -- one training iteration ------------------------------------------------------------------------------------
+    def _iteration(self, updated, replay):
+        """The host's share around an iteration's body: the model's step callback, the step's scalars, the camera parts
+        outside the captured body; the body itself runs as eager launches, as the replay of its captured variant, or as the
+        data-parallel segments (which replay their own graphs once captured)."""
+        pending = self._pending_main
+        if self.drive_callbacks:
+            self.model.set_step(self.step)  # BEFORE_TRAIN_ITERATION callback: proposal weight anneal
+        self._push_hyper()
+        if self._cams_outside:
+            self._cameras_before()
+        if self.pipelined:
+            self.exchange.iteration(updated)
+        elif replay:
+            self.graphs[("all", updated, pending)].replay()
+            for name in self._stepped(updated, pending):
+                self.arena.step_counts[name] += 1  # the replayed Adam launches did step these groups
+        elif self.runner is not None:
+            self._body(updated, pending)
+        else:
+            self._module_body(updated)
+        if self.defer:
+            self._pending_main = True
+        if self._cams_outside:
+            self._cameras_after(updated)
+        self._true_steps = dict(self.arena.step_counts)
+
     def train_iteration(self):
         ps = self.model.proposal_sampler
         updated = ps.updated_this_step()
-        if self.graphs is None or self.pipelined:
-            self._eager_iteration(updated)  # (pipelined: the segments replay their graphs)
-        else:
-            self._prologue(updated)
-            if self._cams_outside:
-                self._cameras_before()
-            if self.defer:
-                self.graphs[("all", updated, self._pending_main)].replay()
-                stepped = (("fields",) if self._pending_main else ()) + (("proposal_networks",) if updated else ())
-                self._pending_main = True
-            else:
-                self.graphs[("all", updated)].replay()
-                stepped = ("fields", "proposal_networks") if updated else ("fields",)
-            if self.cam_inside:
-                stepped = stepped + (self.cam_group,)
-            for name in stepped:
-                self.arena.step_counts[name] += 1  # the replayed Adam launches did step these groups
-            if self._cams_outside:
-                self._cameras_after(updated)
-            self._true_steps = dict(self.arena.step_counts)
+        self._iteration(updated, replay=self.graphs is not None)
         self.opt_step += 1
         if updated:
             ps.mark_updated()

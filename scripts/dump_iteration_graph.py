@@ -36,7 +36,7 @@ for upd in (True, False):
         g = torch.cuda.CUDAGraph()
         g.enable_debug_mode()
         with torch.cuda.graph(g):
-            tr._deferred_iteration_body(upd, pend)
+            tr._body(upd, pend)
         path = os.path.join(out, f"iteration_updated{int(upd)}_pending{int(pend)}.dot")
         g.debug_dump(path)
         try:

@@ -59,10 +59,12 @@ class CpuRunner:
     def apply_camera_corrections(self):
         pass
 
-    def forward_proposals(self, draw_jitter=True, need_enc=True):
+    def forward_proposals(self, draw_jitter=True, need_enc=True, after_bins=None):
         self.calls.append("pfwd")
+        if after_bins is not None:
+            after_bins()
 
-    def forward_main_and_losses(self, updated):
+    def forward_main_and_losses(self, updated, terms_ready=False):
         """The whole forward + the gradient of the summed losses, through the module path (autograd, CPU stand-in kernels)."""
         from nerfstudio_amd.cameras.rays import RayBundle
 

@@ -275,13 +275,11 @@ def test_step_prologue_rows_follow_the_table_and_draws_are_philox(F):
     assert np.array_equal(seen.cpu().numpy(), want)
 
 
-@pytest.mark.parametrize("mode", ["ring", "table"])
-def test_trainer_prologue_hands_every_iteration_the_scalars_the_host_computes(F, monkeypatch, mode):
-    """trainer.HipTrainer with the device-side prologue (scalars from the ring in host memory / from the predicted table): over
-    300 / 150 replayed iterations — past the end of the 256-row ring / of the 128-row table, across a `finish()` in the middle and
-    a rewind of the training state (bench.py's repeated windows) — `hyper` holds after every iteration exactly the scalars the
-    host computes for it (what the per-iteration upload used to carry); and graph replay trains through the same bits as eager
-    launches."""
+def test_trainer_prologue_ring_hands_every_iteration_the_scalars_the_host_computes(F):
+    """trainer.HipTrainer with the device-side prologue (scalars from the ring in host memory): over 300 replayed iterations —
+    past the end of the 256-row ring, across a `finish()` in the middle and a rewind of the training state (bench.py's
+    repeated windows) — `hyper` holds after every iteration exactly the scalars the host computes for it (what the
+    per-iteration upload used to carry); and graph replay trains through the same bits as eager launches."""
     import hashlib
 
     import bench
@@ -289,7 +287,6 @@ def test_trainer_prologue_hands_every_iteration_the_scalars_the_host_computes(F,
     from nerfstudio_amd.arena import ParamArena
     from nerfstudio_amd.trainer import HipTrainer
 
-    monkeypatch.setenv("NSAMD_STEP_PROLOGUE", mode)
     dev = torch.device("cuda")
     digests = {}
     for arm in ("graph", "eager"):
@@ -299,7 +296,7 @@ def test_trainer_prologue_hands_every_iteration_the_scalars_the_host_computes(F,
         arena = ParamArena(model.get_param_groups_ordered(), lr=1e-2, eps=1e-15)
         rb, batch, pool = bench.synthetic_batch(dev, seed=1000)
         tr = HipTrainer(model, arena, rb, batch, world=1, use_graph=arm == "graph", use_runner=True, pool=pool)
-        assert tr.prologue and tr.prologue_table == (mode == "table") and tr.prologue_ring == (mode == "ring")
+        assert tr.prologue and tr.prologue_ring
         if arm == "graph":
             tr.train_iteration()
             tr.finish()
@@ -310,20 +307,17 @@ def test_trainer_prologue_hands_every_iteration_the_scalars_the_host_computes(F,
             tr.warm_variants()  # (the same real iterations the capture's warm-up runs)
         state = bench.TrainingState(tr, arena, model)
         want = np.zeros(8, dtype=np.float32)
-        checked, refills = 0, []
-        for i in range((300 if mode == "ring" else 150) if arm == "graph" else 12):
+        checked = 0
+        for i in range(300 if arm == "graph" else 12):
             if arm == "graph" and i == 40:
                 tr.finish()
             if arm == "graph" and i == 90:
                 state.restore()
-            model.set_step(tr.step)  # (what `_prologue` is about to do: the anneal exponent of this iteration)
+            model.set_step(tr.step)  # (what `_iteration` is about to do: the anneal exponent of this iteration)
             tr._hyper_row(want, tr.step, arena.step_counts, tr._have_pending)
-            # (an iteration without a pending main-field update launches no main-field Adam and may be handed the row predicted
-            #  for one with: its first two scalars are not read)
+            # (an iteration without a pending main-field update launches no main-field Adam: its first two scalars are not read)
             read = slice(2, 8) if (tr.defer and not tr._have_pending) else slice(0, 8)
-            before = (tr._table_base if tr._table_valid else None) if mode == "table" else 0
             tr.train_iteration()
-            refills.append((i, before != (tr._table_base if mode == "table" else 0)))
             if arm == "graph" and (i < 12 or i % 7 == 0 or 38 <= i <= 44 or 85 <= i <= 95 or 125 <= i <= 135 or 250 <= i <= 262):
                 torch.cuda.synchronize()
                 got = tr.hyper.cpu().numpy()
@@ -335,10 +329,5 @@ def test_trainer_prologue_hands_every_iteration_the_scalars_the_host_computes(F,
                 digests[arm] = tuple(hashlib.sha256(x.detach().cpu().numpy().tobytes()).hexdigest()
                                      for x in (arena.flat, arena.exp_avg, arena.exp_avg_sq))
         assert arm == "eager" or checked > 40
-        if arm == "graph" and mode == "table":
-            # a new table when the rows run out or the state is rewound to BEFORE the table's first row — not after `finish()`
-            # (i = 40), whose next iteration is served by the row predicted for an iteration with a pending update
-            new_tables = [i for i, refilled in refills if refilled]
-            assert len(new_tables) <= 3 and 40 not in new_tables and 41 not in new_tables, new_tables
         del tr, arena, model
     assert digests["graph"] == digests["eager"], digests
