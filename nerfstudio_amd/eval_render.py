@@ -19,6 +19,7 @@ Same kernels, same order as the module path: the outputs are equal bit for bit (
 """
 from __future__ import annotations
 
+import os
 from typing import Dict, Optional
 
 import torch
@@ -66,55 +67,17 @@ class EvalRenderer:
                     self.app_const.zero_()
 
     def _launch_chunk(self) -> None:
-        """The kernel schedule of one chunk (all arguments are static buffers: capturable)."""
+        """The kernel schedule of one chunk (all arguments are static buffers: capturable): the training runner's forward in
+        eval mode, then weights + compositing with the clamp."""
         s, lib, st, n = self.step, N.load(), N.stream(), self.chunk
-        ck = N.check
-        S0 = s.counts[0]
-        ck(lib.nsamd_piecewise_bins(N.ptr(s.nears), N.ptr(s.fars), N.ptr(s.edges), None, 0, n, S0, s.spacing,
-                                    N.ptr(s.s_bins[0]), N.ptr(s.t_bins[0]), st), "piecewise_bins")
-        for lvl in range(s.n_prop):
-            net = s.props[lvl]
-            S, m = s.counts[lvl], n * s.counts[lvl]
-            W0, b0, W1, b1 = net.mlp_base[1].param_tensors()
-            dm = N.DensityMlp(N.ptr(W0), N.ptr(b0), N.ptr(W1), N.ptr(b1), W0.shape[1], W0.shape[0],
-                              float(net.average_init_density))
-            fused = lib.nsamd_density_field_fwd(s._points(lvl), m, net._transform, net._box, N.ptr(net.encoding.hash_table),
-                                                net.encoding.spec.native(), dm, None, None, N.ptr(s.p_dens[lvl]), None, st)
-            if fused == N.ERR_UNSUPPORTED:
-                s.ensure_proposal_features(lvl)
-                ck(lib.nsamd_hashgrid_encode_fwd(s._points(lvl), m, net._transform, net._box, N.ptr(net.encoding.hash_table),
-                                                 net.encoding.spec.native(), N.ptr(s.p_enc[lvl]), 1, m, N.ptr(s.p_sel[lvl]), st),
-                   "hashgrid_encode_fwd")
-                ck(lib.nsamd_density_mlp_fwd(N.ptr(s.p_enc[lvl]), N.ptr(s.p_sel[lvl]), m, dm, N.ptr(s.p_dens[lvl]), None, st),
-                   "density_mlp_fwd")
-            else:
-                ck(fused, "density_field_fwd")
-            S2 = s.counts[lvl + 1]
-            ck(lib.nsamd_proposal_resample(N.ptr(s.t_bins[lvl]), N.ptr(s.s_bins[lvl]), N.ptr(s.p_dens[lvl]), S,
-                                           N.ptr(s.u_base[lvl + 1]), None, N.ptr(s.nears), N.ptr(s.fars), 1.0,
-                                           N.ptr(s.anneal_dev), 0.01, 1e-5, 1.0 / (2 * (S2 + 1)), s.spacing, n, S2,
-                                           N.ptr(s.weights[lvl]), N.ptr(s.depth_med[lvl]), N.ptr(s.s_bins[lvl + 1]),
-                                           N.ptr(s.t_bins[lvl + 1]), st), "proposal_resample")
+        s.forward_proposals(need_enc=False, stratified=False)
+        s.forward_main(app_const=self.app_const)
         L = s.n_prop
-        S, mm = s.counts[L], s.m_main
-        fld = self.model.field
-        enc = fld.mlp_base.encoding
-        params = [*fld.mlp_base.mlp.param_tensors(), *fld.mlp_head.param_tensors()]
-        emb = fld.embedding_appearance.embedding.weight if fld.embedding_appearance is not None else None
-        fm = N.FieldMlp(*(N.ptr(p) for p in params), N.ptr(emb), emb.shape[0] if emb is not None else 0,
-                        float(fld.average_init_density))
-        if s.ray_terms_on:  # head layer 0's per-ray share once per ray (include/nsamd.h, nsamd_field_mlp.ray_terms)
-            ck(lib.nsamd_field_ray_terms(N.ptr(s.directions), None, N.ptr(self.app_const), n, fm, N.ptr(s.ray_terms), None, st),
-               "field_ray_terms")
-            fm.ray_terms = N.ptr(s.ray_terms)
-        ck(lib.nsamd_hashgrid_encode_fwd(s._points(L), mm, fld._transform, fld._box, N.ptr(enc.hash_table), enc.spec.native(),
-                                         N.ptr(s.f_enc), 1, mm, N.ptr(s.f_sel), st), "hashgrid_encode_fwd")
-        ck(lib.nsamd_field_mlp_fwd(N.ptr(s.f_enc), N.ptr(s.f_sel), N.ptr(s.directions), None, N.ptr(self.app_const), S, mm, fm,
-                                   N.ptr(s.f_dens), N.ptr(s.f_rgb), st), "field_mlp_fwd")
-        ck(lib.nsamd_weights_fwd(N.ptr(s.t_bins[L]), N.ptr(s.f_dens), n, S, N.ptr(s.weights[L]), st), "weights_fwd")
-        ck(lib.nsamd_composite_fwd(N.ptr(s.f_rgb), N.ptr(s.weights[L]), N.ptr(s.t_bins[L]), n, S, self.bg_mode, self.bg_vals, 1,
-                                   N.ptr(s.rgb), N.ptr(s.acc), N.ptr(s.depth_exp), N.ptr(s.depth_med[L]), None,
-                                   N.ptr(s.minmax_ws), st), "composite_fwd")
+        S = s.counts[L]
+        N.check(lib.nsamd_weights_fwd(N.ptr(s.t_bins[L]), N.ptr(s.f_dens), n, S, N.ptr(s.weights[L]), st), "weights_fwd")
+        N.check(lib.nsamd_composite_fwd(N.ptr(s.f_rgb), N.ptr(s.weights[L]), N.ptr(s.t_bins[L]), n, S, self.bg_mode, self.bg_vals,
+                                        1, N.ptr(s.rgb), N.ptr(s.acc), N.ptr(s.depth_exp), N.ptr(s.depth_med[L]), None,
+                                        N.ptr(s.minmax_ws), st), "composite_fwd")
 
     def _addresses(self):
         """Everything the captured launches read through raw pointers that this object does not own: the model's parameters
@@ -145,6 +108,28 @@ class EvalRenderer:
         self.graph.replay()
 
     # ---- a frame ----------------------------------------------------------------------------------------------------------
+    def _render_rays(self, total: int, dev, load_chunk) -> Dict[str, Tensor]:
+        """The frame's chunk loop over `total` rays: `load_chunk(a, k)` puts rays a .. a + k - 1 into the schedule's input
+        buffers, the chunk runs, and its k valid rows are copied into the preallocated `[total, C]` outputs."""
+        s, n = self.step, self.chunk
+        out = {"rgb": torch.empty((total, 3), device=dev), "accumulation": torch.empty((total, 1), device=dev),
+               "depth": torch.empty((total, 1), device=dev), "expected_depth": torch.empty((total, 1), device=dev)}
+        for i in range(s.n_prop):
+            out[f"prop_depth_{i}"] = torch.empty((total, 1), device=dev)
+        self._refresh_constants()
+        for a in range(0, total, n):
+            k = min(a + n, total) - a
+            b = a + k
+            load_chunk(a, k)
+            self._run_chunk()
+            out["rgb"][a:b].copy_(s.rgb[:k])
+            out["accumulation"][a:b, 0].copy_(s.acc[:k])
+            out["expected_depth"][a:b, 0].copy_(s.depth_exp[:k])
+            out["depth"][a:b, 0].copy_(s.depth_med[-1][:k])
+            for i in range(s.n_prop):
+                out[f"prop_depth_{i}"][a:b, 0].copy_(s.depth_med[i][:k])
+        return out
+
     @profiler.time_function
     @torch.no_grad()
     def render(self, camera_ray_bundle) -> Dict[str, Tensor]:
@@ -154,28 +139,16 @@ class EvalRenderer:
         image_shape = camera_ray_bundle.origins.shape[:-1]
         o = camera_ray_bundle.origins.reshape(-1, 3)
         d = camera_ray_bundle.directions.reshape(-1, 3)
-        total = o.shape[0]
-        dev = o.device
-        out = {"rgb": torch.empty((total, 3), device=dev), "accumulation": torch.empty((total, 1), device=dev),
-               "depth": torch.empty((total, 1), device=dev), "expected_depth": torch.empty((total, 1), device=dev)}
-        for i in range(s.n_prop):
-            out[f"prop_depth_{i}"] = torch.empty((total, 1), device=dev)
-        self._refresh_constants()
-        for a in range(0, total, n):
-            b = min(a + n, total)
-            k = b - a
+
+        def load_chunk(a, k):
+            b = a + k
             s.origins[:k].copy_(o[a:b])
             s.directions[:k].copy_(d[a:b])
             if k < n:  # pad with copies of the last ray: the chunk's depth clip range is unchanged
                 s.origins[k:].copy_(o[b - 1:b].expand(n - k, 3))
                 s.directions[k:].copy_(d[b - 1:b].expand(n - k, 3))
-            self._run_chunk()
-            out["rgb"][a:b].copy_(s.rgb[:k])
-            out["accumulation"][a:b, 0].copy_(s.acc[:k])
-            out["expected_depth"][a:b, 0].copy_(s.depth_exp[:k])
-            out["depth"][a:b, 0].copy_(s.depth_med[-1][:k])
-            for i in range(s.n_prop):
-                out[f"prop_depth_{i}"][a:b, 0].copy_(s.depth_med[i][:k])
+
+        out = self._render_rays(o.shape[0], o.device, load_chunk)
         return {k_: v.view(*image_shape, -1) for k_, v in out.items()}
 
     @profiler.time_function
@@ -187,27 +160,15 @@ class EvalRenderer:
         Model.get_outputs_for_camera (models/base_model.py:166-175) builds as an [H, W] bundle with ~40 torch launches over
         full-image tensors and then slices. Same bits as `render` on that bundle. c2w: [3, 4] on the model's device."""
         s, n = self.step, self.chunk
-        total = int(height) * int(width)
         dev = s.origins.device
         c2w = c2w.reshape(3, 4).to(device=dev, dtype=torch.float32).contiguous()
-        out = {"rgb": torch.empty((total, 3), device=dev), "accumulation": torch.empty((total, 1), device=dev),
-               "depth": torch.empty((total, 1), device=dev), "expected_depth": torch.empty((total, 1), device=dev)}
-        for i in range(s.n_prop):
-            out[f"prop_depth_{i}"] = torch.empty((total, 1), device=dev)
-        self._refresh_constants()
-        lib = N.load()
-        for a in range(0, total, n):
-            k = min(a + n, total) - a
-            N.check(lib.nsamd_raygen_pinhole_grid(N.ptr(c2w), float(fx), float(fy), float(cx), float(cy), int(width), a, k, n,
-                                                  N.ptr(s.origins), N.ptr(s.directions), None, N.stream()), "raygen_pinhole_grid")
-            self._run_chunk()
-            b = a + k
-            out["rgb"][a:b].copy_(s.rgb[:k])
-            out["accumulation"][a:b, 0].copy_(s.acc[:k])
-            out["expected_depth"][a:b, 0].copy_(s.depth_exp[:k])
-            out["depth"][a:b, 0].copy_(s.depth_med[-1][:k])
-            for i in range(s.n_prop):
-                out[f"prop_depth_{i}"][a:b, 0].copy_(s.depth_med[i][:k])
+
+        def load_chunk(a, k):
+            N.check(N.load().nsamd_raygen_pinhole_grid(N.ptr(c2w), float(fx), float(fy), float(cx), float(cy), int(width), a, k,
+                                                       n, N.ptr(s.origins), N.ptr(s.directions), None, N.stream()),
+                    "raygen_pinhole_grid")
+
+        out = self._render_rays(int(height) * int(width), dev, load_chunk)
         return {k_: v.view(int(height), int(width), -1) for k_, v in out.items()}
 
 
@@ -244,3 +205,15 @@ def supported(model) -> Optional[str]:
     if not all(hasattr(model, a) for a in ("proposal_networks", "field", "proposal_sampler")):
         return "not a nerfacto model"
     return None
+
+
+def runner_for(model, device) -> Optional[EvalRenderer]:
+    """The model's cached EvalRenderer (rebuilt when the chunk size changed) for an eval render of rays on `device`, or None:
+    the module path (training mode, not a GPU, NSAMD_EVAL_RUNNER=0, or a configuration `supported` refuses)."""
+    if (model.training or torch.device(device).type != "cuda" or os.environ.get("NSAMD_EVAL_RUNNER", "1") != "1"
+            or supported(model) is not None):
+        return None
+    runner = getattr(model, "_eval_runner", None)
+    if runner is None or runner.chunk != model.config.eval_num_rays_per_chunk:
+        runner = model._eval_runner = EvalRenderer(model)
+    return runner

@@ -188,25 +188,21 @@ def density_bwd_workspace(device, slot: int = 0) -> Tensor:
 _SCATTER_BUCKET = 1 << 16  # workspaces are sized for M rounded up to a multiple of this many points
 
 
-def _scatter_workspace(grid: HashGridSpec, device, num_points: int = 0, write_only: bool = False) -> Tuple[Optional[Tensor], int]:
-    """Device scratch for the table-gradient scatter (csrc/scatter.hip): per (level, tile) a queue of 16-B records, the
-    per-workgroup segment counts, a spill list. The library says how many words it wants
-    (nsamd_hashgrid_encode_bwd_workspace) and how many leading words must start as zero (..._workspace_state: header +
-    cursors, a few KB that depend on the grid only — the kernels leave them at zero); the bulk is never initialised.
-    Cached per (grid, M rounded up to 64 k points, device): the packed instant-ngp path changes M every step
-    (occupancy-grid sampling, DynamicBatch), and a cache keyed by the exact M would allocate a fresh ~GB workspace per
-    step. A cached workspace serves every M of its bucket — the kernels lay the buffer out for the M of
-    the call — and is re-allocated only if the library asks for more words than it holds. At most _SCATTER_WS_MAX
-    entries; evicting one waits for the device first (a side-stream scatter may still be reading it). One workspace
-    serves one call at a time: callers that overlap scatters on different streams must use different (grid, bucket)
-    keys or serialise (train_step does)."""
+def _cached_workspace(grid: HashGridSpec, device, num_points: int, kind, plan) -> Tuple[Optional[Tensor], int]:
+    """A scatter workspace out of `_SCATTER_WS`, keyed (grid, bucket, device, kind). `plan(M)` is the library's query for M
+    points: (words it wants — 0 when that path does not apply —, leading words that must start as zero). Only those state
+    words are initialised (the kernels leave them at zero); the bulk never is.
+    Cached per M rounded up to 64 k points: the packed instant-ngp path changes M every step (occupancy-grid sampling,
+    DynamicBatch), and a cache keyed by the exact M would allocate a fresh ~GB workspace per step. A cached
+    workspace serves every M of its bucket — the kernels lay the buffer out for the M of the call — and is re-allocated
+    only if the library asks for more words than it holds. At most _SCATTER_WS_MAX entries; evicting one waits for the
+    device first (a side-stream scatter may still be reading it). One workspace serves one call at a time: callers that
+    overlap scatters on different streams must use different (grid, bucket) keys or serialise (train_step does)."""
     bucket = max(1, -(-int(num_points) // _SCATTER_BUCKET)) * _SCATTER_BUCKET
-    key = (grid, bucket, str(device), write_only)
-    lib = N.load()
+    key = (grid, bucket, str(device), kind)
     ws = _SCATTER_WS.get(key)
     if ws is not None:
-        need = int(lib.nsamd_hashgrid_encode_bwd_workspace(grid.native(), num_points, 1 if write_only else 0)) \
-            if num_points != bucket else ws.numel()
+        need = plan(num_points)[0] if num_points != bucket else ws.numel()  # (sized for the bucket's own M)
         if 0 < need <= ws.numel():
             _SCATTER_WS[key] = _SCATTER_WS.pop(key)  # most recently used last
             return ws, ws.numel()
@@ -214,13 +210,12 @@ def _scatter_workspace(grid: HashGridSpec, device, num_points: int = 0, write_on
             return None, 0
         torch.cuda.synchronize(device)  # (never seen: the plan grows with M) replace it by a larger one
         _SCATTER_WS.pop(key)
-    words = max(int(lib.nsamd_hashgrid_encode_bwd_workspace(grid.native(), m, 1 if write_only else 0))
-                for m in {bucket, max(int(num_points), 1)})
+    plans = [plan(m) for m in {bucket, max(int(num_points), 1)}]
+    words, states = max(p[0] for p in plans), max(p[1] for p in plans)
     if words <= 0:
         return None, 0
     ws = torch.empty(words, device=device, dtype=torch.float32)
-    state = int(lib.nsamd_hashgrid_encode_bwd_workspace_state(grid.native(), bucket))
-    ws[:state].zero_()
+    ws[:states].zero_()
     while len(_SCATTER_WS) >= _SCATTER_WS_MAX:
         torch.cuda.synchronize(device)  # no kernel on any stream may still be using the evicted buffer
         _SCATTER_WS.pop(next(iter(_SCATTER_WS)))
@@ -228,37 +223,28 @@ def _scatter_workspace(grid: HashGridSpec, device, num_points: int = 0, write_on
     return ws, ws.numel()
 
 
+def _scatter_workspace(grid: HashGridSpec, device, num_points: int = 0, write_only: bool = False) -> Tuple[Optional[Tensor], int]:
+    """Device scratch for the table-gradient scatter (csrc/scatter.hip): per (level, tile) a queue of 16-B records, the
+    per-workgroup segment counts, a spill list (nsamd_hashgrid_encode_bwd_workspace; the state words are header + cursors,
+    a few KB that depend on the grid only). Cached by `_cached_workspace` under kind `write_only`."""
+    lib, g = N.load(), grid.native()
+    return _cached_workspace(grid, device, num_points, write_only, lambda m: (
+        int(lib.nsamd_hashgrid_encode_bwd_workspace(g, m, 1 if write_only else 0)),
+        int(lib.nsamd_hashgrid_encode_bwd_workspace_state(g, m))))
+
+
 def _producer_scatter_workspace(grid: HashGridSpec, device, num_points: int) -> Tuple[Optional[Tensor], int]:
     """Scratch of nsamd_field_mlp_bwd_scatter (the main field's backward emits the scatter's records itself): one static
     segment per (MLP workgroup, table tile) + dynamic areas + the worst-case spill list, ~1.4 GB for the nerfacto main table at
-    196 608 points — untouched bulk, only the leading state words are ever initialised. Cached like `_scatter_workspace`."""
-    bucket = max(1, -(-int(num_points) // _SCATTER_BUCKET)) * _SCATTER_BUCKET
-    key = (grid, bucket, str(device), "producer")
-    lib = N.load()
-    ws = _SCATTER_WS.get(key)
-    state = C.c_int64(0)
-    if ws is not None:
-        need = int(lib.nsamd_field_mlp_bwd_scatter_workspace(grid.native(), num_points, C.byref(state)))
-        if 0 < need <= ws.numel():
-            _SCATTER_WS[key] = _SCATTER_WS.pop(key)
-            return ws, ws.numel()
-        if need <= 0:
-            return None, 0
-        torch.cuda.synchronize(device)
-        _SCATTER_WS.pop(key)
-    words, states = 0, 0
-    for m in {bucket, max(int(num_points), 1)}:
-        w = int(lib.nsamd_field_mlp_bwd_scatter_workspace(grid.native(), m, C.byref(state)))
-        words, states = max(words, w), max(states, int(state.value))
-    if words <= 0:
-        return None, 0
-    ws = torch.empty(words, device=device, dtype=torch.float32)
-    ws[:states].zero_()
-    while len(_SCATTER_WS) >= _SCATTER_WS_MAX:
-        torch.cuda.synchronize(device)
-        _SCATTER_WS.pop(next(iter(_SCATTER_WS)))
-    _SCATTER_WS[key] = ws
-    return ws, ws.numel()
+    196 608 points. Cached by `_cached_workspace` under kind "producer"."""
+    lib, g = N.load(), grid.native()
+
+    def plan(m):
+        state = C.c_int64(0)
+        words = int(lib.nsamd_field_mlp_bwd_scatter_workspace(g, m, C.byref(state)))
+        return words, int(state.value)
+
+    return _cached_workspace(grid, device, num_points, "producer", plan)
 
 
 def scatter_events(ws: Tensor) -> Tuple[int, int, int]:
@@ -267,6 +253,95 @@ def scatter_events(ws: Tensor) -> Tuple[int, int, int]:
     ev = (C.c_uint32 * 3)()
     N.check(N.load().nsamd_hashgrid_scatter_events(N.ptr(ws), C.cast(ev, C.c_void_p), N.stream()), "scatter_events")
     return int(ev[0]), int(ev[1]), int(ev[2])
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# launch records and launches shared by the autograd functions below and the explicit schedules (train_step,
+# eval_render, ngp_step). Records are built at launch time, never cached: they hold raw addresses, and an arena built
+# later re-homes the parameters.
+# ---------------------------------------------------------------------------------------------------------------
+def density_mlp(W0: Tensor, b0: Tensor, W1: Tensor, b1: Tensor, average_init_density: float) -> N.DensityMlp:
+    """nsamd_density_mlp of a proposal network's MLP (HashMLPDensityField: `mlp_base[1].param_tensors()`)."""
+    return N.DensityMlp(N.ptr(W0), N.ptr(b0), N.ptr(W1), N.ptr(b1), W0.shape[1], W0.shape[0], float(average_init_density))
+
+
+def field_params(fld):
+    """(the ten MLP tensors of a NerfactoField in nsamd_field_mlp order, its appearance table or None)."""
+    emb = fld.embedding_appearance.embedding.weight if fld.embedding_appearance is not None else None
+    return [*fld.mlp_base.mlp.param_tensors(), *fld.mlp_head.param_tensors()], emb
+
+
+def field_mlp(params: Sequence[Tensor], appearance: Optional[Tensor], average_init_density: float,
+              ray_terms: Optional[Tensor] = None, ray_inputs: Optional[Tensor] = None) -> N.FieldMlp:
+    """nsamd_field_mlp: the ten MLP tensors, the appearance table and, when the per-ray terms of head layer 0 are in use
+    (include/nsamd.h), their buffers."""
+    fm = N.FieldMlp(*(N.ptr(p) for p in params), N.ptr(appearance), appearance.shape[0] if appearance is not None else 0,
+                    float(average_init_density))
+    fm.ray_terms, fm.ray_inputs = N.ptr(ray_terms), N.ptr(ray_inputs)
+    return fm
+
+
+def field_mlp_grads(params: Sequence[Tensor], appearance: Optional[Tensor], grad_of) -> N.FieldMlpGrads:
+    """nsamd_field_mlp_grads: `grad_of(tensor)` -> the buffer its gradient accumulates into; appearance None: no gradient of
+    the appearance table."""
+    return N.FieldMlpGrads(*(N.ptr(grad_of(p)) for p in params), N.ptr(grad_of(appearance)) if appearance is not None else None)
+
+
+def table_scatter(pts: N.Points, M: int, transform: int, box: N.Aabb, table: Tensor, grid: HashGridSpec, denc: Tensor,
+                  stride_p: int, stride_k: int, dtable: Optional[Tensor], dpos: Optional[Tensor] = None,
+                  write_only: bool = False) -> None:
+    """The hash table's gradient scatter of M points from their encoded-feature gradient `denc` (point p, feature k at
+    p * stride_p + k * stride_k), on the current stream: `dtable` written (nsamd_hashgrid_encode_bwd_set, write_only) or
+    accumulated into (nsamd_hashgrid_encode_bwd, which can also return dL/dposition in `dpos`)."""
+    lib = N.load()
+    ws, ws_n = _scatter_workspace(grid, denc.device, M, write_only=write_only)
+    fn = lib.nsamd_hashgrid_encode_bwd_set if write_only else lib.nsamd_hashgrid_encode_bwd
+    N.check(fn(pts, M, transform, box, N.ptr(table), grid.native(), N.ptr(denc), stride_p, stride_k, N.ptr(dtable), N.ptr(dpos),
+               N.ptr(ws), ws_n, N.stream()), "hashgrid_encode_bwd")
+
+
+def field_forward(fld, pts: N.Points, M: int, enc: Tensor, sel: Tensor, dirs: Tensor, cams: Optional[Tensor],
+                  app_const: Optional[Tensor], dir_group: int, mlp: N.FieldMlp, density: Tensor, rgb: Optional[Tensor]) -> None:
+    """Hash grid + MLPs of a NerfactoField on M points, on the current stream: encoded features `enc` (feature-major) and
+    selector `sel`, then density and rgb (None: density only). Point p takes direction / camera row p // dir_group;
+    cams None -> the appearance row `app_const` for every point."""
+    lib, st = N.load(), N.stream()
+    tbl = fld.mlp_base.encoding
+    N.check(lib.nsamd_hashgrid_encode_fwd(pts, M, fld._transform, fld._box, N.ptr(tbl.hash_table), tbl.spec.native(), N.ptr(enc),
+                                          1, M, N.ptr(sel), st), "hashgrid_encode_fwd")
+    N.check(lib.nsamd_field_mlp_fwd(N.ptr(enc), N.ptr(sel), N.ptr(dirs), N.ptr(cams), N.ptr(app_const), dir_group, M, mlp,
+                                    N.ptr(density), N.ptr(rgb), st), "field_mlp_fwd")
+
+
+def field_backward(fld, pts: N.Points, M: int, enc: Tensor, sel: Tensor, dirs: Tensor, cams: Optional[Tensor],
+                   app_const: Optional[Tensor], dir_group: int, mlp: N.FieldMlp, ddens: Tensor, drgb: Tensor, denc: Tensor,
+                   grads: N.FieldMlpGrads, fws: Tensor, dtable: Tensor, write_only: bool, fuse: bool = True,
+                   keep_denc: bool = False, on_denc=None, fused_launch=None) -> None:
+    """Backward of `field_forward` from the density / rgb gradients: the MLPs' gradients into `grads` (`fws`: the
+    field_bwd_workspace), the table's into `dtable`. When the table gradient is written (write_only), the grid has 16
+    levels and the library plans a producer workspace, the MLP backward emits the table scatter's records itself
+    (nsamd_field_mlp_bwd_scatter: no `denc` round trip, no route launch; `denc` is stored only with keep_denc) —
+    `fused_launch(args)` issues it instead of the single launch when given (args: the entry point's arguments before the
+    phase and the stream). Otherwise nsamd_field_mlp_bwd writes `denc`, then `on_denc()` runs, then the table scatter."""
+    lib, st = N.load(), N.stream()
+    tbl = fld.mlp_base.encoding
+    grid = tbl.spec
+    if fuse and write_only and grid.num_levels == 16:
+        sws, sws_n = _producer_scatter_workspace(grid, denc.device, M)
+        if sws is not None:
+            args = (pts, fld._transform, fld._box, grid.native(), N.ptr(enc), N.ptr(sel), N.ptr(dirs), N.ptr(cams),
+                    N.ptr(app_const), dir_group, M, mlp, N.ptr(ddens), N.ptr(drgb), N.ptr(denc) if keep_denc else None, grads,
+                    N.ptr(fws), fws.numel(), N.ptr(dtable), N.ptr(sws), sws_n)
+            if fused_launch is not None:
+                fused_launch(args)
+            else:
+                N.check(lib.nsamd_field_mlp_bwd_scatter(*args, st), "field_mlp_bwd_scatter")
+            return
+    N.check(lib.nsamd_field_mlp_bwd(N.ptr(enc), N.ptr(sel), N.ptr(dirs), N.ptr(cams), N.ptr(app_const), dir_group, M, mlp,
+                                    N.ptr(ddens), N.ptr(drgb), N.ptr(denc), grads, N.ptr(fws), fws.numel(), st), "field_mlp_bwd")
+    if on_denc is not None:
+        on_denc()
+    table_scatter(pts, M, fld._transform, fld._box, tbl.hash_table, grid, denc, 1, M, dtable, write_only=write_only)
 
 
 def _position_grads(spec: PointSpec, dpos: Tensor):
@@ -308,14 +383,7 @@ class _HashEncodeFn(torch.autograd.Function):
         dtable = torch.zeros_like(table) if ctx.needs_input_grad[1] else None
         dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
         if dtable is not None or dx is not None:
-            pts = N.make_points(positions=x)
-            ws, ws_n = _scatter_workspace(grid, x.device, M)
-            N.check(
-                N.load().nsamd_hashgrid_encode_bwd(pts, M, N.XFORM_NONE, N.Aabb(), N.ptr(table), grid.native(),
-                                                  N.ptr(gout), grid.out_dim, 1, N.ptr(dtable), N.ptr(dx), N.ptr(ws),
-                                                  ws_n, N.stream()),
-                "hashgrid_encode_bwd",
-            )
+            table_scatter(N.make_points(positions=x), M, N.XFORM_NONE, N.Aabb(), table, grid, gout, grid.out_dim, 1, dtable, dx)
         return dx, dtable, None
 
 
@@ -354,10 +422,7 @@ class _SpecEncodeFn(torch.autograd.Function):
         ttable, rtable = _grad_target(ctx.table_ref, ctx.needs_input_grad[4])
         dpos = torch.empty((M, 3), device=table.device, dtype=torch.float32) if need_pos else None
         if ttable is not None or dpos is not None:
-            ws, ws_n = _scatter_workspace(ctx.grid, table.device, M)
-            N.check(N.load().nsamd_hashgrid_encode_bwd(spec.native(), M, ctx.transform, ctx.box, N.ptr(table),
-                                                       ctx.grid.native(), N.ptr(genc), ctx.grid.out_dim, 1, N.ptr(ttable),
-                                                       N.ptr(dpos), N.ptr(ws), ws_n, N.stream()), "hashgrid_encode_bwd")
+            table_scatter(spec.native(), M, ctx.transform, ctx.box, table, ctx.grid, genc, ctx.grid.out_dim, 1, ttable, dpos)
         gp, go, gd = _position_grads(spec, dpos) if dpos is not None else (None, None, None)
         return gp, go, gd, None, rtable, None, None, None
 
@@ -474,7 +539,7 @@ class _DensityFieldFn(torch.autograd.Function):
         box = aabb if isinstance(aabb, N.Aabb) else N.make_aabb(aabb)
         N.check(lib.nsamd_hashgrid_encode_fwd(spec.native(), M, transform, box, N.ptr(table), g, N.ptr(enc), 1, M,
                                               N.ptr(sel), N.stream()), "hashgrid_encode_fwd")
-        mlp = N.DensityMlp(N.ptr(W0), N.ptr(b0), N.ptr(W1), N.ptr(b1), W0.shape[1], W0.shape[0], avg_density)
+        mlp = density_mlp(W0, b0, W1, b1, avg_density)
         density = torch.empty((M,), device=dev, dtype=torch.float32)
         pre = torch.empty((M,), device=dev, dtype=torch.float32)
         N.check(lib.nsamd_density_mlp_fwd(N.ptr(enc), N.ptr(sel), M, mlp, N.ptr(density), N.ptr(pre), N.stream()),
@@ -494,7 +559,7 @@ class _DensityFieldFn(torch.autograd.Function):
         denc = torch.empty_like(enc)
         refs = ctx.param_refs
         (tW0, rW0), (tb0, rb0), (tW1, rW1), (tb1, rb1) = (_grad_target(r, True) for r in refs[1:])
-        mlp = N.DensityMlp(N.ptr(W0), N.ptr(b0), N.ptr(W1), N.ptr(b1), W0.shape[1], W0.shape[0], ctx.avg)
+        mlp = density_mlp(W0, b0, W1, b1, ctx.avg)
         dws = density_bwd_workspace(table.device)
         N.check(lib.nsamd_density_mlp_bwd(N.ptr(enc), N.ptr(sel), N.ptr(pre), N.ptr(gdens), M, mlp, N.ptr(denc),
                                           N.ptr(tW0), N.ptr(tb0), N.ptr(tW1), N.ptr(tb1), N.ptr(dws), dws.numel(),
@@ -504,10 +569,7 @@ class _DensityFieldFn(torch.autograd.Function):
         ttable, rtable = _grad_target(refs[0], ctx.needs_input_grad[4])
         dpos = torch.empty((M, 3), device=table.device, dtype=torch.float32) if need_pos else None
         if ttable is not None or dpos is not None:
-            ws, ws_n = _scatter_workspace(ctx.grid, table.device, M)
-            N.check(lib.nsamd_hashgrid_encode_bwd(spec.native(), M, ctx.transform, ctx.box, N.ptr(table),
-                                                  ctx.grid.native(), N.ptr(denc), 1, M, N.ptr(ttable), N.ptr(dpos),
-                                                  N.ptr(ws), ws_n, N.stream()), "hashgrid_encode_bwd")
+            table_scatter(spec.native(), M, ctx.transform, ctx.box, table, ctx.grid, denc, 1, M, ttable, dpos)
         gp, go, gd = _position_grads(spec, dpos) if dpos is not None else (None, None, None)
         return gp, go, gd, None, rtable, rW0, rb0, rW1, rb1, None, None, None, None
 
@@ -546,8 +608,7 @@ class _NerfactoFieldFn(torch.autograd.Function):
         box = aabb if isinstance(aabb, N.Aabb) else N.make_aabb(aabb)
         N.check(lib.nsamd_hashgrid_encode_fwd(spec.native(), M, transform, box, N.ptr(table), grid.native(),
                                               N.ptr(enc), 1, M, N.ptr(sel), N.stream()), "hashgrid_encode_fwd")
-        mlp = N.FieldMlp(*(N.ptr(p) for p in params), N.ptr(appearance),
-                         appearance.shape[0] if appearance is not None else 0, avg_density)
+        mlp = field_mlp(params, appearance, avg_density)
         density = torch.empty((M,), device=dev, dtype=torch.float32)
         rgb = torch.empty((M, 3), device=dev, dtype=torch.float32)
         # samples grouped by ray, a whole number of 16-sample tiles per ray: head layer 0's share of the 48 per-ray inputs once
@@ -587,11 +648,8 @@ class _NerfactoFieldFn(torch.autograd.Function):
         targets = [_grad_target(r, True) for r in refs[1:11]]
         tparams, gparams = [t for t, _ in targets], [r for _, r in targets]
         tapp, gapp = _grad_target(refs[11], True) if (appearance is not None and ctx.cams is not None) else (None, None)
-        mlp = N.FieldMlp(*(N.ptr(p) for p in params), N.ptr(appearance),
-                         appearance.shape[0] if appearance is not None else 0, ctx.avg)
-        if ctx.ray_terms is not None:
-            mlp.ray_terms, mlp.ray_inputs = N.ptr(ctx.ray_terms), N.ptr(ctx.ray_inputs)
-        grads = N.FieldMlpGrads(*(N.ptr(g) for g in tparams), N.ptr(tapp))
+        mlp = field_mlp(params, appearance, ctx.avg, ctx.ray_terms, ctx.ray_inputs)
+        grads = field_mlp_grads(tparams, tapp, lambda g: g)  # (the targets themselves)
         fws, fws_n = field_bwd_workspace(table.device)
         N.check(lib.nsamd_field_mlp_bwd(N.ptr(enc), N.ptr(sel), N.ptr(view_dirs), N.ptr(ctx.cams),
                                         N.ptr(ctx.app_const), ctx.dir_group, M, mlp, N.ptr(gdens), N.ptr(grgb),
@@ -600,10 +658,7 @@ class _NerfactoFieldFn(torch.autograd.Function):
         ttable, dtable = _grad_target(refs[0], ctx.needs_input_grad[4])
         dpos = torch.empty((M, 3), device=table.device, dtype=torch.float32) if need_pos else None
         if ttable is not None or dpos is not None:
-            ws, ws_n = _scatter_workspace(ctx.grid, table.device, M)
-            N.check(lib.nsamd_hashgrid_encode_bwd(spec.native(), M, ctx.transform, ctx.box, N.ptr(table),
-                                                  ctx.grid.native(), N.ptr(denc), 1, M, N.ptr(ttable), N.ptr(dpos),
-                                                  N.ptr(ws), ws_n, N.stream()), "hashgrid_encode_bwd")
+            table_scatter(spec.native(), M, ctx.transform, ctx.box, table, ctx.grid, denc, 1, M, ttable, dpos)
         gp, go, gd = _position_grads(spec, dpos) if dpos is not None else (None, None, None)
         return (gp, go, gd, None, dtable, *gparams, gapp, None, None, None, None, None, None, None, None)
 

@@ -297,17 +297,11 @@ class NerfactoModel(nn.Module):
         """models/base_model.py:166-175. Eval mode, one undistorted pinhole camera, no crop box: the rays of each chunk are
         generated inside the device-side chunk loop (eval_render.EvalRenderer.render_camera) — no [H, W] bundle in HBM; anything
         else generates the bundle (`camera.generate_rays(camera_indices=0, keep_shape=True)`) and takes the loop below."""
-        import os
-
         from . import eval_render
 
-        dev = next(self.parameters()).device
         args = eval_render.pinhole_camera_args(camera) if obb_box is None else None
-        if (args is not None and not self.training and dev.type == "cuda" and os.environ.get("NSAMD_EVAL_RUNNER", "1") == "1"
-                and eval_render.supported(self) is None):
-            runner = getattr(self, "_eval_runner", None)
-            if runner is None or runner.chunk != self.config.eval_num_rays_per_chunk:
-                runner = self._eval_runner = eval_render.EvalRenderer(self)
+        runner = eval_render.runner_for(self, next(self.parameters()).device) if args is not None else None
+        if runner is not None:
             return runner.render_camera(*args)
         return self.get_outputs_for_camera_ray_bundle(camera.generate_rays(camera_indices=0, keep_shape=True, obb_box=obb_box))
 
@@ -317,15 +311,10 @@ class NerfactoModel(nn.Module):
         (eval_render.EvalRenderer: one captured kernel schedule per chunk over static buffers, outputs copied into
         preallocated image buffers — no per-chunk module graph, no torch.cat); NSAMD_EVAL_RUNNER=0, training mode or an
         unsupported configuration take the reference's Python loop over `forward`."""
-        import os
-
         from . import eval_render
 
-        if (not self.training and camera_ray_bundle.origins.is_cuda and os.environ.get("NSAMD_EVAL_RUNNER", "1") == "1"
-                and eval_render.supported(self) is None):
-            runner = getattr(self, "_eval_runner", None)
-            if runner is None or runner.chunk != self.config.eval_num_rays_per_chunk:
-                runner = self._eval_runner = eval_render.EvalRenderer(self)
+        runner = eval_render.runner_for(self, camera_ray_bundle.origins.device)
+        if runner is not None:
             return runner.render(camera_ray_bundle)
         image_shape = camera_ray_bundle.origins.shape[:-1]
         num_rays = len(camera_ray_bundle)

@@ -159,13 +159,6 @@ class NgpTrainStep:
         if target is not None:
             self.target.copy_(target.reshape(-1, 3))
 
-    def _field_mlp(self) -> N.FieldMlp:
-        fld = self.model.field
-        params = [*fld.mlp_base.mlp.param_tensors(), *fld.mlp_head.param_tensors()]
-        emb = fld.embedding_appearance.embedding.weight if fld.embedding_appearance is not None else None
-        return N.FieldMlp(*(N.ptr(p) for p in params), N.ptr(emb), emb.shape[0] if emb is not None else 0,
-                          float(fld.average_init_density))
-
     # ---- forward -------------------------------------------------------------------------------------------------------
     @profiler.time_function
     @torch.no_grad()
@@ -191,9 +184,7 @@ class NgpTrainStep:
         mc = self._read_total(0)
         self.num_candidates = mc
         fld = m.field
-        enc = fld.mlp_base.encoding
-        table = enc.hash_table
-        fm = self._field_mlp()
+        fm = F.field_mlp(*F.field_params(fld), fld.average_init_density)
         mk = 0
         if mc:
             if mc > self.cap_c:
@@ -204,10 +195,8 @@ class NgpTrainStep:
             # -- sigma_fn (ray_samplers.py:420-429): density of the candidates; no direction, a constant appearance row
             ck(lib.nsamd_packed_positions(o, d, N.ptr(self.c_ri), N.ptr(self.c_ts), N.ptr(self.c_te), mc, N.ptr(self.c_pos), st),
                "packed_positions")
-            ck(lib.nsamd_hashgrid_encode_fwd(N.make_points(positions=self.c_pos), mc, fld._transform, fld._box, N.ptr(table),
-                                             self.grid.native(), N.ptr(self.c_enc), 1, mc, N.ptr(self.c_sel), st), "hashgrid_encode_fwd")
-            ck(lib.nsamd_field_mlp_fwd(N.ptr(self.c_enc), N.ptr(self.c_sel), N.ptr(self.view0), None, N.ptr(self.app0), mc, mc, fm,
-                                       N.ptr(self.c_sigma), N.ptr(self.c_rgb) if _TWO_PASS else None, st), "field_mlp_fwd")  # (rgb NULL: density only)
+            F.field_forward(fld, N.make_points(positions=self.c_pos), mc, self.c_enc, self.c_sel, self.view0, None, self.app0, mc, fm,
+                            self.c_sigma, self.c_rgb if _TWO_PASS else None)  # (rgb NULL: density only)
             # -- visibility-ordered early termination + alpha threshold, then compaction (OccGridEstimator.sampling)
             alpha = float(cfg.alpha_thre)
             if alpha > 0.0:
@@ -238,14 +227,12 @@ class NgpTrainStep:
             torch.index_select(self.cams, 0, self.k_ri[:mk], out=self.k_cams[:mk])
         ck(lib.nsamd_packed_positions(o, d, N.ptr(self.k_ri), N.ptr(self.k_ts), N.ptr(self.k_te), mk, N.ptr(self.k_pos), st),
            "packed_positions")
-        ck(lib.nsamd_hashgrid_encode_fwd(N.make_points(positions=self.k_pos), mk, fld._transform, fld._box, N.ptr(table),
-                                         self.grid.native(), N.ptr(self.k_enc), 1, mk, N.ptr(self.k_sel), st), "hashgrid_encode_fwd")
         self._app_const = None
         if self.app0 is not None and not train_app:  # eval semantics of the embedding (nerfacto_field.py:253-261)
             emb = fld.embedding_appearance.embedding.weight
             self._app_const = (emb.mean(dim=0) if fld.use_average_appearance_embedding else torch.zeros_like(emb[0])).contiguous()
-        ck(lib.nsamd_field_mlp_fwd(N.ptr(self.k_enc), N.ptr(self.k_sel), N.ptr(self.k_dirs), N.ptr(self.k_cams) if train_app else None,
-                                   N.ptr(self._app_const), 1, mk, fm, N.ptr(self.k_dens), N.ptr(self.k_rgb), st), "field_mlp_fwd")
+        F.field_forward(fld, N.make_points(positions=self.k_pos), mk, self.k_enc, self.k_sel, self.k_dirs,
+                        self.k_cams if train_app else None, self._app_const, 1, fm, self.k_dens, self.k_rgb)
         self._train_app = train_app
         # -- packed weights and the three renderers in one launch (models/instant_ngp.py:191-214)
         ck(lib.nsamd_packed_weights_fwd(N.ptr(self.k_ts), N.ptr(self.k_te), N.ptr(self.k_dens), N.ptr(self.info2), n, N.ptr(self.k_w),
@@ -308,40 +295,22 @@ class NgpTrainStep:
         m, n, mk = self.model, self.n, self.num_kept
         lib, st, ck = N.load(), N.stream(), N.check
         fld = m.field
-        enc = fld.mlp_base.encoding
-        table = enc.hash_table
         self.prepare_grads()
         ck(lib.nsamd_packed_composite_bwd(N.ptr(self.k_rgb), N.ptr(self.k_w), N.ptr(self.k_ri), mk, self.bg_mode, self.bg_vals,
                                           N.ptr(self.g_rgb), N.ptr(self.g_acc) if self.random_bg else None, N.ptr(self.k_drgb),
                                           N.ptr(self.k_dw), st), "packed_composite_bwd")
         ck(lib.nsamd_packed_weights_bwd(N.ptr(self.k_ts), N.ptr(self.k_te), N.ptr(self.k_dens), N.ptr(self.k_dw), N.ptr(self.info2), n,
                                         N.ptr(self.k_dsigma), st), "packed_weights_bwd")
-        params = [*fld.mlp_base.mlp.param_tensors(), *fld.mlp_head.param_tensors()]
-        emb = fld.embedding_appearance.embedding.weight if fld.embedding_appearance is not None else None
+        params, emb = F.field_params(fld)
         gl = self.grad_lookup
         grad_of = (lambda p: gl[id(p)]) if gl is not None else (lambda p: p.grad)  # noqa: E731
-        grads = N.FieldMlpGrads(*(N.ptr(grad_of(p)) for p in params), N.ptr(grad_of(emb)) if (emb is not None and self._train_app) else None)
-        fws, fws_n = F.field_bwd_workspace(self.dev)
-        write_only = not self.accumulate_table
-        if write_only and self.fuse_route and self.grid.num_levels == 16:
-            # as the nerfacto schedule does (train_step.backward_field_and_table): the field backward emits the table scatter's
-            # pass-1 records from its registers — no `denc` round trip, no route launch over the kept samples
-            # (NSAMD_NGP_FUSE_ROUTE=0: the two entry points, A/B)
-            sws, sws_n = F._producer_scatter_workspace(self.grid, self.dev, mk)
-            if sws is not None:
-                ck(lib.nsamd_field_mlp_bwd_scatter(
-                    N.make_points(positions=self.k_pos), fld._transform, fld._box, self.grid.native(), N.ptr(self.k_enc),
-                    N.ptr(self.k_sel), N.ptr(self.k_dirs), N.ptr(self.k_cams) if self._train_app else None, N.ptr(self._app_const), 1,
-                    mk, self._field_mlp(), N.ptr(self.k_dsigma), N.ptr(self.k_drgb), None, grads, N.ptr(fws), fws_n,
-                    N.ptr(grad_of(table)), N.ptr(sws), sws_n, st), "field_mlp_bwd_scatter")
-                return
-        ck(lib.nsamd_field_mlp_bwd(N.ptr(self.k_enc), N.ptr(self.k_sel), N.ptr(self.k_dirs), N.ptr(self.k_cams) if self._train_app else None,
-                                   N.ptr(self._app_const), 1, mk, self._field_mlp(), N.ptr(self.k_dsigma), N.ptr(self.k_drgb),
-                                   N.ptr(self.k_denc), grads, N.ptr(fws), fws_n, st), "field_mlp_bwd")
-        ws, ws_n = F._scatter_workspace(self.grid, self.dev, mk, write_only=write_only)
-        fn = lib.nsamd_hashgrid_encode_bwd_set if write_only else lib.nsamd_hashgrid_encode_bwd
-        ck(fn(N.make_points(positions=self.k_pos), mk, fld._transform, fld._box, N.ptr(table), self.grid.native(), N.ptr(self.k_denc), 1, mk,
-              N.ptr(grad_of(table)), None, N.ptr(ws), ws_n, st), "hashgrid_encode_bwd")
+        # as the nerfacto schedule does (train_step.backward_field_and_table): while the table's gradient is written, the field
+        # backward emits the table scatter's pass-1 records from its registers (NSAMD_NGP_FUSE_ROUTE=0: the two entry points, A/B)
+        F.field_backward(fld, N.make_points(positions=self.k_pos), mk, self.k_enc, self.k_sel, self.k_dirs,
+                         self.k_cams if self._train_app else None, self._app_const, 1,
+                         F.field_mlp(params, emb, fld.average_init_density), self.k_dsigma, self.k_drgb, self.k_denc,
+                         F.field_mlp_grads(params, emb if self._train_app else None, grad_of), F.field_bwd_workspace(self.dev)[0],
+                         grad_of(fld.mlp_base.encoding.hash_table), not self.accumulate_table, fuse=self.fuse_route)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

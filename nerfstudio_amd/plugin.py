@@ -156,19 +156,12 @@ def _model_classes():
             generated inside the device-side chunk loop (EvalRenderer.render_camera over nsamd_raygen_pinhole_grid: the arithmetic
             of `camera.generate_rays(camera_indices=0, keep_shape=True)`, cameras/cameras.py:321-503) — no [H, W] ray bundle is
             built. Anything else is the reference's own path."""
-            import os
-
             from . import eval_render
 
             self._flush_pending()
-            col = getattr(self, "collider", None)
             args = eval_render.pinhole_camera_args(camera) if obb_box is None else None
-            if (args is not None and not self.training and self.device.type == "cuda" and os.environ.get("NSAMD_EVAL_RUNNER", "1") == "1"
-                    and eval_render.supported(self) is None and getattr(col, "near_plane", None) == self.config.near_plane
-                    and getattr(col, "far_plane", None) == self.config.far_plane):
-                runner = getattr(self, "_eval_runner", None)
-                if runner is None or runner.chunk != self.config.eval_num_rays_per_chunk:
-                    runner = self._eval_runner = eval_render.EvalRenderer(self)
+            runner = eval_render.runner_for(self, self.device) if (args is not None and self._collider_is_configs()) else None
+            if runner is not None:
                 return runner.render_camera(*args)
             return super().get_outputs_for_camera(camera, obb_box=obb_box)
 
@@ -179,21 +172,20 @@ def _model_classes():
             per-chunk module graph, no torch.cat — 30.5 against 23.3 M rays/s, profiles/r03_final2_bench_render_*.json; same
             outputs bit for bit, tests/test_gpu_kernels.py); anything else takes the reference's own loop.
             NSAMD_EVAL_RUNNER=0 switches it off."""
-            import os
-
             from . import eval_render
 
             self._flush_pending()
-            col = getattr(self, "collider", None)
-            if (not self.training and camera_ray_bundle.origins.is_cuda and os.environ.get("NSAMD_EVAL_RUNNER", "1") == "1"
-                    and camera_ray_bundle.origins.device == self.device and eval_render.supported(self) is None
-                    and getattr(col, "near_plane", None) == self.config.near_plane
-                    and getattr(col, "far_plane", None) == self.config.far_plane):
-                runner = getattr(self, "_eval_runner", None)
-                if runner is None or runner.chunk != self.config.eval_num_rays_per_chunk:
-                    runner = self._eval_runner = eval_render.EvalRenderer(self)
+            dev = camera_ray_bundle.origins.device
+            runner = eval_render.runner_for(self, dev) if (dev == self.device and self._collider_is_configs()) else None
+            if runner is not None:
                 return runner.render(camera_ray_bundle)
             return super().get_outputs_for_camera_ray_bundle(camera_ray_bundle)
+
+        def _collider_is_configs(self):
+            """The device-side chunk loop samples between the config's near / far planes: only a model whose collider does too."""
+            col = getattr(self, "collider", None)
+            return (getattr(col, "near_plane", None) == self.config.near_plane
+                    and getattr(col, "far_plane", None) == self.config.far_plane)
 
         def get_loss_dict(self, outputs, batch, metrics_dict=None):
             """models/nerfacto.py:363-392 with the proposal losses on the fused HIP kernels (the reference's torch

@@ -414,17 +414,19 @@ class NerfactoTrainStep:
         self._corrected = None
 
     @profiler.time_function
-    def forward_proposals(self, draw_jitter: bool = True, need_enc: bool = True, after_bins=None) -> None:
+    def forward_proposals(self, draw_jitter: bool = True, need_enc: bool = True, after_bins=None,
+                          stratified: bool = True) -> None:
         """Initial bins and the proposal levels (density fields + resampling): reads only the proposal networks'
         parameters, so with data parallelism it can run while the main-field gradients of the previous step are still
         being all-reduced (bench.py). need_enc: keep the levels' encoded features / selector / pre-activation for
         backward_proposals (False on the steps where the proposal networks get no gradient, ray_samplers.py:590: the
         fused forward then writes nothing but the densities). after_bins: called right behind the launch that writes the
-        initial bins (and selects the batch), before the proposal levels."""
+        initial bins (and selects the batch), before the proposal levels. stratified=False: eval sampling (ray_samplers.py:
+        104-111, 323-327) — bin centres in the initial sampler, the fixed offset in the PDF resampling, nothing drawn."""
         lib, st, n = N.load(), N.stream(), self.n
         ck = N.check
-        per_edge = not self.single_jitter
-        if draw_jitter:
+        per_edge = stratified and not self.single_jitter
+        if draw_jitter and stratified:
             if per_edge:
                 for j in self.jitter_edges:
                     j.uniform_()
@@ -433,7 +435,7 @@ class NerfactoTrainStep:
             if self.bg_rays is not None:
                 self.bg_rays.uniform_()  # rand_like(pred) of the loss blend (renderers.py:195)
         S0 = self.counts[0]
-        jit0 = self.jitter_edges[0] if per_edge else self.jitter[0]
+        jit0 = (self.jitter_edges[0] if per_edge else self.jitter[0]) if stratified else None
         sel, self.pending_select = self.pending_select, None
         if sel is not None:
             # the step's batch out of the caller's pool of batches AND the initial bins in one launch (trainer.HipTrainer hands
@@ -453,10 +455,7 @@ class NerfactoTrainStep:
         for lvl in range(self.n_prop):
             net = self.props[lvl]
             S, m = self.counts[lvl], n * self.counts[lvl]
-            mlp = net.mlp_base[1]
-            W0, b0, W1, b1 = mlp.param_tensors()
-            dm = N.DensityMlp(N.ptr(W0), N.ptr(b0), N.ptr(W1), N.ptr(b1), W0.shape[1], W0.shape[0],
-                              float(net.average_init_density))
+            dm = F.density_mlp(*net.mlp_base[1].param_tensors(), net.average_init_density)
             # hash grid + MLP + trunc_exp in one launch, features in registers (nsamd_density_field_fwd); networks the
             # fused kernel is not built for go through the two-kernel pair
             fused = lib.nsamd_density_field_fwd(
@@ -464,11 +463,12 @@ class NerfactoTrainStep:
                 N.ptr(self.p_enc[lvl]) if need_enc else None, N.ptr(self.p_sel[lvl]) if need_enc else None,
                 N.ptr(self.p_dens[lvl]), N.ptr(self.p_pre[lvl]) if need_enc else None, st)
             if fused == N.ERR_UNSUPPORTED:
+                self.ensure_proposal_features(lvl)
                 ck(lib.nsamd_hashgrid_encode_fwd(self._points(lvl), m, net._transform, net._box, N.ptr(net.encoding.hash_table),
                                                  net.encoding.spec.native(), N.ptr(self.p_enc[lvl]), 1, m,
                                                  N.ptr(self.p_sel[lvl]), st), "hashgrid_encode_fwd")
                 ck(lib.nsamd_density_mlp_fwd(N.ptr(self.p_enc[lvl]), N.ptr(self.p_sel[lvl]), m, dm, N.ptr(self.p_dens[lvl]),
-                                             N.ptr(self.p_pre[lvl]), st), "density_mlp_fwd")
+                                             None if self.forward_only else N.ptr(self.p_pre[lvl]), st), "density_mlp_fwd")
             else:
                 ck(fused, "density_field_fwd")
             S2 = self.counts[lvl + 1]
@@ -487,7 +487,8 @@ class NerfactoTrainStep:
                 continue
             # weights of this level, its median depth (prop_depth_i, models/nerfacto.py:346-347) and the PDF resampling
             ck(lib.nsamd_proposal_resample(N.ptr(self.t_bins[lvl]), N.ptr(self.s_bins[lvl]), N.ptr(self.p_dens[lvl]), S,
-                                           N.ptr(self.u_base[lvl + 1]), N.ptr(self.jitter[lvl + 1]), N.ptr(self.nears),
+                                           N.ptr(self.u_base[lvl + 1]), N.ptr(self.jitter[lvl + 1]) if stratified else None,
+                                           N.ptr(self.nears),
                                            N.ptr(self.fars), 1.0, N.ptr(self.anneal_dev), 0.01, 1e-5,
                                            1.0 / (2 * (S2 + 1)), self.spacing, n, S2, N.ptr(self.weights[lvl]),
                                            N.ptr(self.depth_med[lvl]) if self.compute_depths else None,
@@ -499,44 +500,38 @@ class NerfactoTrainStep:
         self.forward_main(terms_ready)
         self.losses(updated)
 
-    def ray_terms_launch(self) -> None:
+    def _field_mlp(self) -> N.FieldMlp:
+        fld = self.model.field
+        return F.field_mlp(*F.field_params(fld), fld.average_init_density)
+
+    def _cams(self, app_const: Optional[Tensor]) -> Optional[Tensor]:
+        """The camera indices the main field reads its appearance rows by (None: no appearance table, or `app_const`)."""
+        return self.camera_indices if (self.model.field.embedding_appearance is not None and app_const is None) else None
+
+    def ray_terms_launch(self, fm: Optional[N.FieldMlp] = None, app_const: Optional[Tensor] = None) -> None:
         """nsamd_field_ray_terms for the batch in the static buffers: head layer 0's share of the 48 per-ray inputs. Needs the
         batch's (pose-corrected) directions and camera indices and the CURRENT head_W0 / head_b0 / appearance table — i.e. it
-        runs after batch selection and after the main-field Adam of the previous iteration. On torch's current stream."""
-        lib, st, n = N.load(), N.stream(), self.n
-        fld = self.model.field
-        params = [*fld.mlp_base.mlp.param_tensors(), *fld.mlp_head.param_tensors()]
-        emb = fld.embedding_appearance.embedding.weight if fld.embedding_appearance is not None else None
-        fm = N.FieldMlp(*(N.ptr(p) for p in params), N.ptr(emb), emb.shape[0] if emb is not None else 0,
-                        float(fld.average_init_density))
-        cams = N.ptr(self.camera_indices) if emb is not None else None
-        N.check(lib.nsamd_field_ray_terms(N.ptr(self.directions), cams, None, n, fm, N.ptr(self.ray_terms), N.ptr(self.ray_inputs),
-                                          st), "field_ray_terms")
+        runs after batch selection and after the main-field Adam of the previous iteration. On torch's current stream.
+        app_const: see forward_main (the per-ray inputs are then not kept: no backward reads them)."""
+        inputs = self.ray_inputs if app_const is None else None
+        N.check(N.load().nsamd_field_ray_terms(N.ptr(self.directions), N.ptr(self._cams(app_const)), N.ptr(app_const), self.n,
+                                               fm if fm is not None else self._field_mlp(), N.ptr(self.ray_terms), N.ptr(inputs),
+                                               N.stream()), "field_ray_terms")
 
     @profiler.time_function
-    def forward_main(self, terms_ready: bool = False) -> None:
+    def forward_main(self, terms_ready: bool = False, app_const: Optional[Tensor] = None) -> None:
         """Hash grid + MLPs of the main field on the final samples -> per-sample density and rgb. terms_ready: the caller has
-        launched `ray_terms_launch` for this batch and these parameters itself (trainer.HipTrainer: off the critical path)."""
-        lib, st, n, cfg = N.load(), N.stream(), self.n, self.cfg
-        ck = N.check
-        fld = self.model.field
+        launched `ray_terms_launch` for this batch and these parameters itself (trainer.HipTrainer: off the critical path).
+        app_const: one appearance row for every sample instead of the rays' cameras' (eval mode, eval_render.EvalRenderer)."""
         L = self.n_prop
-        S, mm = self.counts[L], self.m_main
-        enc = fld.mlp_base.encoding
-        params = [*fld.mlp_base.mlp.param_tensors(), *fld.mlp_head.param_tensors()]
-        emb = fld.embedding_appearance.embedding.weight if fld.embedding_appearance is not None else None
-        fm = N.FieldMlp(*(N.ptr(p) for p in params), N.ptr(emb), emb.shape[0] if emb is not None else 0,
-                        float(fld.average_init_density))
-        cams = N.ptr(self.camera_indices) if emb is not None else None
+        fm = self._field_mlp()
         if self.ray_terms_on:
             if not terms_ready:
-                self.ray_terms_launch()
-            fm.ray_terms, fm.ray_inputs = N.ptr(self.ray_terms), N.ptr(self.ray_inputs)
-        ck(lib.nsamd_hashgrid_encode_fwd(self._points(L), mm, fld._transform, fld._box, N.ptr(enc.hash_table),
-                                         enc.spec.native(), N.ptr(self.f_enc), 1, mm, N.ptr(self.f_sel), st),
-           "hashgrid_encode_fwd")
-        ck(lib.nsamd_field_mlp_fwd(N.ptr(self.f_enc), N.ptr(self.f_sel), N.ptr(self.directions), cams, None, S, mm, fm,
-                                   N.ptr(self.f_dens), N.ptr(self.f_rgb), st), "field_mlp_fwd")
+                self.ray_terms_launch(fm, app_const)
+            fm.ray_terms = N.ptr(self.ray_terms)
+            fm.ray_inputs = N.ptr(self.ray_inputs if app_const is None else None)
+        F.field_forward(self.model.field, self._points(L), self.m_main, self.f_enc, self.f_sel, self.directions,
+                        self._cams(app_const), app_const, self.counts[L], fm, self.f_dens, self.f_rgb)
 
     @profiler.time_function
     def losses(self, updated: bool) -> None:
@@ -587,79 +582,44 @@ class NerfactoTrainStep:
 
     def backward_field_and_table(self) -> None:
         """Second half of backward_main: the main field's MLPs (from `d_dens_main`, `d_rgb_s`) and the table scatter. Separate
-        so that tests can drive the field backward with upstream gradients of their own."""
-        lib, st, n = N.load(), N.stream(), self.n
-        ck = N.check
+        so that tests can drive the field backward with upstream gradients of their own. The table's gradient is written, or
+        accumulated into an existing one (prepare_grads)."""
         fld = self.model.field
         L = self.n_prop
-        S, mm = self.counts[L], self.m_main
-        enc = fld.mlp_base.encoding
-        params = [*fld.mlp_base.mlp.param_tensors(), *fld.mlp_head.param_tensors()]
-        emb = fld.embedding_appearance.embedding.weight if fld.embedding_appearance is not None else None
-        fm = N.FieldMlp(*(N.ptr(p) for p in params), N.ptr(emb), emb.shape[0] if emb is not None else 0,
-                        float(fld.average_init_density))
-        cams = N.ptr(self.camera_indices) if emb is not None else None
-        if self.ray_terms_on:  # (what forward_main computed for this batch and these parameters)
-            fm.ray_terms, fm.ray_inputs = N.ptr(self.ray_terms), N.ptr(self.ray_inputs)
-        grads = N.FieldMlpGrads(*(N.ptr(self._grad(p)) for p in params), N.ptr(self._grad(emb)) if emb is not None else None)
-        if self.fuse_route and self.main_table_write_only and enc.spec.num_levels == 16:
-            sws, sws_n = F._producer_scatter_workspace(enc.spec, self.f_enc.device, mm)
-            if sws is not None:
-                want_denc = self.cam_opt is not None or self.keep_denc  # the camera optimiser's share needs the feature gradient as well
-                args = (self._points(L), fld._transform, fld._box, enc.spec.native(), N.ptr(self.f_enc), N.ptr(self.f_sel),
-                        N.ptr(self.directions), cams, None, S, mm, fm, N.ptr(self.d_dens_main), N.ptr(self.d_rgb_s),
-                        N.ptr(self.f_denc) if want_denc else None, grads, N.ptr(self.field_ws), self.field_ws.numel(),
-                        N.ptr(self._grad(enc.hash_table)), N.ptr(sws), sws_n)
-                if N.PROFILE is not None:  # the per-kernel table (utils/roofline.py): one launch group at a time, same bits
-                    for phase in (1, 2, 4):
-                        ck(lib.nsamd_field_mlp_bwd_scatter_phase(*args, phase, st), "field_mlp_bwd_scatter_phase")
-                elif self.cam_opt is not None:
-                    # camera optimiser: the rays' gradient through the main grid (a gather pass over the table, 96 us) needs the
-                    # encoded-feature gradient the kernel has just written and nothing of the table scatter's apply pass (LDS
-                    # atomics, latency-bound): beside it on the second stream instead of behind it
-                    ck(lib.nsamd_field_mlp_bwd_scatter_phase(*args, 1, st), "field_mlp_bwd_scatter_phase")
-                    main = N.current_stream()
-                    self._red_fork.record(main)
-                    self.reduce_stream.wait_event(self._red_fork)
-                    with N.on_stream(self.reduce_stream):
-                        self._rays_backward(L, fld, self.f_denc)
-                        self._red_join.record(self.reduce_stream)
-                    ck(lib.nsamd_field_mlp_bwd_scatter_phase(*args, 6, st), "field_mlp_bwd_scatter_phase")  # (the reduce rides the apply pass)
-                    main.wait_event(self._red_join)
-                    return
-                else:
-                    ck(lib.nsamd_field_mlp_bwd_scatter(*args, st), "field_mlp_bwd_scatter")
-                if self.cam_opt is not None:
-                    self._rays_backward(L, fld, self.f_denc)
-                return
-        ck(lib.nsamd_field_mlp_bwd(N.ptr(self.f_enc), N.ptr(self.f_sel), N.ptr(self.directions), cams, None, S, mm, fm,
-                                   N.ptr(self.d_dens_main), N.ptr(self.d_rgb_s), N.ptr(self.f_denc), grads,
-                                   N.ptr(self.field_ws), self.field_ws.numel(), st), "field_mlp_bwd")
-        if self.cam_opt is not None:
-            self._rays_backward(L, fld, self.f_denc)
-        self.backward_table()
+        params, emb = F.field_params(fld)
+        # (the ray terms are what forward_main computed for this batch and these parameters)
+        fm = F.field_mlp(params, emb, fld.average_init_density, self.ray_terms, self.ray_inputs)
+        cam = self.cam_opt is not None  # the camera optimiser's share needs the encoded-feature gradient as well
+        F.field_backward(fld, self._points(L), self.m_main, self.f_enc, self.f_sel, self.directions, self._cams(None), None,
+                         self.counts[L], fm, self.d_dens_main, self.d_rgb_s, self.f_denc, F.field_mlp_grads(params, emb, self._grad),
+                         self.field_ws, self._grad(fld.mlp_base.encoding.hash_table), self.main_table_write_only,
+                         fuse=self.fuse_route, keep_denc=cam or self.keep_denc,
+                         on_denc=(lambda: self._rays_backward(L, fld, self.f_denc)) if cam else None,
+                         fused_launch=self._field_bwd_phases if (cam or N.PROFILE is not None) else None)
 
-    def backward_table(self) -> None:
-        """The main table's gradient scatter from `f_denc`."""
-        lib, st = N.load(), N.stream()
-        ck = N.check
-        fld = self.model.field
-        L = self.n_prop
-        mm = self.m_main
-        enc = fld.mlp_base.encoding
-        pts = self._points(L)
-        if self.main_table_write_only:
-            ws, ws_n = F._scatter_workspace(enc.spec, self.f_enc.device, mm, write_only=True)
-            ck(lib.nsamd_hashgrid_encode_bwd_set(pts, mm, fld._transform, fld._box, N.ptr(enc.hash_table),
-                                                 enc.spec.native(), N.ptr(self.f_denc), 1, mm,
-                                                 N.ptr(self._grad(enc.hash_table)), None, N.ptr(ws), ws_n, st),
-               "hashgrid_encode_bwd")
-        else:  # accumulate into an existing gradient (prepare_grads)
-            ws, ws_n = F._scatter_workspace(enc.spec, self.f_enc.device, mm)
-            ck(lib.nsamd_hashgrid_encode_bwd(pts, mm, fld._transform, fld._box, N.ptr(enc.hash_table),
-                                             enc.spec.native(), N.ptr(self.f_denc), 1, mm,
-                                             N.ptr(self._grad(enc.hash_table)), None, N.ptr(ws), ws_n, st),
-               "hashgrid_encode_bwd")
+    def _field_bwd_phases(self, args) -> None:
+        """The fused main-field backward (nsamd_field_mlp_bwd_scatter) as separate phases: under N.PROFILE one launch group at
+        a time (the per-kernel table, utils/roofline.py; same bits), else for the camera optimiser's share."""
+        lib, st, ck = N.load(), N.stream(), N.check
+        L, fld = self.n_prop, self.model.field
+        if N.PROFILE is not None:
+            for phase in (1, 2, 4):
+                ck(lib.nsamd_field_mlp_bwd_scatter_phase(*args, phase, st), "field_mlp_bwd_scatter_phase")
+            if self.cam_opt is not None:
+                self._rays_backward(L, fld, self.f_denc)
+            return
+        # camera optimiser: the rays' gradient through the main grid (a gather pass over the table, 96 us) needs the
+        # encoded-feature gradient the kernel has just written and nothing of the table scatter's apply pass (LDS
+        # atomics, latency-bound): beside it on the second stream instead of behind it
+        ck(lib.nsamd_field_mlp_bwd_scatter_phase(*args, 1, st), "field_mlp_bwd_scatter_phase")
+        main = N.current_stream()
+        self._red_fork.record(main)
+        self.reduce_stream.wait_event(self._red_fork)
+        with N.on_stream(self.reduce_stream):
+            self._rays_backward(L, fld, self.f_denc)
+            self._red_join.record(self.reduce_stream)
+        ck(lib.nsamd_field_mlp_bwd_scatter_phase(*args, 6, st), "field_mlp_bwd_scatter_phase")  # (the reduce rides the apply pass)
+        main.wait_event(self._red_join)
 
     @profiler.time_function
     def backward_proposals(self, levels=None) -> None:
@@ -679,10 +639,8 @@ class NerfactoTrainStep:
         for lvl in lvls:
             net = self.props[lvl]
             S, m = self.counts[lvl], n * self.counts[lvl]
-            mlp = net.mlp_base[1]
-            W0, b0, W1, b1 = mlp.param_tensors()
-            dm = N.DensityMlp(N.ptr(W0), N.ptr(b0), N.ptr(W1), N.ptr(b1), W0.shape[1], W0.shape[0],
-                              float(net.average_init_density))
+            W0, b0, W1, b1 = net.mlp_base[1].param_tensors()
+            dm = F.density_mlp(W0, b0, W1, b1, net.average_init_density)
             gate = self._gate(lvl)
             dws = self.density_ws[lvl]
             spec = net.encoding.spec
@@ -696,10 +654,8 @@ class NerfactoTrainStep:
                                              N.ptr(dws), dws.numel(), st), "density_mlp_bwd")
                 if self.cam_opt is not None:
                     self._rays_backward(lvl, net, self.p_denc[lvl])
-                ck(lib.nsamd_hashgrid_encode_bwd(self._points(lvl), m, net._transform, net._box,
-                                                 N.ptr(net.encoding.hash_table), spec.native(), N.ptr(self.p_denc[lvl]),
-                                                 1, m, N.ptr(self._grad(net.encoding.hash_table)), None, N.ptr(ws), ws_n,
-                                                 st), "hashgrid_encode_bwd")
+                F.table_scatter(self._points(lvl), m, net._transform, net._box, net.encoding.hash_table, spec, self.p_denc[lvl],
+                                1, m, self._grad(net.encoding.hash_table))
                 continue
             # the weights backward raises the level's flag when any ray carries interlevel gradient; the rest of the
             # chain returns at once while it is clear (the zero-filled gradients are then already the result)
@@ -737,8 +693,7 @@ class NerfactoTrainStep:
             e.t_bins, e.density, e.dweights = N.ptr(self.t_bins[lvl]), N.ptr(self.p_dens[lvl]), N.ptr(self.dw_prop[lvl])
             e.ddensity, e.gate, e.ray_mask = N.ptr(self.p_ddens[lvl]), self._gate(lvl), N.ptr(self.prop_ray_masks[lvl])
             e.enc, e.selector, e.pre = N.ptr(self.p_enc[lvl]), N.ptr(self.p_sel[lvl]), N.ptr(self.p_pre[lvl])
-            e.mlp = N.DensityMlp(N.ptr(W0), N.ptr(b0), N.ptr(W1), N.ptr(b1), W0.shape[1], W0.shape[0],
-                                 float(net.average_init_density))
+            e.mlp = F.density_mlp(W0, b0, W1, b1, net.average_init_density)
             e.denc = N.ptr(self.p_denc[lvl])
             e.dW0, e.db0, e.dW1, e.db1 = (N.ptr(self._grad(t)) for t in (W0, b0, W1, b1))
             e.mlp_workspace, e.mlp_workspace_floats = N.ptr(dws), dws.numel()
