@@ -104,6 +104,47 @@ def hashgrid_encode(x: Tensor, table: Tensor, scalings: Tensor, table_size: int)
     return torch.cat(outs, dim=-1).reshape(M, -1)
 
 
+# corners in the order `hashgrid_encode` gathers them: (x ceil, y ceil, z ceil)
+_CORNERS = ((True, True, True), (False, True, True), (True, False, True), (False, False, True),
+            (True, False, False), (False, False, False), (True, True, False), (False, True, False))
+
+
+def hashgrid_scatter64(x: Tensor, denc: Tensor, scalings: Tensor, table_size: int) -> Tuple[Tensor, Tensor, Tensor]:
+    """Float64 table gradient of `hashgrid_encode` (its backward, an index_put accumulate into `[L*T, 2]`).
+
+    x: `[M,3]` fp32 grid inputs (already normalised); denc: `[M, 2L]` fp32 feature gradient. Every contribution is
+    c = g * w with w the product of the three fp32 axis weights of `hashgrid_encode` (`scaled - floor`, `1 - w`), taken in
+    autograd's order ((g*wz)*wy)*wx in float64; a corner of an integral coordinate (ceil == floor) counts twice, as
+    autograd counts it. Returns float64 `[L*T, 2]` tensors (ref = sum c, abs = sum |c|, count = number of contributions).
+    The sum runs corner by corner in the order autograd accumulates the gathers' gradients (the last gather first), each
+    corner's partial over the points in index order, so with a float64 table it is autograd's result bit for bit."""
+    M, L = x.shape[0], scalings.numel()
+    ref = torch.zeros(L, table_size * 2, dtype=torch.float64)
+    acc = torch.zeros_like(ref)
+    cnt = torch.zeros_like(ref)
+    part = torch.empty(table_size * 2, dtype=torch.float64)
+    g = denc.reshape(M, L, 2).to(torch.float64)
+    ones = torch.ones(2 * M, dtype=torch.float64)
+    for lvl in range(L):
+        scaled = x * scalings[lvl]
+        lo = torch.floor(scaled)
+        hi = torch.ceil(scaled)
+        w = scaled - lo
+        lo_i = lo.numpy().astype(np.int32)
+        hi_i = hi.numpy().astype(np.int32)
+        wc, wf = w.to(torch.float64), (1 - w).to(torch.float64)
+        for cx, cy, cz in reversed(_CORNERS):
+            idx = hash_corner_index((hi_i if cx else lo_i)[:, 0], (hi_i if cy else lo_i)[:, 1], (hi_i if cz else lo_i)[:, 2],
+                                    0, table_size)
+            flat = (2 * torch.from_numpy(idx)[:, None] + torch.arange(2)).reshape(-1)
+            c = ((g[:, lvl] * (wc if cz else wf)[:, 2:3]) * (wc if cy else wf)[:, 1:2]) * (wc if cx else wf)[:, 0:1]
+            part.zero_().index_add_(0, flat, c.reshape(-1))
+            ref[lvl] += part
+            acc[lvl].index_add_(0, flat, c.abs().reshape(-1))
+            cnt[lvl].index_add_(0, flat, ones)
+    return ref.view(-1, 2), acc.view(-1, 2), cnt.view(-1, 2)
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # a7  L-inf scene contraction   (field_components/spatial_distortions.py:66-69)
 # ---------------------------------------------------------------------------------------------------------------
