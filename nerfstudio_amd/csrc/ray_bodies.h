@@ -768,9 +768,12 @@ __device__ __forceinline__ void interlevel_body(
         dwp[ray * Sp + k] = g * grad_scale;
       }
     } else {
+      // d outer_i / d wp_k = [k <= hi_i] - [k < lo_i] (the gather of the prefix sums, losses.py:71-82): the cover [lo_i, hi_i]
+      // when lo_i <= hi_i, MINUS the range (hi_i, lo_i) when an unsorted row gives lo_i > hi_i. (rr - rr = 0 and rr - 0 = rr:
+      // on every other interval the same bits as a test of the range alone.)
       for (int k = lane; k < Sp; k += 64) {
         float g = 0.0f;
-        for (int i = 0; i < Sf; ++i) g -= (lo_i[i] <= k && k <= hi_i[i]) ? rr[i] : 0.0f;
+        for (int i = 0; i < Sf; ++i) g -= (k <= hi_i[i] ? rr[i] : 0.0f) - (k < lo_i[i] ? rr[i] : 0.0f);
         dwp[ray * Sp + k] = g * grad_scale;
       }
     }

@@ -495,6 +495,66 @@ def weights_from_density(t_bins: Tensor, density: Tensor) -> Tensor:
     return torch.nan_to_num(alphas * torch.exp(-acc))
 
 
+
+def weights_bwd64(t_bins: Tensor, density: Tensor, dweights: Tensor) -> Dict[str, Tensor]:
+    """Float64 backward of `weights_from_density` on fp32 (or float64) inputs: autograd's own sequence of operations
+    (nan_to_num passes the gradient where the weight is finite, as grad * isfinite(w); the cumsum's backward is the
+    reversed cumsum), so with float64 inputs it is autograd's result bit for bit. Returns float64 `[N,S]` tensors:
+    ddensity; suf = sum_{i>j} g_i w_i (the exclusive suffix sum of the masked gradient times the weight) and suf_abs =
+    sum_{i>j} |g_i w_i|; X = the optical depth in front of sample j, dd = delta_j * density_j, delta, E = exp(-X),
+    e = exp(-dd), alpha = 1 - e, w = alpha * E (before nan_to_num), g = the masked upstream gradient."""
+    t, dens, gw = t_bins.double(), density.double(), dweights.double()
+    delta = t[:, 1:] - t[:, :-1]
+    dd = delta * dens
+    e = torch.exp(-dd)
+    alpha = 1 - e
+    X = torch.cat([torch.zeros_like(dd[:, :1]), torch.cumsum(dd[:, :-1], dim=-1)], dim=-1)
+    E = torch.exp(-X)
+    w = alpha * E
+    g = gw * torch.isfinite(w)
+    d_acc = -((g * alpha) * E)  # d loss / d X_i
+    rev = torch.flip(torch.cumsum(torch.flip(d_acc[:, 1:], [-1]), dim=-1), [-1])  # sum_{i>j} d_acc_i, j < S-1
+    d_dd = (g * E) * e + torch.cat([rev, torch.zeros_like(dd[:, :1])], dim=-1)
+    gwv = g * w
+    suf = torch.cat([torch.flip(torch.cumsum(torch.flip(gwv[:, 1:], [-1]), dim=-1), [-1]), torch.zeros_like(dd[:, :1])], -1)
+    suf_abs = torch.cat([torch.flip(torch.cumsum(torch.flip(gwv[:, 1:].abs(), [-1]), dim=-1), [-1]),
+                         torch.zeros_like(dd[:, :1])], -1)
+    return dict(ddensity=d_dd * delta, suf=suf, suf_abs=suf_abs, X=X, dd=dd, delta=delta, E=E, e=e, alpha=alpha, w=w, g=g)
+
+
+def composite_bwd64(rgb: Tensor, weights: Tensor, d_rgb_out: Tensor, background: int, bg_color=None,
+                    bg_rays: Optional[Tensor] = None, d_weights_add: Optional[Tensor] = None) -> Dict[str, Tensor]:
+    """Float64 gradient of the training composite (`composite_rgb` in training mode, the loss blend of background
+    "random") with respect to the per-sample colours and weights, for the upstream gradient d_rgb_out `[N,3]` of the
+    composited colour: the `nsamd_render_train_bwd` contract. background: 0 none, 1 last_sample, 2 the constant colour
+    bg_color (3 floats), 3 the per-ray colours bg_rays `[N,3]` of the loss blend. d_weights_add `[N,S]` (nullable) is
+    added to the weights' gradient. Returns d_rgb `[N,S,3]`, d_weights `[N,S]` and their abs companions: d_rgb_abs (the
+    terms of the last sample's d_rgb under last_sample: |g| (w + |1 - acc|)), dw_abs = sum |terms| of d_weights."""
+    c, w, g = rgb.double(), weights.double(), d_rgb_out.double()
+    N, S = w.shape
+    if background == 1:
+        bg = c[:, -1, :]
+    elif background == 2:
+        bg = torch.tensor([float(v) for v in bg_color], dtype=torch.float64).expand(N, 3)
+    elif background == 3:
+        bg = bg_rays.double()
+    else:
+        bg = torch.zeros(N, 3, dtype=torch.float64)
+    dw = (g[:, None, :] * c).sum(-1) - (g * bg).sum(-1, keepdim=True)
+    dw_abs = (g[:, None, :] * c).abs().sum(-1) + (g * bg).abs().sum(-1, keepdim=True)
+    if d_weights_add is not None:
+        dw = dw + d_weights_add.double()
+        dw_abs = dw_abs + d_weights_add.double().abs()
+    e = w.clone()
+    e_abs = w.abs()
+    if background == 1:
+        rem = 1.0 - w.sum(-1)
+        e[:, -1] += rem
+        e_abs[:, -1] += rem.abs()
+    d_rgb = g[:, None, :] * e[..., None]
+    return dict(d_rgb=d_rgb, d_rgb_abs=g.abs()[:, None, :] * e_abs[..., None], d_weights=dw, dw_abs=dw_abs)
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # a14  PDF resampling   (model_components/ray_samplers.py:276-372, include_original=False)
 # ---------------------------------------------------------------------------------------------------------------
@@ -628,6 +688,105 @@ def distortion_loss(weights: Tensor, s_bins: Tensor) -> Tensor:
     inter = torch.sum(weights * torch.sum(weights[:, None, :] * pair, dim=-1), dim=-1)
     intra = torch.sum(weights**2 * (s_bins[:, 1:] - s_bins[:, :-1]), dim=-1) / 3
     return torch.mean(inter + intra)
+
+
+
+def _cover_sum(lo: Tensor, hi: Tensor, v: Tensor, S1: int) -> Tensor:
+    """[N,S1] float64: entry k = sum_i v_i over the fine intervals i with start_i <= k <= end_i (difference array)."""
+    d = torch.zeros(lo.shape[0], S1 + 1, dtype=torch.float64)
+    d.scatter_add_(1, lo, v)
+    d.scatter_add_(1, hi + 1, -v)
+    return torch.cumsum(d, dim=-1)[:, :S1]
+
+
+def interlevel_bwd64(c: Tensor, w: Tensor, cp: Tensor, wp: Tensor) -> Dict[str, Tensor]:
+    """Float64 per-ray `lossfun_outer` term sum_i clip(w_i - outer_i, 0)^2 / (w_i + eps) (losses.py:85-102) and its
+    gradient with respect to the proposal weights wp, on fp32 edges c `[N,Sf+1]` (fine) and cp `[N,Sp+1]` (proposal).
+    The cover ranges lo, hi are `_outer_bound`'s, searchsorted on the same fp32 edges (integers: exact). outer = cum[hi+1]
+    - cum[lo] with cum the float64 prefix sums of wp; d outer_i / d wp_k = [k <= hi_i] - [k < lo_i], which is the cover
+    [lo_i, hi_i] when lo_i <= hi_i and minus (hi_i, lo_i) otherwise. Returns loss `[N]`, dwp `[N,Sp]` (unscaled),
+    rr = -d loss / d outer `[N,Sf]`, lo, hi, outer, outer_abs (|cum[hi+1]| + |cum[lo]| of the |wp| prefix sums), diff =
+    w - outer, den = w + eps, cover_abs `[N,Sp]` = sum |rr_i| and cover_n = the number of intervals over k's range (either sign)."""
+    Sp = wp.shape[-1]
+    wp64, w64 = wp.double(), w.double()
+    lo = torch.clamp(torch.searchsorted(cp[:, :-1].contiguous(), c[:, :-1].contiguous(), side="right") - 1, 0, Sp - 1)
+    hi = torch.clamp(torch.searchsorted(cp[:, 1:].contiguous(), c[:, 1:].contiguous(), side="right"), 0, Sp - 1)
+    cum = torch.cat([torch.zeros_like(wp64[:, :1]), torch.cumsum(wp64, dim=-1)], dim=-1)
+    cabs = torch.cat([torch.zeros_like(wp64[:, :1]), torch.cumsum(wp64.abs(), dim=-1)], dim=-1)
+    outer = torch.gather(cum, -1, hi + 1) - torch.gather(cum, -1, lo)
+    outer_abs = torch.gather(cabs, -1, hi + 1) + torch.gather(cabs, -1, lo)
+    diff = w64 - outer
+    clipped = torch.clamp(diff, min=0)
+    den = w64 + LOSS_EPS
+    loss = (clipped * clipped / den).sum(-1)
+    rr = 2 * clipped / den
+    fwd = lo <= hi
+    start = torch.where(fwd, lo, hi + 1)
+    end = torch.where(fwd, hi, lo - 1)
+    sgn = torch.where(fwd, 1.0, -1.0).double()
+    dwp = -_cover_sum(start, end, rr * sgn, Sp)
+    cover_abs = _cover_sum(start, end, rr.abs(), Sp)
+    cover_n = _cover_sum(start, end, torch.ones_like(rr), Sp)
+    return dict(loss=loss, dwp=dwp, rr=rr, lo=lo, hi=hi, outer=outer, outer_abs=outer_abs, diff=diff, den=den,
+                cover_abs=cover_abs, cover_n=cover_n)
+
+
+def distortion_bwd64(s_bins: Tensor, w: Tensor) -> Dict[str, Tensor]:
+    """Float64 per-ray distortion loss (losses.py:135-154, before the mean) and its gradient dw `[N,S]` on fp32 bins
+    and weights: dw_i = 2 inner_i + 2 w_i delta_i / 3 with inner_i = sum_k w_k |m_i - m_k|. Also inner, inner_abs =
+    sum_k |w_k| |m_i - m_k|, mid_abs = sum_k |w_k| (|m_i| + |m_k|) (what the midpoints' rounding is relative to), delta."""
+    b, w64 = s_bins.double(), w.double()
+    mid = (b[:, 1:] + b[:, :-1]) / 2
+    delta = b[:, 1:] - b[:, :-1]
+    pair = torch.abs(mid[:, :, None] - mid[:, None, :])
+    inner = torch.einsum("nik,nk->ni", pair, w64)
+    inner_abs = torch.einsum("nik,nk->ni", pair, w64.abs())
+    wa = w64.abs()
+    mid_abs = mid.abs() * wa.sum(-1, keepdim=True) + (wa * mid.abs()).sum(-1, keepdim=True)
+    loss = (w64 * inner).sum(-1) + (w64 * w64 * delta).sum(-1) / 3
+    dw = 2 * inner + 2 * w64 * delta / 3
+    return dict(loss=loss, dw=dw, inner=inner, inner_abs=inner_abs, mid_abs=mid_abs, delta=delta)
+
+
+def density_mlp_fwd64(enc: Tensor, sel: Optional[Tensor], W0: Tensor, b0: Tensor, W1: Tensor, b1: Tensor,
+                      avg: float) -> Dict[str, Tensor]:
+    """Float64 proposal density head (density_fields.py:104-117) on fp32 features enc `[M,IN]`: hidden pre-activations
+    a = enc W0^T + b0 `[M,H]`, pre = relu(a) W1^T + b1 `[M]`, density = avg exp(pre) sel. a_abs = |b0| + |enc| |W0|^T and
+    pre_abs = |b1| + relu(a) |W1|^T are the abs companions of the two dot products."""
+    x = enc.double()
+    a = x @ W0.double().t() + b0.double()
+    h = torch.relu(a)
+    pre = h @ W1.double().reshape(-1) + b1.double().reshape(-1)[0]
+    dens = avg * torch.exp(pre)
+    if sel is not None:
+        dens = dens * sel.double()
+    a_abs = x.abs() @ W0.double().abs().t() + b0.double().abs()
+    pre_abs = h @ W1.double().abs().reshape(-1) + abs(float(b1.reshape(-1)[0]))
+    return dict(a=a, pre=pre, density=dens, a_abs=a_abs, pre_abs=pre_abs)
+
+
+def density_mlp_bwd64(enc: Tensor, sel: Optional[Tensor], pre: Tensor, gd: Tensor, W0: Tensor, b0: Tensor, W1: Tensor,
+                      b1: Tensor, avg: float) -> Dict[str, Tensor]:
+    """Float64 backward of the proposal density head for the upstream gradient gd `[M]` of the density. `pre` `[M]` is
+    taken as given (autograd saves trunc_exp's input the same way), d density / d pre = avg sel exp(clamp(pre, -15, 15))
+    (activations.py:39-42); the hidden pre-activations are recomputed in float64 and returned (`a`) so that callers can
+    classify the points whose ReLU lies within a bound of zero. Returns denc `[M,IN]`, dW0 `[H,IN]`, db0 `[H]`, dW1 `[H]`,
+    db1 `[1]`, their abs companions (sums of |terms| over the points: *_abs; denc_abs = |gh| |W0|), g_pre `[M]`, a, a_abs,
+    and dW1_a = sum_p |g_pre| a_abs (what the hidden layer's rounding reaches dW1 through)."""
+    x = enc.double()
+    W0d, b0d, W1d = W0.double(), b0.double(), W1.double().reshape(-1)
+    a = x @ W0d.t() + b0d
+    a_abs = x.abs() @ W0d.abs().t() + b0d.abs()
+    g_pre = gd.double() * avg * torch.exp(torch.clamp(pre.double(), -15.0, 15.0))
+    if sel is not None:
+        g_pre = g_pre * sel.double()
+    on = (a > 0).double()
+    gh = on * g_pre[:, None] * W1d
+    h = torch.relu(a)
+    return dict(denc=gh @ W0d, denc_abs=gh.abs() @ W0d.abs(), dW0=gh.t() @ x, dW0_abs=gh.abs().t() @ x.abs(),
+                db0=gh.sum(0), db0_abs=gh.abs().sum(0), dW1=(h * g_pre[:, None]).sum(0),
+                dW1_abs=(h * g_pre[:, None].abs()).sum(0), dW1_a=(a_abs * on * g_pre[:, None].abs()).sum(0),
+                db1=g_pre.sum().reshape(1), db1_abs=g_pre.abs().sum().reshape(1), g_pre=g_pre, a=a, a_abs=a_abs)
 
 
 # ---------------------------------------------------------------------------------------------------------------

@@ -168,8 +168,12 @@ def test_bench_configuration_parity_through_replayed_graph(F, init):
         # reference. The perturbed pass is only evaluated when a tensor is outside 2 e_ref. (The floor: the proposal
         # networks' gradient comes through lossfun_outer's clip(w - w_outer, 0) — a difference of nearly equal numbers,
         # which amplifies the 1e-6-level fp32 differences of the forward; measured 1.3-1.6e-4 on the first proposal network
-        # against 2e-5 for the fp32 reference.) That the MLP backward kernel itself carries no such error is shown on
-        # identical inputs by test_field_mlp_backward_at_bench_size_vs_float64.
+        # against 2e-5 for the fp32 reference.) That the kernels themselves carry no such error is shown on identical inputs:
+        # for the main field by test_field_mlp_backward_at_bench_size_vs_float64, and for the proposal chain by
+        # test_gpu_proposal_backward.py::test_bench_shape_proposal_chain_vs_float64 — on a proposal-update iteration's own
+        # buffers at this size, the interlevel dw_prop, the weights backward and the density MLP backward are each within
+        # their per-entry rounding bound of float64 (worst 0.67 of it), and the MLP weight gradients 1e-7 from float64 in
+        # relative L2. The excess therefore enters through the forward's inputs to lossfun_outer, not through the backward.
         # The floor. A ReLU whose pre-activation lies within the forward discrepancy of zero comes out on either side,
         # and each such event moves its sample's gradient by a finite amount. With near-uniform default tables there is
         # essentially no such event (floor 5e-4: everything sits at the reference's own 3e-4). With N(0, 0.3) tables the
