@@ -652,6 +652,22 @@ int nsamd_raygen_pinhole_grid(const float* c2w, float fx, float fy, float cx, fl
                               int64_t num_rays, int64_t padded_rays, float* origins, float* directions, float* pixel_area,
                               nsamd_stream_t stream);
 
+/* Ray generation for cameras of type PERSPECTIVE = 1, FISHEYE = 2, EQUIRECTANGULAR = 3 (CameraType, cameras/cameras.py:41-52)
+ * with per-camera OpenCV distortion (k1, k2, k3, k4, p1, p2): cameras.py:598-656, 781-817, 887-909 and
+ * radial_and_tangential_undistort (camera_utils.py:375-478: 10 Newton iterations, no early exit). camera_type [C] int32
+ * (device; the caller has checked that every entry is 1 - 3); distortion [C,6] or NULL. One `Cameras` may mix types. A camera
+ * whose six parameters are zero, and every equirectangular camera, is not undistorted. Other arguments as nsamd_raygen_pinhole. */
+int nsamd_raygen_lens(const int64_t* ray_indices, const float* c2w, const float* fx, const float* fy, const float* cx,
+                      const float* cy, const int32_t* camera_type, const float* distortion, int64_t num_rays,
+                      int32_t num_cameras, float* origins, float* directions, float* pixel_area, float* directions_norm,
+                      nsamd_stream_t stream);
+
+/* nsamd_raygen_pinhole_grid for ONE camera of type 1 - 3 (by value; any other type returns NSAMD_ERR_UNSUPPORTED with nothing
+ * launched); distortion: the camera's 6 parameters in device memory, or NULL. Same bits as nsamd_raygen_lens. */
+int nsamd_raygen_lens_grid(const float* c2w, float fx, float fy, float cx, float cy, int32_t camera_type,
+                           const float* distortion, int32_t width, int64_t first_pixel, int64_t num_rays, int64_t padded_rays,
+                           float* origins, float* directions, float* pixel_area, nsamd_stream_t stream);
+
 /* Data-parallel exchange of a hash-table gradient whose coarse levels reach only a few of their rows (the torch path
  * hashes every level, encodings.py:398-415: level l touches at most (res_l + 1)^3 of its 2^log2_T rows): pack the
  * `n` reachable rows `index` (int64, sorted) of `rows` [*, feat] into `packed` [n, feat] before the all-reduce

@@ -136,6 +136,8 @@ _SIGNATURES = {
     "nsamd_packed_positions": [vp, vp, vp, vp, vp, i64, vp, vp],
     "nsamd_raygen_pinhole": [vp, vp, vp, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp],
     "nsamd_raygen_pinhole_grid": [vp, f32, f32, f32, f32, i32, i64, i64, i64, vp, vp, vp, vp],
+    "nsamd_raygen_lens": [vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp],
+    "nsamd_raygen_lens_grid": [vp, f32, f32, f32, f32, i32, vp, i32, i64, i64, i64, vp, vp, vp, vp],
     "nsamd_rows_gather": [vp, vp, i64, i32, vp, vp],
     "nsamd_rows_scatter": [vp, vp, i64, i32, vp, vp],
     "nsamd_select_batch": [vp, i32, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp],

@@ -1,7 +1,8 @@
-// Pinhole ray generation, fused Adam and library introspection for gfx950.
+// Ray generation (pinhole and lens cameras), fused Adam and library introspection for gfx950.
 #include <string.h>
 
 #include "common.h"
+#include "lens.h"
 
 namespace nsamd {
 
@@ -13,39 +14,12 @@ __device__ __forceinline__ void raygen_pinhole_one(float x, float y, float fxr, 
                                                    const float* __restrict__ m, float* __restrict__ origin,
                                                    float* __restrict__ direction, float* __restrict__ pixel_area,
                                                    float* __restrict__ direction_norm) {
-  const float eps = 8.881784197001252e-16f;  // camera_utils._EPS = 4 * float64 eps, cast to fp32
   // three coords: centre, +1 in x, +1 in y  (cameras.py:622-634)
   const float px[3] = {(x - cxr) / fxr, (x - cxr + 1.0f) / fxr, (x - cxr) / fxr};
   const float py[3] = {(y - cyr) / fyr, (y - cyr) / fyr, (y - cyr + 1.0f) / fyr};
-  float d[3][3];
-  float n0 = 0.0f;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const float lx = px[k], ly = -py[k], lz = -1.0f;  // OpenCV -> OpenGL (cameras.py:655-656), z = -1 (:787)
-    float v[3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) v[r] = (lx * m[4 * r + 0] + ly * m[4 * r + 1]) + lz * m[4 * r + 2];
-    const float nrm = fmaxf(sqrtf((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]), eps);
-    if (k == 0) n0 = nrm;
-#pragma unroll
-    for (int r = 0; r < 3; ++r) d[k][r] = v[r] / nrm;
-  }
-  float dx = 0.0f, dy = 0.0f;
-#pragma unroll
-  for (int r = 0; r < 3; ++r) {
-    const float a = d[0][r] - d[1][r], b = d[0][r] - d[2][r];
-    dx += a * a;
-    dy += b * b;
-  }
-  dx = sqrtf(dx);
-  dy = sqrtf(dy);
-#pragma unroll
-  for (int r = 0; r < 3; ++r) {
-    origin[r] = m[4 * r + 3];
-    direction[r] = d[0][r];
-  }
-  if (pixel_area) *pixel_area = dx * dy;
-  if (direction_norm) *direction_norm = n0;
+  // OpenCV -> OpenGL (cameras.py:655-656), z = -1 (:787); rotation, normalisation and pixel area are lens.h's shared tail
+  const float l[3][3] = {{px[0], -py[0], -1.0f}, {px[1], -py[1], -1.0f}, {px[2], -py[2], -1.0f}};
+  raygen_finish(l, m, origin, direction, pixel_area, direction_norm);
 }
 
 __global__ void raygen_pinhole_kernel(const int64_t* __restrict__ ray_indices, const float* __restrict__ c2w,
@@ -76,6 +50,38 @@ __global__ void raygen_pinhole_grid_kernel(const float* __restrict__ c2w, float 
   const int64_t row = p / width, col = p - row * width;
   raygen_pinhole_one((float)col + 0.5f, (float)row + 0.5f, fx, fy, cx, cy, c2w, origins + 3 * i, directions + 3 * i,
                      pixel_area ? pixel_area + i : nullptr, nullptr);
+}
+
+// The same for cameras of type 1 - 3 with per-camera distortion (lens.h): one ray per lane, the camera's record (pose,
+// intrinsics, type, six distortion parameters) gathered through L2. A wave whose rays come from cameras of different types
+// diverges at lens_local_direction only; rays are not sorted (4096 rays per step).
+__global__ void raygen_lens_kernel(const int64_t* __restrict__ ray_indices, const float* __restrict__ c2w,
+                                   const float* __restrict__ fx, const float* __restrict__ fy, const float* __restrict__ cx,
+                                   const float* __restrict__ cy, const int32_t* __restrict__ camera_type,
+                                   const float* __restrict__ distortion, int64_t num_rays, int32_t num_cameras,
+                                   float* __restrict__ origins, float* __restrict__ directions, float* __restrict__ pixel_area,
+                                   float* __restrict__ directions_norm) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= num_rays) return;
+  int64_t cam = ray_indices[3 * i + 0];
+  cam = cam < 0 ? 0 : (cam >= num_cameras ? num_cameras - 1 : cam);  // never read outside the camera arrays
+  const float y = (float)ray_indices[3 * i + 1] + 0.5f;
+  const float x = (float)ray_indices[3 * i + 2] + 0.5f;
+  raygen_lens_one(x, y, fx[cam], fy[cam], cx[cam], cy[cam], camera_type[cam], distortion ? distortion + 6 * cam : nullptr,
+                  c2w + cam * 12, origins + 3 * i, directions + 3 * i, pixel_area + i, directions_norm ? directions_norm + i : nullptr);
+}
+
+// raygen_pinhole_grid_kernel for one camera of type 1 - 3: the same bits as raygen_lens_kernel over the image's index list.
+__global__ void raygen_lens_grid_kernel(const float* __restrict__ c2w, float fx, float fy, float cx, float cy, int32_t camera_type,
+                                        const float* __restrict__ distortion, int32_t width, int64_t first_pixel, int64_t num_rays,
+                                        int64_t padded, float* __restrict__ origins, float* __restrict__ directions,
+                                        float* __restrict__ pixel_area) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= padded) return;
+  const int64_t p = first_pixel + (i < num_rays ? i : num_rays - 1);
+  const int64_t row = p / width, col = p - row * width;
+  raygen_lens_one((float)col + 0.5f, (float)row + 0.5f, fx, fy, cx, cy, camera_type, distortion, c2w, origins + 3 * i,
+                  directions + 3 * i, pixel_area ? pixel_area + i : nullptr, nullptr);
 }
 
 // The step's ray batch out of a pool of pre-generated batches resident in HBM: what VanillaDataManager.next_train
@@ -269,6 +275,39 @@ extern "C" int nsamd_raygen_pinhole_grid(const float* c2w, float fx, float fy, f
   NSAMD_REQUIRE(c2w && origins && directions && fx != 0.0f && fy != 0.0f);
   raygen_pinhole_grid_kernel<<<(unsigned)((padded_rays + 255) / 256), 256, 0, (hipStream_t)stream>>>(
       c2w, fx, fy, cx, cy, width, first_pixel, num_rays, padded_rays, origins, directions, pixel_area);
+  NSAMD_CHECK_LAUNCH();
+  return NSAMD_OK;
+}
+
+extern "C" int nsamd_raygen_lens(const int64_t* ray_indices, const float* c2w, const float* fx, const float* fy, const float* cx,
+                                 const float* cy, const int32_t* camera_type, const float* distortion, int64_t num_rays,
+                                 int32_t num_cameras, float* origins, float* directions, float* pixel_area,
+                                 float* directions_norm, nsamd_stream_t stream) {
+  NSAMD_REQUIRE(num_rays >= 0 && num_cameras > 0);
+  if (num_rays == 0) return NSAMD_OK;
+  NSAMD_REQUIRE(ray_indices && c2w && fx && fy && cx && cy && camera_type && origins && directions && pixel_area);
+  const int64_t nb = (num_rays + 255) / 256;
+  if (nb > 0x7fffffffLL) return NSAMD_ERR_UNSUPPORTED;
+  raygen_lens_kernel<<<(unsigned)nb, 256, 0, (hipStream_t)stream>>>(ray_indices, c2w, fx, fy, cx, cy, camera_type, distortion,
+                                                                    num_rays, num_cameras, origins, directions, pixel_area,
+                                                                    directions_norm);
+  NSAMD_CHECK_LAUNCH();
+  return NSAMD_OK;
+}
+
+extern "C" int nsamd_raygen_lens_grid(const float* c2w, float fx, float fy, float cx, float cy, int32_t camera_type,
+                                      const float* distortion, int32_t width, int64_t first_pixel, int64_t num_rays,
+                                      int64_t padded_rays, float* origins, float* directions, float* pixel_area,
+                                      nsamd_stream_t stream) {
+  NSAMD_REQUIRE(num_rays >= 0 && padded_rays >= num_rays && width > 0 && first_pixel >= 0);
+  if (!lens_type_supported(camera_type)) return NSAMD_ERR_UNSUPPORTED;
+  if (num_rays == 0) return NSAMD_OK;
+  NSAMD_REQUIRE(c2w && origins && directions && fx != 0.0f && fy != 0.0f);
+  const int64_t nb = (padded_rays + 255) / 256;
+  if (nb > 0x7fffffffLL) return NSAMD_ERR_UNSUPPORTED;
+  raygen_lens_grid_kernel<<<(unsigned)nb, 256, 0, (hipStream_t)stream>>>(c2w, fx, fy, cx, cy, camera_type, distortion, width,
+                                                                         first_pixel, num_rays, padded_rays, origins, directions,
+                                                                         pixel_area);
   NSAMD_CHECK_LAUNCH();
   return NSAMD_OK;
 }

@@ -153,20 +153,34 @@ class EvalRenderer:
 
     @profiler.time_function
     @torch.no_grad()
-    def render_camera(self, c2w: Tensor, fx: float, fy: float, cx: float, cy: float, height: int, width: int) -> Dict[str, Tensor]:
+    def render_camera(self, c2w: Tensor, fx: float, fy: float, cx: float, cy: float, height: int, width: int,
+                      lens=None) -> Dict[str, Tensor]:
         """`render` for ONE pinhole camera WITHOUT a ray bundle: each chunk's rays are generated straight into the schedule's
         static input buffers (nsamd_raygen_pinhole_grid: pixel first + i of the implicit row-major grid, the arithmetic of
         Cameras.generate_rays(camera_indices=0, keep_shape=True), cameras/cameras.py:321-503 perspective branch) — what
         Model.get_outputs_for_camera (models/base_model.py:166-175) builds as an [H, W] bundle with ~40 torch launches over
-        full-image tensors and then slices. Same bits as `render` on that bundle. c2w: [3, 4] on the model's device."""
+        full-image tensors and then slices. Same bits as `render` on that bundle. c2w: [3, 4] on the model's device.
+        lens = (camera_type, distortion): the camera is of CameraType 1 - 3 (perspective, fisheye, equirectangular) with six
+        distortion parameters or None, and its chunks come from nsamd_raygen_lens_grid (the bits of functional.raygen_lens)."""
         s, n = self.step, self.chunk
         dev = s.origins.device
         c2w = c2w.reshape(3, 4).to(device=dev, dtype=torch.float32).contiguous()
+        lib, st = N.load(), N.stream()
+        if lens is None:
+            def load_chunk(a, k):
+                N.check(lib.nsamd_raygen_pinhole_grid(N.ptr(c2w), float(fx), float(fy), float(cx), float(cy), int(width), a, k, n,
+                                                      N.ptr(s.origins), N.ptr(s.directions), None, st), "raygen_pinhole_grid")
+        else:
+            camera_type, dist = int(lens[0]), lens[1]
+            if camera_type not in F.LENS_TYPES:
+                raise ValueError(f"render_camera: camera type {camera_type} is not one of {sorted(F.LENS_TYPES)}")
+            if dist is not None:
+                dist = torch.as_tensor(dist).reshape(6).to(device=dev, dtype=torch.float32).contiguous()
 
-        def load_chunk(a, k):
-            N.check(N.load().nsamd_raygen_pinhole_grid(N.ptr(c2w), float(fx), float(fy), float(cx), float(cy), int(width), a, k,
-                                                       n, N.ptr(s.origins), N.ptr(s.directions), None, N.stream()),
-                    "raygen_pinhole_grid")
+            def load_chunk(a, k):
+                N.check(lib.nsamd_raygen_lens_grid(N.ptr(c2w), float(fx), float(fy), float(cx), float(cy), camera_type,
+                                                   N.ptr(dist), int(width), a, k, n, N.ptr(s.origins), N.ptr(s.directions), None,
+                                                   st), "raygen_lens_grid")
 
         out = self._render_rays(int(height) * int(width), dev, load_chunk)
         return {k_: v.view(int(height), int(width), -1) for k_, v in out.items()}
@@ -195,6 +209,48 @@ def pinhole_camera_args(camera):
         return c2w[:3, :4], one(camera.fx), one(camera.fy), one(camera.cx), one(camera.cy), h, w
     except (AttributeError, TypeError, ValueError, IndexError):
         return None
+
+
+def lens_camera_args(camera):
+    """`pinhole_camera_args`' tuple plus (camera_type, distortion) for a single `Cameras` object of type PERSPECTIVE, FISHEYE or
+    EQUIRECTANGULAR (1 - 3): distortion is the camera's six parameters `[6]`, or None when it has none. None for several
+    cameras, missing intrinsics and the lens types the generator does not cover."""
+    try:
+        c2w = camera.camera_to_worlds
+        if c2w.dim() == 3:
+            if c2w.shape[0] != 1:
+                return None
+            c2w = c2w[0]
+        ctype = getattr(camera, "camera_type", None)
+        ctype = 1 if ctype is None else int(torch.as_tensor(ctype).reshape(-1)[0])
+        if ctype not in F.LENS_TYPES:
+            return None
+        dist = getattr(camera, "distortion_params", None)
+        if dist is not None:
+            dist = torch.as_tensor(dist).float().reshape(-1)
+            if dist.numel() != 6:
+                return None
+        one = lambda t: float(torch.as_tensor(t).reshape(-1)[0])  # noqa: E731
+        h, w = int(one(camera.height)), int(one(camera.width))
+        if h <= 0 or w <= 0 or torch.as_tensor(camera.fx).numel() != 1:
+            return None
+        return c2w[:3, :4], one(camera.fx), one(camera.fy), one(camera.cx), one(camera.cy), h, w, ctype, dist
+    except (AttributeError, TypeError, ValueError, IndexError):
+        return None
+
+
+def in_loop_camera_args(camera):
+    """(render_camera's positional arguments, its `lens`) for the cameras Model.get_outputs_for_camera renders without a ray
+    bundle: one undistorted pinhole camera (lens None), or one perspective camera with non-zero distortion. None otherwise —
+    fisheye and equirectangular cameras still take `camera.generate_rays` there; `render_camera(lens=...)` and RayGenerator
+    cover them."""
+    args = pinhole_camera_args(camera)
+    if args is not None:
+        return args, None
+    args = lens_camera_args(camera)
+    if args is not None and args[7] == 1:  # CameraType.PERSPECTIVE
+        return args[:7], (args[7], args[8])
+    return None
 
 
 def supported(model) -> Optional[str]:

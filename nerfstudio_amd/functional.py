@@ -1025,7 +1025,7 @@ def camera_correct_rays(pose: Tensor, mode: str, origins: Tensor, directions: Te
 
 
 # ---------------------------------------------------------------------------------------------------------------
-# a1  pinhole ray generation
+# a1  ray generation: pinhole, and perspective / fisheye / equirectangular lenses with distortion
 # ---------------------------------------------------------------------------------------------------------------
 @torch.no_grad()
 def raygen_pinhole(ray_indices: Tensor, c2w: Tensor, fx: Tensor, fy: Tensor, cx: Tensor, cy: Tensor):
@@ -1044,6 +1044,55 @@ def raygen_pinhole(ray_indices: Tensor, c2w: Tensor, fx: Tensor, fy: Tensor, cx:
     N.check(N.load().nsamd_raygen_pinhole(N.ptr(idx), N.ptr(c2w), N.ptr(fx), N.ptr(fy), N.ptr(cx), N.ptr(cy), n,
                                           c2w.shape[0], N.ptr(o), N.ptr(d), N.ptr(pa), N.ptr(dn), N.stream()),
             "raygen_pinhole")
+    return o, d, pa, dn
+
+
+LENS_TYPES = {1: "PERSPECTIVE", 2: "FISHEYE", 3: "EQUIRECTANGULAR"}  # CameraType values the lens generator covers
+_CAMERA_TYPE_NAMES = {**LENS_TYPES, 4: "OMNIDIRECTIONALSTEREO_L", 5: "OMNIDIRECTIONALSTEREO_R", 6: "VR180_L", 7: "VR180_R",
+                      8: "ORTHOPHOTO", 9: "FISHEYE624"}  # cameras/cameras.py:41-52
+
+
+def check_lens_types(camera_type: Tensor) -> None:
+    """ValueError naming the first camera type outside PERSPECTIVE / FISHEYE / EQUIRECTANGULAR (the kernels are not launched
+    for one: the indexed entry point cannot read device memory on the host, so this layer checks)."""
+    for t in torch.unique(camera_type.detach().reshape(-1).cpu()).tolist():
+        if int(t) not in LENS_TYPES:
+            raise ValueError(f"the hip ray generator does not cover camera type {int(t)} "
+                             f"({_CAMERA_TYPE_NAMES.get(int(t), 'unknown')}); it handles {sorted(LENS_TYPES.values())}")
+
+
+@torch.no_grad()
+def raygen_lens(ray_indices: Tensor, c2w: Tensor, fx: Tensor, fy: Tensor, cx: Tensor, cy: Tensor, camera_type: Tensor,
+                distortion: Optional[Tensor] = None, check_types: bool = True):
+    """RayGenerator.forward for perspective, fisheye and equirectangular cameras with per-camera distortion parameters
+    `[C,6] = (k1, k2, k3, k4, p1, p2)` (cameras.py:598-656, 781-817, 887-909; camera_utils.py:375-478); `camera_type` `[C]`
+    holds CameraType values 1 - 3 and may mix them. -> origins `[N,3]`, directions `[N,3]`, pixel_area `[N,1]`,
+    directions_norm `[N,1]`. check_types=False: the caller has run `check_lens_types` on these cameras already (it reads the
+    types back to the host)."""
+    N.require_cuda(ray_indices, c2w, fx, fy, cx, cy, camera_type)
+    if check_types:
+        check_lens_types(camera_type)
+    idx = ray_indices.contiguous().to(torch.int64)
+    c2w = _f32c(c2w.reshape(-1, 3, 4))
+    fx, fy, cx, cy = (_f32c(t.reshape(-1)) for t in (fx, fy, cx, cy))
+    ctype = camera_type.reshape(-1).to(torch.int32).contiguous()
+    num_cameras = c2w.shape[0]
+    if not (fx.numel() == fy.numel() == cx.numel() == cy.numel() == ctype.numel() == num_cameras):
+        raise ValueError("raygen_lens: c2w, fx, fy, cx, cy and camera_type must describe the same number of cameras")
+    if distortion is not None:
+        N.require_cuda(distortion)
+        distortion = _f32c(distortion.reshape(-1, 6))
+        if distortion.shape[0] != num_cameras:
+            raise ValueError("raygen_lens: distortion must be [num_cameras, 6]")
+    n = idx.shape[0]
+    dev = idx.device
+    o = torch.empty((n, 3), device=dev, dtype=torch.float32)
+    d = torch.empty((n, 3), device=dev, dtype=torch.float32)
+    pa = torch.empty((n, 1), device=dev, dtype=torch.float32)
+    dn = torch.empty((n, 1), device=dev, dtype=torch.float32)
+    N.check(N.load().nsamd_raygen_lens(N.ptr(idx), N.ptr(c2w), N.ptr(fx), N.ptr(fy), N.ptr(cx), N.ptr(cy), N.ptr(ctype),
+                                       N.ptr(distortion) if distortion is not None else None, n, num_cameras, N.ptr(o),
+                                       N.ptr(d), N.ptr(pa), N.ptr(dn), N.stream()), "raygen_lens")
     return o, d, pa, dn
 
 

@@ -294,15 +294,17 @@ class NerfactoModel(nn.Module):
 
     @torch.no_grad()
     def get_outputs_for_camera(self, camera, obb_box=None) -> Dict[str, Tensor]:
-        """models/base_model.py:166-175. Eval mode, one undistorted pinhole camera, no crop box: the rays of each chunk are
-        generated inside the device-side chunk loop (eval_render.EvalRenderer.render_camera) — no [H, W] bundle in HBM; anything
-        else generates the bundle (`camera.generate_rays(camera_indices=0, keep_shape=True)`) and takes the loop below."""
+        """models/base_model.py:166-175. Eval mode, one perspective camera (undistorted, or with OpenCV distortion parameters),
+        no crop box: the rays of each chunk are generated inside the device-side chunk loop
+        (eval_render.EvalRenderer.render_camera) — no [H, W] bundle in HBM; anything else generates the bundle
+        (`camera.generate_rays(camera_indices=0, keep_shape=True)`) and takes the loop below. Fisheye and equirectangular
+        cameras are among "anything else" here; `render_camera(lens=...)` and RayGenerator generate their rays."""
         from . import eval_render
 
-        args = eval_render.pinhole_camera_args(camera) if obb_box is None else None
+        args = eval_render.in_loop_camera_args(camera) if obb_box is None else None
         runner = eval_render.runner_for(self, next(self.parameters()).device) if args is not None else None
         if runner is not None:
-            return runner.render_camera(*args)
+            return runner.render_camera(*args[0], lens=args[1])
         return self.get_outputs_for_camera_ray_bundle(camera.generate_rays(camera_indices=0, keep_shape=True, obb_box=obb_box))
 
     @torch.no_grad()

@@ -152,17 +152,18 @@ def _model_classes():
 
         @torch.no_grad()
         def get_outputs_for_camera(self, camera, obb_box=None):  # models/base_model.py:162-176 (viewer, ns-render)
-            """One undistorted pinhole camera without a crop box, in eval mode on the model's GPU: the rays of every chunk are
-            generated inside the device-side chunk loop (EvalRenderer.render_camera over nsamd_raygen_pinhole_grid: the arithmetic
-            of `camera.generate_rays(camera_indices=0, keep_shape=True)`, cameras/cameras.py:321-503) — no [H, W] ray bundle is
-            built. Anything else is the reference's own path."""
+            """One perspective camera (undistorted, or with OpenCV distortion parameters) without a crop box, in eval mode on the
+            model's GPU: the rays of every chunk are generated inside the device-side chunk loop (EvalRenderer.render_camera over
+            nsamd_raygen_pinhole_grid / nsamd_raygen_lens_grid: the arithmetic of `camera.generate_rays(camera_indices=0,
+            keep_shape=True)`, cameras/cameras.py:321-503) — no [H, W] ray bundle is built. Anything else — fisheye and
+            equirectangular cameras included, which `render_camera(lens=...)` covers — is the reference's own path."""
             from . import eval_render
 
             self._flush_pending()
-            args = eval_render.pinhole_camera_args(camera) if obb_box is None else None
+            args = eval_render.in_loop_camera_args(camera) if obb_box is None else None
             runner = eval_render.runner_for(self, self.device) if (args is not None and self._collider_is_configs()) else None
             if runner is not None:
-                return runner.render_camera(*args)
+                return runner.render_camera(*args[0], lens=args[1])
             return super().get_outputs_for_camera(camera, obb_box=obb_box)
 
         @torch.no_grad()

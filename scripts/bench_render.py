@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Eval-mode render throughput of the nerfacto path (the "render" half of north_star): a full image of
-synthetic pinhole rays through RayGenerator -> NerfactoModel.get_outputs_for_camera_ray_bundle (models/base_model.py:178-205:
+synthetic pinhole (or, with --distortion, OpenCV-distorted perspective) rays through RayGenerator -> NerfactoModel.get_outputs_for_camera_ray_bundle (models/base_model.py:178-205:
 chunks of eval_num_rays_per_chunk = 32768 rays; no jitter, near plane 0, mean appearance embedding, nan_to_num + clamp),
-random-init weights. GPU box only:  python scripts/bench_render.py [--height 800 --width 800 --frames 5]
+random-init weights. GPU box only:  python scripts/bench_render.py [--height 800 --width 800 --frames 5] [--distortion k1 k2 k3 k4 p1 p2]
 Prints one JSON line: rays/s (= pixels/s) and ms per frame."""
 import argparse
 import json
@@ -26,6 +26,8 @@ ap.add_argument("--module-loop", action="store_true", help="the reference-shaped
 ap.add_argument("--bundle", action="store_true",
                 help="build the camera's [H, W] ray bundle first (nsamd_raygen_pinhole over an index list) and render it, as round 5 "
                      "did; default: Model.get_outputs_for_camera with the rays generated inside the chunk loop")
+ap.add_argument("--distortion", type=float, nargs=6, metavar=("K1", "K2", "K3", "K4", "P1", "P2"),
+                help="OpenCV distortion parameters of the camera (ns-process-data's OPENCV model): rays from nsamd_raygen_lens(_grid)")
 args = ap.parse_args()
 if args.module_loop:
     os.environ["NSAMD_EVAL_RUNNER"] = "0"
@@ -48,7 +50,7 @@ cams.cx = torch.tensor([[W / 2.0]])
 cams.cy = torch.tensor([[H / 2.0]])
 cams.height, cams.width = torch.tensor([[H]]), torch.tensor([[W]])
 cams.camera_type = torch.tensor([[1]])  # CameraType.PERSPECTIVE
-cams.distortion_params = None
+cams.distortion_params = None if args.distortion is None else torch.tensor([args.distortion])
 gen = RayGenerator(cams).to(dev)
 cams.camera_to_worlds = cams.camera_to_worlds.to(dev)
 yy, xx = torch.meshgrid(torch.arange(H), torch.arange(W), indexing="ij")
@@ -80,5 +82,6 @@ print(json.dumps({"metric": "eval render rays/sec (nerfacto, 256 -> 96 -> 48 sam
                   "launch": "Python loop over forward + torch.cat (eager)" if args.module_loop else
                             ("device-side chunk loop: one captured kernel schedule per chunk (eval_render.py)"
                              + (", rays from a prebuilt [H,W] bundle" if args.bundle else ", rays generated per chunk (no bundle)")),
+                  "distortion": args.distortion,
                   "forward_ceiling_rays_per_s": round(CEILING, 1), "frac_of_forward_ceiling": round(H * W / dt / CEILING, 4),
                   "data": "synthetic", "dtype": "f32"}))
