@@ -284,8 +284,13 @@ __global__ __launch_bounds__(kPackThreads) void packed_weights_kernel(
 }
 
 // d w / d sigma: d(sigma_j dt_j) gets  g_j T_j exp(-dd_j)  -  sum_{i>j} g_i w_i  (as the dense weights_bwd_kernel), with
-// no per-ray LDS row: pass A sums the segment, pass B walks it backwards — the exclusive prefix is total minus the
-// inclusive suffix (double), the suffix of g w comes from the same reverse scan.
+// no per-ray LDS row. The transmittance in front of a sample comes from the FORWARD exclusive prefix, chunk for chunk the
+// sums of packed_weights_kernel (so T here is bit for bit the forward's T): pass A walks the ray forwards and leaves the
+// carry in front of chunk c in lane c of `held`, pass B walks the chunks backwards with the suffix of g w carried in
+// double. "Total minus inclusive suffix" is not a prefix: it carries total * 2^-53 as an absolute error of the exponent,
+// which one opaque sample (dd 1e10) behind thin ones makes visible in every T in front of it, and Inf - Inf is NaN.
+// A ray longer than 64 chunks (4096 samples) is handled in blocks of 64 chunks, last block first; pass A runs again from
+// the ray's start for each block (same sums, same bits).
 __global__ __launch_bounds__(kPackThreads) void packed_weights_bwd_kernel(
     const float* __restrict__ t_starts, const float* __restrict__ t_ends, const float* __restrict__ sigmas,
     const float* __restrict__ dweights, const int64_t* __restrict__ info, int64_t num_rays, float* __restrict__ dsigmas) {
@@ -293,30 +298,38 @@ __global__ __launch_bounds__(kPackThreads) void packed_weights_bwd_kernel(
   const int64_t ray = (int64_t)blockIdx.x * kPackWaves + (threadIdx.x >> 6);
   if (ray >= num_rays) return;
   const int64_t s0 = info[2 * ray], cnt = info[2 * ray + 1];
-  double total = 0.0;
-  for (int64_t i0 = 0; i0 < cnt; i0 += 64) {
-    const int64_t i = i0 + lane;
-    const float dd = i < cnt ? sigmas[s0 + i] * (t_ends[s0 + i] - t_starts[s0 + i]) : 0.0f;
-    total += __shfl(pk_scan_inclusive((double)dd, lane), 63);
-  }
-  double suf_dd = 0.0, suf_gw = 0.0;  // sums over the samples behind the current chunk
-  for (int64_t r0 = 0; r0 < cnt; r0 += 64) {
-    const int64_t r = r0 + lane;   // reversed position
-    const int64_t i = cnt - 1 - r; // sample
-    const bool in = r < cnt;
-    const float dt = in ? t_ends[s0 + i] - t_starts[s0 + i] : 0.0f;
-    const float dd = in ? sigmas[s0 + i] * dt : 0.0f;
-    const double incl_dd = suf_dd + pk_scan_inclusive((double)dd, lane);  // sum over samples >= i
-    const float ex = expf(-dd);
-    const float trans = expf(-(float)(total - incl_dd));
-    const float g = in ? dweights[s0 + i] : 0.0f;
-    const float gw = g * ((1.0f - ex) * trans);
-    const double incl_gw = suf_gw + pk_scan_inclusive((double)gw, lane);
-    double excl_gw = __shfl_up(incl_gw, 1);
-    if (lane == 0) excl_gw = suf_gw;
-    suf_dd = __shfl(incl_dd, 63);
-    suf_gw = __shfl(incl_gw, 63);
-    if (in) dsigmas[s0 + i] = dt * (g * trans * ex - (float)excl_gw);
+  const int64_t chunks = (cnt + 63) >> 6;
+  double suf_gw = 0.0;  // sum of g w over the samples behind the current chunk
+  for (int64_t b0 = chunks > 0 ? ((chunks - 1) >> 6) << 6 : -1; b0 >= 0; b0 -= 64) {
+    const int64_t b1 = b0 + 64 < chunks ? b0 + 64 : chunks;  // this block: chunks [b0, b1)
+    double carry = 0.0, held = 0.0;
+    for (int64_t c = 0; c < b1; ++c) {
+      const int64_t i = c * 64 + lane;
+      const float dd = i < cnt ? sigmas[s0 + i] * (t_ends[s0 + i] - t_starts[s0 + i]) : 0.0f;
+      if (c - b0 == lane) held = carry;
+      carry = __shfl(carry + pk_scan_inclusive((double)dd, lane), 63);
+    }
+    for (int64_t c = b1 - 1; c >= b0; --c) {
+      const int64_t i = c * 64 + lane;
+      const bool in = i < cnt;
+      const float dt = in ? t_ends[s0 + i] - t_starts[s0 + i] : 0.0f;
+      const float dd = in ? sigmas[s0 + i] * dt : 0.0f;
+      const double before = __shfl(held, (int)(c - b0));
+      const double incl = before + pk_scan_inclusive((double)dd, lane);
+      double excl = __shfl_up(incl, 1);
+      if (lane == 0) excl = before;
+      const float ex = expf(-dd);
+      const float trans = expf(-(float)excl);
+      const float g = in ? dweights[s0 + i] : 0.0f;
+      const float gw = in ? g * ((1.0f - ex) * trans) : 0.0f;
+      // suffix over the later samples: the lanes mirrored, scanned, mirrored back
+      const double incl_gw = suf_gw + pk_scan_inclusive(__shfl((double)gw, 63 - lane), lane);
+      double excl_gw = __shfl_up(incl_gw, 1);
+      if (lane == 0) excl_gw = suf_gw;
+      suf_gw = __shfl(incl_gw, 63);
+      excl_gw = __shfl(excl_gw, 63 - lane);
+      if (in) dsigmas[s0 + i] = dt * (g * trans * ex - (float)excl_gw);
+    }
   }
 }
 

@@ -185,3 +185,232 @@ def occgrid_thresholds(occs, occ_thre: float = 0.01):
     mean = float(occs[seen].astype(np.float64).mean()) if seen.any() else 0.0
     thre = np.float32(min(mean, float(np.float32(occ_thre))))
     return occs > thre
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# float64 references of the packed kernels (csrc/packed.hip), per ray over `packed_info` segments: what
+# tests/test_gpu_packed_float64.py holds the kernels to entry by entry. The inputs are the kernels' fp32 inputs; the two
+# products the kernels form in fp32 before anything else (delta = fl32(te - ts), dd = fl32(delta * sigma)) are taken in
+# fp32 here too, as the dense references of oracle/nerfacto_oracle.py take theirs; everything after them is float64.
+# Rays are grouped by length (next power of two) and evaluated as rows of a dense float64 matrix padded with zeros, so no
+# sum ever runs across a ray boundary (a global scan minus the ray's base would cancel, in any precision, next to a ray
+# of optical depth 1e30).
+# ---------------------------------------------------------------------------------------------------------------------
+def _f64(x):
+    import numpy as np
+
+    return x.detach().cpu().double().numpy() if isinstance(x, Tensor) else np.asarray(x, dtype=np.float64)
+
+
+def _f32(x):
+    import numpy as np
+
+    return x.detach().cpu().float().numpy() if isinstance(x, Tensor) else np.asarray(x, dtype=np.float32)
+
+
+def _info(packed_info):
+    import numpy as np
+
+    info = packed_info.detach().cpu().numpy() if isinstance(packed_info, Tensor) else np.asarray(packed_info)
+    return info.astype(np.int64).reshape(-1, 2)
+
+
+def packed_ray_indices(packed_info):
+    """int64 `[n]`: the ray of every packed sample."""
+    import numpy as np
+
+    info = _info(packed_info)
+    return np.repeat(np.arange(len(info), dtype=np.int64), info[:, 1])
+
+
+def _buckets(packed_info):
+    """Rays of similar length together: yields (rays `[rows]`, flat `[rows, width]` int64 sample indices, valid `[rows,
+    width]` bool)."""
+    import numpy as np
+
+    info = _info(packed_info)
+    cnt = info[:, 1]
+    width = np.where(cnt > 0, 2 ** np.ceil(np.log2(np.maximum(cnt, 1))).astype(np.int64), 0)
+    for wd in np.unique(width[width > 0]):
+        rays = np.flatnonzero(width == wd)
+        col = np.arange(wd, dtype=np.int64)[None, :]
+        valid = col < cnt[rays, None]
+        yield rays, np.where(valid, info[rays, 0:1] + col, 0), valid
+
+
+def _excl_prefix(x):
+    import numpy as np
+
+    return np.concatenate([np.zeros_like(x[:, :1]), np.cumsum(x[:, :-1], axis=1)], axis=1)
+
+
+def _excl_suffix(x):
+    return _excl_prefix(x[:, ::-1])[:, ::-1]
+
+
+def _rowwise(packed_info, n, ins, fn, outs):
+    """Evaluates fn(valid, *rows of `ins`) -> dict of rows per bucket of rays (the padding holds zeros); scatters the entries
+    named in `outs` to `[n]`."""
+    import numpy as np
+
+    res = {k: np.zeros(n, np.float64) for k in outs}
+    for _, flat, valid in _buckets(packed_info):
+        rows = [np.where(valid, a[flat], 0.0) for a in ins]
+        with np.errstate(all="ignore"):
+            r = fn(valid, *rows)
+        for k in outs:
+            res[k][flat[valid]] = r[k][valid]
+    return res
+
+
+def segment_exclusive_suffix64(x, packed_info):
+    """Float64 `[n]`: sum of x over the LATER samples of the same ray."""
+    import numpy as np
+
+    x = np.asarray(x, np.float64)
+    return _rowwise(packed_info, len(x), [x], lambda valid, v: dict(s=_excl_suffix(v)), ("s",))["s"]
+
+
+def _fl32_products(t_starts, t_ends, sigmas):
+    import numpy as np
+
+    ts, te, sg = _f32(t_starts), _f32(t_ends), _f32(sigmas)
+    with np.errstate(all="ignore"):
+        delta = (te - ts).astype(np.float32)
+        dd = (sg * delta).astype(np.float32)
+    return delta.astype(np.float64), dd.astype(np.float64)
+
+
+def _weights_rows(valid, dd):
+    import numpy as np
+
+    X = _excl_prefix(dd)
+    T, e = np.exp(-X), np.exp(-dd)
+    alpha = 1.0 - e
+    return dict(X=X, X_abs=_excl_prefix(np.abs(dd)), T=T, e=e, alpha=alpha, w=alpha * T)
+
+
+def packed_weights64(t_starts, t_ends, sigmas, packed_info):
+    """Float64 `render_weight_from_density` over packed segments. Returns float64 `[n]` arrays: delta = fl32(te - ts),
+    dd = fl32(delta * sigma) (the kernels' own fp32 products), X = the exclusive prefix sum of dd along the ray, X_abs =
+    the same sum of |dd|, T = exp(-X), e = exp(-dd), alpha = 1 - e, w = alpha T."""
+    delta, dd = _fl32_products(t_starts, t_ends, sigmas)
+    r = _rowwise(packed_info, len(dd), [dd], _weights_rows, ("X", "X_abs", "T", "e", "alpha", "w"))
+    return dict(r, delta=delta, dd=dd)
+
+
+def packed_weights_bwd64(t_starts, t_ends, sigmas, packed_info, dweights):
+    """Float64 gradient of the packed weights with respect to sigma for the upstream gradient `dweights`:
+    dsigma_j = delta_j (g_j T_j e_j - sum_{i>j} g_i w_i). Returns packed_weights64's arrays plus g, dsigmas, suf (the
+    exclusive suffix sum of g w along the ray) and suf_abs (of |g w|)."""
+    import numpy as np
+
+    delta, dd = _fl32_products(t_starts, t_ends, sigmas)
+    g = _f64(dweights)
+
+    def rows(valid, dd_, g_, delta_):
+        r = _weights_rows(valid, dd_)
+        gw = np.where(valid, g_ * r["w"], 0.0)  # (behind a NaN sample the padding's own weight is NaN)
+        r["suf"], r["suf_abs"] = _excl_suffix(gw), _excl_suffix(np.abs(gw))
+        r["dsigmas"] = delta_ * (g_ * r["T"] * r["e"] - r["suf"])
+        return r
+
+    r = _rowwise(packed_info, len(dd), [dd, g, delta], rows,
+                 ("X", "X_abs", "T", "e", "alpha", "w", "suf", "suf_abs", "dsigmas"))
+    return dict(r, delta=delta, dd=dd, g=g)
+
+
+def packed_visibility64(t_starts, t_ends, sigmas, packed_info, early_stop_eps, alpha_thre):
+    """Float64 `render_visibility_from_density`: keep = T >= fl32(early_stop_eps) and alpha >= fl32(alpha_thre), with the
+    margins m_T = T - eps and m_alpha = alpha - thre of every sample (and packed_weights64's arrays)."""
+    import numpy as np
+
+    r = packed_weights64(t_starts, t_ends, sigmas, packed_info)
+    eps, thre = float(np.float32(early_stop_eps)), float(np.float32(alpha_thre))
+    m_T, m_alpha = r["T"] - eps, r["alpha"] - thre
+    return dict(r, keep=(m_T >= 0) & (m_alpha >= 0), m_T=m_T, m_alpha=m_alpha)
+
+
+def _per_ray_sum(x, packed_info):
+    """Float64 per-ray sums of `[n]` or `[n, D]`."""
+    import numpy as np
+
+    info = _info(packed_info)
+    x = np.asarray(x, np.float64)
+    out = np.zeros((len(info),) + x.shape[1:], np.float64)
+    for rays, flat, valid in _buckets(packed_info):
+        v = x[flat]
+        v = np.where(valid.reshape(valid.shape + (1,) * (x.ndim - 1)), v, 0.0)
+        out[rays] = v.sum(axis=1)
+    return out
+
+
+def packed_composite64(rgb, weights, t_starts, t_ends, packed_info, background_mode=0, bg_color=None, eval_mode=False):
+    """Float64 packed compositing (csrc/packed.hip, nsamd_packed_composite_fwd): rgb = sum w c [+ bg (1 - acc)], acc =
+    sum w, depth = sum w fl32(fl32(ts + te) / 2) / (acc + 1e-10). eval_mode: nan_to_num on the samples' colours, the result
+    clamped to [0, 1]. Returns rgb `[N,3]`, acc, depth `[N]`, the abs sums rgb_abs / acc_abs / depth_abs of the terms, and
+    dsum (the depth's numerator)."""
+    import numpy as np
+
+    c, w = _f64(rgb).reshape(-1, 3), _f64(weights)
+    if eval_mode:
+        c = np.nan_to_num(c, nan=0.0, posinf=float(np.finfo(np.float32).max), neginf=float(np.finfo(np.float32).min))
+    with np.errstate(all="ignore"):
+        wc = w[:, None] * c
+        comp, comp_abs = _per_ray_sum(wc, packed_info), _per_ray_sum(np.abs(wc), packed_info)
+        acc, acc_abs = _per_ray_sum(w, packed_info), _per_ray_sum(np.abs(w), packed_info)
+        out = dict(acc=acc, acc_abs=acc_abs, sum_wc=comp, rgb_abs=comp_abs)
+        if background_mode == 1:
+            bg = np.asarray([float(np.float32(v)) for v in bg_color], np.float64)
+            comp = comp + bg[None, :] * (1.0 - acc)[:, None]
+        if eval_mode:
+            comp = np.clip(comp, 0.0, 1.0)
+        out["rgb"] = comp
+        if t_starts is not None:
+            mid = ((_f32(t_starts) + _f32(t_ends)).astype(np.float32) / np.float32(2.0)).astype(np.float64)
+            out["dsum"], out["depth_abs"] = _per_ray_sum(w * mid, packed_info), _per_ray_sum(np.abs(w * mid), packed_info)
+            out["depth"] = out["dsum"] / (acc + float(np.float32(1e-10)))
+    return out
+
+
+def packed_composite_bwd64(rgb, weights, packed_info, background_mode, bg_color, g_rgb, g_accumulation=None):
+    """Float64 gradients of (rgb, accumulation) of the training composite: d_rgb_s = w_s g_rgb[ray],
+    d_w_s = g_rgb . c_s [+ g_acc[ray]] [- g_rgb . bg]. Returns d_rgb `[n,3]`, d_weights `[n]`, dw_abs = sum |terms|."""
+    import numpy as np
+
+    c, w, g = _f64(rgb).reshape(-1, 3), _f64(weights), _f64(g_rgb).reshape(-1, 3)
+    ri = packed_ray_indices(packed_info)
+    gs = g[ri]
+    with np.errstate(all="ignore"):
+        dw, dw_abs = (gs * c).sum(-1), np.abs(gs * c).sum(-1)
+        if g_accumulation is not None:
+            ga = _f64(g_accumulation)[ri]
+            dw, dw_abs = dw + ga, dw_abs + np.abs(ga)
+        if background_mode == 1:
+            bg = np.asarray([float(np.float32(v)) for v in bg_color], np.float64)
+            dw, dw_abs = dw - (gs * bg).sum(-1), dw_abs + np.abs(gs * bg).sum(-1)
+        return dict(d_rgb=w[:, None] * gs, d_weights=dw, dw_abs=dw_abs)
+
+
+def prefix_by_forward_sum(dd):
+    """The transmittance in front of every sample of ONE ray as the forward kernel forms it: expf(-(float) X) with X the
+    exclusive forward prefix sum in double. (Restated in numpy: float64 sums, one fp32 cast.)"""
+    import numpy as np
+
+    dd = np.asarray(dd, np.float64)
+    X = np.concatenate([[0.0], np.cumsum(dd[:-1])])
+    with np.errstate(all="ignore"):
+        return np.exp(-X.astype(np.float32).astype(np.float64))
+
+
+def prefix_by_total_minus_suffix(dd):
+    """The same transmittance as `total - inclusive suffix` in double: what a backward scan without a per-ray row is
+    tempted to use. Equal to the forward prefix only while total * 2^-53 is small against fp32 rounding of X; Inf - Inf
+    is NaN."""
+    import numpy as np
+
+    dd = np.asarray(dd, np.float64)
+    with np.errstate(all="ignore"):
+        total = np.cumsum(dd)[-1] if len(dd) else 0.0
+        suffix = np.cumsum(dd[::-1])[::-1]
+        return np.exp(-(total - suffix).astype(np.float32).astype(np.float64))
