@@ -404,83 +404,89 @@ static int launch_fwd(const float* enc, const float* selector, int64_t M, nsamd_
   return NSAMD_OK;
 }
 
-template <int IN, int H>
-static int launch_bwd(const float* enc, const float* selector, const float* pre, const float* ddensity, int64_t M,
-                      nsamd_density_mlp mlp, float* denc, float* dW0, float* db0, float* dW1, float* db1,
-                      float* workspace, int64_t workspace_floats, const uint32_t* gate, const uint8_t* ray_mask, int spr,
-                      hipStream_t stream) {
-  const unsigned blocks = (unsigned)min((int64_t)kMaxBlocks, (M + kMlpBlock - 1) / kMlpBlock);
-  const size_t lds = sizeof(float) * ((size_t)(2 * H + IN + 1) * (kMlpBlock + 1) + 8 + (size_t)H * (((IN + 3) & ~3) + 2)) +
-                     kDensityActMax;
-  if (lds > 64 * 1024) {  // per-device opt-in; cheap enough to repeat
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&density_mlp_bwd_kernel<IN, H>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-      return NSAMD_ERR_LAUNCH;
-  }
-  constexpr int stride = density_partial_stride(IN, H);
-  float* partials = (workspace != nullptr && workspace_floats >= (int64_t)blocks * stride) ? workspace : nullptr;
-  density_mlp_bwd_kernel<IN, H><<<blocks, kMlpBlock, lds, stream>>>(enc, selector, pre, ddensity, M, mlp, denc, dW0,
-                                                                   db0, dW1, db1, partials, gate, ray_mask, spr);
-  NSAMD_CHECK_LAUNCH();
-  if (partials != nullptr) {
-    const int total = H * IN + 2 * H + 1;
-    density_dw_reduce_kernel<<<(total + 63) / 64, 64 * kDwGroups, 0, stream>>>(partials, (int)blocks, stride, H * IN, H,
-                                                                             dW0, db0, dW1, db1, gate);
-    NSAMD_CHECK_LAUNCH();
-  }
-  return NSAMD_OK;
-}
-
-template <int IN, int H>
-static int launch_bwd_pair(const DensityBwdCall& a, const DensityBwdCall& b, hipStream_t stream) {
-  const DensityBwdCall* c[2] = {&a, &b};
-  const size_t lds = sizeof(float) * ((size_t)(2 * H + IN + 1) * (kMlpBlock + 1) + 8 + (size_t)H * (((IN + 3) & ~3) + 2)) +
-                     kDensityActMax;
-  if (lds > 64 * 1024) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&density_mlp_bwd_pair_kernel<IN, H>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-      return NSAMD_ERR_LAUNCH;
-  }
-  constexpr int stride = density_partial_stride(IN, H);
-  DensityBwdArgs k[2];
-  unsigned gx = 0;
-  for (int i = 0; i < 2; ++i) {
-    const unsigned blocks = (unsigned)min((int64_t)kMaxBlocks, (c[i]->M + kMlpBlock - 1) / kMlpBlock);
-    // (the merged launch is for the training step's calls, which bring the scratch of the fixed-order reduce)
-    if (c[i]->workspace == nullptr || c[i]->workspace_floats < (int64_t)blocks * stride) return NSAMD_ERR_UNSUPPORTED;
-    k[i] = DensityBwdArgs{c[i]->enc, c[i]->selector, c[i]->pre, c[i]->ddensity, c[i]->M, c[i]->mlp, c[i]->denc, c[i]->dW0,
-                          c[i]->db0, c[i]->dW1, c[i]->db1, c[i]->workspace, c[i]->gate, c[i]->ray_mask,
-                          c[i]->ray_mask ? c[i]->spr : 1, (int)blocks};
-    gx = blocks > gx ? blocks : gx;
-  }
-  if (a.workspace == b.workspace || a.dW0 == b.dW0) return NSAMD_ERR_UNSUPPORTED;  // one network for both levels: in turn
-  density_mlp_bwd_pair_kernel<IN, H><<<dim3(gx, 2u), kMlpBlock, lds, stream>>>(k[0], k[1]);
-  NSAMD_CHECK_LAUNCH();
-  const int total = H * IN + 2 * H + 1;
-  density_dw_reduce_pair_kernel<<<dim3((total + 63) / 64, 2u), 64 * kDwGroups, 0, stream>>>(k[0], k[1], stride, H * IN, H);
-  NSAMD_CHECK_LAUNCH();
-  return NSAMD_OK;
-}
-
-int density_bwd_launch_pair(const DensityBwdCall& a, const DensityBwdCall& b, hipStream_t stream) {
-  if (a.mlp.in_dim != b.mlp.in_dim || a.mlp.hidden != b.mlp.hidden || a.M <= 0 || b.M <= 0) return NSAMD_ERR_UNSUPPORTED;
-  if (a.mlp.in_dim == 10 && a.mlp.hidden == 16) return launch_bwd_pair<10, 16>(a, b, stream);
-  if (a.mlp.in_dim == 16 && a.mlp.hidden == 16) return launch_bwd_pair<16, 16>(a, b, stream);
-  if (a.mlp.in_dim == 10 && a.mlp.hidden == 64) return launch_bwd_pair<10, 64>(a, b, stream);
-  if (a.mlp.in_dim == 16 && a.mlp.hidden == 64) return launch_bwd_pair<16, 64>(a, b, stream);
-  return NSAMD_ERR_UNSUPPORTED;
-}
-
-}  // namespace nsamd
-
-using namespace nsamd;
-
+// The (IN, H) instantiations: nerfacto's proposal networks and the wide ones (`mlp` in scope).
 #define NSAMD_DENSITY_DISPATCH(CALL)                                  \
   if (mlp.in_dim == 10 && mlp.hidden == 16) return CALL(10, 16);      \
   if (mlp.in_dim == 16 && mlp.hidden == 16) return CALL(16, 16);      \
   if (mlp.in_dim == 10 && mlp.hidden == 64) return CALL(10, 64);      \
   if (mlp.in_dim == 16 && mlp.hidden == 64) return CALL(16, 64);      \
   return NSAMD_ERR_UNSUPPORTED;
+
+// Backward + the fixed-order reduce of its partials for calls that passed density_bwd_check, M > 0, all (IN, H). Two calls
+// share the launches (blockIdx.y selects the call) when both bring the scratch of the reduce and share none of it and no
+// gradient (one network for both levels: in turn); otherwise they run one after the other.
+template <int IN, int H>
+static int launch_bwd(const DensityBwdCall* c, int n, hipStream_t stream) {
+  constexpr int stride = density_partial_stride(IN, H);
+  constexpr int total = H * IN + 2 * H + 1;
+  const size_t lds = sizeof(float) * ((size_t)(2 * H + IN + 1) * (kMlpBlock + 1) + 8 + (size_t)H * (((IN + 3) & ~3) + 2)) +
+                     kDensityActMax;
+  DensityBwdArgs k[2];
+  for (int i = 0; i < n; ++i) {
+    const int blocks = (int)min((int64_t)kMaxBlocks, (c[i].M + kMlpBlock - 1) / kMlpBlock);
+    float* partials = (c[i].workspace != nullptr && c[i].workspace_floats >= (int64_t)blocks * stride) ? c[i].workspace : nullptr;
+    k[i] = DensityBwdArgs{c[i].enc, c[i].selector, c[i].pre, c[i].ddensity, c[i].M, c[i].mlp, c[i].denc, c[i].dW0, c[i].db0,
+                          c[i].dW1, c[i].db1, partials, c[i].gate, c[i].ray_mask, c[i].ray_mask ? c[i].spr : 1, blocks};
+  }
+  const bool pair = n == 2 && k[0].partials != nullptr && k[1].partials != nullptr && k[0].partials != k[1].partials &&
+                    k[0].dW0 != k[1].dW0;
+  if (n == 2 && !pair) {
+    const int rc = launch_bwd<IN, H>(c, 1, stream);
+    return rc ? rc : launch_bwd<IN, H>(c + 1, 1, stream);
+  }
+  if (lds > 64 * 1024) {  // per-device opt-in; cheap enough to repeat
+    const void* kernel = pair ? reinterpret_cast<const void*>(&density_mlp_bwd_pair_kernel<IN, H>)
+                              : reinterpret_cast<const void*>(&density_mlp_bwd_kernel<IN, H>);
+    if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return NSAMD_ERR_LAUNCH;
+  }
+  const DensityBwdArgs& a = k[0];
+  if (pair) {
+    density_mlp_bwd_pair_kernel<IN, H><<<dim3((unsigned)max(a.nblocks, k[1].nblocks), 2u), kMlpBlock, lds, stream>>>(a, k[1]);
+    NSAMD_CHECK_LAUNCH();
+    density_dw_reduce_pair_kernel<<<dim3((total + 63) / 64, 2u), 64 * kDwGroups, 0, stream>>>(a, k[1], stride, H * IN, H);
+    NSAMD_CHECK_LAUNCH();
+    return NSAMD_OK;
+  }
+  density_mlp_bwd_kernel<IN, H><<<(unsigned)a.nblocks, kMlpBlock, lds, stream>>>(
+      a.enc, a.selector, a.pre, a.ddensity, a.M, a.mlp, a.denc, a.dW0, a.db0, a.dW1, a.db1, a.partials, a.gate, a.ray_mask, a.spr);
+  NSAMD_CHECK_LAUNCH();
+  if (a.partials != nullptr) {
+    density_dw_reduce_kernel<<<(total + 63) / 64, 64 * kDwGroups, 0, stream>>>(a.partials, a.nblocks, stride, H * IN, H, a.dW0,
+                                                                             a.db0, a.dW1, a.db1, a.gate);
+    NSAMD_CHECK_LAUNCH();
+  }
+  return NSAMD_OK;
+}
+
+static int density_bwd_check(const DensityBwdCall& c) {
+  NSAMD_REQUIRE(c.M >= 0);
+  NSAMD_REQUIRE(c.ray_mask == nullptr || (c.spr > 0 && c.M % c.spr == 0));
+  if (c.M == 0) return NSAMD_OK;
+  NSAMD_REQUIRE(c.enc && c.pre && c.ddensity && c.denc && c.dW0 && c.db0 && c.dW1 && c.db1 && c.mlp.W0 && c.mlp.b0 && c.mlp.W1 &&
+                c.mlp.b1);
+  return NSAMD_OK;
+}
+
+int density_bwd_launch(const DensityBwdCall* c, int n, hipStream_t stream) {
+  NSAMD_REQUIRE(c != nullptr && (n == 1 || n == 2));
+  const nsamd_density_mlp& mlp = c[0].mlp;
+  if (n == 2 && (mlp.in_dim != c[1].mlp.in_dim || mlp.hidden != c[1].mlp.hidden || c[0].M <= 0 || c[1].M <= 0 ||
+                 density_bwd_check(c[0]) || density_bwd_check(c[1]))) {
+    const int rc = density_bwd_launch(c, 1, stream);
+    return rc ? rc : density_bwd_launch(c + 1, 1, stream);
+  }
+  if (n == 1) {
+    const int rc = density_bwd_check(c[0]);
+    if (rc || c[0].M == 0) return rc;
+  }
+#define CALL(IN, H) launch_bwd<IN, H>(c, n, stream)
+  NSAMD_DENSITY_DISPATCH(CALL)
+#undef CALL
+}
+
+}  // namespace nsamd
+
+using namespace nsamd;
 
 extern "C" int nsamd_density_mlp_fwd(const float* enc, const float* selector, int64_t M, nsamd_density_mlp mlp,
                                      float* density, float* pre, nsamd_stream_t stream) {
@@ -530,14 +536,9 @@ extern "C" int nsamd_density_mlp_bwd(const float* enc, const float* selector, co
                                      const float* ddensity, int64_t M, nsamd_density_mlp mlp, float* denc,
                                      float* dW0, float* db0, float* dW1, float* db1, float* workspace,
                                      int64_t workspace_floats, nsamd_stream_t stream) {
-  NSAMD_REQUIRE(M >= 0);
-  if (M == 0) return NSAMD_OK;
-  NSAMD_REQUIRE(enc && pre && ddensity && denc && dW0 && db0 && dW1 && db1 && mlp.W0 && mlp.b0 && mlp.W1 && mlp.b1);
-#define CALL(IN, H)                                                                                          \
-  launch_bwd<IN, H>(enc, selector, pre, ddensity, M, mlp, denc, dW0, db0, dW1, db1, workspace, workspace_floats, \
-                    nullptr, nullptr, 1, (hipStream_t)stream)
-  NSAMD_DENSITY_DISPATCH(CALL)
-#undef CALL
+  const DensityBwdCall c{enc, selector, pre, ddensity, M, mlp, denc, dW0, db0, dW1, db1, workspace, workspace_floats,
+                         nullptr, nullptr, 1};
+  return density_bwd_launch(&c, 1, (hipStream_t)stream);
 }
 
 extern "C" int nsamd_density_mlp_bwd_gated(const float* enc, const float* selector, const float* pre,
@@ -545,13 +546,8 @@ extern "C" int nsamd_density_mlp_bwd_gated(const float* enc, const float* select
                                            float* dW0, float* db0, float* dW1, float* db1, float* workspace,
                                            int64_t workspace_floats, const uint32_t* gate, const uint8_t* ray_mask,
                                            int32_t samples_per_ray, nsamd_stream_t stream) {
-  NSAMD_REQUIRE(M >= 0 && gate != nullptr);
-  NSAMD_REQUIRE(ray_mask == nullptr || (samples_per_ray > 0 && M % samples_per_ray == 0));
-  if (M == 0) return NSAMD_OK;
-  NSAMD_REQUIRE(enc && pre && ddensity && denc && dW0 && db0 && dW1 && db1 && mlp.W0 && mlp.b0 && mlp.W1 && mlp.b1);
-#define CALL(IN, H)                                                                                          \
-  launch_bwd<IN, H>(enc, selector, pre, ddensity, M, mlp, denc, dW0, db0, dW1, db1, workspace, workspace_floats, \
-                    gate, ray_mask, ray_mask ? samples_per_ray : 1, (hipStream_t)stream)
-  NSAMD_DENSITY_DISPATCH(CALL)
-#undef CALL
+  NSAMD_REQUIRE(gate != nullptr);
+  const DensityBwdCall c{enc, selector, pre, ddensity, M, mlp, denc, dW0, db0, dW1, db1, workspace, workspace_floats,
+                         gate, ray_mask, samples_per_ray};
+  return density_bwd_launch(&c, 1, (hipStream_t)stream);
 }

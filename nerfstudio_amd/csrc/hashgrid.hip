@@ -512,10 +512,7 @@ static int hashgrid_encode_bwd_impl(nsamd_points pts, int64_t M, int transform, 
   NSAMD_REQUIRE(dtable != nullptr || dpositions != nullptr);
   // The binned, order-independent scatter (scatter.hip) whenever the caller's scratch holds its plan
   ScatterPlan plan{};
-  if (dtable != nullptr && M > 0 && workspace != nullptr) {
-    plan = scatter_plan(grid, M, overwrite);
-    if (plan.ok && plan.total_words > workspace_floats) plan.ok = false;
-  }
+  if (dtable != nullptr) plan = scatter_plan_in(grid, M, overwrite, workspace, workspace_floats);
   if (overwrite) {
     // write-only table gradient: the binned path overwrites every tile; anything else zero-fills first
     NSAMD_REQUIRE(dtable != nullptr);
@@ -530,8 +527,8 @@ static int hashgrid_encode_bwd_impl(nsamd_points pts, int64_t M, int transform, 
   const int64_t nb = (M + kHashBlock - 1) / kHashBlock;
   if (nb > 0x7fffffffLL) return NSAMD_ERR_UNSUPPORTED;
   if (dtable != nullptr && plan.ok) {
-    st = scatter_launch(pts, M, transform, aabb, grid, denc, stride_p, stride_k, dtable, workspace, plan, overwrite,
-                        gate, ray_mask, (hipStream_t)stream);
+    const ScatterCall call{pts, M, transform, aabb, grid, denc, stride_p, stride_k, dtable, workspace, plan, overwrite, gate, ray_mask};
+    st = scatter_launch(&call, 1, (hipStream_t)stream);
     if (st) return st;
   } else if (gate != nullptr) {
     return NSAMD_ERR_INVALID_ARG;  // gated calls exist for the binned scatter only (the training step's workspaces)

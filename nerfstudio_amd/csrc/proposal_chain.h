@@ -1,13 +1,15 @@
-// Internal interface of the merged proposal-level backward (proposal_chain.hip: nsamd_proposal_levels_bwd): every stage of
-// two levels' chains as ONE launch. Each `*_launch_pair` returns NSAMD_ERR_UNSUPPORTED with nothing enqueued when its two
-// calls cannot share a launch; the caller then issues them one after the other. Not part of the C ABI.
+// Internal interface of the proposal-level backward's stages (proposal_chain.hip: nsamd_proposal_levels_bwd, and the per-level
+// entry points of sampler.hip and density_mlp.hip). Each `*_launch` takes n = 1 or 2 calls: one call is the per-level launch;
+// two calls share ONE launch per kernel where they can, and otherwise run one after the other. The scatter stage is
+// scatter.h's scatter_launch, of the same shape. Not part of the C ABI.
 #pragma once
 
 #include "common.h"
 
 namespace nsamd {
 
-// RaySamples.get_weights backward with the zero-gradient gate (sampler.hip: weights_bwd_kernel)
+// RaySamples.get_weights backward (sampler.hip: weights_bwd_kernel); `gate` (nullable, cleared by the caller) and `ray_mask`
+// (nullable) are its zero-gradient outputs
 struct WeightsBwdCall {
   const float* t_bins;
   const float* density;
@@ -18,7 +20,7 @@ struct WeightsBwdCall {
   uint32_t* gate;
   uint8_t* ray_mask;
 };
-int weights_bwd_launch_pair(const WeightsBwdCall& a, const WeightsBwdCall& b, hipStream_t stream);
+int weights_bwd_launch(const WeightsBwdCall* calls, int n, hipStream_t stream);
 
 // density MLP backward + the fixed-order reduce of its weight-gradient partials (density_mlp.hip)
 struct DensityBwdCall {
@@ -37,8 +39,8 @@ struct DensityBwdCall {
   int64_t workspace_floats;
   const uint32_t* gate;
   const uint8_t* ray_mask;
-  int spr;
+  int spr;  // samples per ray (read with `ray_mask` only)
 };
-int density_bwd_launch_pair(const DensityBwdCall& a, const DensityBwdCall& b, hipStream_t stream);
+int density_bwd_launch(const DensityBwdCall* calls, int n, hipStream_t stream);
 
 }  // namespace nsamd

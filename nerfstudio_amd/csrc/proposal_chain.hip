@@ -9,7 +9,8 @@
 // waves spend 16 - 30 us in two sweeps whether 5 or 900 of 4096 rays carry gradient). The levels share nothing — separate
 // networks, tables, gradients, scratch —, so here the SAME stage of two levels is one launch (blockIdx.y / .z selects the
 // level, every workgroup runs the unchanged per-level body): twelve launches become six, and two latency chains run side
-// by side. Same bits as the per-level entry points, call by call.
+// by side. Same bits as the per-level entry points, call by call. Whether two calls of a stage can share its launches is the
+// stage's own launcher's business (proposal_chain.h, scatter.h); where they cannot, it runs them one after the other.
 #include "proposal_chain.h"
 #include "scatter.h"
 
@@ -36,20 +37,10 @@ static nsamd_points level_points(const nsamd_proposal_level_bwd& l) {
   return p;
 }
 
-// one level through the per-level entry points (an odd level out, or a stage whose two calls cannot share a launch)
-static int weights_single(const nsamd_proposal_level_bwd& l, nsamd_stream_t st) {
-  return nsamd_weights_bwd_gate(l.t_bins, l.density, l.dweights, l.num_rays, l.samples_per_ray, l.ddensity, l.gate, l.ray_mask,
-                                /*gate_precleared=*/1, st);
-}
-static int density_single(const nsamd_proposal_level_bwd& l, nsamd_stream_t st) {
-  return nsamd_density_mlp_bwd_gated(l.enc, l.selector, l.pre, l.ddensity, l.num_rays * l.samples_per_ray, l.mlp, l.denc, l.dW0,
-                                     l.db0, l.dW1, l.db1, l.mlp_workspace, l.mlp_workspace_floats, l.gate, l.ray_mask,
-                                     l.samples_per_ray, st);
-}
-static int scatter_single(const nsamd_proposal_level_bwd& l, nsamd_stream_t st) {
+static ScatterCall level_scatter(const nsamd_proposal_level_bwd& l) {
   const int64_t M = l.num_rays * l.samples_per_ray;
-  return nsamd_hashgrid_encode_bwd_gated(level_points(l), M, l.transform, l.aabb, l.table, l.grid, l.denc, 1, M, l.dtable,
-                                         l.scatter_workspace, l.scatter_workspace_floats, l.gate, l.ray_mask, st);
+  return ScatterCall{level_points(l), M, l.transform, l.aabb, l.grid, l.denc, 1, M, l.dtable, l.scatter_workspace,
+                     scatter_plan_in(l.grid, M, false, l.scatter_workspace, l.scatter_workspace_floats), false, l.gate, l.ray_mask};
 }
 
 extern "C" int nsamd_proposal_levels_bwd(const nsamd_proposal_level_bwd* levels, int32_t num_levels, int32_t gates_precleared,
@@ -65,52 +56,20 @@ extern "C" int nsamd_proposal_levels_bwd(const nsamd_proposal_level_bwd* levels,
       if (hipMemsetAsync(levels[i].gate, 0, sizeof(uint32_t), st) != hipSuccess) return NSAMD_ERR_LAUNCH;
   }
   for (int i = 0; i < num_levels; i += 2) {
-    const nsamd_proposal_level_bwd& a = levels[i];
-    if (i + 1 >= num_levels) {
-      int rc = weights_single(a, stream);
-      if (!rc) rc = density_single(a, stream);
-      if (!rc) rc = scatter_single(a, stream);
-      if (rc) return rc;
-      break;
+    const int n = i + 1 < num_levels ? 2 : 1;  // levels i, i + 1 stage by stage, or an odd level out alone
+    WeightsBwdCall weights[2];
+    DensityBwdCall density[2];
+    ScatterCall scatter[2];
+    for (int j = 0; j < n; ++j) {
+      const nsamd_proposal_level_bwd& l = levels[i + j];
+      weights[j] = WeightsBwdCall{l.t_bins, l.density, l.dweights, l.num_rays, l.samples_per_ray, l.ddensity, l.gate, l.ray_mask};
+      density[j] = DensityBwdCall{l.enc, l.selector, l.pre, l.ddensity, l.num_rays * l.samples_per_ray, l.mlp, l.denc, l.dW0, l.db0,
+                                  l.dW1, l.db1, l.mlp_workspace, l.mlp_workspace_floats, l.gate, l.ray_mask, l.samples_per_ray};
+      scatter[j] = level_scatter(l);
     }
-    const nsamd_proposal_level_bwd& b = levels[i + 1];
-    const int64_t Ma = a.num_rays * a.samples_per_ray, Mb = b.num_rays * b.samples_per_ray;
-    // ---- RaySamples.get_weights backward + gate ------------------------------------------------------------------------
-    int rc = weights_bwd_launch_pair(
-        WeightsBwdCall{a.t_bins, a.density, a.dweights, a.num_rays, a.samples_per_ray, a.ddensity, a.gate, a.ray_mask},
-        WeightsBwdCall{b.t_bins, b.density, b.dweights, b.num_rays, b.samples_per_ray, b.ddensity, b.gate, b.ray_mask}, st);
-    if (rc == NSAMD_ERR_UNSUPPORTED) {
-      rc = weights_single(a, stream);
-      if (!rc) rc = weights_single(b, stream);
-    }
-    if (rc) return rc;
-    // ---- density MLP backward + weight-gradient reduce -------------------------------------------------------------------
-    rc = density_bwd_launch_pair(
-        DensityBwdCall{a.enc, a.selector, a.pre, a.ddensity, Ma, a.mlp, a.denc, a.dW0, a.db0, a.dW1, a.db1, a.mlp_workspace,
-                       a.mlp_workspace_floats, a.gate, a.ray_mask, a.samples_per_ray},
-        DensityBwdCall{b.enc, b.selector, b.pre, b.ddensity, Mb, b.mlp, b.denc, b.dW0, b.db0, b.dW1, b.db1, b.mlp_workspace,
-                       b.mlp_workspace_floats, b.gate, b.ray_mask, b.samples_per_ray},
-        st);
-    if (rc == NSAMD_ERR_UNSUPPORTED) {
-      rc = density_single(a, stream);
-      if (!rc) rc = density_single(b, stream);
-    }
-    if (rc) return rc;
-    // ---- table scatter: route, apply, finish -----------------------------------------------------------------------------
-    ScatterPlan pa = scatter_plan(a.grid, Ma, false), pb = scatter_plan(b.grid, Mb, false);
-    rc = NSAMD_ERR_UNSUPPORTED;
-    if (pa.ok && pb.ok && pa.total_words <= a.scatter_workspace_floats && pb.total_words <= b.scatter_workspace_floats) {
-      rc = scatter_launch_pair(
-          ScatterCall{level_points(a), Ma, a.transform, a.aabb, a.grid, a.denc, 1, Ma, a.dtable, a.scatter_workspace, pa, false,
-                      a.gate, a.ray_mask},
-          ScatterCall{level_points(b), Mb, b.transform, b.aabb, b.grid, b.denc, 1, Mb, b.dtable, b.scatter_workspace, pb, false,
-                      b.gate, b.ray_mask},
-          st);
-    }
-    if (rc == NSAMD_ERR_UNSUPPORTED) {
-      rc = scatter_single(a, stream);
-      if (!rc) rc = scatter_single(b, stream);
-    }
+    int rc = weights_bwd_launch(weights, n, st);        // RaySamples.get_weights backward + gate
+    if (!rc) rc = density_bwd_launch(density, n, st);  // density MLP backward + weight-gradient reduce
+    if (!rc) rc = scatter_launch(scatter, n, st);      // table scatter: route, apply, finish
     if (rc) return rc;
   }
   return NSAMD_OK;

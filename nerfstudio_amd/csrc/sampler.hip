@@ -201,32 +201,33 @@ extern "C" int nsamd_weights_fwd(const float* t_bins, const float* density, int6
   return NSAMD_OK;
 }
 
-static int weights_bwd_launch(const float* t_bins, const float* density, const float* dweights, int64_t num_rays,
-                              int32_t S, float* ddensity, uint32_t* gate_out, uint8_t* ray_mask, nsamd_stream_t stream,
-                              bool gate_precleared = false) {
-  NSAMD_REQUIRE(num_rays >= 0 && S > 0);
-  if (gate_out != nullptr && !gate_precleared &&  // cleared on the stream ahead of the launch (a memset node inside a captured graph)
-      hipMemsetAsync(gate_out, 0, sizeof(uint32_t), (hipStream_t)stream) != hipSuccess)
-    return NSAMD_ERR_LAUNCH;
-  if (num_rays == 0) return NSAMD_OK;
-  NSAMD_REQUIRE(t_bins && density && dweights && ddensity);
-  if (S > 1024) return NSAMD_ERR_UNSUPPORTED;
-  const size_t lds = sizeof(float) * 3 * kWaves * (size_t)S;
-  weights_bwd_kernel<<<ray_blocks(num_rays), kThreads, lds, (hipStream_t)stream>>>(t_bins, density, dweights,
-                                                                                   num_rays, S, ddensity, gate_out, ray_mask);
-  NSAMD_CHECK_LAUNCH();
+static int weights_bwd_check(const WeightsBwdCall& c) {
+  NSAMD_REQUIRE(c.num_rays >= 0 && c.S > 0);
+  if (c.num_rays == 0) return NSAMD_OK;
+  NSAMD_REQUIRE(c.t_bins && c.density && c.dweights && c.ddensity);
+  if (c.S > 1024) return NSAMD_ERR_UNSUPPORTED;
   return NSAMD_OK;
 }
 
 namespace nsamd {
-int weights_bwd_launch_pair(const WeightsBwdCall& a, const WeightsBwdCall& b, hipStream_t stream) {
-  // (the gates are cleared by the caller)
-  if (a.num_rays <= 0 || b.num_rays <= 0 || a.S <= 0 || b.S <= 0 || a.S > 1024 || b.S > 1024) return NSAMD_ERR_UNSUPPORTED;
-  if (!(a.t_bins && a.density && a.dweights && a.ddensity && b.t_bins && b.density && b.dweights && b.ddensity))
-    return NSAMD_ERR_INVALID_ARG;
-  const int64_t rays = a.num_rays > b.num_rays ? a.num_rays : b.num_rays;
-  const size_t lds = sizeof(float) * 3 * kWaves * (size_t)(a.S > b.S ? a.S : b.S);
-  weights_bwd_pair_kernel<<<dim3(ray_blocks(rays), 2u), kThreads, lds, stream>>>(a, b);
+// (the gates are cleared by the caller)
+int weights_bwd_launch(const WeightsBwdCall* c, int n, hipStream_t stream) {
+  NSAMD_REQUIRE(c != nullptr && (n == 1 || n == 2));
+  const auto lds = [](int S) { return sizeof(float) * 3 * kWaves * (size_t)S; };
+  if (n == 2) {
+    const WeightsBwdCall &a = c[0], &b = c[1];
+    if (a.num_rays <= 0 || b.num_rays <= 0 || weights_bwd_check(a) || weights_bwd_check(b)) {
+      const int rc = weights_bwd_launch(c, 1, stream);
+      return rc ? rc : weights_bwd_launch(c + 1, 1, stream);
+    }
+    const int64_t rays = a.num_rays > b.num_rays ? a.num_rays : b.num_rays;
+    weights_bwd_pair_kernel<<<dim3(ray_blocks(rays), 2u), kThreads, lds(a.S > b.S ? a.S : b.S), stream>>>(a, b);
+  } else {
+    const int rc = weights_bwd_check(c[0]);
+    if (rc || c[0].num_rays == 0) return rc;
+    weights_bwd_kernel<<<ray_blocks(c[0].num_rays), kThreads, lds(c[0].S), stream>>>(
+        c[0].t_bins, c[0].density, c[0].dweights, c[0].num_rays, c[0].S, c[0].ddensity, c[0].gate, c[0].ray_mask);
+  }
   NSAMD_CHECK_LAUNCH();
   return NSAMD_OK;
 }
@@ -234,15 +235,19 @@ int weights_bwd_launch_pair(const WeightsBwdCall& a, const WeightsBwdCall& b, hi
 
 extern "C" int nsamd_weights_bwd(const float* t_bins, const float* density, const float* dweights,
                                  int64_t num_rays, int32_t S, float* ddensity, nsamd_stream_t stream) {
-  return weights_bwd_launch(t_bins, density, dweights, num_rays, S, ddensity, nullptr, nullptr, stream);
+  const WeightsBwdCall c{t_bins, density, dweights, num_rays, S, ddensity, nullptr, nullptr};
+  return weights_bwd_launch(&c, 1, (hipStream_t)stream);
 }
 
 extern "C" int nsamd_weights_bwd_gate(const float* t_bins, const float* density, const float* dweights,
                                       int64_t num_rays, int32_t S, float* ddensity, uint32_t* gate_out,
                                       uint8_t* ray_mask_out, int32_t gate_precleared, nsamd_stream_t stream) {
-  NSAMD_REQUIRE(gate_out != nullptr);
-  return weights_bwd_launch(t_bins, density, dweights, num_rays, S, ddensity, gate_out, ray_mask_out, stream,
-                            gate_precleared != 0);
+  NSAMD_REQUIRE(gate_out != nullptr && num_rays >= 0 && S > 0);
+  if (!gate_precleared &&  // cleared on the stream ahead of the launch (a memset node inside a captured graph)
+      hipMemsetAsync(gate_out, 0, sizeof(uint32_t), (hipStream_t)stream) != hipSuccess)
+    return NSAMD_ERR_LAUNCH;
+  const WeightsBwdCall c{t_bins, density, dweights, num_rays, S, ddensity, gate_out, ray_mask_out};
+  return weights_bwd_launch(&c, 1, (hipStream_t)stream);
 }
 
 extern "C" int nsamd_pdf_resample(const float* s_bins_prev, const float* weights, int32_t S_prev,

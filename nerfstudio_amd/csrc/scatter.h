@@ -196,6 +196,8 @@ struct ScatterPlan {
 
 // Host: geometry for (grid, M); `max_spill` = true sizes the spill list for the worst case (write-only calls).
 ScatterPlan scatter_plan(const nsamd_grid& grid, int64_t M, bool max_spill);
+// ... for a call whose scratch is `workspace` (nullable) of `workspace_floats` words: not ok when the scratch does not hold it.
+ScatterPlan scatter_plan_in(const nsamd_grid& grid, int64_t M, bool max_spill, const float* workspace, int64_t workspace_floats);
 
 // Host: geometry for records emitted by `workgroups` PERSISTENT producer workgroups (the main field's backward kernel emits
 // the pass-1 records of its own points: nsamd_field_mlp_bwd_scatter): one static segment of `seg_cap` records per
@@ -214,17 +216,10 @@ bool scatter_apply_takes_rider(const ScatterPlan& plan);
 int scatter_apply_launch(const nsamd_grid& grid, const ScatterPlan& plan, float* workspace, float* dtable, bool overwrite,
                          hipStream_t stream, const ReduceRider* rider = nullptr);
 
-// Host: enqueue route (pass 1) + apply (pass 2) + finish on `stream`. Returns an nsamd_status. `gate` (nullable, device):
-// accumulating calls only — while *gate == 0 all kernels return at once (the gradient being scattered is all zeros);
-// `ray_mask` (nullable, [rays] bytes, ray mode + gate only): samples of rays whose byte is 0 are zeros and are not loaded.
-int scatter_launch(const nsamd_points& pts, int64_t M, int transform, const nsamd_aabb& aabb, const nsamd_grid& grid,
-                   const float* denc, int64_t stride_p, int64_t stride_k, float* dtable, float* workspace,
-                   const ScatterPlan& plan, bool overwrite, const uint32_t* gate, const uint8_t* ray_mask,
-                   hipStream_t stream);
-
-// Host: TWO independent calls (different tables, workspaces and gradients) with their route, apply and finish passes merged
-// pairwise into one launch each. NSAMD_ERR_UNSUPPORTED (nothing enqueued): the calls cannot be merged — the caller issues
-// scatter_launch for each.
+// One call of the scatter: route (pass 1) + apply (pass 2) + finish. `plan`: scatter_plan_in's for `workspace`. `gate`
+// (nullable, device): accumulating calls only — while *gate == 0 all kernels return at once (the gradient being scattered is
+// all zeros); `ray_mask` (nullable, [rays] bytes, ray mode + gate only): samples of rays whose byte is 0 are zeros and are
+// not loaded.
 struct ScatterCall {
   nsamd_points pts;
   int64_t M;
@@ -240,6 +235,10 @@ struct ScatterCall {
   const uint32_t* gate;
   const uint8_t* ray_mask;
 };
-int scatter_launch_pair(const ScatterCall& a, const ScatterCall& b, hipStream_t stream);
+
+// Host: enqueue n = 1 or 2 calls on `stream`; returns an nsamd_status. Two independent calls (different tables, workspaces
+// and gradients) that route every level through the run kernel have their route, apply and finish passes merged pairwise
+// into one launch each; any other two run one after the other.
+int scatter_launch(const ScatterCall* calls, int n, hipStream_t stream);
 
 }  // namespace nsamd

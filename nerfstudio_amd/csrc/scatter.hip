@@ -740,8 +740,6 @@ __global__ void scatter_finish_pair_kernel(ApplyCall a, ApplyCall b) {  // (same
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------
-static unsigned apply_threads(int slice_log2);
-
 // fine-kernel shape: threads and levels per thread (one point per thread). Measured on MI355X
 // (profiles/r02_scatter_variants.txt): 1024 x 1 x 4 is the fastest or within noise of it; 512 threads, two points per thread,
 // two levels per thread and an LDS-staged coalescing variant were slower and are gone.
@@ -750,9 +748,10 @@ constexpr int kScatterTargetTiles = 512;
 
 constexpr int kSliceLog2Max = 13;  // 8192 entries x 2 x int64 = 128 KiB of the 160 KiB LDS
 
-ScatterPlan scatter_plan(const nsamd_grid& grid, int64_t M, bool max_spill) {
-  ScatterPlan p{};
-  if (M <= 0 || grid.num_levels <= 0 || grid.num_levels > NSAMD_MAX_LEVELS) return p;
+// Tiles of a grid: slice_log2, log2_bins and num_levels of `g`. False: no such grid, or more than 2^max_log2_bins tiles per
+// level (the LDS counters of whoever routes: kMaxLog2Bins for the route kernels, kProducerMaxLog2Bins for producers).
+static bool tile_geometry(const nsamd_grid& grid, int max_log2_bins, ScatterGeom& g) {
+  if (grid.num_levels <= 0 || grid.num_levels > NSAMD_MAX_LEVELS) return false;
   int bits = 0;
   while ((grid.num_levels << bits) < kScatterTargetTiles) ++bits;
   int sl = grid.log2_table_size - bits;
@@ -764,14 +763,62 @@ ScatterPlan scatter_plan(const nsamd_grid& grid, int64_t M, bool max_spill) {
   sl = sl < sl_pair ? sl_pair : sl;
   sl = sl > kSliceLog2Max ? kSliceLog2Max : (sl < 8 ? 8 : sl);
   if (sl > grid.log2_table_size) sl = grid.log2_table_size;
-  const int log2_bins = grid.log2_table_size - sl;
-  if (log2_bins > kMaxLog2Bins) return p;
-  ScatterGeom& g = p.geom;
   g.slice_log2 = sl;
-  g.log2_bins = log2_bins;
+  g.log2_bins = grid.log2_table_size - sl;
   g.num_levels = grid.num_levels;
+  return g.log2_bins <= max_log2_bins;
+}
+
+// The workspace, in 32-bit words: [header | per-tile cursors | counts[tile][seg] | queues | spill records | spill tiles].
+// Header and cursors are the state that must be zero before the first call.
+struct ScatterLayout {
+  int64_t counts, queues, spill_rec, spill_tile, total;  // first word of each region; `counts` = the state's words
+};
+static ScatterLayout scatter_layout(int64_t tiles, int64_t segs, int64_t queue_records, int64_t spill_cap) {
+  ScatterLayout w;
+  const int64_t cursor_words = (tiles + 3) & ~(int64_t)3;
+  const int64_t count_words = (tiles * segs + 3) & ~(int64_t)3;
+  w.counts = kHdrWords + cursor_words;
+  w.queues = w.counts + count_words;  // 16-B aligned: all sizes above are multiples of 4 words
+  w.spill_rec = w.queues + 4 * queue_records;
+  w.spill_tile = w.spill_rec + 4 * spill_cap;
+  w.total = w.spill_tile + ((spill_cap + 3) & ~(int64_t)3);
+  return w;
+}
+
+// Completes a plan whose tile geometry is set: `Q[level]` records per tile queue, of which `segs` static segments of
+// `seg_cap`, and a spill list of `spill` records. Sets `ok` unless a count leaves the 32-bit fields of the kernels.
+static void plan_queues(ScatterPlan& p, const int64_t* Q, int64_t segs, int64_t seg_cap, int64_t spill) {
+  ScatterGeom& g = p.geom;
+  const int64_t bins = (int64_t)1 << g.log2_bins;
+  p.tiles = bins * g.num_levels;
+  int64_t total = 0;
+  for (int l = 0; l < g.num_levels; ++l) {
+    if (total >= 0x7fffffffLL) return;
+    if (Q[l] + (int64_t)kSpillFold >= ((int64_t)1 << 30)) return;  // the per-level headroom is derived in pass 2
+    g.level_off[l] = (uint32_t)total;
+    g.level_cap[l] = (uint32_t)Q[l];
+    total += bins * Q[l];
+  }
+  if (total >= 0x7fffffffLL || segs >= 0x7fffffffLL || seg_cap >= 0x3fffffffLL || spill >= 0x7fffffffLL) return;
+  g.queue_records = (uint32_t)total;
+  g.segs = (uint32_t)segs;
+  g.seg_cap = (uint32_t)seg_cap;
+  g.spill_cap = (uint32_t)spill;
+  g.headroom = 0;
+  g.coarse_mask = 0u;
+  const ScatterLayout w = scatter_layout(p.tiles, segs, total, spill);
+  p.state_words = w.counts;
+  p.total_words = w.total;
+  p.ok = true;
+}
+
+ScatterPlan scatter_plan(const nsamd_grid& grid, int64_t M, bool max_spill) {
+  ScatterPlan p{};
+  ScatterGeom& g = p.geom;
+  if (M <= 0 || !tile_geometry(grid, kMaxLog2Bins, g)) return p;
   g.block_points = (uint32_t)kFineThreads;
-  const int64_t bins = (int64_t)1 << log2_bins;
+  const int64_t bins = (int64_t)1 << g.log2_bins;
   const int64_t segs = (M + g.block_points - 1) / g.block_points;
   // static segment: 2x the uniform-hash expectation of 4 pair records per point and level
   int64_t C = 2 * ((4 * (int64_t)g.block_points + bins - 1) / bins);
@@ -788,21 +835,11 @@ ScatterPlan scatter_plan(const nsamd_grid& grid, int64_t M, bool max_spill) {
   int64_t Qs = segs * C + 6 * expect + 64;
   if (Qs < 8 * expect + 64) Qs = 8 * expect + 64;
   Qs = (Qs + 3) & ~(int64_t)3;
-  p.tiles = bins * grid.num_levels;
-  int64_t total = 0, Qmax = 0;
+  int64_t Q[NSAMD_MAX_LEVELS];
   for (int l = 0; l < grid.num_levels; ++l) {
     const double lattice = ((double)grid.scalings[l] + 1.0) * ((double)grid.scalings[l] + 1.0) * ((double)grid.scalings[l] + 1.0);
-    const int64_t Ql = lattice * 2.0 <= (double)((int64_t)1 << grid.log2_table_size) ? Qs : Qn;
-    if (total >= 0x7fffffffLL) return p;
-    g.level_off[l] = (uint32_t)total;
-    g.level_cap[l] = (uint32_t)Ql;
-    total += bins * Ql;
-    Qmax = Ql > Qmax ? Ql : Qmax;
+    Q[l] = lattice * 2.0 <= (double)((int64_t)1 << grid.log2_table_size) ? Qs : Qn;
   }
-  if (total >= 0x7fffffffLL || segs >= 0x7fffffffLL || C >= 0x3fffffffLL) return p;
-  g.queue_records = (uint32_t)total;
-  g.segs = (uint32_t)segs;
-  g.seg_cap = (uint32_t)C;
   // spill list: worst case (every record of the call: 4 pairs, or after run merging at most as many singles, per point
   // and level) for write-only calls; otherwise a quarter of the expected total
   int64_t spill = 4 * M * grid.num_levels + 64;
@@ -810,70 +847,50 @@ ScatterPlan scatter_plan(const nsamd_grid& grid, int64_t M, bool max_spill) {
     const int64_t part = M * grid.num_levels + 4096;
     spill = spill < part ? spill : part;
   }
-  if (spill >= 0x7fffffffLL) return p;
-  g.spill_cap = (uint32_t)spill;
-  if (Qmax + (int64_t)kSpillFold >= ((int64_t)1 << 30)) return p;  // the per-level headroom is derived in pass 2
-  g.headroom = 0;
-  g.coarse_mask = 0u;
-  const int64_t cursor_words = (p.tiles + 3) & ~(int64_t)3;
-  const int64_t count_words = (p.tiles * segs + 3) & ~(int64_t)3;
-  p.state_words = kHdrWords + cursor_words;
-  p.total_words = kHdrWords + cursor_words + count_words + 4 * total + 4 * spill + ((spill + 3) & ~(int64_t)3);
-  p.ok = true;
+  plan_queues(p, Q, segs, C, spill);
+  return p;
+}
+
+ScatterPlan scatter_plan_in(const nsamd_grid& grid, int64_t M, bool max_spill, const float* workspace, int64_t workspace_floats) {
+  ScatterPlan p{};
+  if (workspace != nullptr) p = scatter_plan(grid, M, max_spill);
+  if (p.ok && p.total_words > workspace_floats) p.ok = false;
   return p;
 }
 
 ScatterPlan scatter_plan_producers(const nsamd_grid& grid, int64_t M, int workgroups, int seg_cap) {
   ScatterPlan p{};
-  if (M <= 0 || workgroups <= 0 || seg_cap < 16 || grid.num_levels <= 0 || grid.num_levels > NSAMD_MAX_LEVELS) return p;
-  // tiles as scatter_plan chooses them: wide enough for every x-pair to stay inside one tile, 128 KiB of LDS at most
-  int bits = 0;
-  while ((grid.num_levels << bits) < kScatterTargetTiles) ++bits;
-  int sl = grid.log2_table_size - bits;
-  float res_max = 0.0f;
-  for (int l = 0; l < grid.num_levels; ++l) res_max = grid.scalings[l] > res_max ? grid.scalings[l] : res_max;
-  int sl_pair = 1;
-  while ((1 << sl_pair) < (int)res_max + 2 && sl_pair < kSliceLog2Max) ++sl_pair;
-  sl = sl < sl_pair ? sl_pair : sl;
-  sl = sl > kSliceLog2Max ? kSliceLog2Max : (sl < 8 ? 8 : sl);
-  if (sl > grid.log2_table_size) sl = grid.log2_table_size;
-  const int log2_bins = grid.log2_table_size - sl;
-  if (log2_bins > kProducerMaxLog2Bins) return p;  // the producer keeps one LDS counter per (level, tile)
   ScatterGeom& g = p.geom;
-  g.slice_log2 = sl;
-  g.log2_bins = log2_bins;
-  g.num_levels = grid.num_levels;
+  // tiles as scatter_plan chooses them; the producer keeps one LDS counter per (level, tile)
+  if (M <= 0 || workgroups <= 0 || seg_cap < 16 || !tile_geometry(grid, kProducerMaxLog2Bins, g)) return p;
   g.block_points = 0u;
-  const int64_t bins = (int64_t)1 << log2_bins;
+  const int64_t bins = (int64_t)1 << g.log2_bins;
   const int64_t segs = workgroups, C = (seg_cap + 3) & ~3;
   const int64_t expect = (4 * M + bins - 1) / bins;  // pair records per tile, uniform hash
   // static segments (scripts/study_fused_route_overflow.py: a 256-record segment holds every level of the benchmark's
   // batches but ~60 records of level 0) + a dynamic area for what overflows them
-  int64_t Q = segs * C + expect / 2 + 64;
-  Q = (Q + 3) & ~(int64_t)3;
-  p.tiles = bins * grid.num_levels;
-  int64_t total = 0;
-  for (int l = 0; l < grid.num_levels; ++l) {
-    if (total >= 0x7fffffffLL) return p;
-    g.level_off[l] = (uint32_t)total;
-    g.level_cap[l] = (uint32_t)Q;
-    total += bins * Q;
-  }
-  if (total >= 0x7fffffffLL || Q + (int64_t)kSpillFold >= ((int64_t)1 << 30)) return p;
-  g.queue_records = (uint32_t)total;
-  g.segs = (uint32_t)segs;
-  g.seg_cap = (uint32_t)C;
-  const int64_t spill = 4 * M * grid.num_levels + 64;  // worst case: the gradient is write-only, nothing may be lost
-  if (spill >= 0x7fffffffLL) return p;
-  g.spill_cap = (uint32_t)spill;
-  g.headroom = 0;
-  g.coarse_mask = 0u;
-  const int64_t cursor_words = (p.tiles + 3) & ~(int64_t)3;
-  const int64_t count_words = (p.tiles * segs + 3) & ~(int64_t)3;
-  p.state_words = kHdrWords + cursor_words;
-  p.total_words = kHdrWords + cursor_words + count_words + 4 * total + 4 * spill + ((spill + 3) & ~(int64_t)3);
-  p.ok = true;
+  int64_t Q[NSAMD_MAX_LEVELS];
+  for (int l = 0; l < grid.num_levels; ++l) Q[l] = (segs * C + expect / 2 + 64 + 3) & ~(int64_t)3;
+  // spill list, worst case: the gradient is write-only, nothing may be lost
+  plan_queues(p, Q, segs, C, 4 * M * grid.num_levels + 64);
   return p;
+}
+
+ScatterBufs scatter_bufs(float* workspace, const ScatterPlan& p) {
+  const ScatterLayout w = scatter_layout(p.tiles, p.geom.segs, p.geom.queue_records, p.geom.spill_cap);
+  ScatterBufs b;
+  uint32_t* base = reinterpret_cast<uint32_t*>(workspace);
+  b.hdr = base;
+  b.dyn_cursor = base + kHdrWords;
+  b.counts = base + w.counts;
+  b.queues = reinterpret_cast<uint4*>(base + w.queues);
+  b.spill_rec = reinterpret_cast<uint4*>(base + w.spill_rec);
+  b.spill_tile = base + w.spill_tile;
+  b.direct_table = nullptr;
+  b.log2_table_size = 0;
+  b.log2_bins = p.geom.log2_bins;
+  b.slice_log2 = p.geom.slice_log2;
+  return b;
 }
 
 // 128 KiB of dynamic LDS need the opt-in, per device
@@ -894,33 +911,6 @@ static int apply_lds_attribute() {
   return NSAMD_OK;
 }
 
-int scatter_apply_launch(const nsamd_grid& grid, const ScatterPlan& plan, float* workspace, float* dtable, bool overwrite,
-                         hipStream_t st, const ReduceRider* rider) {
-  ScatterGeom G = plan.geom;
-  ScatterBufs buf = scatter_bufs(workspace, plan);
-  buf.log2_table_size = grid.log2_table_size;
-  if (!overwrite) buf.direct_table = dtable;
-  int rc = apply_lds_attribute();
-  if (rc) return rc;
-  const unsigned threads = apply_threads(G.slice_log2);
-  ReduceRider rd{};
-  unsigned extra_rows = 0u;
-  if (rider != nullptr && rider->blocks > 0) {
-    if (threads != (unsigned)kReduceThreads) return NSAMD_ERR_UNSUPPORTED;  // (callers check `scatter_apply_takes_rider` first)
-    rd = *rider;
-    extra_rows = ((unsigned)rd.blocks + (1u << G.log2_bins) - 1u) >> G.log2_bins;
-  }
-  dim3 g2(1u << G.log2_bins, (unsigned)grid.num_levels + extra_rows);
-  if (extra_rows != 0u)
-    scatter_apply_kernel<true><<<g2, threads, (size_t)16 << G.slice_log2, st>>>(grid, G, buf, dtable, overwrite ? 1 : 0, nullptr, rd);
-  else
-    scatter_apply_kernel<false><<<g2, threads, (size_t)16 << G.slice_log2, st>>>(grid, G, buf, dtable, overwrite ? 1 : 0, nullptr, rd);
-  NSAMD_CHECK_LAUNCH();
-  scatter_finish_kernel<<<32, 256, 0, st>>>(grid, G, buf, dtable, nullptr);
-  NSAMD_CHECK_LAUNCH();
-  return NSAMD_OK;
-}
-
 // threads of an apply-pass workgroup for tiles of 2^slice_log2 entries
 static unsigned apply_threads(int slice_log2) {
   return slice_log2 > 11 ? 1024u : (slice_log2 > 9 ? 512u : 256u);
@@ -928,25 +918,11 @@ static unsigned apply_threads(int slice_log2) {
 
 bool scatter_apply_takes_rider(const ScatterPlan& plan) { return apply_threads(plan.geom.slice_log2) == 1024u; }
 
-ScatterBufs scatter_bufs(float* workspace, const ScatterPlan& p) {
-  ScatterBufs b;
-  uint32_t* w = reinterpret_cast<uint32_t*>(workspace);
-  b.hdr = w;
-  b.dyn_cursor = w + kHdrWords;
-  const int64_t cursor_words = (p.tiles + 3) & ~(int64_t)3;
-  b.counts = b.dyn_cursor + cursor_words;
-  const int64_t count_words = (p.tiles * (int64_t)p.geom.segs + 3) & ~(int64_t)3;
-  b.queues = reinterpret_cast<uint4*>(b.counts + count_words);  // 16-B aligned: all sizes above are multiples of 4 words
-  b.spill_rec = b.queues + (size_t)p.geom.queue_records;
-  b.spill_tile = reinterpret_cast<uint32_t*>(b.spill_rec + p.geom.spill_cap);
-  b.direct_table = nullptr;
-  b.log2_table_size = 0;
-  b.log2_bins = p.geom.log2_bins;
-  b.slice_log2 = p.geom.slice_log2;
-  return b;
-}
-
 // Which levels of a call go through the run-merging kernel (coarse) and which through the plain route (fine); sets G.coarse_mask.
+// Levels whose cells are wide against the sample spacing go through the run-merging kernel: with >= 192 samples per
+// ray (the first proposal level) consecutive samples share cells on every level of the small proposal grids and
+// merging pays (75 vs 107 us at M = 1 M); with 48 samples per ray the plain route is faster on every level
+// (178 vs 197 us for the main table; profiles/r02a_*).
 static void classify_levels(const nsamd_points& pts, const nsamd_grid& grid, ScatterGeom& G, LevelList& coarse,
                             LevelList& fine) {
   float coarse_below = 0.0f;
@@ -971,108 +947,120 @@ static void classify_levels(const nsamd_points& pts, const nsamd_grid& grid, Sca
 // (MI355X, driver window of the bench: 4 -> 75 us, 2 -> 54, 1 -> 54 per launch of the 256-sample level's scatter)
 constexpr int kRunLevels = 2;
 
-int scatter_launch(const nsamd_points& pts, int64_t M, int transform, const nsamd_aabb& aabb, const nsamd_grid& grid,
-                   const float* denc, int64_t stride_p, int64_t stride_k, float* dtable, float* workspace,
-                   const ScatterPlan& plan, bool overwrite, const uint32_t* gate, const uint8_t* ray_mask, hipStream_t st) {
-  if (gate != nullptr && overwrite) return NSAMD_ERR_INVALID_ARG;  // a write-only gradient must always be written
-  if (ray_mask != nullptr && (gate == nullptr || pts.positions != nullptr)) return NSAMD_ERR_INVALID_ARG;  // ray mode only
-  ScatterGeom G = plan.geom;
-  ScatterBufs buf = scatter_bufs(workspace, plan);
-  buf.log2_table_size = grid.log2_table_size;
-  if (!overwrite) buf.direct_table = dtable;
-  // Levels whose cells are wide against the sample spacing go through the run-merging kernel: with >= 192 samples per
-  // ray (the first proposal level) consecutive samples share cells on every level of the small proposal grids and
-  // merging pays (75 vs 107 us at M = 1 M); with 96 or 48 samples per ray the plain route is faster on every level
-  // (65 vs 88 us, 178 vs 197 us for the main table; profiles/r02a_*).
-  LevelList coarse{}, fine{};
-  classify_levels(pts, grid, G, coarse, fine);
-  {
-    const int rc = apply_lds_attribute();
-    if (rc) return rc;
+// A checked call with everything its launches take: what the kernels are passed, and the shapes of the run kernel's launch
+// (coarse levels) and of the apply pass's.
+struct ScatterPrepared {
+  ScatterGeom G;  // coarse_mask set
+  ScatterBufs buf;  // log2_table_size and direct_table set
+  LevelList coarse, fine;
+  dim3 runs_grid, apply_grid;  // (apply: without a rider's rows)
+  size_t runs_lds, apply_lds;
+  unsigned apply_threads;
+};
+
+static int scatter_prepare(const ScatterCall& c, ScatterPrepared& p) {
+  NSAMD_REQUIRE(c.plan.ok);                          // (a plan the caller's scratch does not hold is not ok: scatter_plan_in)
+  NSAMD_REQUIRE(c.gate == nullptr || !c.overwrite);  // a write-only gradient must always be written
+  NSAMD_REQUIRE(c.ray_mask == nullptr || (c.gate != nullptr && c.pts.positions == nullptr));  // ray mode only
+  p.G = c.plan.geom;
+  p.buf = scatter_bufs(c.workspace, c.plan);
+  p.buf.log2_table_size = c.grid.log2_table_size;
+  if (!c.overwrite) p.buf.direct_table = c.dtable;
+  p.coarse = LevelList{};
+  p.fine = LevelList{};
+  classify_levels(c.pts, c.grid, p.G, p.coarse, p.fine);
+  const int64_t per_block = (int64_t)kRunThreads * kRunLen;
+  p.runs_grid = dim3((unsigned)((c.M + per_block - 1) / per_block), (unsigned)((p.coarse.count + kRunLevels - 1) / kRunLevels));
+  p.runs_lds = sizeof(uint32_t) * (3 * (size_t)kRunLevels * ((size_t)1 << p.G.log2_bins) + kRunLevels);
+  p.apply_grid = dim3(1u << p.G.log2_bins, (unsigned)c.grid.num_levels);
+  p.apply_lds = (size_t)16 << p.G.slice_log2;
+  p.apply_threads = apply_threads(p.G.slice_log2);
+  return apply_lds_attribute();
+}
+
+// apply (pass 2) + finish of a prepared call; `rider` (nullable): extra rows of workgroups behind the levels
+static int scatter_apply_finish(const ScatterCall& c, const ScatterPrepared& p, const ReduceRider* rider, hipStream_t st) {
+  dim3 g2 = p.apply_grid;
+  const int overwrite = c.overwrite ? 1 : 0;
+  if (rider != nullptr && rider->blocks > 0) {
+    if (p.apply_threads != (unsigned)kReduceThreads) return NSAMD_ERR_UNSUPPORTED;  // (callers check `scatter_apply_takes_rider` first)
+    g2.y += ((unsigned)rider->blocks + g2.x - 1u) >> p.G.log2_bins;
+    scatter_apply_kernel<true><<<g2, p.apply_threads, p.apply_lds, st>>>(c.grid, p.G, p.buf, c.dtable, overwrite, c.gate, *rider);
+  } else {
+    scatter_apply_kernel<false><<<g2, p.apply_threads, p.apply_lds, st>>>(c.grid, p.G, p.buf, c.dtable, overwrite, c.gate,
+                                                                         ReduceRider{});
   }
-  if (fine.count > 0) {
-    const size_t lds = sizeof(uint32_t) * (3 * (size_t)kFineLevels * ((size_t)1 << G.log2_bins) + kFineLevels);
-    dim3 g1(G.segs, (unsigned)((fine.count + kFineLevels - 1) / kFineLevels));
-    scatter_route_fine_kernel<kFineThreads, 1, kFineLevels><<<g1, kFineThreads, lds, st>>>(
-        pts, M, transform, aabb, grid, denc, stride_p, stride_k, G, fine, buf, gate, ray_mask);
-    NSAMD_CHECK_LAUNCH();
-  }
-  if (coarse.count > 0) {
-    constexpr int kL = kRunLevels;
-    const int64_t per_block = (int64_t)kRunThreads * kRunLen;
-    const size_t lds = sizeof(uint32_t) * (3 * (size_t)kL * ((size_t)1 << G.log2_bins) + kL);
-    dim3 g1((unsigned)((M + per_block - 1) / per_block), (unsigned)((coarse.count + kL - 1) / kL));
-    scatter_route_runs_kernel<kL><<<g1, kRunThreads, lds, st>>>(pts, M, transform, aabb, grid, denc, stride_p, stride_k, G,
-                                                              coarse, buf, gate, ray_mask);
-    NSAMD_CHECK_LAUNCH();
-  }
-  const unsigned threads = apply_threads(G.slice_log2);
-  dim3 g2(1u << G.log2_bins, (unsigned)grid.num_levels);
-  scatter_apply_kernel<false><<<g2, threads, (size_t)16 << G.slice_log2, st>>>(grid, G, buf, dtable, overwrite ? 1 : 0, gate,
-                                                                               ReduceRider{});
   NSAMD_CHECK_LAUNCH();
-  scatter_finish_kernel<<<32, 256, 0, st>>>(grid, G, buf, dtable, gate);
+  scatter_finish_kernel<<<32, 256, 0, st>>>(c.grid, p.G, p.buf, c.dtable, c.gate);
   NSAMD_CHECK_LAUNCH();
   return NSAMD_OK;
 }
 
-int scatter_launch_pair(const ScatterCall& a, const ScatterCall& b, hipStream_t st) {
-  const ScatterCall* c[2] = {&a, &b};
-  ScatterGeom G[2];
-  ScatterBufs buf[2];
-  LevelList coarse[2], fine[2];
-  for (int i = 0; i < 2; ++i) {
-    if (c[i]->gate != nullptr && c[i]->overwrite) return NSAMD_ERR_INVALID_ARG;
-    if (c[i]->ray_mask != nullptr && (c[i]->gate == nullptr || c[i]->pts.positions != nullptr)) return NSAMD_ERR_INVALID_ARG;
-    if (!c[i]->plan.ok || c[i]->M <= 0) return NSAMD_ERR_UNSUPPORTED;
-    G[i] = c[i]->plan.geom;
-    buf[i] = scatter_bufs(c[i]->workspace, c[i]->plan);
-    buf[i].log2_table_size = c[i]->grid.log2_table_size;
-    if (!c[i]->overwrite) buf[i].direct_table = c[i]->dtable;
-    coarse[i] = LevelList{};
-    fine[i] = LevelList{};
-    classify_levels(c[i]->pts, c[i]->grid, G[i], coarse[i], fine[i]);
-    // only calls that route every level through the run kernel are merged (the proposal levels of nerfacto: 256 and 96
-    // samples per ray on small grids); anything else goes through scatter_launch, call by call
-    if (fine[i].count != 0 || coarse[i].count == 0) return NSAMD_ERR_UNSUPPORTED;
+int scatter_apply_launch(const nsamd_grid& grid, const ScatterPlan& plan, float* workspace, float* dtable, bool overwrite,
+                         hipStream_t st, const ReduceRider* rider) {
+  // (no points: nothing is routed here, and every level's records sit in static segments + dynamic area)
+  const ScatterCall c{nsamd_points{}, 0, 0, nsamd_aabb{}, grid, nullptr, 0, 0, dtable, workspace, plan, overwrite, nullptr, nullptr};
+  ScatterPrepared p;
+  const int rc = scatter_prepare(c, p);
+  return rc ? rc : scatter_apply_finish(c, p, rider, st);
+}
+
+// route (fine levels, then coarse levels) + apply + finish of one prepared call
+static int scatter_launch_one(const ScatterCall& c, const ScatterPrepared& p, hipStream_t st) {
+  if (p.fine.count > 0) {
+    const size_t lds = sizeof(uint32_t) * (3 * (size_t)kFineLevels * ((size_t)1 << p.G.log2_bins) + kFineLevels);
+    dim3 g1(p.G.segs, (unsigned)((p.fine.count + kFineLevels - 1) / kFineLevels));
+    scatter_route_fine_kernel<kFineThreads, 1, kFineLevels><<<g1, kFineThreads, lds, st>>>(
+        c.pts, c.M, c.transform, c.aabb, c.grid, c.denc, c.stride_p, c.stride_k, p.G, p.fine, p.buf, c.gate, c.ray_mask);
+    NSAMD_CHECK_LAUNCH();
   }
-  if (a.workspace == b.workspace || a.dtable == b.dtable) return NSAMD_ERR_UNSUPPORTED;  // shared state: one after the other
-  const unsigned threads = apply_threads(G[0].slice_log2);
-  if (threads != apply_threads(G[1].slice_log2)) return NSAMD_ERR_UNSUPPORTED;
-  {
-    const int rc = apply_lds_attribute();
-    if (rc) return rc;
+  if (p.coarse.count > 0) {
+    scatter_route_runs_kernel<kRunLevels><<<p.runs_grid, kRunThreads, p.runs_lds, st>>>(
+        c.pts, c.M, c.transform, c.aabb, c.grid, c.denc, c.stride_p, c.stride_k, p.G, p.coarse, p.buf, c.gate, c.ray_mask);
+    NSAMD_CHECK_LAUNCH();
   }
-  constexpr int kL = kRunLevels;
-  const int64_t per_block = (int64_t)kRunThreads * kRunLen;
+  return scatter_apply_finish(c, p, nullptr, st);
+}
+
+// Two calls share their route, apply and finish launches (blockIdx.z selects the call; a call's own grid is a corner of the
+// launch's) when both route every level through the run kernel (the proposal levels of nerfacto: 256 and 96 samples per ray
+// on small grids), with the same apply workgroup size, and share neither workspace nor gradient.
+static bool scatter_pair_shares_launches(const ScatterCall* c, const ScatterPrepared* p) {
+  for (int i = 0; i < 2; ++i)
+    if (p[i].fine.count != 0 || p[i].coarse.count == 0) return false;
+  return c[0].workspace != c[1].workspace && c[0].dtable != c[1].dtable && p[0].apply_threads == p[1].apply_threads;
+}
+
+static int scatter_launch_pair(const ScatterCall* c, const ScatterPrepared* p, hipStream_t st) {
   RunsCall rc[2];
-  size_t run_lds = 0;
-  unsigned gx = 0, gy = 0;
-  for (int i = 0; i < 2; ++i) {
-    rc[i] = RunsCall{c[i]->pts, c[i]->M, c[i]->transform, c[i]->aabb, c[i]->grid, c[i]->denc, c[i]->stride_p, c[i]->stride_k,
-                     G[i], coarse[i], buf[i], c[i]->gate, c[i]->ray_mask,
-                     (uint32_t)((c[i]->M + per_block - 1) / per_block), (uint32_t)((coarse[i].count + kL - 1) / kL)};
-    const size_t l = sizeof(uint32_t) * (3 * (size_t)kL * ((size_t)1 << G[i].log2_bins) + kL);
-    run_lds = l > run_lds ? l : run_lds;
-    gx = rc[i].grid_x > gx ? rc[i].grid_x : gx;
-    gy = rc[i].grid_y > gy ? rc[i].grid_y : gy;
-  }
-  scatter_route_runs_pair_kernel<kL><<<dim3(gx, gy, 2u), kRunThreads, run_lds, st>>>(rc[0], rc[1]);
-  NSAMD_CHECK_LAUNCH();
   ApplyCall ac[2];
-  unsigned bins = 0, levels = 0;
-  size_t lds = 0;
   for (int i = 0; i < 2; ++i) {
-    ac[i] = ApplyCall{c[i]->grid, G[i], buf[i], c[i]->dtable, c[i]->overwrite ? 1 : 0, c[i]->gate};
-    bins = (1u << G[i].log2_bins) > bins ? (1u << G[i].log2_bins) : bins;
-    levels = (unsigned)c[i]->grid.num_levels > levels ? (unsigned)c[i]->grid.num_levels : levels;
-    const size_t l = (size_t)16 << G[i].slice_log2;
-    lds = l > lds ? l : lds;
+    rc[i] = RunsCall{c[i].pts, c[i].M, c[i].transform, c[i].aabb, c[i].grid, c[i].denc, c[i].stride_p, c[i].stride_k, p[i].G,
+                     p[i].coarse, p[i].buf, c[i].gate, c[i].ray_mask, p[i].runs_grid.x, p[i].runs_grid.y};
+    ac[i] = ApplyCall{c[i].grid, p[i].G, p[i].buf, c[i].dtable, c[i].overwrite ? 1 : 0, c[i].gate};
   }
-  scatter_apply_pair_kernel<<<dim3(bins, levels, 2u), threads, lds, st>>>(ac[0], ac[1]);
+  const auto larger = [](dim3 a, dim3 b) { return dim3(a.x > b.x ? a.x : b.x, a.y > b.y ? a.y : b.y, 2u); };
+  scatter_route_runs_pair_kernel<kRunLevels><<<larger(p[0].runs_grid, p[1].runs_grid), kRunThreads,
+                                               p[0].runs_lds > p[1].runs_lds ? p[0].runs_lds : p[1].runs_lds, st>>>(rc[0], rc[1]);
+  NSAMD_CHECK_LAUNCH();
+  scatter_apply_pair_kernel<<<larger(p[0].apply_grid, p[1].apply_grid), p[0].apply_threads,
+                              p[0].apply_lds > p[1].apply_lds ? p[0].apply_lds : p[1].apply_lds, st>>>(ac[0], ac[1]);
   NSAMD_CHECK_LAUNCH();
   scatter_finish_pair_kernel<<<dim3(32u, 1u, 2u), 256, 0, st>>>(ac[0], ac[1]);
   NSAMD_CHECK_LAUNCH();
+  return NSAMD_OK;
+}
+
+int scatter_launch(const ScatterCall* calls, int n, hipStream_t st) {
+  NSAMD_REQUIRE(calls != nullptr && (n == 1 || n == 2));
+  ScatterPrepared p[2];
+  int rc[2];
+  for (int i = 0; i < n; ++i) rc[i] = scatter_prepare(calls[i], p[i]);
+  if (n == 2 && !rc[0] && !rc[1] && scatter_pair_shares_launches(calls, p)) return scatter_launch_pair(calls, p, st);
+  for (int i = 0; i < n; ++i) {
+    if (!rc[i]) rc[i] = scatter_launch_one(calls[i], p[i], st);
+    if (rc[i]) return rc[i];
+  }
   return NSAMD_OK;
 }
 
