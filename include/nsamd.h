@@ -521,6 +521,23 @@ int nsamd_proposal_losses(const float* s_bins_fine, const float* w_fine, int32_t
                           float* const* interlevel_per_ray, float* const* dw_prop, float* distortion_per_ray,
                           float* dw_distortion, nsamd_stream_t stream);
 
+/* Depth supervision of depth-nerfacto (model_components/losses.py:225-325, models/depth_nerfacto.py:90-104): the DS-NeRF
+ * (loss_type 1) or Urban Radiance Fields (loss_type 2) loss over the weights of every sampling level of one training step,
+ * value and gradient in one launch — one wavefront per (ray, level). t_bins / weights / S / d_weights are HOST arrays of
+ * `levels` (<= 8) entries: Euclidean bin edges [n, S_l + 1], weights [n, S_l], 1 <= S_l <= 4096. The ray's target is
+ * termination_depth [n] times directions_norm [n] (NULL: the depth is Euclidean already); rays with target <= 0 are masked:
+ * value and gradients exactly 0. predicted_depth [n]: required for URF, else NULL. sigma by value.
+ * per_ray [levels, n] (nullable): the unscaled masked per-ray sums, each summed in a fixed order (bit-reproducible); the loss
+ * of the reference is mult * sum(per_ray) / (n * levels). d_weights[l] [n, S_l] (the array or any entry nullable) and
+ * d_predicted [n] (nullable; URF only — DS_NERF ignores it and leaves the buffer as it is): the gradients times `scale`
+ * (= mult / (n * levels)); accumulate != 0 ADDS them to what
+ * the buffers hold instead of overwriting. Another loss_type, S_l outside 1 .. 4096 or levels > 8: NSAMD_ERR_UNSUPPORTED with
+ * nothing launched; num_rays == 0 is a no-op. No atomics. */
+int nsamd_depth_loss(int32_t levels, const float* const* t_bins, const float* const* weights, const int32_t* S,
+                     int64_t num_rays, const float* termination_depth, const float* directions_norm,
+                     const float* predicted_depth, float sigma, int32_t loss_type, float scale, int32_t accumulate,
+                     float* per_ray, float* const* d_weights, float* d_predicted, nsamd_stream_t stream);
+
 /* The iteration's loss values and training metrics from the per-ray terms the launches above left behind (nsamd_render_train's
  * sq_err, nsamd_proposal_losses' per-ray values): one small launch instead of a dozen host-issued reductions for a trainer that
  * logs the loss dictionary every iteration (engine/trainer.py:487-531). loss_values: 32 floats = 8 results + scratch of the

@@ -117,6 +117,7 @@ _SIGNATURES = {
     "nsamd_interlevel_loss": [vp, vp, i32, vp, vp, i32, i64, f32, vp, vp, vp],
     "nsamd_distortion_loss": [vp, vp, i32, i64, f32, vp, vp, vp],
     "nsamd_proposal_losses": [vp, vp, i32, i32, vp, vp, vp, i64, f32, f32, vp, vp, vp, vp, vp],
+    "nsamd_depth_loss": [i32, vp, vp, vp, i64, vp, vp, vp, f32, i32, f32, i32, vp, vp, vp, vp],
     "nsamd_train_loss_values": [vp, vp, i32, vp, i64, i32, f32, f32, vp, vp],
     "nsamd_occgrid_march_count": [vp, vp, vp, vp, i64, f32, f32, OccGrid, f32, f32, vp, vp, vp],
     "nsamd_occgrid_march_write": [vp, vp, vp, vp, i64, f32, f32, OccGrid, f32, f32, vp, vp, vp, vp, vp, vp],

@@ -5,6 +5,7 @@
 // and gradient in one pass (the losses are scalars whose upstream gradient is a known constant). The eager
 // reference spends ~20 launches and several [N,S,S] temporaries on this; here it is two launches and O(N*S) bytes.
 #include "ray_bodies.h"
+#include "depth_loss.h"
 
 namespace nsamd {
 
@@ -49,6 +50,70 @@ __global__ __launch_bounds__(kLossThreads) void proposal_losses_kernel(
                     a.weights[job], a.S[job], num_rays, inter_scale, a.per_ray[job], a.dw[job]);
   } else {
     distortion_body(lds + (size_t)wave_index() * 2 * Sf, s_fine, w_fine, Sf, num_rays, dist_scale, dist_per_ray, dw_dist);
+  }
+}
+
+// Depth supervision of depth-nerfacto (models/depth_nerfacto.py:90-104; the arithmetic is depth_loss.h): one wavefront per
+// (ray, level), blockIdx.y = level, lanes striding over the level's samples. Each lane adds its terms in sample order in double,
+// the lanes meet through the DPP scan of wave.h: a fixed order, so the per-ray value is the same bits run to run. Gradients are
+// plain stores; `accumulate` adds them to what the buffer holds (the explicit schedule: behind the proposal losses' own
+// gradients) — for a masked ray too, whose `old + 0` is what an addition of the zero gradient gives (-0 becomes +0).
+constexpr int kMaxDepthLevels = 8;
+constexpr int kMaxDepthSamples = 4096;
+struct DepthLossArgs {
+  const float* t_bins[kMaxDepthLevels];
+  const float* weights[kMaxDepthLevels];
+  float* dw[kMaxDepthLevels];
+  int S[kMaxDepthLevels];
+  int levels;
+};
+
+__global__ __launch_bounds__(kLossThreads) void depth_loss_kernel(
+    DepthLossArgs a, int64_t num_rays, const float* __restrict__ termination_depth,
+    const float* __restrict__ directions_norm, const float* __restrict__ predicted_depth, float sigma, float log_scale,
+    int loss_type, float scale, int accumulate, float* __restrict__ per_ray, float* __restrict__ d_predicted) {
+  const int lane = threadIdx.x & 63, wave = wave_index();
+  const int64_t ray = (int64_t)blockIdx.x * kLossRays + wave;
+  if (ray >= num_rays) return;  // wave-uniform
+  const int lvl = blockIdx.y;
+  const int S = a.S[lvl];
+  const float target = depth_target(termination_depth[ray], directions_norm != nullptr ? directions_norm[ray] : 1.0f,
+                                    directions_norm == nullptr);
+  const bool supervised = target > 0.0f;  // depth_mask; wave-uniform
+  const float* __restrict__ tb = a.t_bins[lvl] + ray * (S + 1);
+  const float* __restrict__ w = a.weights[lvl] + ray * S;
+  float* __restrict__ dw = a.dw[lvl] != nullptr ? a.dw[lvl] + ray * S : nullptr;
+  const bool urf = loss_type == kDepthLossUrf;
+  double sum0 = 0.0, sum1 = 0.0;  // DS_NERF: the terms; URF: the near and the empty terms
+  for (int i = lane; i < S; i += 64) {
+    float g = 0.0f;
+    if (supervised) {
+      float t0 = 0.0f, t1 = 0.0f, d = 0.0f;
+      if (urf) urf_sample(tb[i], tb[i + 1], w[i], target, sigma, log_scale, &t0, &t1, &d);
+      else ds_nerf_sample(tb[i], tb[i + 1], w[i], target, sigma, &t0, &d);
+      sum0 += (double)t0;
+      sum1 += (double)t1;
+      g = d * scale;
+    }
+    if (dw != nullptr) dw[i] = accumulate ? dw[i] + g : g;
+  }
+  // (every lane is back here: the DPP moves need the whole wave)
+  const float tot0 = (float)wave_read_f64<63>(wave_scan_inclusive_f64(sum0));
+  const float tot1 = urf ? (float)wave_read_f64<63>(wave_scan_inclusive_f64(sum1)) : 0.0f;  // (wave-uniform branch)
+  if (lane != 0) return;
+  float loss = tot0, dpred = 0.0f;
+  if (urf) {
+    float expected = 0.0f;
+    urf_ray(target, predicted_depth[ray], &expected, &dpred);
+    loss = expected + (tot0 + tot1);  // expected_depth_loss + (near + empty), losses.py:283-285
+  }
+  if (per_ray != nullptr) per_ray[(int64_t)lvl * num_rays + ray] = supervised ? loss : 0.0f;
+  if (urf && lvl == 0 && d_predicted != nullptr) {
+    // every level's call of the reference adds the same term to predicted_depth's gradient: the sum of `levels` equal summands
+    const float g = supervised ? dpred * scale : 0.0f;
+    float total = 0.0f;
+    for (int l = 0; l < a.levels; ++l) total += g;
+    d_predicted[ray] = accumulate ? d_predicted[ray] + total : total;
   }
 }
 
@@ -116,6 +181,36 @@ extern "C" int nsamd_distortion_loss(const float* s_bins, const float* weights, 
   const unsigned blocks = (unsigned)((num_rays + kLossRays - 1) / kLossRays);
   distortion_kernel<<<blocks, kLossThreads, sizeof(float) * 2 * S * kLossRays, (hipStream_t)stream>>>(
       s_bins, weights, S, num_rays, grad_scale, per_ray_loss, dweights);
+  NSAMD_CHECK_LAUNCH();
+  return NSAMD_OK;
+}
+
+extern "C" int nsamd_depth_loss(int32_t levels, const float* const* t_bins, const float* const* weights, const int32_t* S,
+                                int64_t num_rays, const float* termination_depth, const float* directions_norm,
+                                const float* predicted_depth, float sigma, int32_t loss_type, float scale,
+                                int32_t accumulate, float* per_ray, float* const* d_weights, float* d_predicted,
+                                nsamd_stream_t stream) {
+  NSAMD_REQUIRE(num_rays >= 0 && levels >= 1 && t_bins && weights && S);
+  if (!depth_loss_type_supported(loss_type) || levels > kMaxDepthLevels) return NSAMD_ERR_UNSUPPORTED;
+  for (int i = 0; i < levels; ++i)
+    if (S[i] < 1 || S[i] > kMaxDepthSamples) return NSAMD_ERR_UNSUPPORTED;
+  if (num_rays > (int64_t)kLossRays * 0x7fffffff) return NSAMD_ERR_UNSUPPORTED;
+  if (num_rays == 0) return NSAMD_OK;
+  NSAMD_REQUIRE(termination_depth && (loss_type != kDepthLossUrf || predicted_depth));
+  DepthLossArgs a{};
+  a.levels = levels;
+  for (int i = 0; i < levels; ++i) {
+    NSAMD_REQUIRE(t_bins[i] && weights[i]);
+    a.t_bins[i] = t_bins[i];
+    a.weights[i] = weights[i];
+    a.dw[i] = d_weights ? d_weights[i] : nullptr;
+    a.S[i] = S[i];
+  }
+  const float log_scale = loss_type == kDepthLossUrf ? urf_log_scale(sigma) : 0.0f;  // host, once per launch
+  dim3 g((unsigned)((num_rays + kLossRays - 1) / kLossRays), (unsigned)levels);
+  depth_loss_kernel<<<g, kLossThreads, 0, (hipStream_t)stream>>>(a, num_rays, termination_depth, directions_norm,
+                                                                 predicted_depth, sigma, log_scale, loss_type, scale, accumulate,
+                                                                 per_ray, d_predicted);
   NSAMD_CHECK_LAUNCH();
   return NSAMD_OK;
 }

@@ -977,6 +977,71 @@ def distortion_loss(weights: Tensor, s_bins: Tensor) -> Tensor:
     return _DistortionFn.apply(weights, s_bins)
 
 
+DEPTH_DS_NERF, DEPTH_URF = 1, 2  # DepthLossType values the kernel covers (losses.py:41-46)
+
+
+def depth_loss_launch(weights: Sequence[Tensor], t_bins: Sequence[Tensor], termination_depth: Tensor,
+                      directions_norm: Optional[Tensor], predicted_depth: Optional[Tensor], sigma: float, loss_type: int,
+                      scale: float, per_ray: Optional[Tensor], d_weights: Optional[Sequence[Optional[Tensor]]],
+                      d_predicted: Optional[Tensor], accumulate: bool = False) -> None:
+    """nsamd_depth_loss on dense fp32 device tensors (weights `[n,S_l]`, bins `[n,S_l+1]`, per-ray vectors `[n]`)."""
+    levels, n = len(weights), termination_depth.shape[0]
+    parr = lambda ts: (C.c_void_p * levels)(*[N.ptr(t) for t in ts])  # noqa: E731
+    counts = (C.c_int32 * levels)(*[int(w.shape[1]) for w in weights])
+    N.check(N.load().nsamd_depth_loss(levels, parr(t_bins), parr(weights), counts, n, N.ptr(termination_depth),
+                                      N.ptr(directions_norm), N.ptr(predicted_depth), float(sigma), int(loss_type),
+                                      float(scale), 1 if accumulate else 0, N.ptr(per_ray),
+                                      parr(d_weights) if d_weights is not None else None, N.ptr(d_predicted), N.stream()),
+            "depth_loss")
+
+
+class _DepthLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, levels: int, sigma: float, loss_type: int, termination_depth, directions_norm, predicted_depth, *rest):
+        weights, t_bins = rest[:levels], rest[levels:]
+        N.require_cuda(termination_depth, directions_norm, predicted_depth, *weights, *t_bins)
+        ws = [_f32c(w) for w in weights]
+        bins = [_f32c(b.detach()) for b in t_bins]
+        n = ws[0].shape[0]
+        td = _f32c(termination_depth.detach().reshape(-1))
+        dn = None if directions_norm is None else _f32c(directions_norm.detach().reshape(-1))
+        urf = loss_type == DEPTH_URF
+        pred = _f32c(predicted_depth.reshape(-1)) if urf else None
+        per_ray = torch.empty((levels, n), device=td.device, dtype=torch.float32)
+        # a level whose weights take no gradient (the proposal levels of a step that does not update them) gets no buffer
+        dws = [torch.empty_like(w) if ctx.needs_input_grad[6 + i] else None for i, w in enumerate(ws)]
+        dpred = torch.empty_like(pred) if (urf and ctx.needs_input_grad[5]) else None
+        scale = 1.0 / (n * levels) if n > 0 else 0.0
+        depth_loss_launch(ws, bins, td, dn, pred, sigma, loss_type, scale, per_ray, dws, dpred)
+        ctx.levels, ctx.pred_shape = levels, None if predicted_depth is None else predicted_depth.shape
+        ctx.dws, ctx.dpred = dws, dpred
+        return per_ray.sum() * scale  # mean over rays of every level, averaged over the levels (depth_nerfacto.py:94-104)
+
+    @staticmethod
+    def backward(ctx, g):
+        dws = [None if d is None else d * g for d in ctx.dws]
+        dpred = None if ctx.dpred is None else (ctx.dpred * g).reshape(ctx.pred_shape)
+        return (None, None, None, None, None, dpred, *dws, *([None] * ctx.levels))
+
+
+def depth_loss(weights_list: Sequence[Tensor], t_bins_list: Sequence[Tensor], termination_depth: Tensor,
+               predicted_depth: Optional[Tensor], sigma, directions_norm: Optional[Tensor], is_euclidean: bool,
+               loss_type: int) -> Tensor:
+    """The depth loss of depth-nerfacto over every sampling level, already averaged over the levels
+    (models/depth_nerfacto.py:94-104 over losses.py:289-325): weights `[n,S_l]`, Euclidean bin edges `[n,S_l+1]`,
+    termination_depth / predicted_depth / directions_norm `[n]` or `[n,1]`, loss_type 1 (DS_NERF) or 2 (URF). 0-dim."""
+    loss_type = int(getattr(loss_type, "value", loss_type))
+    if loss_type not in (DEPTH_DS_NERF, DEPTH_URF):
+        raise NotImplementedError("Provided depth loss type not implemented.")  # losses.py:325
+    if loss_type == DEPTH_URF and predicted_depth is None:
+        raise ValueError("the URF depth loss needs predicted_depth")
+    if not is_euclidean and directions_norm is None:
+        raise ValueError("a depth that is not Euclidean needs directions_norm")
+    levels = len(weights_list)
+    return _DepthLossFn.apply(levels, float(sigma), loss_type, termination_depth, None if is_euclidean else directions_norm,
+                              predicted_depth, *weights_list, *t_bins_list)
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # a3  camera-pose corrections of the rays
 # ---------------------------------------------------------------------------------------------------------------

@@ -52,7 +52,7 @@ class _FusedLosses(torch.autograd.Function):
         ctx.step = step
         ctx.updated = step.updated
         ld = step.runner.loss_dict()
-        return tuple(ld[k].clone() for k in _LOSS_KEYS)
+        return tuple(ld[k].clone() for k in step.loss_keys())
 
     @staticmethod
     def backward(ctx, *grads):  # noqa: D102
@@ -86,7 +86,16 @@ class FusedTrainStep:
         cfg = self.model.config
         if getattr(cfg, "predict_normals", False):
             return "predict_normals"
+        kind = getattr(cfg, "depth_loss_type", None)  # a depth model (depth_nerfacto.py): the schedule covers DS_NERF
+        if kind is not None and int(getattr(kind, "value", kind)) != 1:
+            return f"depth loss type {getattr(kind, 'name', kind)}"
         return ddp_reason()
+
+    def is_depth_model(self) -> bool:
+        return hasattr(self.model.config, "depth_loss_type")
+
+    def loss_keys(self):
+        return _LOSS_KEYS + ("depth_loss",) if self.is_depth_model() else _LOSS_KEYS
 
     def _runner_for(self, num_rays: int, device):
         from .train_step import NerfactoTrainStep
@@ -118,11 +127,17 @@ class FusedTrainStep:
         r.apply_camera_corrections()
         r.forward_proposals(draw_jitter=jitters is None, need_enc=self.updated)
         r.forward_main()
+        if self.is_depth_model():
+            r.set_depth_target(None)  # the last batch's target is stale: the depth launch waits for get_loss_dict's
         r.losses(self.updated)  # compositing = the model outputs (its loss half is redone once the target is known)
         if self.updated and forced is None:
             ps.mark_updated()  # ray_samplers.py:606-607
         out = r.outputs()
         out["fused_step"] = self
+        if self.is_depth_model():
+            md = getattr(ray_bundle, "metadata", None)
+            if md is not None and "directions_norm" in md:  # models/depth_nerfacto.py:76-77
+                out["directions_norm"] = md["directions_norm"]
         return out
 
     # --- Model.get_loss_dict (models/nerfacto.py:363-392) ----------------------------------------------------------------
@@ -139,9 +154,16 @@ class FusedTrainStep:
             image = image.reshape(-1, 4)
             image = self.model.renderer_rgb.blend_background(image, background_color=r.bg_rays if r.bg_rays is not None else None)
         r.target.copy_(image.reshape(-1, 3))
+        if self.is_depth_model():
+            # the batch's depth image is this iteration's depth target (models/depth_nerfacto.py:92-104, :124-125); sigma
+            # decays once per iteration, here (the fused step's get_metrics_dict does not evaluate the depth loss)
+            cfg = self.model.config
+            r.set_depth_target(batch["depth_image"].to(r.target.device), outputs.get("directions_norm"),
+                               sigma=float(self.model._get_sigma()), mult=cfg.depth_loss_mult,
+                               is_euclidean=cfg.is_euclidean_depth, loss_type=cfg.depth_loss_type)
         r.losses(self.updated)
         anchor = self.model.field.mlp_base.encoding.hash_table  # any parameter: makes autograd call backward
-        loss_dict = dict(zip(_LOSS_KEYS, _FusedLosses.apply(anchor, self)))
+        loss_dict = dict(zip(self.loss_keys(), _FusedLosses.apply(anchor, self)))
         if hasattr(self.model, "camera_optimizer"):
             # L2 regulariser on the pose corrections: plain autograd on the [num_cameras, 6] parameter; the runner adds
             # only the rays' share of that parameter's gradient (reg_in_backward = False)

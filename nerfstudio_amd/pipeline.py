@@ -77,8 +77,13 @@ class _LossValuesBackpropagated(torch.autograd.Function):
 
 def unsupported_model_reason(model) -> Optional[str]:
     """Configuration-level reasons the captured schedule cannot run this model (None: it can). use_gradient_scaling and
-    per-edge jitter are covered by the explicit schedule (train_step.py); the normals options are module path only."""
-    return "predict_normals" if getattr(model.config, "predict_normals", False) else None
+    per-edge jitter are covered by the explicit schedule (train_step.py); the normals options and depth supervision are
+    module path only."""
+    if getattr(model.config, "predict_normals", False):
+        return "predict_normals"
+    # depth-nerfacto (depth_nerfacto.py, plugin.depth_nerfacto_hip): the captured iteration has no depth target; the module
+    # path trains it, and the explicit schedule covers DS_NERF eagerly (train_step.NerfactoTrainStep.set_depth_target)
+    return "depth supervision" if hasattr(model.config, "depth_loss_type") else None
 
 
 class TrainEngine:

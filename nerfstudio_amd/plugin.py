@@ -325,6 +325,83 @@ def _ngp_model_classes():
     return HipInstantNGPModelConfig, HipNGPModel
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# depth-nerfacto: the reference's DepthNerfactoModel over the same hot-path modules, its depth loss on nsamd_depth_loss
+# ---------------------------------------------------------------------------------------------------------------------
+DEPTH_DESCRIPTION = ("depth-nerfacto on MI355X: nerfacto-hip plus the DS-NeRF / Urban Radiance Fields depth loss over the "
+                     "weights of every sampling level as one gfx950 HIP kernel (nerfstudio_amd)")
+
+
+def _depth_model_classes():
+    """(HipDepthNerfactoModelConfig, HipDepthNerfactoModel), built ONCE against the installed nerfstudio."""
+    if "HipDepthNerfactoModel" in globals():
+        return globals()["HipDepthNerfactoModelConfig"], globals()["HipDepthNerfactoModel"]
+    from dataclasses import dataclass, field
+    from typing import Literal, Type
+
+    from nerfstudio.models.depth_nerfacto import DepthNerfactoModel, DepthNerfactoModelConfig
+
+    _, hip_nerfacto = _model_classes()
+
+    class HipDepthNerfactoModel(hip_nerfacto, DepthNerfactoModel):
+        """The reference DepthNerfactoModel with the hot path on MI355X kernels. HipNerfactoModel comes first in the method
+        resolution order: its populate_modules / get_outputs call on into the reference's DepthNerfactoModel (`depth_sigma`,
+        `directions_norm` in the outputs), `_get_sigma` and the image metrics are the reference's own code, and the loop of depth
+        losses over the levels (models/depth_nerfacto.py:94-104) is one launch of nsamd_depth_loss."""
+
+        def get_metrics_dict(self, outputs, batch):
+            from .depth_nerfacto import depth_metrics
+
+            metrics_dict = hip_nerfacto.get_metrics_dict(self, outputs, batch)
+            if self.training and "fused_step" not in outputs:
+                depth_metrics(self, outputs, batch, metrics_dict)
+            return metrics_dict
+
+        def get_loss_dict(self, outputs, batch, metrics_dict=None):
+            from .depth_nerfacto import depth_loss_terms
+
+            loss_dict = hip_nerfacto.get_loss_dict(self, outputs, batch, metrics_dict)
+            if self.training and "fused_step" not in outputs:
+                depth_loss_terms(self, loss_dict, metrics_dict)
+            return loss_dict
+
+    @dataclass
+    class HipDepthNerfactoModelConfig(DepthNerfactoModelConfig):
+        _target: Type = field(default_factory=lambda: HipDepthNerfactoModel)
+        implementation: Literal["tcnn", "torch", "hip"] = "hip"
+        fused_train_step: bool = False
+        """Run training iterations on the explicit kernel schedule behind the Model API (DS_NERF only; fused_step.py)."""
+
+    _publish(HipDepthNerfactoModelConfig, HipDepthNerfactoModel)
+    return HipDepthNerfactoModelConfig, HipDepthNerfactoModel
+
+
+def depth_nerfacto_hip():
+    """-> MethodSpecification for `ns-train depth-nerfacto-hip` (the reference's `depth-nerfacto` recipe,
+    method_configs.py:215-249: its depth datamanager, optimisers and pipeline). Reached through
+    NERFSTUDIO_METHOD_CONFIGS="depth-nerfacto-hip=nerfstudio_amd.plugin:depth_nerfacto_hip"; the iterations run on the module
+    path (pipeline.unsupported_model_reason: "depth supervision"). Raises ImportError when nerfstudio is not importable."""
+    import copy
+    import dataclasses
+
+    try:
+        from nerfstudio.configs.method_configs import method_configs
+        from nerfstudio.plugins.types import MethodSpecification
+    except Exception as e:  # noqa: BLE001
+        raise ImportError(f"nerfstudio_amd.plugin: nerfstudio (with its trainer dependencies) is not importable: {e}") from e
+    from .utils import profiler
+
+    profiler.hook_reference_profiler()
+    cfg_cls, _ = _depth_model_classes()
+    base = copy.deepcopy(method_configs["depth-nerfacto"])
+    old = base.pipeline.model
+    kwargs = {f.name: getattr(old, f.name) for f in dataclasses.fields(old) if f.name not in ("_target", "implementation")}
+    base.pipeline.model = cfg_cls(**kwargs)
+    base.method_name = "depth-nerfacto-hip"
+    base.mixed_precision = False  # fp32 kernels: no autocast, no loss scaling
+    return MethodSpecification(config=base, description=DEPTH_DESCRIPTION)
+
+
 def instant_ngp_hip():
     """-> MethodSpecification for `ns-train instant-ngp-hip` (the reference's `instant-ngp` recipe, method_configs.py:251-273:
     DynamicBatchPipeline, one Adam group). Raises ImportError when nerfstudio is not importable."""
@@ -394,7 +471,8 @@ _LAZY_SPECS = {"nerfacto_hip_spec": nerfacto_hip, "instant_ngp_hip_spec": instan
 
 
 _LAZY_CLASSES = {"HipNerfactoModelConfig": _model_classes, "HipNerfactoModel": _model_classes,
-                 "HipInstantNGPModelConfig": _ngp_model_classes, "HipNGPModel": _ngp_model_classes}
+                 "HipInstantNGPModelConfig": _ngp_model_classes, "HipNGPModel": _ngp_model_classes,
+                 "HipDepthNerfactoModelConfig": _depth_model_classes, "HipDepthNerfactoModel": _depth_model_classes}
 
 
 def __getattr__(name: str):

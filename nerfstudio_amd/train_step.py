@@ -147,6 +147,9 @@ class NerfactoTrainStep:
         # (slot pointer, slots, pool) of a batch selection the caller leaves to `forward_proposals` (one launch with the initial
         # bins, nsamd_select_bins); NSAMD_FUSE_SELECT=0: the caller launches nsamd_select_batch itself (A/B)
         self.pending_select = None
+        # depth supervision (set_depth_target): None = today's launches, nothing else
+        self.depth = None
+        self._depth_buffers = None
         self._slot0 = None  # a device zero: `set_batch` as a one-slot batch selection
         self._outputs = None
         self.fuse_select = os.environ.get("NSAMD_FUSE_SELECT", "1") == "1"
@@ -223,6 +226,43 @@ class NerfactoTrainStep:
         self.camera_indices.copy_(camera_indices.reshape(-1))
         if target_rgb is not None:
             self.target.copy_(target_rgb)
+
+    def set_depth_target(self, termination_depth: Optional[Tensor], directions_norm: Optional[Tensor] = None,
+                         sigma: float = 0.01, mult: float = 1e-3, is_euclidean: bool = False, loss_type: int = 1) -> None:
+        """Depth supervision of depth-nerfacto (models/depth_nerfacto.py:90-104, :124-125) on the explicit schedule, DS_NERF only:
+        with a target set, `losses()` issues one nsamd_depth_loss launch behind nsamd_proposal_losses that ADDS mult * d(depth
+        loss) to `dw_dist` and — on proposal-update steps, where the reference's proposal weights carry gradient — to
+        `dw_prop`; `loss_dict()` reports `depth_loss`. termination_depth `[n]` / `[n,1]` (None: no depth supervision again),
+        directions_norm likewise (required unless the depth is Euclidean). The buffers are static: a new target of the same
+        batch size is copied into them. Eager launches only: trainer.HipTrainer and captured graphs decline."""
+        if termination_depth is None:
+            self.depth = None  # (the static buffers stay in `_depth_buffers` for the next target)
+            return
+        loss_type = int(getattr(loss_type, "value", loss_type))
+        if loss_type != F.DEPTH_DS_NERF:
+            raise NotImplementedError("explicit schedule: only the DS_NERF depth loss; URF and the depth ranking loss are "
+                                      "on the module path")
+        if self.forward_only:
+            raise RuntimeError("a forward-only runner has no gradient buffers")
+        if not is_euclidean and directions_norm is None:
+            raise ValueError("a depth that is not Euclidean needs directions_norm")
+        d = self._depth_buffers
+        if d is None:
+            dev, levels = self.origins.device, len(self.counts)
+            f32 = dict(device=dev, dtype=torch.float32)
+            parr = lambda ts: (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])  # noqa: E731
+            d = self._depth_buffers = {"target": torch.empty(self.n, **f32), "norm": torch.empty(self.n, **f32),
+                              "per_ray": torch.empty(levels, self.n, **f32), "value": torch.zeros((), **f32),
+                              "t_bins": parr(self.t_bins), "weights": parr(self.weights),
+                              "S": (C.c_int32 * levels)(*self.counts),
+                              # the final level always; the proposal levels on update steps only
+                              "dw_all": parr(self.dw_prop + [self.dw_dist]),
+                              "dw_final": (C.c_void_p * levels)(*([None] * self.n_prop + [self.dw_dist.data_ptr()]))}
+        d["target"].copy_(termination_depth.reshape(-1))
+        if not is_euclidean:
+            d["norm"].copy_(directions_norm.reshape(-1))
+        d["euclidean"], d["sigma"], d["mult"] = bool(is_euclidean), float(sigma), float(mult)
+        self.depth = d
 
     def prepare_grads(self, updated: bool) -> None:
         """For callers without a gradient arena (a trainer that runs `zero_grad(set_to_none=True)`, engine/optimizers.py:
@@ -554,6 +594,19 @@ class NerfactoTrainStep:
                                      float(cfg.distortion_loss_mult) / n, self._pl_per_ray,
                                      self._pl_dw if updated else None, N.ptr(self.dist_per_ray), N.ptr(self.dw_dist), st),
            "proposal_losses")
+        d = self.depth
+        if d is not None:
+            # ---- depth supervision: one more launch that adds its gradients to the ones just written ----
+            if torch.cuda.is_current_stream_capturing():
+                raise NotImplementedError("explicit schedule: a depth target inside a captured graph; depth supervision in "
+                                          "captured iterations is only on the module path")
+            levels = len(self.counts)
+            scale = d["mult"] / (n * levels)
+            ck(lib.nsamd_depth_loss(levels, d["t_bins"], d["weights"], d["S"], n, N.ptr(d["target"]),
+                                    None if d["euclidean"] else N.ptr(d["norm"]), None, d["sigma"], F.DEPTH_DS_NERF, scale, 1,
+                                    N.ptr(d["per_ray"]), d["dw_all"] if updated else d["dw_final"], None, st), "depth_loss")
+            torch.sum(d["per_ray"], dim=(0, 1), out=d["value"])
+            d["value"].mul_(scale)
         if self.want_loss_vals:
             # a caller that reads the loss dictionary every iteration (pipeline.TrainEngine): the values and the training metrics
             # as five floats from one small launch instead of a dozen reductions issued by the host
@@ -715,6 +768,8 @@ class NerfactoTrainStep:
             out = {"rgb_loss": v[0], "distortion_loss": v[2], "interlevel_loss": v[1]}
             if self.cam_opt is not None:
                 out["camera_opt_regularizer"] = self.camera_reg
+            if self.depth is not None:
+                out["depth_loss"] = self.depth["value"].clone()
             return out
         out = {"rgb_loss": self.sq_err.sum() / (3 * n),
                "distortion_loss": self.cfg.distortion_loss_mult * self.dist_per_ray.sum() / n}
@@ -722,6 +777,8 @@ class NerfactoTrainStep:
         out["interlevel_loss"] = self.cfg.interlevel_loss_mult * inter
         if self.cam_opt is not None:
             out["camera_opt_regularizer"] = self.camera_reg
+        if self.depth is not None:
+            out["depth_loss"] = self.depth["value"].clone()
         return out
 
     def outputs(self) -> Dict[str, Tensor]:

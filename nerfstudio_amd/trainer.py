@@ -70,6 +70,9 @@ class HipTrainer:
     def __init__(self, model, arena, ray_bundle, batch, world: int = 1, use_graph: bool = True, use_runner: bool = True,
                  pool=None, force_dp: bool = False, dp_mode: str = "allreduce",
                  lr_source: Optional[Callable[[str, int], float]] = None, drive_callbacks: bool = True, runner=None) -> None:
+        if hasattr(getattr(model, "config", None), "depth_loss_type"):
+            # its iteration (and the graphs captured from it) carries no depth target, sigma decay or depth batch
+            raise NotImplementedError("HipTrainer: depth supervision (depth-nerfacto) is only on the module path")
         self.model, self.arena, self.rb, self.batch, self.world = model, arena, ray_bundle, batch, world
         self.dp = world > 1 or force_dp  # force_dp: the data-parallel schedule with a one-rank communicator
         # "sharded": reduce-scatter -> Adam on the rank's 1/N arena shard -> all-gather (dp_schedule.py); "allreduce": the
