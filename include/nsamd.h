@@ -313,18 +313,6 @@ int nsamd_field_mlp_bwd_scatter_phase(nsamd_points pts, int transform, nsamd_aab
                                       float* workspace, int64_t workspace_floats, float* dtable, float* scatter_workspace,
                                       int64_t scatter_workspace_floats, int phase, nsamd_stream_t stream);
 
-/* nsamd_field_mlp_bwd in two launches, so that a caller can put the second on another stream: phase 1 = the gradient
- * kernel (denc + the per-workgroup weight-gradient partials in `workspace`, which is REQUIRED here), phase 2 = the
- * fixed-order sum of the partials into `grads` (needs nothing but workspace, grads, camera_indices and the sizes). Phase 2
- * depends on phase 1 only; the table scatter that consumes denc (nsamd_hashgrid_encode_bwd) does not depend on phase 2
- * (MLPWithHashEncoding backward, field_components/mlp.py:187-295: weight gradients and input gradients are independent
- * products of the same upstream gradient). Same bits as the single call. */
-int nsamd_field_mlp_bwd_phase(const float* enc, const float* selector, const float* directions,
-                              const int64_t* camera_indices, const float* appearance_const, int64_t dir_group, int64_t M,
-                              nsamd_field_mlp mlp, const float* ddensity, const float* drgb, float* denc,
-                              nsamd_field_mlp_grads grads, float* workspace, int64_t workspace_floats, int phase,
-                              nsamd_stream_t stream);
-
 /* ------------------------------------------------------------------------------------------------------------
  * Generic dense layer for the stand-alone MLP of the plugin API (MLP.pytorch_fwd, field_components/mlp.py:160-179):
  * y[M,N] = act(x[M,K] W[N,K]^T + b[N]); activation 0 = none, 1 = ReLU, 2 = Sigmoid, 3 = Softplus (the DensityFieldHead of
@@ -570,21 +558,15 @@ typedef struct nsamd_occgrid {
                               whose block is empty — same samples, by construction. */
 } nsamd_occgrid;
 
-/* Ray marching through the occupancy grid, two calls: _count fills counts[N] (int32), nsamd_packed_info turns them into
- * packed_info + the total, _write emits ray_indices [n] int64, t_starts / t_ends [n]. A ray marches t = t0, t0 + dt, ...
- * inside [max(near, t_min), min(far, t_max)] clipped to the outermost grid level, dt = clamp(t * cone_angle, step, 1e10);
- * a step is kept when the cell (finest level containing the step's midpoint) is occupied. jitter [N] in [0,1) (nullable)
- * shifts a ray's lattice by jitter * step (stratified training, ray_samplers.py:489). t_min / t_max nullable. */
-int nsamd_occgrid_march_count(const float* origins, const float* directions, const float* t_min, const float* t_max,
-                              int64_t num_rays, float near_plane, float far_plane, nsamd_occgrid grid, float step_size,
-                              float cone_angle, const float* jitter, int32_t* counts, nsamd_stream_t stream);
-int nsamd_occgrid_march_write(const float* origins, const float* directions, const float* t_min, const float* t_max,
-                              int64_t num_rays, float near_plane, float far_plane, nsamd_occgrid grid, float step_size,
-                              float cone_angle, const float* jitter, const int64_t* packed_info, int64_t* ray_indices,
-                              float* t_starts, float* t_ends, nsamd_stream_t stream);
-/* The same two calls marching every ray ONCE: _count_stash also leaves a ray's first stash_cap kept steps as (t_start, t_end)
- * pairs in stash [num_rays, stash_cap, 2]; _write_stashed copies them to their packed places and marches only the rays that
- * kept more than stash_cap steps a second time. Same counts, same values as the plain pair (stash == NULL: the plain pair). */
+/* Ray marching through the occupancy grid, two calls: _count_stash fills counts[N] (int32), nsamd_packed_info turns them
+ * into packed_info + the total, _write_stashed emits ray_indices [n] int64, t_starts / t_ends [n]. A ray marches
+ * t = t0, t0 + dt, ... inside [max(near, t_min), min(far, t_max)] clipped to the outermost grid level,
+ * dt = clamp(t * cone_angle, step, 1e10); a step is kept when the cell (finest level containing the step's midpoint) is
+ * occupied. jitter [N] in [0,1) (nullable) shifts a ray's lattice by jitter * step (stratified training,
+ * ray_samplers.py:489). t_min / t_max nullable.
+ * The pair marches every ray ONCE: _count_stash also leaves a ray's first stash_cap kept steps as (t_start, t_end) pairs in
+ * stash [num_rays, stash_cap, 2]; _write_stashed copies them to their packed places and marches only the rays that kept more
+ * than stash_cap steps a second time. stash == NULL with stash_cap = 0: both calls march every ray; same counts, same values. */
 int nsamd_occgrid_march_count_stash(const float* origins, const float* directions, const float* t_min, const float* t_max,
                                     int64_t num_rays, float near_plane, float far_plane, nsamd_occgrid grid, float step_size,
                                     float cone_angle, const float* jitter, int32_t* counts, float* stash, int32_t stash_cap,

@@ -99,7 +99,6 @@ _SIGNATURES = {
                                           vp, i64, vp, vp, i64, C.c_int, vp],
     "nsamd_field_mlp_bwd_scatter_workspace": [Grid, i64, C.POINTER(C.c_int64)],
     "nsamd_proposal_levels_bwd": [C.POINTER(ProposalLevelBwd), i32, i32, vp],
-    "nsamd_field_mlp_bwd_phase": [vp, vp, vp, vp, vp, i64, i64, FieldMlp, vp, vp, vp, FieldMlpGrads, vp, i64, C.c_int, vp],
     "nsamd_linear_fwd": [vp, vp, vp, i64, i32, i32, C.c_int, vp, vp],
     "nsamd_linear_bwd": [vp, vp, vp, vp, i64, i32, i32, C.c_int, vp, vp, vp, vp],
     "nsamd_piecewise_bins": [vp, vp, vp, vp, i32, i64, i32, C.c_int, vp, vp, vp],
@@ -119,8 +118,6 @@ _SIGNATURES = {
     "nsamd_proposal_losses": [vp, vp, i32, i32, vp, vp, vp, i64, f32, f32, vp, vp, vp, vp, vp],
     "nsamd_depth_loss": [i32, vp, vp, vp, i64, vp, vp, vp, f32, i32, f32, i32, vp, vp, vp, vp],
     "nsamd_train_loss_values": [vp, vp, i32, vp, i64, i32, f32, f32, vp, vp],
-    "nsamd_occgrid_march_count": [vp, vp, vp, vp, i64, f32, f32, OccGrid, f32, f32, vp, vp, vp],
-    "nsamd_occgrid_march_write": [vp, vp, vp, vp, i64, f32, f32, OccGrid, f32, f32, vp, vp, vp, vp, vp, vp],
     "nsamd_occgrid_march_count_stash": [vp, vp, vp, vp, i64, f32, f32, OccGrid, f32, f32, vp, vp, vp, i32, vp],
     "nsamd_occgrid_march_write_stashed": [vp, vp, vp, vp, i64, f32, f32, OccGrid, f32, f32, vp, vp, vp, i32, vp, vp, vp, vp],
     "nsamd_occgrid_coarse_words": [i32, i32],
@@ -217,19 +214,8 @@ def load():
     cdll = C.CDLL(path)
     lib = _Lib()
     lib.cdll = cdll
-    older_ok = "NSAMD_LIB" in os.environ and os.environ.get("NSAMD_LIB_OLDER_ABI") == "1"
     for name, argtypes in _SIGNATURES.items():
-        try:
-            fn = getattr(cdll, name)  # AttributeError here = header / library mismatch
-        except AttributeError:
-            if not older_ok:
-                raise
-            # same-box A/B against an OLDER build (NSAMD_LIB=... NSAMD_LIB_OLDER_ABI=1): an entry point it lacks fails when called
-            def missing(*_a, _n=name):
-                raise RuntimeError(f"nsamd: {_n} is not exported by {path} (an older build loaded for A/B)")
-
-            setattr(lib, name, missing)
-            continue
+        fn = getattr(cdll, name)  # AttributeError here = header / library mismatch
         fn.argtypes = argtypes
         fn.restype = _RESTYPES.get(name, C.c_int)
         setattr(lib, name, _Entry(fn, name) if fn.restype is C.c_int and name not in ("nsamd_device_info",) else fn)
@@ -242,10 +228,6 @@ def profile_summary(prof: dict) -> dict:
     out = {}
     for key, pairs in prof.items():
         ms = [a.elapsed_time(b) for a, b in pairs]
-        if os.environ.get("NSAMD_ROOFLINE_SAMPLES") == "1" and "field_mlp_bwd" in key:  # diagnostics: every launch's time
-            import sys
-
-            print(f"[samples] {key}: " + " ".join(f"{m:.4f}" for m in ms), file=sys.stderr)
         out[key] = (len(ms), float(sum(ms)), float(sum(ms) / max(1, len(ms))))
     return out
 

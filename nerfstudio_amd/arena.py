@@ -25,7 +25,7 @@ from torch.nn import Parameter
 from . import functional as F
 from .utils import profiler
 
-_COALESCE = [os.environ.get("NSAMD_COALESCE_ALLREDUCE", "1") == "1"]  # one collective call per optimiser group (see all_reduce_group)
+_COALESCE = [True]  # one collective call per optimiser group (see all_reduce_group)
 _ALIGN = 64  # floats: every tensor starts on a 256-B boundary
 _GROUP_ALIGN = _ALIGN * 840  # floats: lcm(1..8) aligned shards per optimiser group (<= 215 KB of zero padding per group)
 

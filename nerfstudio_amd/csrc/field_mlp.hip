@@ -656,21 +656,18 @@ __device__ __forceinline__ void coop_dw_pk(v4f* acc, float* dbacc, bool want_db,
   }
 }
 
-// Build-time choice of the weight-gradient arithmetic (same-box A/B, scripts/build_variant.sh): NSAMD_DW_BF16 = 0 every layer on
-// the f32 matrix-core path (rounds 2 - 5), 1 (default) two-piece bf16 for every layer but head layer 0, 2 for all five.
-#ifndef NSAMD_DW_BF16
-#define NSAMD_DW_BF16 1
-#endif
+// The weight-gradient arithmetic of a layer: two-piece bf16 for every layer but head layer 0, which stays on the f32
+// matrix-core path of rounds 2 - 5 (see store_rows_f32).
 template <int T, bool HEAD0 = false>
 __device__ __forceinline__ void store_rows(float* S, const v4f* x, int j, int g) {
-  if (NSAMD_DW_BF16 == 0 || (NSAMD_DW_BF16 == 1 && HEAD0)) store_rows_f32<T>(S, x, j, g);
+  if (HEAD0) store_rows_f32<T>(S, x, j, g);
   else store_rows_pk<T>(S, x, j, g);
 }
 
 template <int TILES, bool HEAD0 = false>
 __device__ __forceinline__ void coop_dw(v4f* acc, float* dbacc, bool want_db, const float* scratch, int first,
                                         int count, int n, int m0, int j, int g) {
-  if (NSAMD_DW_BF16 == 0 || (NSAMD_DW_BF16 == 1 && HEAD0)) coop_dw_f32<TILES>(acc, dbacc, want_db, scratch, first, count, n, m0, j, g);
+  if (HEAD0) coop_dw_f32<TILES>(acc, dbacc, want_db, scratch, first, count, n, m0, j, g);
   else coop_dw_pk<TILES>(acc, dbacc, want_db, scratch, first, count, n, m0, j, g);
 }
 
@@ -1097,61 +1094,38 @@ __global__ __launch_bounds__(kCoopThreads) void field_mlp_bwd_kernel(
   const int64_t per_iter = (int64_t)gridDim.x * kCoopWaves;
   const int64_t iters = (tiles + per_iter - 1) / per_iter;
   PROBE_STAMP(kCoopWaves, 1);
-  // the next tile's inputs are fetched behind the current tile's base-layer-0 barrier (NSAMD_NOROUTE_AHEAD=0 at build time:
-  // only in the record-emitting variant — same-box A/B of the plain backward)
-#ifndef NSAMD_NOROUTE_AHEAD
-#define NSAMD_NOROUTE_AHEAD 1
-#endif
-  constexpr bool AHEAD = ROUTE || NSAMD_NOROUTE_AHEAD;
+  // the next tile's inputs are fetched behind the current tile's base-layer-0 barrier, in the plain backward as in the
+  // record-emitting one
   TileFetch nxt;
-  static_assert(AHEAD || !RAYC, "ray terms are fetched a tile ahead");
-  if (AHEAD && iters > 0)
+  if (iters > 0)
     fetch_tile<RAYC>(nxt, (int64_t)blockIdx.x * kCoopWaves + wave, tiles, lane, M, enc, selector, directions, cams, app_table,
                      app_const, app_dim, dir_group, ddensity, drgb, mlp.ray_terms, mlp.ray_inputs);
   for (int64_t it = 0; it < iters; ++it) {
     PROBE_STAMP(kCoopWaves, 2 + 10 * (int)it);
     const int64_t tile = (it * gridDim.x + blockIdx.x) * kCoopWaves + wave;
-    TileInputs ti;
+    // (tile_fetched: what `fetch_tile` left raw gets its constants / masks here, where the values are first needed)
+    TileInputs ti = nxt.ti;
+    if (selector == nullptr) ti.sel = 1.0f;
+    if (cams == nullptr) ti.cam = 0;
     FieldActs A;
-    float up_rgb[3] = {0.f, 0.f, 0.f}, up_density = 0.f;
-    float nxt_xin = 0.0f;
-    if (AHEAD) {
-      // (tile_fetched: what `fetch_tile` left raw gets its constants / masks here, where the values are first needed)
-      ti = nxt.ti;
-      if (selector == nullptr) ti.sel = 1.0f;
-      if (cams == nullptr) ti.cam = 0;
-      A.enc[0] = nxt.enc[0];
-      A.enc[1] = nxt.enc[1];
-      const bool mine = g == 0 && ti.live;
+    A.enc[0] = nxt.enc[0];
+    A.enc[1] = nxt.enc[1];
+    const bool mine = g == 0 && ti.live;
+    float up_rgb[3];
 #pragma unroll
-      for (int c = 0; c < 3; ++c) up_rgb[c] = mine ? nxt.up[c] : 0.0f;
-      up_density = mine ? nxt.up[3] : 0.0f;
-      const float dir[3] = {nxt.dir[0], nxt.dir[1], nxt.dir[2]};
-      const v4f zero4 = v4f{0.f, 0.f, 0.f, 0.f};
-      const v4f app[2] = {app_dim > 0 ? nxt.app[0] : zero4, app_dim > 0 ? nxt.app[1] : zero4};
-      const v4f cterm[4] = {nxt.cterm[0], nxt.cterm[1], nxt.cterm[2], nxt.cterm[3]};
-      nxt_xin = nxt.xin;
-      if (ROUTE) {
-        // records 0..6 of the PREVIOUS tile leave between this tile's forward GEMMs, the other nine between the phases below
-        const RouteBetween rb{RL, RL->stash[wave], lane, it > 0};
-        coop_forward_tile<RouteBetween, RAYC>(W, bias, dir, app_table, app_const, app_dim, ti, lane, A, app, rb, cterm);
-      } else {
-        coop_forward_tile<NoBetween, RAYC>(W, bias, dir, app_table, app_const, app_dim, ti, lane, A, app, NoBetween{}, cterm);
-      }
+    for (int c = 0; c < 3; ++c) up_rgb[c] = mine ? nxt.up[c] : 0.0f;
+    const float up_density = mine ? nxt.up[3] : 0.0f;
+    const float dir[3] = {nxt.dir[0], nxt.dir[1], nxt.dir[2]};
+    const v4f zero4 = v4f{0.f, 0.f, 0.f, 0.f};
+    const v4f app[2] = {app_dim > 0 ? nxt.app[0] : zero4, app_dim > 0 ? nxt.app[1] : zero4};
+    const v4f cterm[4] = {nxt.cterm[0], nxt.cterm[1], nxt.cterm[2], nxt.cterm[3]};
+    const float nxt_xin = nxt.xin;
+    if (ROUTE) {
+      // records 0..6 of the PREVIOUS tile leave between this tile's forward GEMMs, the other nine between the phases below
+      const RouteBetween rb{RL, RL->stash[wave], lane, it > 0};
+      coop_forward_tile<RouteBetween, RAYC>(W, bias, dir, app_table, app_const, app_dim, ti, lane, A, app, rb, cterm);
     } else {
-      ti = tile_inputs(tile < tiles ? tile : tiles - 1, lane, M, selector, cams, dir_group);
-      if (tile >= tiles) ti.live = false;  // idle wave of the last round: computes, contributes zeros
-      load_enc_tile(enc, M, ti.p, lane, A.enc);
-      // the upstream gradients of this tile (lanes g == 0 use them two and five phases further down): fetched with the
-      // inputs, so their latency hides behind the forward instead of opening the head-2 and base-1 phases
-      if (g == 0 && ti.live) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) up_rgb[c] = drgb[3 * ti.p + c];
-        up_density = ddensity[ti.p];
-      }
-      const float* d = directions + 3 * ti.ray;  // consumed two layers further down
-      const float dir[3] = {d[0], d[1], d[2]};
-      coop_forward_tile(W, bias, dir, app_table, app_const, app_dim, ti, lane, A);
+      coop_forward_tile<NoBetween, RAYC>(W, bias, dir, app_table, app_const, app_dim, ti, lane, A, app, NoBetween{}, cterm);
     }
     PROBE_STAMP(kCoopWaves, 3 + 10 * (int)it);
     const bool emit = ROUTE && it > 0;  // the previous tile's records are still going out
@@ -1356,7 +1330,7 @@ __global__ __launch_bounds__(kCoopThreads) void field_mlp_bwd_kernel(
       RL->stash[wave][10][lane] = pz;
     }
     __syncthreads();
-    if (AHEAD && it + 1 < iters)  // the next tile's inputs (see TileFetch)
+    if (it + 1 < iters)  // the next tile's inputs (see TileFetch)
       fetch_tile<RAYC>(nxt, tile + per_iter, tiles, lane, M, enc, selector, directions, cams, app_table, app_const, app_dim,
                        dir_group, ddensity, drgb, mlp.ray_terms, mlp.ray_inputs);
     PROBE_STAMP(kCoopWaves, 9 + 10 * (int)it);
@@ -1719,16 +1693,6 @@ extern "C" int nsamd_field_mlp_bwd(const float* enc, const float* selector, cons
                                    int64_t workspace_floats, nsamd_stream_t stream) {
   return field_mlp_bwd_impl(enc, selector, directions, camera_indices, appearance_const, dir_group, M, mlp, ddensity,
                             drgb, denc, grads, workspace, workspace_floats, stream);
-}
-
-extern "C" int nsamd_field_mlp_bwd_phase(const float* enc, const float* selector, const float* directions,
-                                         const int64_t* camera_indices, const float* appearance_const,
-                                         int64_t dir_group, int64_t M, nsamd_field_mlp mlp, const float* ddensity,
-                                         const float* drgb, float* denc, nsamd_field_mlp_grads grads, float* workspace,
-                                         int64_t workspace_floats, int phase, nsamd_stream_t stream) {
-  NSAMD_REQUIRE(phase == 1 || phase == 2);
-  return field_mlp_bwd_impl(enc, selector, directions, camera_indices, appearance_const, dir_group, M, mlp, ddensity,
-                            drgb, denc, grads, workspace, workspace_floats, stream, phase);
 }
 
 extern "C" int nsamd_probe_mfma_bf16(const float* A, const float* B, float* out, nsamd_stream_t stream) {

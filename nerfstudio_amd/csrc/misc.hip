@@ -180,25 +180,14 @@ __global__ __launch_bounds__(1024) void step_prologue_kernel(int64_t* __restrict
 // Python scalars are when ATen takes them; correctly rounded sqrt and division (hipcc default), no FMA contraction.
 // The moments (2 x 67 MB for the main table) are touched exactly once per step: streamed past the caches with
 // non-temporal accesses, so that the parameters and the gradient — which the next launches read again — keep their place
-// (NSAMD_ADAM_NT=0 at build time: plain accesses, for A/B).
-#ifndef NSAMD_ADAM_NT
-#define NSAMD_ADAM_NT 1
-#endif
+// (against plain accesses: driver window 0.768 -> 0.755 ms, profiles/NOTEBOOK.md 4.1).
 typedef float adam_v4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ float4 stream_load4(const float* base, int64_t i) {
-#if NSAMD_ADAM_NT
   const adam_v4 v = __builtin_nontemporal_load(reinterpret_cast<const adam_v4*>(base) + i);
   return make_float4(v.x, v.y, v.z, v.w);
-#else
-  return reinterpret_cast<const float4*>(base)[i];
-#endif
 }
 __device__ __forceinline__ void stream_store4(float* base, int64_t i, const float4& x) {
-#if NSAMD_ADAM_NT
   __builtin_nontemporal_store(adam_v4{x.x, x.y, x.z, x.w}, reinterpret_cast<adam_v4*>(base) + i);
-#else
-  reinterpret_cast<float4*>(base)[i] = x;
-#endif
 }
 
 __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,

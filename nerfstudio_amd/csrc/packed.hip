@@ -579,14 +579,6 @@ extern "C" int nsamd_occgrid_march_count_stash(const float* origins, const float
   return NSAMD_OK;
 }
 
-extern "C" int nsamd_occgrid_march_count(const float* origins, const float* directions, const float* t_min,
-                                         const float* t_max, int64_t num_rays, float near_plane, float far_plane,
-                                         nsamd_occgrid grid, float step_size, float cone_angle, const float* jitter,
-                                         int32_t* counts, nsamd_stream_t stream) {
-  return nsamd_occgrid_march_count_stash(origins, directions, t_min, t_max, num_rays, near_plane, far_plane, grid, step_size,
-                                         cone_angle, jitter, counts, nullptr, 0, stream);
-}
-
 extern "C" int nsamd_occgrid_march_write_stashed(const float* origins, const float* directions, const float* t_min,
                                                  const float* t_max, int64_t num_rays, float near_plane, float far_plane,
                                                  nsamd_occgrid grid, float step_size, float cone_angle, const float* jitter,
@@ -606,15 +598,6 @@ extern "C" int nsamd_occgrid_march_write_stashed(const float* origins, const flo
       packed_info, ray_indices, t_starts, t_ends, cw, const_cast<float2*>(reinterpret_cast<const float2*>(stash)), stash_cap);
   NSAMD_CHECK_LAUNCH();
   return NSAMD_OK;
-}
-
-extern "C" int nsamd_occgrid_march_write(const float* origins, const float* directions, const float* t_min,
-                                         const float* t_max, int64_t num_rays, float near_plane, float far_plane,
-                                         nsamd_occgrid grid, float step_size, float cone_angle, const float* jitter,
-                                         const int64_t* packed_info, int64_t* ray_indices, float* t_starts, float* t_ends,
-                                         nsamd_stream_t stream) {
-  return nsamd_occgrid_march_write_stashed(origins, directions, t_min, t_max, num_rays, near_plane, far_plane, grid, step_size,
-                                           cone_angle, jitter, packed_info, nullptr, 0, ray_indices, t_starts, t_ends, stream);
 }
 
 extern "C" int64_t nsamd_occgrid_coarse_words(int32_t levels, int32_t resolution) {

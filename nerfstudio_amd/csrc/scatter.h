@@ -34,21 +34,13 @@ __device__ __forceinline__ FixedScale fixed_scale(uint32_t max_bits, int headroo
 // trunc(v * 2^k) as a 64-bit two's-complement integer, |v * 2^k| < 2^44 (headroom >= 18). 8 VALU operations: the scaled
 // value is split into a high part (multiple of 2^24) and the rest, both exactly representable, each converted with the
 // hardware float -> int32 conversion (round toward zero: symmetric, -0 -> 0) and rejoined by one 64-bit multiply-add.
-#ifndef NSAMD_FIXED_ROUND
-#define NSAMD_FIXED_ROUND 0
-#endif
+// (Round-to-nearest-even of the low part — unbiased, |error| <= 2^-(k+1) per summand where the truncation's is one-sided,
+// <= 2^-k — moved the PSNR stand-in by nothing: profiles/r05_psnr_ab.txt.)
 __device__ __forceinline__ unsigned long long to_fixed(float v, int k) {
   const float t = ldexpf(v, k);                          // exact (or flushed to zero when denormal)
   const float hi_f = truncf(t * 5.9604644775390625e-8f); // t * 2^-24
   const float lo_f = fmaf(hi_f, -16777216.0f, t);        // exact: t minus its high part
-#if NSAMD_FIXED_ROUND
-  // round-to-nearest-even of the low part (one v_rndne_f32 more): |error| <= 2^-(k+1) per summand and unbiased, where the
-  // truncation's error is one-sided (toward zero, <= 2^-k). Measured against each other on the PSNR stand-in
-  // (profiles/r05_psnr_ab.txt); a build-time switch because the sums' bits differ.
-  const long long r = (long long)(int)hi_f * 16777216ll + (long long)(int)rintf(lo_f);
-#else
   const long long r = (long long)(int)hi_f * 16777216ll + (long long)(int)lo_f;
-#endif
   return (unsigned long long)r;  // the atomics add modulo 2^64
 }
 
@@ -102,10 +94,7 @@ constexpr uint32_t kSpillFold = 8192;  // spill records pass 2 folds into its ti
 #if defined(__HIPCC__)
 // ---- device helpers shared by the route kernels (scatter.hip) and the field backward's record emission (field_mlp.hip) ----
 // Queue records are written once (pass 1) and read once (pass 2, another launch): streaming accesses, kept out of the way of
-// the table rows and gradients that do get re-used (NSAMD_SCATTER_NT=0 at build time: plain accesses, for A/B).
-#ifndef NSAMD_SCATTER_NT
-#define NSAMD_SCATTER_NT 1
-#endif
+// the table rows and gradients that do get re-used (against plain loads: loop 0.792 -> 0.772 ms, profiles/NOTEBOOK.md 4.1).
 typedef uint32_t rec_vec __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void rec_store(uint4* dst, const uint4& r) {
   // (nontemporal STORES: 175 -> 399 us for the main table — the scattered 16-B records lose L2's write combining)
@@ -116,11 +105,7 @@ __device__ __forceinline__ void rec_store(uint4* dst, const uint4& r) {
   *global_ptr(reinterpret_cast<rec_vec*>(dst)) = v;
 }
 __device__ __forceinline__ uint4 rec_load(const uint4* src) {
-#if NSAMD_SCATTER_NT
   const rec_vec v = __builtin_nontemporal_load(global_ptr(reinterpret_cast<const rec_vec*>(src)));
-#else
-  const rec_vec v = *global_ptr(reinterpret_cast<const rec_vec*>(src));
-#endif
   return make_uint4(v.x, v.y, v.z, v.w);
 }
 

@@ -10,22 +10,13 @@
 
 namespace nsamd {
 
-// Index of this wavefront inside its workgroup. NSAMD_SCALAR_RAY=1 at build time makes it a SCALAR (wave-uniform by
-// construction, which the compiler cannot prove of threadIdx.x >> 6): everything derived from it — the wave's ray, its row
-// pointers, the ray's near / far / jitter — then lives in scalar registers and is fetched through the scalar cache. Measured on
-// MI355X (profiles/r05_s5_ab_scalar_ray.txt): nothing — every per-ray launch within 1 % either way, the step 0.698 against
-// 0.692 ms — so the plain expression is the default: the scalar cache is not coherent with a wave's own vector stores inside
-// one launch, which a kernel that reads back what it wrote (csrc/fused_rays.hip) would have to keep in mind for no gain.
-#ifndef NSAMD_SCALAR_RAY
-#define NSAMD_SCALAR_RAY 0
-#endif
-__device__ __forceinline__ int wave_index() {
-#if NSAMD_SCALAR_RAY
-  return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-#else
-  return (int)(threadIdx.x >> 6);
-#endif
-}
+// Index of this wavefront inside its workgroup. As a SCALAR (readfirstlane: wave-uniform by construction, which the compiler
+// cannot prove of threadIdx.x >> 6) everything derived from it — the wave's ray, its row pointers, the ray's near / far /
+// jitter — lives in scalar registers and is fetched through the scalar cache. Measured on MI355X
+// (profiles/r05_s5_ab_scalar_ray.txt): nothing — every per-ray launch within 1 % either way, the step 0.698 against
+// 0.692 ms — so it is the plain expression: the scalar cache is not coherent with a wave's own vector stores inside one
+// launch, which a kernel that reads back what it wrote would have to keep in mind for no gain.
+__device__ __forceinline__ int wave_index() { return (int)(threadIdx.x >> 6); }
 
 template <int CTRL, int ROW_MASK>
 __device__ __forceinline__ double dpp_move_f64(double v) {

@@ -8,7 +8,6 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-import os
 from dataclasses import dataclass
 from typing import Optional, Sequence, Tuple
 
@@ -614,7 +613,7 @@ class _NerfactoFieldFn(torch.autograd.Function):
         # samples grouped by ray, a whole number of 16-sample tiles per ray: head layer 0's share of the 48 per-ray inputs once
         # per ray (include/nsamd.h, nsamd_field_mlp.ray_terms)
         ctx.ray_terms = ctx.ray_inputs = None
-        if dir_group % 16 == 0 and M % dir_group == 0 and M > 0 and os.environ.get("NSAMD_RAY_TERMS", "1") == "1":
+        if dir_group % 16 == 0 and M % dir_group == 0 and M > 0:
             rays = M // dir_group
             has_app = cams is not None or appearance_const is not None
             ctx.ray_terms = torch.empty((rays, 64), device=dev, dtype=torch.float32)

@@ -21,7 +21,6 @@ written out by hand. tests/test_gpu_packed.py compares a step of the two routes 
 """
 from __future__ import annotations
 
-import os
 from typing import Dict, Optional
 
 import torch
@@ -35,7 +34,6 @@ from .utils import profiler
 # kept steps per ray the count pass of the marcher leaves behind for the write pass (nsamd_occgrid_march_count_stash): a ray
 # that keeps more is marched a second time (the benchmark's rays keep ~42 of ~840 lattice steps)
 STASH_CAP = 128
-_TWO_PASS = os.environ.get("NSAMD_NGP_TWO_PASS", "0") == "1"
 
 
 class NgpTrainStep:
@@ -70,7 +68,7 @@ class NgpTrainStep:
         # pipeline.NgpEngine under a trainer whose own optimiser must find `.grad` None); None: `param.grad`
         self.grad_lookup = None
         self.accumulate_table = False
-        self.fuse_route = os.environ.get("NSAMD_NGP_FUSE_ROUTE", "1") == "1"  # the field backward emits the scatter's records (backward)
+        self.fuse_route = True  # the field backward emits the scatter's records (backward)
         self.has_bounds = False
         bgc = model.renderer_rgb.background_color
         if isinstance(bgc, str) and bgc == "last_sample":
@@ -112,7 +110,6 @@ class NgpTrainStep:
         self.c_pos = torch.empty(cap, 3, device=dev, dtype=f32)
         self.c_enc = torch.empty(self.L2 * cap, device=dev, dtype=f32)
         self.c_sel, self.c_sigma = torch.empty(cap, device=dev, dtype=f32), torch.empty(cap, device=dev, dtype=f32)
-        self.c_rgb = torch.empty(cap, 3, device=dev, dtype=f32)
         self.c_mask = torch.empty(cap, device=dev, dtype=torch.uint8)
 
     def _grow_kept(self, cap: int) -> None:
@@ -177,9 +174,9 @@ class NgpTrainStep:
         near, far, step, cone = float(cfg.near_plane), min(float(cfg.far_plane), 3.0e38), float(cfg.render_step_size), float(cfg.cone_angle)
         # -- candidates: count -> prefix -> (host read) -> write
         tmin, tmax = (N.ptr(self.t_min), N.ptr(self.t_max)) if self.has_bounds else (None, None)
-        stash = None if _TWO_PASS else N.ptr(self.stash)  # (NSAMD_NGP_TWO_PASS=1: march twice, full head on the candidates — A/B)
+        stash = N.ptr(self.stash)
         ck(lib.nsamd_occgrid_march_count_stash(o, d, tmin, tmax, n, near, far, og, step, cone, N.ptr(self.jitter), N.ptr(self.counts),
-                                               stash, 0 if _TWO_PASS else STASH_CAP, st), "occgrid_march_count_stash")
+                                               stash, STASH_CAP, st), "occgrid_march_count_stash")
         ck(lib.nsamd_packed_info(N.ptr(self.counts), n, N.ptr(self.info), N.ptr(self.totals[0:1]), st), "packed_info")
         mc = self._read_total(0)
         self.num_candidates = mc
@@ -190,13 +187,13 @@ class NgpTrainStep:
             if mc > self.cap_c:
                 self._grow_candidates(int(1.5 * mc))
             ck(lib.nsamd_occgrid_march_write_stashed(o, d, tmin, tmax, n, near, far, og, step, cone, N.ptr(self.jitter), N.ptr(self.info),
-                                                     stash, 0 if _TWO_PASS else STASH_CAP, N.ptr(self.c_ri), N.ptr(self.c_ts), N.ptr(self.c_te), st),
+                                                     stash, STASH_CAP, N.ptr(self.c_ri), N.ptr(self.c_ts), N.ptr(self.c_te), st),
                "occgrid_march_write_stashed")
             # -- sigma_fn (ray_samplers.py:420-429): density of the candidates; no direction, a constant appearance row
             ck(lib.nsamd_packed_positions(o, d, N.ptr(self.c_ri), N.ptr(self.c_ts), N.ptr(self.c_te), mc, N.ptr(self.c_pos), st),
                "packed_positions")
             F.field_forward(fld, N.make_points(positions=self.c_pos), mc, self.c_enc, self.c_sel, self.view0, None, self.app0, mc, fm,
-                            self.c_sigma, self.c_rgb if _TWO_PASS else None)  # (rgb NULL: density only)
+                            self.c_sigma, None)  # (rgb NULL: density only)
             # -- visibility-ordered early termination + alpha threshold, then compaction (OccGridEstimator.sampling)
             alpha = float(cfg.alpha_thre)
             if alpha > 0.0:
@@ -305,7 +302,7 @@ class NgpTrainStep:
         gl = self.grad_lookup
         grad_of = (lambda p: gl[id(p)]) if gl is not None else (lambda p: p.grad)  # noqa: E731
         # as the nerfacto schedule does (train_step.backward_field_and_table): while the table's gradient is written, the field
-        # backward emits the table scatter's pass-1 records from its registers (NSAMD_NGP_FUSE_ROUTE=0: the two entry points, A/B)
+        # backward emits the table scatter's pass-1 records from its registers (`fuse_route` False: the two entry points)
         F.field_backward(fld, N.make_points(positions=self.k_pos), mk, self.k_enc, self.k_sel, self.k_dirs,
                          self.k_cams if self._train_app else None, self._app_const, 1,
                          F.field_mlp(params, emb, fld.average_init_density), self.k_dsigma, self.k_drgb, self.k_denc,

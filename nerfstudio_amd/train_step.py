@@ -113,8 +113,8 @@ class NerfactoTrainStep:
         self._pl_dw = parr(self.dw_prop)
         self._pl_S = (C.c_int32 * self.n_prop)(*self.counts[: self.n_prop])
         # Ray terms (include/nsamd.h, nsamd_field_mlp.ray_terms): head layer 0's share of the 48 per-ray inputs (SH of the view
-        # direction, appearance row) once per ray instead of once per sample. NSAMD_RAY_TERMS=0: the plain kernels (A/B).
-        self.ray_terms_on = os.environ.get("NSAMD_RAY_TERMS", "1") == "1" and self.counts[-1] % 16 == 0
+        # direction, appearance row) once per ray instead of once per sample (a 16-point tile must lie inside one ray).
+        self.ray_terms_on = self.counts[-1] % 16 == 0
         self.ray_terms = e(n, 64) if self.ray_terms_on else None
         self.ray_inputs = e(n, 16 + (32 if fld.embedding_appearance is not None else 0)) \
             if (self.ray_terms_on and not forward_only) else None  # (the backward's: weight gradient of the 48 per-ray columns)
@@ -127,8 +127,8 @@ class NerfactoTrainStep:
         # Zero-gradient gating of the proposal chains (include/nsamd.h): one device flag per level, raised by the level's
         # weights backward when any ray carries interlevel-loss gradient; while it is clear the rest of the chain
         # (density MLP backward, table scatter, ray gradients) returns at once — the zero-filled gradients are the result.
-        # NSAMD_GATE_PROPOSALS=0: the ungated entry points (A/B).
-        self.gate_proposals = os.environ.get("NSAMD_GATE_PROPOSALS", "1") == "1"
+        # False: the ungated entry points.
+        self.gate_proposals = True
         self.prop_gates = torch.zeros(max(self.n_prop, 1) * 4, device=device, dtype=torch.int32)  # 16 B apart
         self.gates_precleared = False  # True: the caller zeroes `prop_gates` before every proposal backward (trainer.HipTrainer)
         # ... and its per-ray form (1 = the ray carries gradient): levels that are only partly without gradient
@@ -137,8 +137,8 @@ class NerfactoTrainStep:
         # round trip, no route launch); NSAMD_FUSE_ROUTE=0: the two entry points (A/B).
         self.fuse_route = os.environ.get("NSAMD_FUSE_ROUTE", "1") == "1"
         self.keep_denc = False  # True: the fused launch also stores the encoded-feature gradient in `f_denc` (tests read it)
-        # the same stage of the proposal levels' backward chains as one launch across the levels (0: level by level, A/B)
-        self.merge_prop_levels = os.environ.get("NSAMD_MERGE_PROP_LEVELS", "1") == "1"
+        # the same stage of the proposal levels' backward chains as one launch across the levels (False: level by level)
+        self.merge_prop_levels = True
         # the iteration's loss values and training metrics, written by the losses launch's finishing pass (nsamd.h):
         # rgb_loss, interlevel_loss, distortion_loss, psnr, distortion, sum of the three losses
         self.loss_vals = torch.zeros(32, **f32)  # (8 results + the finishing pass's scratch: partial sums, ticket)
@@ -699,7 +699,7 @@ class NerfactoTrainStep:
             spec = net.encoding.spec
             ws, ws_n = F._scatter_workspace(spec, self.f_enc.device, m)
             grads = (N.ptr(self._grad(W0)), N.ptr(self._grad(b0)), N.ptr(self._grad(W1)), N.ptr(self._grad(b1)))
-            if gate is None or ws is None:  # ungated chain (A/B switch, or no binned-scatter workspace for this shape)
+            if gate is None or ws is None:  # ungated chain (`gate_proposals` off, or no binned-scatter workspace for this shape)
                 ck(lib.nsamd_weights_bwd(N.ptr(self.t_bins[lvl]), N.ptr(self.p_dens[lvl]), N.ptr(self.dw_prop[lvl]),
                                          n, S, N.ptr(self.p_ddens[lvl]), st), "weights_bwd")
                 ck(lib.nsamd_density_mlp_bwd(N.ptr(self.p_enc[lvl]), N.ptr(self.p_sel[lvl]), N.ptr(self.p_pre[lvl]),

@@ -43,7 +43,6 @@ from __future__ import annotations
 
 import os
 import sys
-import time
 from typing import Callable, Dict, Optional
 
 import torch
@@ -150,8 +149,6 @@ class HipTrainer:
             cam_on = getattr(r, "cam_opt", None) is not None
             self.cam_inside = cam_on and self.cam_group is not None and not self.dp and os.environ.get("NSAMD_CAMERAS_OUTSIDE", "0") != "1"
             r.cameras_outside = cam_on and not self.cam_inside  # see the module docstring
-            if os.environ.get("NSAMD_SIDE_STREAM", "1") == "0":  # A/B switch: proposal backward on the main stream
-                r.side_stream = None
             # N = 1: the main-field Adam of iteration k (470 MB of HBM streaming) runs BESIDE the proposal forward of
             # iteration k+1 (L2-resident gathers and per-ray scans that read only proposal-network parameters) — the
             # single-GPU form of the pipelined schedule above; same dependencies, same bits. Measured on three MI355X boxes
@@ -195,8 +192,8 @@ class HipTrainer:
 
                 self.exchange = PipelinedExchange(arena, self._run, before_main_update=self._push_hyper,
                                                   sharded=self.dp_sharded)
-                # eager segments only (a captured segment must end with its streams joined); NSAMD_DP_FORK=0: round-2 order
-                self.dp_fork = os.environ.get("NSAMD_DP_FORK", "1") == "1" and getattr(r, "side_stream", None) is not None
+                # eager segments only (a captured segment must end with its streams joined)
+                self.dp_fork = getattr(r, "side_stream", None) is not None
                 # the coarse levels of the main table can only ever touch 288 k of their 2.6 M rows: exchange those
                 # compactly (2.3 MB instead of 21 MB of the 67 MB main-field all-reduce)
                 enc = model.field.mlp_base.encoding
@@ -478,17 +475,6 @@ class HipTrainer:
             raise KeyError(name)
 
     def _run(self, name):
-        if os.environ.get("NSAMD_DP_TIMING") == "1":  # diagnostics: host-synchronous per-segment timing
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            self._run_inner(name)
-            torch.cuda.synchronize()
-            self._seg_times = getattr(self, "_seg_times", {})
-            self._seg_times.setdefault(str(name), []).append((time.perf_counter() - t0) * 1e3)
-            return
-        self._run_inner(name)
-
-    def _run_inner(self, name):
         if self.graphs is not None:
             self.graphs[name].replay()
             if name == "mopt":

@@ -2,7 +2,9 @@
 # GPU box: rocprofv3 evidence for the bench command (run via gpurun). Writes under gpurun_out/<tag = $1, default final>/:
 #   kernel_stats.csv     per-kernel time (rocprofv3 --kernel-trace --stats of `bench.py --steps 20`, graph replay)
 #   pmc_summary.csv      SQ counters (MFMA busy, LDS waits, ...), FETCH_SIZE, WRITE_SIZE per kernel — three separate
-#                        passes with --kernel-trace only (no sys/hip/hsa tracing), as required on this pool
+#                        passes with --kernel-trace only (no sys/hip/hsa tracing), as required on this pool; eager
+#                        launches, the proposal backward chains on their side stream as in training (the passes of the
+#                        committed profiles/pmc_* ran them in line, through a switch the package no longer reads)
 #   pmc_traffic.json     HBM-side bytes per launch for the bench's kernel keys (MI355X_MICROARCH.md "HBM": FETCH_SIZE and
 #                        WRITE_SIZE are reported in KiB; FETCH_SIZE counts 128-B requests at 64 B for wide coalesced
 #                        streaming reads -> doubled for the kernels that stream 16 B per lane, raw value kept too)
@@ -12,7 +14,6 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 timeout ${PMC_STATS_TIMEOUT:-600} rocprofv3 --kernel-trace --stats -d /tmp/kstats -o k -- python $R/bench.py --full --steps 20 --warmup 5 --windows 1 --long-steps 0 --no-cpu-baseline --profile-steps 1 > $OUT/rocprof_bench.log 2>&1
 CMD="python $R/bench.py --full --steps 3 --warmup 3 --windows 1 --long-steps 0 --no-graph --no-cpu-baseline --profile-steps 1 --fixed-batch"
-export NSAMD_SIDE_STREAM=0
 timeout ${PMC_PASS_TIMEOUT:-600} rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_WAIT_INST_LDS --output-format csv -d /tmp/pmc_sq -o sq -- $CMD > $OUT/pmc_sq.log 2>&1
 timeout ${PMC_PASS_TIMEOUT:-600} rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d /tmp/pmc_fetch -o f -- $CMD > $OUT/pmc_fetch.log 2>&1
 timeout ${PMC_PASS_TIMEOUT:-600} rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d /tmp/pmc_write -o w -- $CMD > $OUT/pmc_write.log 2>&1

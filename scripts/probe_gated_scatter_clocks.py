@@ -10,7 +10,6 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 os.environ["NSAMD_LIB"] = os.path.join(ROOT, "nerfstudio_amd", "libnsamd_probe.so")
-os.environ.setdefault("NSAMD_SIDE_STREAM", "0")
 sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
@@ -27,6 +26,7 @@ model = bench.build_model(device, seed=0)
 arena = ParamArena(model.get_param_groups_ordered(), lr=1e-2, eps=1e-15)
 rb, batch, pool = bench.synthetic_batch(device, seed=1000, workload="bounded")
 trainer = bench.Trainer(model, arena, rb, batch, world=1, use_graph=False, use_runner=True, pool=pool)
+trainer.runner.side_stream = None  # proposal backward in line: every kernel alone
 for _ in range(int(os.environ.get("PROBE_STEPS", "14"))):
     trainer.train_iteration()
 while not model.proposal_sampler.updated_this_step():

@@ -3,7 +3,8 @@
 back: proposal networks updated / not updated x main-field Adam of the previous iteration pending / not pending. The
 replays train (parameters move), which does not matter for timing. One line per variant: median and minimum of
 PROBE_REPLAYS (default 60) replays, HIP events on the launch stream.
-Environment: NSAMD_DEFER_MAIN_ADAM, NSAMD_SIDE_STREAM (read by bench.Trainer / NerfactoTrainStep)."""
+PROBE_IN_LINE=1: the proposal backward in line (`runner.side_stream = None`).
+Environment: NSAMD_DEFER_MAIN_ADAM (read by bench.Trainer)."""
 import os
 import sys
 
@@ -21,6 +22,8 @@ model = bench.build_model(dev, seed=0)
 arena = ParamArena(model.get_param_groups_ordered(), lr=1e-2, eps=1e-15)
 rb, batch, pool = bench.synthetic_batch(dev, seed=1000)
 tr = bench.Trainer(model, arena, rb, batch, world=1, use_graph=True, use_runner=True, pool=pool)
+if os.environ.get("PROBE_IN_LINE") == "1":
+    tr.runner.side_stream = None
 for _ in range(12):
     tr.train_iteration()
 tr.finish()

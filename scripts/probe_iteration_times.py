@@ -2,7 +2,8 @@
 """GPU box: wall time per training iteration INSIDE the real loop of bench.py (alternating update / non-update iterations
 from step 10 on), split by kind: HIP events on the launch stream around every Trainer.train_iteration(), median per kind, and
 the host-clock average over the whole loop. PROBE_EAGER=1: eager launches instead of hipGraph replay.
-Environment: NSAMD_DEFER_MAIN_ADAM, NSAMD_SIDE_STREAM."""
+PROBE_IN_LINE=1: the proposal
+backward in line (`runner.side_stream = None`). Environment: NSAMD_DEFER_MAIN_ADAM."""
 import os
 import sys
 import time
@@ -22,6 +23,8 @@ model = bench.build_model(dev, seed=0)
 arena = ParamArena(model.get_param_groups_ordered(), lr=1e-2, eps=1e-15)
 rb, batch, pool = bench.synthetic_batch(dev, seed=1000)
 tr = bench.Trainer(model, arena, rb, batch, world=1, use_graph=not eager, use_runner=True, pool=pool)
+if os.environ.get("PROBE_IN_LINE") == "1":
+    tr.runner.side_stream = None
 for _ in range(5):
     tr.train_iteration()
 tr.finish()

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """PSNR stand-in, many seeds, several arms on ONE box: is the GPU path's PSNR after 300 steps biased
-against the CPU oracle's, and does the fused record emission's fixed-point scale (NSAMD_FUSE_ROUTE) or the conversion's
-rounding (library built with -DNSAMD_FIXED_ROUND=1, through NSAMD_LIB) move it?
+against the CPU oracle's, and does the fused record emission's fixed-point scale (NSAMD_FUSE_ROUTE) move it? (Round 5 also
+ran a library whose fixed-point conversion rounds to nearest, through NSAMD_LIB: no difference, profiles/r05_psnr_ab.txt.)
 
 Per seed and arm: the training of tests/test_gpu_training.py::test_psnr_on_procedural_scene_matches_oracle_training from the
 fixture's initial state (twin 0) and from `twins` copies whose hash tables are perturbed by 1e-6 relative (the GPU path's own

@@ -433,3 +433,23 @@ def test_environment_switches_match_the_design_table():
     rows = [ln for ln in section.splitlines() if ln.startswith("| `NSAMD_")]
     listed = set(re.findall(r"`(NSAMD_\w+)`", "\n".join(rows)))
     assert read == listed, (sorted(read - listed), sorted(listed - read))
+
+
+def test_kernel_sources_have_one_build_configuration():
+    """The only NSAMD_* name a preprocessor conditional of csrc/ tests is NSAMD_PROBE_CLOCKS (the instrumented `make probe`
+    build): a decided A/B arm is deleted, not kept behind a macro that nothing sets."""
+    import glob
+    import os
+    import re
+
+    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "nerfstudio_amd", "csrc")
+    sources = glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.h"))
+    assert sources
+    tested = {}
+    for p in sources:
+        text = open(p).read().replace("\\\n", " ")  # (a directive continued over several lines is one directive)
+        for line in re.findall(r"^[ \t]*#[ \t]*(?:if|ifdef|ifndef|elif)\b.*$", text, re.M):
+            for name in re.findall(r"\bNSAMD_\w+", line):
+                if not re.search(r"_H_*$", name):  # (an include guard is no switch)
+                    tested.setdefault(name, []).append(os.path.basename(p))
+    assert set(tested) == {"NSAMD_PROBE_CLOCKS"}, tested
