@@ -314,6 +314,30 @@ int nsamd_field_mlp_bwd_scatter_phase(nsamd_points pts, int transform, nsamd_aab
                                       int64_t scatter_workspace_floats, int phase, nsamd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Normals of the nerfacto field, forward only (the eval render of a `predict_normals` model).
+ * nsamd_field_normals: for each of M samples (`pts` as nsamd_hashgrid_encode_fwd takes them) the gradient of the density
+ * pre-activation with respect to the NORMALISED, selector-masked position (Field.get_normals, fields/base_field.py:79-99:
+ * first order, no contraction Jacobian), from the encoded features `enc` [32, M] (feature-major, as the hash forward left
+ * them), the main table and the base MLP (W0 [64,32], b0 [64], W1 [16,64], b1 [16]): z = W0 enc + b0, g_enc = W0^T (W1[0,:] *
+ * [z > 0]), then the position gradient of HashEncoding.pytorch_fwd (encodings.py:417-458) — an axis on which ceil == floor
+ * contributes exactly 0 on that level, a masked-out sample has gradient 0 and normal 0. Outputs, each nullable:
+ * normals [M,3] = -g / max(|g|, 1e-12); gradient [M,3] = g; geo: the base MLP's outputs 1..15 of sample p at
+ * geo[p * geo_stride + geo_offset + 0..14] (geo_stride >= geo_offset + 15: e.g. columns 12..26 of the 27-wide input rows of
+ * the predicted-normals MLP). 16 levels only (other counts: NSAMD_ERR_UNSUPPORTED); M == 0 is a no-op. No atomics, the same
+ * bits on every run.
+ * nsamd_normals_composite: per ray, from weights [N,S], per-sample normals [N*S,3] and the predicted-normals head's
+ * pre-activation [N*S,3]: pred = normalize(tanh(x)) (PredNormalsFieldHead, field_heads.py), r = sum_s w n / (|sum_s w n| +
+ * 1e-10) (NormalsRenderer) and the shaded value (r + 1) / 2 (NormalsShader without weights, models/nerfacto.py:325-329) of
+ * both channels -> normals_out / pred_out [N,3] (each nullable with its input); a ray of zero weights gives 0.5. S <= 4096.
+ * ------------------------------------------------------------------------------------------------------------ */
+int nsamd_field_normals(nsamd_points pts, int64_t M, int transform, nsamd_aabb aabb, const float* table, nsamd_grid grid,
+                        const float* enc, const float* base_W0, const float* base_b0, const float* base_W1,
+                        const float* base_b1, float* normals, float* gradient, float* geo, int64_t geo_stride,
+                        int64_t geo_offset, nsamd_stream_t stream);
+int nsamd_normals_composite(const float* weights, const float* normals, const float* pred_pre, int64_t num_rays, int32_t S,
+                            float* normals_out, float* pred_out, nsamd_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Generic dense layer for the stand-alone MLP of the plugin API (MLP.pytorch_fwd, field_components/mlp.py:160-179):
  * y[M,N] = act(x[M,K] W[N,K]^T + b[N]); activation 0 = none, 1 = ReLU, 2 = Sigmoid, 3 = Softplus (the DensityFieldHead of
  * vanilla-nerf, field_heads.py:98-108); any K, N (layers wider than 128 run as 128 x 128 blocks of W: the 8 x 256 MLP with

@@ -99,6 +99,8 @@ _SIGNATURES = {
                                           vp, i64, vp, vp, i64, C.c_int, vp],
     "nsamd_field_mlp_bwd_scatter_workspace": [Grid, i64, C.POINTER(C.c_int64)],
     "nsamd_proposal_levels_bwd": [C.POINTER(ProposalLevelBwd), i32, i32, vp],
+    "nsamd_field_normals": [Points, i64, C.c_int, Aabb, vp, Grid, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, vp],
+    "nsamd_normals_composite": [vp, vp, vp, i64, i32, vp, vp, vp],
     "nsamd_linear_fwd": [vp, vp, vp, i64, i32, i32, C.c_int, vp, vp],
     "nsamd_linear_bwd": [vp, vp, vp, vp, i64, i32, i32, C.c_int, vp, vp, vp, vp],
     "nsamd_piecewise_bins": [vp, vp, vp, vp, i32, i64, i32, C.c_int, vp, vp, vp],

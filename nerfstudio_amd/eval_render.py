@@ -30,11 +30,41 @@ from . import functional as F  # noqa: F401
 from .utils import profiler
 
 
+_PN_BLOCK = 1 << 18  # samples per pass of the predicted-normals MLP (its two [block, 64] activation buffers: 64 MiB each)
+
+
+def pred_normals_mlp_launch(fld, pts: N.Points, M: int, freqs: Tensor, pn_enc: Tensor, pn_in: Tensor, pn_a: Tensor, pn_b: Tensor,
+                            pn_pre: Tensor) -> None:
+    """The predicted-normals branch of a NerfactoField in eval (nerfacto_field.py:287-295) on M points whose geometry features
+    already sit in columns 12..26 of `pn_in` [M, 27], over caller-owned buffers on the current stream: nsamd_nerf_encode of the
+    raw positions (`pn_enc` [M, 12], copied into columns 0..11), then the MLP's three layers (ReLU, ReLU, none) and the 64 -> 3
+    head with no activation — nsamd_normals_composite applies tanh and the normalisation — into `pn_pre` [M, 3], in blocks of
+    the rows `pn_a` / `pn_b` [block, 64] hold."""
+    lib, st = N.load(), N.stream()
+    pe = fld.position_encoding
+    N.check(lib.nsamd_nerf_encode(pts, M, N.ptr(freqs), pe.num_frequencies, 0, N.ptr(pn_enc), st), "nerf_encode")
+    pn_in[:, :12].copy_(pn_enc)  # (the encoder writes dense 12-wide rows)
+    W0, b0, W1, b1, W2, b2 = fld.mlp_pred_normals.param_tensors()
+    head = fld.field_head_pred_normals.net
+    block = pn_a.shape[0]
+    for a in range(0, M, block):
+        k = min(a + block, M) - a
+        layers = ((pn_in[a:a + k], W0, b0, 27, 64, 1, pn_a), (pn_a, W1, b1, 64, 64, 1, pn_b), (pn_b, W2, b2, 64, 64, 0, pn_a),
+                  (pn_a, head.weight, head.bias, 64, 3, 0, pn_pre[a:a + k]))
+        for x, W, b, K, n_out, act, y in layers:
+            N.check(lib.nsamd_linear_fwd(N.ptr(x), N.ptr(W), N.ptr(b), k, K, n_out, act, N.ptr(y), st), "linear_fwd")
+
+
 class EvalRenderer:
-    def __init__(self, model, chunk: Optional[int] = None, use_graph: bool = True) -> None:
+    def __init__(self, model, chunk: Optional[int] = None, use_graph: bool = True, normals: bool = False) -> None:
+        """normals: also render `normals` and `pred_normals` (a `predict_normals` model; `supported(model, normals=True)`): three
+        more stages behind the chunk's weights — see `_launch_normals`."""
         from .train_step import NerfactoTrainStep
 
         self.model = model
+        self.normals = bool(normals)
+        if self.normals and supported(model, normals=True) is not None:
+            raise ValueError(f"EvalRenderer(normals=True): {supported(model, normals=True)}")
         self.chunk = int(chunk or model.config.eval_num_rays_per_chunk)
         dev = next(model.parameters()).device
         N.require_cuda(next(model.parameters()))
@@ -50,6 +80,18 @@ class EvalRenderer:
             self.bg_mode, self.bg_vals = N.BG_NONE, None
         else:
             self.bg_mode, self.bg_vals = self.step.bg_mode, self.step.bg_vals
+        if self.normals:
+            # static buffers of the normals stages, allocated once: per-sample analytic normals, the predicted-normals MLP's
+            # 27-wide input rows (12 encoded columns | 15 geometry features), its head's pre-activation, two ping-pong activation
+            # blocks, and the chunk's two rendered channels
+            e = lambda *shape: torch.empty(shape, device=dev, dtype=torch.float32)  # noqa: E731
+            mm = self.step.m_main
+            pe = model.field.position_encoding
+            self.pn_freqs = (2 ** torch.linspace(pe.min_freq, pe.max_freq, pe.num_frequencies)).to(dev)
+            self.n_smp, self.pn_enc, self.pn_in, self.pn_pre = e(mm, 3), e(mm, 12), e(mm, 27), e(mm, 3)
+            blk = min(mm, _PN_BLOCK)
+            self.pn_a, self.pn_b = e(blk, 64), e(blk, 64)
+            self.normals_img, self.pred_normals_img = e(self.chunk, 3), e(self.chunk, 3)
 
     # ---- one chunk ------------------------------------------------------------------------------------------------------
     def _refresh_constants(self) -> None:
@@ -78,6 +120,24 @@ class EvalRenderer:
         N.check(lib.nsamd_composite_fwd(N.ptr(s.f_rgb), N.ptr(s.weights[L]), N.ptr(s.t_bins[L]), n, S, self.bg_mode, self.bg_vals,
                                         1, N.ptr(s.rgb), N.ptr(s.acc), N.ptr(s.depth_exp), N.ptr(s.depth_med[L]), None,
                                         N.ptr(s.minmax_ws), st), "composite_fwd")
+        if self.normals:
+            self._launch_normals()
+
+    def _launch_normals(self) -> None:
+        """The normals stages of one chunk, behind forward_main (which left the hash features in `f_enc`) and the weights:
+        1. nsamd_field_normals: per-sample analytic normals + the geometry features into columns 12..26 of `pn_in`;
+        2. the predicted-normals MLP as the module path runs it (nerfacto_field.py:287-295): nsamd_nerf_encode of the raw
+           positions into columns 0..11, three nsamd_linear_fwd layers (ReLU, ReLU, none) and the 64 -> 3 head, block by block
+           over the two ping-pong buffers;
+        3. nsamd_normals_composite: head activation, both weighted sums, renormalisation and shading per ray."""
+        s, fld = self.step, self.model.field
+        L = s.n_prop
+        M, pts = s.m_main, s._points(L)
+        enc = fld.mlp_base.encoding
+        F.field_normals_launch(pts, M, fld._transform, fld._box, enc.hash_table, enc.spec, s.f_enc,
+                               fld.mlp_base.mlp.param_tensors(), self.n_smp, None, self.pn_in, 27, 12)
+        pred_normals_mlp_launch(fld, pts, M, self.pn_freqs, self.pn_enc, self.pn_in, self.pn_a, self.pn_b, self.pn_pre)
+        F.normals_composite_launch(s.weights[L], self.n_smp, self.pn_pre, self.normals_img, self.pred_normals_img)
 
     def _addresses(self):
         """Everything the captured launches read through raw pointers that this object does not own: the model's parameters
@@ -116,6 +176,8 @@ class EvalRenderer:
                "depth": torch.empty((total, 1), device=dev), "expected_depth": torch.empty((total, 1), device=dev)}
         for i in range(s.n_prop):
             out[f"prop_depth_{i}"] = torch.empty((total, 1), device=dev)
+        if self.normals:
+            out["normals"], out["pred_normals"] = torch.empty((total, 3), device=dev), torch.empty((total, 3), device=dev)
         self._refresh_constants()
         for a in range(0, total, n):
             k = min(a + n, total) - a
@@ -128,13 +190,16 @@ class EvalRenderer:
             out["depth"][a:b, 0].copy_(s.depth_med[-1][:k])
             for i in range(s.n_prop):
                 out[f"prop_depth_{i}"][a:b, 0].copy_(s.depth_med[i][:k])
+            if self.normals:
+                out["normals"][a:b].copy_(self.normals_img[:k])
+                out["pred_normals"][a:b].copy_(self.pred_normals_img[:k])
         return out
 
     @profiler.time_function
     @torch.no_grad()
     def render(self, camera_ray_bundle) -> Dict[str, Tensor]:
-        """-> the reference's output dict for a camera (`rgb`, `accumulation`, `depth`, `expected_depth`, `prop_depth_i`),
-        each `[*image_shape, C]`."""
+        """-> the reference's output dict for a camera (`rgb`, `accumulation`, `depth`, `expected_depth`, `prop_depth_i`; a
+        normals runner: also `normals`, `pred_normals`), each `[*image_shape, C]`."""
         s, n = self.step, self.chunk
         image_shape = camera_ray_bundle.origins.shape[:-1]
         o = camera_ray_bundle.origins.reshape(-1, 3)
@@ -253,23 +318,32 @@ def in_loop_camera_args(camera):
     return None
 
 
-def supported(model) -> Optional[str]:
-    """None, or why this model's eval render has to stay on the module path."""
+def supported(model, normals: bool = False) -> Optional[str]:
+    """None, or why this model's eval render has to stay on the module path. normals=False: the plain runner (it has no normals
+    outputs, so it refuses a `predict_normals` model); normals=True: the runner with the normals stages."""
     cfg = model.config
-    if getattr(cfg, "predict_normals", False):
+    if not normals and getattr(cfg, "predict_normals", False):
         return "predict_normals"
     if not all(hasattr(model, a) for a in ("proposal_networks", "field", "proposal_sampler")):
         return "not a nerfacto model"
+    if normals:
+        fld = model.field
+        if not (getattr(cfg, "predict_normals", False) and getattr(fld, "use_pred_normals", False)):
+            return "not a predict_normals model"
+        if fld.mlp_base.encoding.spec.num_levels != 16:
+            return "normals need a 16-level main grid"
     return None
 
 
 def runner_for(model, device) -> Optional[EvalRenderer]:
     """The model's cached EvalRenderer (rebuilt when the chunk size changed) for an eval render of rays on `device`, or None:
     the module path (training mode, not a GPU, NSAMD_EVAL_RUNNER=0, or a configuration `supported` refuses)."""
-    if (model.training or torch.device(device).type != "cuda" or os.environ.get("NSAMD_EVAL_RUNNER", "1") != "1"
-            or supported(model) is not None):
+    if model.training or torch.device(device).type != "cuda" or os.environ.get("NSAMD_EVAL_RUNNER", "1") != "1":
+        return None
+    normals = bool(getattr(model.config, "predict_normals", False))  # such a model renders through the normals runner
+    if supported(model, normals=normals) is not None:
         return None
     runner = getattr(model, "_eval_runner", None)
-    if runner is None or runner.chunk != model.config.eval_num_rays_per_chunk:
-        runner = model._eval_runner = EvalRenderer(model)
+    if runner is None or runner.chunk != model.config.eval_num_rays_per_chunk or runner.normals != normals:
+        runner = model._eval_runner = EvalRenderer(model, normals=normals)
     return runner

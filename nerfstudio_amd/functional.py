@@ -1042,6 +1042,68 @@ def depth_loss(weights_list: Sequence[Tensor], t_bins_list: Sequence[Tensor], te
 
 
 # ---------------------------------------------------------------------------------------------------------------
+# normals of the nerfacto field, forward only (eval render)       (fields/base_field.py:79-99, models/nerfacto.py:325-329)
+# ---------------------------------------------------------------------------------------------------------------
+def field_normals_launch(pts: N.Points, M: int, transform: int, box: N.Aabb, table: Tensor, grid: HashGridSpec, enc: Tensor,
+                         base_params: Sequence[Tensor], normals: Optional[Tensor], gradient: Optional[Tensor],
+                         geo: Optional[Tensor], geo_stride: int = 15, geo_offset: int = 0) -> None:
+    """nsamd_field_normals on dense fp32 device tensors, on the current stream: `enc` the feature-major `[32, M]` features the
+    hash forward left, base_params = (W0, b0, W1, b1) of the base MLP; normals / gradient `[M,3]` and `geo` (rows of
+    `geo_stride` floats, the 15 geometry features from column `geo_offset`) are each optional."""
+    if tuple(enc.shape) != (32, M) or tuple(table.shape) != (grid.num_levels * grid.table_size, 2):
+        raise ValueError(f"field_normals: enc {tuple(enc.shape)} / table {tuple(table.shape)} do not fit M = {M} and the grid")
+    W0, b0, W1, b1 = base_params
+    if tuple(W0.shape) != (64, 32) or tuple(W1.shape) != (16, 64) or b0.numel() != 64 or b1.numel() != 16:
+        raise ValueError("field_normals: the base MLP must be 32 -> 64 -> 16")
+    for t_ in (normals, gradient):
+        if t_ is not None and t_.numel() != 3 * M:
+            raise ValueError("field_normals: normals / gradient must hold [M, 3]")
+    if geo is not None and (geo_offset < 0 or geo_stride < geo_offset + 15 or geo.numel() < M * geo_stride):
+        raise ValueError("field_normals: geo rows do not hold 15 columns from geo_offset for M samples")
+    N.check(N.load().nsamd_field_normals(pts, M, transform, box, N.ptr(table), grid.native(), N.ptr(enc), N.ptr(W0), N.ptr(b0),
+                                         N.ptr(W1), N.ptr(b1), N.ptr(normals), N.ptr(gradient), N.ptr(geo), int(geo_stride),
+                                         int(geo_offset), N.stream()), "field_normals")
+
+
+def field_normals(spec: PointSpec, table: Tensor, grid: HashGridSpec, transform: int, aabb, enc: Tensor,
+                  base_params: Sequence[Tensor], want_gradient: bool = False):
+    """Analytic normals of the points of `spec` from their hash features `enc` (`[32, M]`, feature-major) and the base MLP
+    (W0, b0, W1, b1) -> (normals `[M,3]` = -normalize(d pre-activation / d normalised position), the raw gradient `[M,3]` or
+    None, the geometry features `[M,15]`). No gradient flows through it: the normals are constants, as in the reference."""
+    N.require_cuda(table, enc, *base_params, *spec.tensors())
+    spec = _spec_from_flat(*(None if t is None else t.detach() for t in spec.tensors()))
+    M = spec.num_points
+    new = lambda *s: torch.empty(s, device=table.device, dtype=torch.float32)  # noqa: E731
+    normals, grad, geo = new(M, 3), (new(M, 3) if want_gradient else None), new(M, 15)
+    box = aabb if isinstance(aabb, N.Aabb) else N.make_aabb(aabb)
+    field_normals_launch(spec.native(), M, transform, box, table.detach(), grid, _f32c(enc.detach()),
+                         [_f32c(p.detach()) for p in base_params], normals, grad, geo)
+    return normals, grad, geo
+
+
+def normals_composite_launch(weights: Tensor, normals: Optional[Tensor], pred_pre: Optional[Tensor],
+                             normals_out: Optional[Tensor], pred_out: Optional[Tensor]) -> None:
+    """nsamd_normals_composite on dense fp32 device tensors (weights `[n,S]`, per-sample `[n*S,3]`, outputs `[n,3]`)."""
+    n, S = weights.shape
+    N.check(N.load().nsamd_normals_composite(N.ptr(weights), N.ptr(normals), N.ptr(pred_pre), n, S, N.ptr(normals_out),
+                                             N.ptr(pred_out), N.stream()), "normals_composite")
+
+
+def normals_composite(weights: Tensor, normals: Tensor, pred_pre: Tensor) -> Tuple[Tensor, Tensor]:
+    """Rendered and shaded normals of both channels (NormalsRenderer + NormalsShader over the analytic normals and over
+    PredNormalsFieldHead of `pred_pre`, the head's pre-activation): weights `[n,S]` or `[n,S,1]`, per-sample `[n,S,3]` ->
+    two `[n,3]` images in [0, 1]."""
+    N.require_cuda(weights, normals, pred_pre)
+    w = _f32c(weights.detach().reshape(weights.shape[0], -1))
+    n, S = w.shape
+    nr, pp = _f32c(normals.detach().reshape(n * S, 3)), _f32c(pred_pre.detach().reshape(n * S, 3))
+    out_n, out_p = torch.empty((n, 3), device=w.device, dtype=torch.float32), torch.empty((n, 3), device=w.device,
+                                                                                            dtype=torch.float32)
+    normals_composite_launch(w, nr, pp, out_n, out_p)
+    return out_n, out_p
+
+
+# ---------------------------------------------------------------------------------------------------------------
 # a3  camera-pose corrections of the rays
 # ---------------------------------------------------------------------------------------------------------------
 CAMERA_MODES = {"SO3xR3": 1, "SE3": 2}
