@@ -16,6 +16,8 @@
 // weight element).
 #include "common.h"
 #include "density_point.h"
+#include "launch.h"
+#include "mfma_chain.h"
 #include "proposal_chain.h"
 
 namespace nsamd {
@@ -154,7 +156,6 @@ __device__ __forceinline__ void density_mlp_bwd_body(
   }
   const bool may_skip = __syncthreads_and(w_finite) != 0;
 
-  typedef float v4f __attribute__((ext_vector_type(4)));
   constexpr int NT = H / 16;  // row tiles of dW0
   static_assert(H % 16 == 0 && IN <= 16, "dW0 tiling");
   v4f accM[NT];
@@ -256,7 +257,7 @@ __device__ __forceinline__ void density_mlp_bwd_body(
       const float b = jj < IN ? x_T[jj * LD + pt] : 0.0f;
 #pragma unroll
       for (int n = 0; n < NT; ++n)
-        accM[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(gh_T[(16 * n + jj) * LD + pt], b, accM[n], 0, 0, 0);
+        accM[n] = mfma16(gh_T[(16 * n + jj) * LD + pt], b, accM[n]);
     }
     if (threadIdx.x < 2 * H + 1) {
       const float* a = (threadIdx.x < H)       ? gh_T + threadIdx.x * LD
@@ -434,10 +435,10 @@ static int launch_bwd(const DensityBwdCall* c, int n, hipStream_t stream) {
     const int rc = launch_bwd<IN, H>(c, 1, stream);
     return rc ? rc : launch_bwd<IN, H>(c + 1, 1, stream);
   }
-  if (lds > 64 * 1024) {  // per-device opt-in; cheap enough to repeat
-    const void* kernel = pair ? reinterpret_cast<const void*>(&density_mlp_bwd_pair_kernel<IN, H>)
-                              : reinterpret_cast<const void*>(&density_mlp_bwd_kernel<IN, H>);
-    if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return NSAMD_ERR_LAUNCH;
+  if (lds > 64 * 1024) {
+    static LdsOptIn opted_in;  // (one per (IN, H): both kernels of the instantiation)
+    const int rc = lds_opt_in(opted_in, density_mlp_bwd_pair_kernel<IN, H>, lds, density_mlp_bwd_kernel<IN, H>, lds);
+    if (rc) return rc;
   }
   const DensityBwdArgs& a = k[0];
   if (pair) {
@@ -505,16 +506,15 @@ extern "C" int nsamd_density_field_fwd(nsamd_points pts, int64_t M, int transfor
   if (M == 0) return NSAMD_OK;
   NSAMD_REQUIRE(table && density && mlp.W0 && mlp.b0 && mlp.W1 && mlp.b1);
   NSAMD_REQUIRE(transform >= 0 && transform <= 2);
-  if (pts.positions == nullptr) {
-    NSAMD_REQUIRE(pts.origins && pts.directions && pts.t_bins && pts.samples_per_ray > 0 && M % pts.samples_per_ray == 0);
-  }
-  if (grid.log2_table_size < 1 || grid.log2_table_size > 28) return NSAMD_ERR_UNSUPPORTED;
+  if (const int st = check_points(pts, M)) return st;
+  // (not check_grid: a level count the kernel has no instantiation for is answered below, behind the width test)
+  if (!table_size_ok(grid)) return NSAMD_ERR_UNSUPPORTED;
   if (mlp.in_dim != 2 * grid.num_levels) return NSAMD_ERR_INVALID_ARG;
-  const int64_t nb = (M + kMlpBlock - 1) / kMlpBlock;
-  if (nb > 0x7fffffffLL) return NSAMD_ERR_UNSUPPORTED;
+  unsigned nb;
+  if (grid_blocks((M + kMlpBlock - 1) / kMlpBlock, &nb)) return NSAMD_ERR_UNSUPPORTED;
   const float2* t2 = reinterpret_cast<const float2*>(table);
 #define NSAMD_DENSITY_FWD(L_, H_)                                                                                       \
-  density_field_fwd_kernel<L_, H_><<<(unsigned)nb, kMlpBlock, 0, (hipStream_t)stream>>>(pts, M, transform, aabb, t2, grid, mlp, \
+  density_field_fwd_kernel<L_, H_><<<nb, kMlpBlock, 0, (hipStream_t)stream>>>(pts, M, transform, aabb, t2, grid, mlp, \
                                                                                       enc, selector, density, pre)
   if (grid.num_levels == 5 && mlp.hidden == 16) {
     NSAMD_DENSITY_FWD(5, 16);

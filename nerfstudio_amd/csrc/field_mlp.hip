@@ -6,13 +6,8 @@
 // is an exact k-ordered fmaf chain at the f32 vector rate — what it buys over VALU is operand bandwidth: 2048 MACs
 // per instruction from two VGPRs, so the weights can stream from LDS at 16 B per lane per 4 MFMAs.
 //
-// Chain layout. One wavefront owns a tile of 16 sample points. A vector of F features of those points lives in
-// registers as X[t][r] (t < F/16, r < 4): lane (j = lane & 15, g = lane >> 4) holds feature 16t + 4g + r of point
-// j. With Y^T = W X^T, MFMA step (t, r) takes  A = W[16n + j][16t + 4g + r]  and  B = X[t][r]; the C/D fragment of
-// output tile n is then neuron 16n + 4g + r' of point j — the SAME layout, so a layer's accumulators are the
-// next layer's B operands with no shuffle or LDS round trip. The K-order permutation this implies is folded into
-// the weight fragments when a workgroup stages them in LDS (once; workgroups are persistent over tiles):
-//   Wf[n][t][lane][r] = W[16n + j][16t + 4g + r]   -> one conflict-free ds_read_b128 per lane feeds 4 MFMAs.
+// Chain layout: mfma_chain.h (one wavefront owns 16 points; lane (j, g) holds feature 16t + 4g + r; a layer's accumulators are
+// the next layer's B operands; weight fragments Wf[n][t][lane][r] staged in LDS).
 // That is the forward kernel (4 waves per workgroup, fragments staged once, workgroups persistent over tiles). The
 // backward kernel (further down) recomputes the forward per tile, runs the data-gradient GEMMs in the same chain
 // layout with W^T operands, and needs points on the k axis for the weight-gradient GEMMs: each wave transposes its
@@ -26,6 +21,8 @@
 
 #include "common.h"
 #include "field_reduce.h"
+#include "launch.h"
+#include "mfma_chain.h"
 #include "scatter.h"
 #include "wave.h"
 
@@ -33,17 +30,11 @@ NSAMD_PROBE_DEFINE(field)
 
 namespace nsamd {
 
-typedef float v4f __attribute__((ext_vector_type(4)));
-
-
 constexpr int kWaves = 4;
 constexpr int kFieldThreads = 64 * kWaves;
 constexpr int kScratchLd = 20;                      // floats per scratch row: 16 points + 4 (row stride = 4 mod 8 words:
                                                     // conflict-free b32 column stores and b128 row reads)
 constexpr int kScratchTile = 64 * kScratchLd;       // one 64-feature x 16-point tile
-__device__ __forceinline__ v4f mfma16(float a, float b, v4f c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
 
 // Wf[n][t][lane][r] = Wint[16n + j][16t + 4g + r]. Staging is split into a load half and a store half so that a
 // workgroup has the loads of ALL five layers in flight at once (48 per thread): as a load-wait-store loop the staging cost
@@ -73,54 +64,6 @@ __device__ __forceinline__ void stage_frag_store(float* dst, const float* v) {
 template <int THREADS>
 __device__ __forceinline__ void stage_bias(float* dst, const float* __restrict__ b, int n_real, int n_pad) {
   for (int e = threadIdx.x; e < n_pad; e += THREADS) dst[e] = (e < n_real) ? b[e] : 0.0f;
-}
-
-// out[n] (+)= sum over input tiles; frag = Wf-style block for this layer: [NT][KT][64][4]
-template <int NT, int KT>
-__device__ __forceinline__ void chain_gemm(const float* frag, const v4f* in, v4f* out, int lane) {
-#pragma unroll
-  for (int t = 0; t < KT; ++t) {
-    v4f a[NT];
-#pragma unroll
-    for (int n = 0; n < NT; ++n) a[n] = *reinterpret_cast<const v4f*>(frag + ((n * KT + t) * 64 + lane) * 4);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-#pragma unroll
-      for (int n = 0; n < NT; ++n) out[n] = mfma16(a[n][r], in[t][r], out[n]);
-    }
-  }
-}
-
-// one input tile `t` of a [NT][KT] fragment block: out[n] += W[16n + j][16t ..] . in
-template <int NT, int KT>
-__device__ __forceinline__ void chain_gemm_tile(const float* frag, int t, const v4f& in, v4f* out, int lane) {
-  v4f a[NT];
-#pragma unroll
-  for (int n = 0; n < NT; ++n) a[n] = *reinterpret_cast<const v4f*>(frag + ((n * KT + t) * 64 + lane) * 4);
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-#pragma unroll
-    for (int n = 0; n < NT; ++n) out[n] = mfma16(a[n][r], in[r], out[n]);
-  }
-}
-
-template <int NT>
-__device__ __forceinline__ void load_bias(const float* bias, v4f* out, int g) {
-#pragma unroll
-  for (int n = 0; n < NT; ++n) out[n] = *reinterpret_cast<const v4f*>(bias + 16 * n + 4 * g);
-}
-
-template <int NT>
-__device__ __forceinline__ void relu_tiles(v4f* x) {
-#pragma unroll
-  for (int n = 0; n < NT; ++n)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) x[n][r] = fmaxf(x[n][r], 0.0f);
-}
-
-// ray (direction / camera row) of point p: 32-bit division whenever both fit (a 64-bit divide is ~100 instructions)
-__device__ __forceinline__ int64_t ray_of(int64_t p, int64_t dir_group) {
-  return (((uint64_t)p | (uint64_t)dir_group) >> 32) ? p / dir_group : (int64_t)((uint32_t)p / (uint32_t)dir_group);
 }
 
 struct TileInputs {
@@ -248,7 +191,7 @@ __device__ __forceinline__ TileInputs tile_inputs(int64_t tile, int lane, int64_
   ti.live = p < M;
   ti.p = ti.live ? p : M - 1;
   ti.sel = selector ? selector[ti.p] : 1.0f;
-  ti.ray = ray_of(ti.p, dir_group);
+  ti.ray = point_ray(ti.p, dir_group);
   ti.cam = cams ? cams[ti.ray] : 0;
   return ti;
 }
@@ -451,12 +394,6 @@ __device__ __forceinline__ void store_rows_pk(float* S, const v4f* x, int j, int
       U[(16 * t + 4 * g + r) * kScratchLd + j] = o0;
       U[(16 * t + 4 * g + r + 1) * kScratchLd + j] = o1;
     }
-}
-
-template <int N>
-__device__ __forceinline__ void zero_tiles(v4f* x) {
-#pragma unroll
-  for (int n = 0; n < N; ++n) x[n] = v4f{0.f, 0.f, 0.f, 0.f};
 }
 
 template <int NT>
@@ -906,7 +843,7 @@ __device__ __forceinline__ void route_issue_position(const RouteLds* L, int64_t 
   const int64_t pt = tile * 16 + (lane & 15);
   const bool rays = route_ray_layout(L, dir_group) && tile < tiles && pt < M;
   const int64_t p = rays ? pt : 0;
-  const int64_t S = dir_group, ray = ray_of(p, S), s = p - ray * S;
+  const int64_t S = dir_group, ray = point_ray(p, S), s = p - ray * S;
   // (pointers that live in LDS: global_ptr, or these are flat loads — common.h)
   const NSAMD_GLOBAL_AS float* dummy = global_ptr(reinterpret_cast<const float*>(L->hdr));
   const NSAMD_GLOBAL_AS float* tb = rays ? global_ptr(L->P.t_bins) + ray * (S + 1) + s : dummy;
@@ -966,7 +903,7 @@ __device__ __forceinline__ void fetch_tile(TileFetch& f, int64_t tile, int64_t t
   const int64_t p = t * 16 + (lane & 15);
   f.ti.live = p < M && tile < tiles;  // (tile >= tiles: idle wave of the last round — computes, contributes zeros)
   f.ti.p = p < M ? p : M - 1;
-  f.ti.ray = ray_of(f.ti.p, dir_group);
+  f.ti.ray = point_ray(f.ti.p, dir_group);
   if (RAYC) {
     f.ti.cam = 0;
   } else {
@@ -1438,6 +1375,14 @@ __global__ void probe_mfma16_kernel(const float* __restrict__ A, const float* __
 
 using namespace nsamd;
 
+// appearance columns of head layer 0: 32 with a camera row per ray or one constant row, 0 for a field built without an
+// appearance embedding (head input is SH16 | geo15)
+static int field_app_dim(const nsamd_field_mlp& mlp, const int64_t* cams, const float* app_const, int* app_dim) {
+  if (cams != nullptr) NSAMD_REQUIRE(mlp.appearance != nullptr && mlp.num_images > 0);
+  *app_dim = (cams != nullptr || app_const != nullptr) ? 32 : 0;
+  return NSAMD_OK;
+}
+
 static int field_common_checks(const float* enc, const float* directions, int64_t dir_group, int64_t M,
                                const nsamd_field_mlp& mlp, const int64_t* cams, const float* app_const, int* app_dim) {
   NSAMD_REQUIRE(M >= 0 && dir_group >= 1);
@@ -1445,33 +1390,16 @@ static int field_common_checks(const float* enc, const float* directions, int64_
   NSAMD_REQUIRE(enc && directions);
   NSAMD_REQUIRE(mlp.base_W0 && mlp.base_b0 && mlp.base_W1 && mlp.base_b1 && mlp.head_W0 && mlp.head_b0 &&
                 mlp.head_W1 && mlp.head_b1 && mlp.head_W2 && mlp.head_b2);
-  if (cams != nullptr) {
-    NSAMD_REQUIRE(mlp.appearance != nullptr && mlp.num_images > 0);
-    *app_dim = 32;
-  } else if (app_const != nullptr) {
-    *app_dim = 32;
-  } else {
-    *app_dim = 0;  // field built without an appearance embedding: head input is SH16 | geo15
-  }
-  return NSAMD_OK;
+  return field_app_dim(mlp, cams, app_const, app_dim);
 }
 
-static int num_cus() {
-  static int cached = 0;
-  if (cached == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 256;
-    cached = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  }
-  return cached;
+// persistent workgroups over `tiles` 16-point tiles, `waves` of them per workgroup pass: one per CU of the current device at most
+static unsigned field_blocks(int64_t tiles, int waves) {
+  return (unsigned)min((int64_t)device_cus(), (tiles + waves - 1) / waves);
 }
 
-// workgroups of a backward launch over M points: one per CU, at most one per group of kCoopWaves 16-point tiles
-static unsigned field_bwd_blocks(int64_t M) {
-  const int64_t tiles = (M + 15) / 16;
-  return (unsigned)min((int64_t)num_cus(), (tiles + kCoopWaves - 1) / kCoopWaves);
-}
+// workgroups of a backward launch over M points
+static unsigned field_bwd_blocks(int64_t M) { return field_blocks((M + 15) / 16, kCoopWaves); }
 
 // the RAYC kernels apply: terms given and every 16-point tile inside one ray
 static bool field_ray_terms_apply(const nsamd_field_mlp& mlp, int64_t dir_group, int64_t M) {
@@ -1485,33 +1413,27 @@ extern "C" int nsamd_field_ray_terms(const float* directions, const int64_t* cam
   if (num_rays == 0) return NSAMD_OK;
   NSAMD_REQUIRE(directions && ray_terms && mlp.head_W0 && mlp.head_b0);
   int app_dim = 0;
-  if (camera_indices != nullptr) {
-    NSAMD_REQUIRE(mlp.appearance != nullptr && mlp.num_images > 0);
-    app_dim = 32;
-  } else if (appearance_const != nullptr) {
-    app_dim = 32;
-  }
-  const int64_t tiles = (num_rays + 15) / 16;
-  const unsigned blocks = (unsigned)min((int64_t)num_cus(), (tiles + kWaves - 1) / kWaves);
+  if (const int st = field_app_dim(mlp, camera_indices, appearance_const, &app_dim)) return st;
+  const unsigned blocks = field_blocks((num_rays + 15) / 16, kWaves);
   field_ray_terms_kernel<<<blocks, kFieldThreads, 0, (hipStream_t)stream>>>(directions, camera_indices, appearance_const, num_rays,
                                                                            mlp, app_dim, ray_terms, ray_inputs);
   NSAMD_CHECK_LAUNCH();
   return NSAMD_OK;
 }
 
-static int field_mlp_fwd_impl(const float* enc, const float* selector, const float* directions,
-                              const int64_t* camera_indices, const float* appearance_const, int64_t dir_group, int64_t M,
-                              nsamd_field_mlp mlp, float* density, float* rgb, nsamd_stream_t stream) {
+extern "C" int nsamd_field_mlp_fwd(const float* enc, const float* selector, const float* directions,
+                                   const int64_t* camera_indices, const float* appearance_const, int64_t dir_group,
+                                   int64_t M, nsamd_field_mlp mlp, float* density, float* rgb,
+                                   nsamd_stream_t stream) {
   if (M == 0) return NSAMD_OK;
   int app_dim = 0;
   int st = field_common_checks(enc, directions, dir_group, M, mlp, camera_indices, appearance_const, &app_dim);
   if (st) return st;
   NSAMD_REQUIRE(density != nullptr);  // rgb NULL: density only
   const size_t lds = sizeof(float) * (kFragTotal + 256);
-  const int64_t tiles = (M + 15) / 16;
   // One 16-wave workgroup per CU (4 waves per SIMD, the weights staged once per CU): 57 us on the bench shape against 59.5
   // (8 waves x 2 workgroups) and 65 (4 waves x 3) on the same box.
-  const unsigned blocks = (unsigned)min((int64_t)num_cus(), (tiles + 15) / 16);
+  const unsigned blocks = field_blocks((M + 15) / 16, 16);
   if (field_ray_terms_apply(mlp, dir_group, M) && rgb != nullptr)
     field_mlp_fwd_kernel<16, true><<<blocks, 1024, lds, (hipStream_t)stream>>>(
         enc, selector, directions, camera_indices, appearance_const, dir_group, M, mlp, app_dim, density, rgb);
@@ -1522,44 +1444,43 @@ static int field_mlp_fwd_impl(const float* enc, const float* selector, const flo
   return NSAMD_OK;
 }
 
-extern "C" int nsamd_field_mlp_fwd(const float* enc, const float* selector, const float* directions,
-                                   const int64_t* camera_indices, const float* appearance_const, int64_t dir_group,
-                                   int64_t M, nsamd_field_mlp mlp, float* density, float* rgb,
-                                   nsamd_stream_t stream) {
-  return field_mlp_fwd_impl(enc, selector, directions, camera_indices, appearance_const, dir_group, M, mlp, density,
-                            rgb, stream);
-}
+// One backward call. route == nullptr: the plain backward (denc is written; dtable and the scatter workspace are unused).
+// Otherwise producer mode: the kernel emits the table scatter's pass-1 records into scatter_ws, and the apply pass writes dtable.
+struct FieldBwdCall {
+  const float *enc, *selector, *directions;
+  const int64_t* cams;
+  const float* app_const;
+  int64_t dir_group, M;
+  nsamd_field_mlp mlp;
+  const float *ddensity, *drgb;
+  float* denc;
+  nsamd_field_mlp_grads grads;
+  float* workspace;
+  int64_t workspace_floats;
+  int phases;  // 1 = the gradient kernel (denc + per-workgroup partials), 2 = the fixed-order sum of the partials, 4 = the
+               // scatter's apply pass (producer mode); any sum of them
+  const RouteArgs* route;
+  float *dtable, *scatter_ws;
+  int64_t scatter_ws_floats;
+};
 
-static int field_mlp_bwd_impl(const float* enc, const float* selector, const float* directions,
-                              const int64_t* camera_indices, const float* appearance_const, int64_t dir_group, int64_t M,
-                              nsamd_field_mlp mlp, const float* ddensity, const float* drgb, float* denc,
-                              nsamd_field_mlp_grads grads, float* workspace, int64_t workspace_floats,
-                              nsamd_stream_t stream, int phases = 3, const RouteArgs* route_in = nullptr,
-                              float* dtable = nullptr, float* scatter_ws = nullptr, int64_t scatter_ws_floats = 0) {
-  // phases: 1 = the gradient kernel (denc + per-workgroup partials), 2 = the fixed-order sum of the partials, 3 = both
+static int field_mlp_bwd_impl(const FieldBwdCall& c, hipStream_t stream) {
+  const int64_t M = c.M, dir_group = c.dir_group;
   if (M == 0) return NSAMD_OK;
   int app_dim = 0;
-  int st = field_common_checks(enc, directions, dir_group, M, mlp, camera_indices, appearance_const, &app_dim);
+  int st = field_common_checks(c.enc, c.directions, dir_group, M, c.mlp, c.cams, c.app_const, &app_dim);
   if (st) return st;
-  NSAMD_REQUIRE(ddensity && drgb && (denc || route_in));
+  NSAMD_REQUIRE(c.ddensity && c.drgb && (c.denc || c.route));
   const int64_t tiles = (M + 15) / 16;
   const size_t lds = sizeof(float) * (kRowTotal + 256 + kCoopWaves * 2 * kScratchTile);
-  static bool attr_set[64] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return NSAMD_ERR_NO_DEVICE;
-  if (dev < 0 || dev >= 64 || !attr_set[dev]) {  // the dynamic-LDS opt-in is per device
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&field_mlp_bwd_kernel<false, false>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&field_mlp_bwd_kernel<true, false>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds + sizeof(uint32_t) * kRouteLdsWords)) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&field_mlp_bwd_kernel<false, true>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&field_mlp_bwd_kernel<true, true>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds + sizeof(uint32_t) * kRouteLdsWords)) != hipSuccess)
-      return NSAMD_ERR_LAUNCH;
-    if (dev >= 0 && dev < 64) attr_set[dev] = true;
-  }
+  const size_t lds_route = lds + sizeof(uint32_t) * kRouteLdsWords;
+  static LdsOptIn opted_in;
+  st = lds_opt_in(opted_in, field_mlp_bwd_kernel<false, false>, lds, field_mlp_bwd_kernel<true, false>, lds_route,
+                  field_mlp_bwd_kernel<false, true>, lds, field_mlp_bwd_kernel<true, true>, lds_route);
+  if (st) return st;
   const unsigned blocks = field_bwd_blocks(M);
+  float* const workspace = c.workspace;
+  const int64_t workspace_floats = c.workspace_floats;
   float* partials = (workspace != nullptr && workspace_floats >= (int64_t)blocks * kPartialStride) ? workspace : nullptr;
   // per-tile rows of the appearance-embedding gradient (fixed-order reduction per camera): needs every 16-point tile
   // inside one ray and room behind the weight-gradient partials; otherwise float atomics (sums in no fixed order)
@@ -1567,76 +1488,61 @@ static int field_mlp_bwd_impl(const float* enc, const float* selector, const flo
   int app_rows_per_point = 0;
   // ray terms (RAYC kernels): need the partial rows (their per-ray columns of head layer 0 are written, never added) and, for
   // the appearance rows, the per-tile scratch below
-  if (partials != nullptr && camera_indices != nullptr && grads.appearance != nullptr && dir_group % 16 == 0 &&
-      M % dir_group == 0 && mlp.num_images <= 8192 &&
+  if (partials != nullptr && c.cams != nullptr && c.grads.appearance != nullptr && dir_group % 16 == 0 &&
+      M % dir_group == 0 && c.mlp.num_images <= 8192 &&
       workspace_floats >= (int64_t)blocks * kPartialStride + tiles * 32) {
     app_partials = workspace + (int64_t)blocks * kPartialStride;
-  } else if (partials != nullptr && camera_indices != nullptr && grads.appearance != nullptr && dir_group == 1 &&
-             mlp.num_images <= 8192 && workspace_floats >= (int64_t)blocks * kPartialStride + M * 32) {
+  } else if (partials != nullptr && c.cams != nullptr && c.grads.appearance != nullptr && dir_group == 1 &&
+             c.mlp.num_images <= 8192 && workspace_floats >= (int64_t)blocks * kPartialStride + M * 32) {
     app_partials = workspace + (int64_t)blocks * kPartialStride;  // one row per POINT (a camera index per sample)
     app_rows_per_point = 1;
   }
-  const bool rayc = partials != nullptr && field_ray_terms_apply(mlp, dir_group, M) && mlp.ray_inputs != nullptr &&
-                    (app_partials != nullptr || camera_indices == nullptr || grads.appearance == nullptr);
-  if (phases != 3) NSAMD_REQUIRE(partials != nullptr);  // without scratch the kernel flushes with atomics: nothing to split
+  const bool rayc = partials != nullptr && field_ray_terms_apply(c.mlp, dir_group, M) && c.mlp.ray_inputs != nullptr &&
+                    (app_partials != nullptr || c.cams == nullptr || c.grads.appearance == nullptr);
+  if (c.phases != 3) NSAMD_REQUIRE(partials != nullptr);  // without scratch the kernel flushes with atomics: nothing to split
   ScatterPlan plan{};
-  if (route_in != nullptr) {
+  RouteArgs R{};
+  if (c.route != nullptr) {
     // producer mode: the kernel emits the scatter's pass-1 records (one static segment per workgroup and tile)
-    NSAMD_REQUIRE(dtable != nullptr && scatter_ws != nullptr && partials != nullptr);
-    plan = scatter_plan_producers(route_in->grid, M, (int)blocks, kProducerSegCap);
+    NSAMD_REQUIRE(c.dtable != nullptr && c.scatter_ws != nullptr && partials != nullptr);
+    plan = scatter_plan_producers(c.route->grid, M, (int)blocks, kProducerSegCap);
     if (!plan.ok) return NSAMD_ERR_UNSUPPORTED;
-    NSAMD_REQUIRE(scatter_ws_floats >= plan.total_words);
-    RouteArgs R = *route_in;
+    NSAMD_REQUIRE(c.scatter_ws_floats >= plan.total_words);
+    R = *c.route;
     R.G = plan.geom;
-    R.buf = scatter_bufs(scatter_ws, plan);
+    R.buf = scatter_bufs(c.scatter_ws, plan);
     R.buf.log2_table_size = R.grid.log2_table_size;
-    if (phases & 1) {
-      if (rayc)
-        field_mlp_bwd_kernel<true, true><<<blocks, kCoopThreads, lds + sizeof(uint32_t) * kRouteLdsWords, (hipStream_t)stream>>>(
-            enc, selector, directions, camera_indices, appearance_const, dir_group, M, mlp, app_dim, ddensity, drgb, denc,
-            grads, partials, app_partials, app_rows_per_point, R);
-      else
-        field_mlp_bwd_kernel<true, false><<<blocks, kCoopThreads, lds + sizeof(uint32_t) * kRouteLdsWords, (hipStream_t)stream>>>(
-            enc, selector, directions, camera_indices, appearance_const, dir_group, M, mlp, app_dim, ddensity, drgb, denc,
-            grads, partials, app_partials, app_rows_per_point, R);
-      NSAMD_CHECK_LAUNCH();
-    }
-  } else if (phases & 1) {
-    if (rayc)
-      field_mlp_bwd_kernel<false, true><<<blocks, kCoopThreads, lds, (hipStream_t)stream>>>(
-          enc, selector, directions, camera_indices, appearance_const, dir_group, M, mlp, app_dim, ddensity, drgb, denc,
-          grads, partials, app_partials, app_rows_per_point, RouteArgs{});
+  }
+  if (c.phases & 1) {
+    auto launch = [&](auto kernel, size_t bytes) {
+      kernel<<<blocks, kCoopThreads, bytes, stream>>>(c.enc, c.selector, c.directions, c.cams, c.app_const, dir_group, M, c.mlp,
+                                                      app_dim, c.ddensity, c.drgb, c.denc, c.grads, partials, app_partials,
+                                                      app_rows_per_point, R);
+    };
+    if (c.route != nullptr)
+      rayc ? launch(&field_mlp_bwd_kernel<true, true>, lds_route) : launch(&field_mlp_bwd_kernel<true, false>, lds_route);
     else
-      field_mlp_bwd_kernel<false, false><<<blocks, kCoopThreads, lds, (hipStream_t)stream>>>(
-          enc, selector, directions, camera_indices, appearance_const, dir_group, M, mlp, app_dim, ddensity, drgb, denc,
-          grads, partials, app_partials, app_rows_per_point, RouteArgs{});
+      rayc ? launch(&field_mlp_bwd_kernel<false, true>, lds) : launch(&field_mlp_bwd_kernel<false, false>, lds);
     NSAMD_CHECK_LAUNCH();
   }
   // weight-gradient partials -> gradients, and (extra blocks, one per camera) the appearance rows -> embedding gradient
-  const unsigned app_blocks = app_partials != nullptr ? (unsigned)mlp.num_images : 0u;
-  const bool reduce = partials != nullptr && (phases & 2);
-  const bool apply = route_in != nullptr && (phases & 4);
+  const unsigned app_blocks = app_partials != nullptr ? (unsigned)c.mlp.num_images : 0u;
+  const ReduceRider rd{partials, (int)blocks, c.grads, app_dim, app_partials, c.cams,
+                       /*num_rays=*/app_rows_per_point ? M : M / dir_group,
+                       /*tiles_per_ray=*/app_rows_per_point ? 1 : (int)(dir_group / 16), (int)(kDwBlocks + app_blocks)};
+  const bool reduce = partials != nullptr && (c.phases & 2);
+  const bool apply = c.route != nullptr && (c.phases & 4);
   // Both asked for in one call: the reduce RIDES the apply pass as extra workgroups (field_reduce.h; the two are independent)
   // — one launch and one dependent-launch gap fewer on the critical path, same sums in the same order.
   const bool ride = reduce && apply && scatter_apply_takes_rider(plan);
   if (reduce && !ride) {
     const size_t red_lds = sizeof(float) * kReduceGroups * 64;
-    field_dw_reduce_kernel<<<kDwBlocks + app_blocks, kReduceThreads, red_lds, (hipStream_t)stream>>>(
-        partials, (int)blocks, grads, app_dim, app_partials, camera_indices, app_rows_per_point ? M : M / dir_group,
-        app_rows_per_point ? 1 : (int)(dir_group / 16));
+    field_dw_reduce_kernel<<<(unsigned)rd.blocks, kReduceThreads, red_lds, stream>>>(
+        rd.partials, rd.num_partials, rd.grads, rd.app_dim, rd.app_rows, rd.cams, rd.num_rays, rd.tiles_per_ray);
     NSAMD_CHECK_LAUNCH();
   }
-  if (apply) {  // pass 2 over the records the kernel left in the queues: the table's gradient is WRITTEN
-    ReduceRider rd{};
-    if (ride) {
-      rd.partials = partials, rd.num_partials = (int)blocks, rd.grads = grads, rd.app_dim = app_dim, rd.app_rows = app_partials;
-      rd.cams = camera_indices, rd.num_rays = app_rows_per_point ? M : M / dir_group;
-      rd.tiles_per_ray = app_rows_per_point ? 1 : (int)(dir_group / 16);
-      rd.blocks = (int)(kDwBlocks + app_blocks);
-    }
-    return scatter_apply_launch(route_in->grid, plan, scatter_ws, dtable, /*overwrite=*/true, (hipStream_t)stream,
-                                ride ? &rd : nullptr);
-  }
+  if (apply)  // pass 2 over the records the kernel left in the queues: the table's gradient is WRITTEN
+    return scatter_apply_launch(c.route->grid, plan, c.scatter_ws, c.dtable, /*overwrite=*/true, stream, ride ? &rd : nullptr);
   return NSAMD_OK;
 }
 
@@ -1659,19 +1565,17 @@ extern "C" int nsamd_field_mlp_bwd_scatter_phase(nsamd_points pts, int transform
   NSAMD_REQUIRE(phase == 1 || phase == 2 || phase == 4 || phase == 6 || phase == 7);
   if (M == 0) return NSAMD_OK;
   if (grid.num_levels != 16) return NSAMD_ERR_UNSUPPORTED;  // 32 features = the K of base layer 0
-  NSAMD_REQUIRE(M > 0 && transform >= 0 && transform <= 2 && grid.log2_table_size >= 1 && grid.log2_table_size <= 28);
-  if (pts.positions == nullptr) {
-    NSAMD_REQUIRE(pts.origins && pts.directions && pts.t_bins && pts.samples_per_ray > 0 && M % pts.samples_per_ray == 0);
-  }
+  // (a table size out of range is an invalid argument HERE, not unsupported as in check_grid: this entry point's code for it)
+  NSAMD_REQUIRE(check_points(pts, M) == NSAMD_OK && transform >= 0 && transform <= 2 && table_size_ok(grid));
   NSAMD_REQUIRE(dtable != nullptr && scatter_workspace != nullptr && workspace != nullptr);
   RouteArgs R{};
   R.P = pts;
   R.transform = transform;
   R.box = aabb;
   R.grid = grid;
-  return field_mlp_bwd_impl(enc, selector, directions, camera_indices, appearance_const, dir_group, M, mlp, ddensity, drgb,
-                            denc, grads, workspace, workspace_floats, stream, phase, &R, dtable, scatter_workspace,
-                            scatter_workspace_floats);
+  const FieldBwdCall c{enc, selector, directions, camera_indices, appearance_const, dir_group, M, mlp, ddensity, drgb, denc,
+                       grads, workspace, workspace_floats, phase, &R, dtable, scatter_workspace, scatter_workspace_floats};
+  return field_mlp_bwd_impl(c, (hipStream_t)stream);
 }
 
 extern "C" int nsamd_field_mlp_bwd_scatter(nsamd_points pts, int transform, nsamd_aabb aabb, nsamd_grid grid,
@@ -1691,8 +1595,9 @@ extern "C" int nsamd_field_mlp_bwd(const float* enc, const float* selector, cons
                                    int64_t M, nsamd_field_mlp mlp, const float* ddensity, const float* drgb,
                                    float* denc, nsamd_field_mlp_grads grads, float* workspace,
                                    int64_t workspace_floats, nsamd_stream_t stream) {
-  return field_mlp_bwd_impl(enc, selector, directions, camera_indices, appearance_const, dir_group, M, mlp, ddensity,
-                            drgb, denc, grads, workspace, workspace_floats, stream);
+  const FieldBwdCall c{enc, selector, directions, camera_indices, appearance_const, dir_group, M, mlp, ddensity, drgb, denc,
+                       grads, workspace, workspace_floats, /*phases=*/3, nullptr, nullptr, nullptr, 0};
+  return field_mlp_bwd_impl(c, (hipStream_t)stream);
 }
 
 extern "C" int nsamd_probe_mfma_bf16(const float* A, const float* B, float* out, nsamd_stream_t stream) {

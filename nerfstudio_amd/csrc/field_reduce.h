@@ -6,10 +6,9 @@
 #pragma once
 
 #include "common.h"
+#include "mfma_chain.h"
 
 namespace nsamd {
-
-typedef float v4f __attribute__((ext_vector_type(4)));
 
 // fragment sizes in floats: (N_out padded to 16) x (K padded to 16)
 constexpr int kFragBase0 = 64 * 32, kFragBase1 = 16 * 64, kFragHead0 = 64 * 64, kFragHead1 = 64 * 64,

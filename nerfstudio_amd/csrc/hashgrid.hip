@@ -30,6 +30,7 @@
 // the main table); tiny problems keep the direct-atomic kernel. DESIGN.md 4.1 has the measurements behind each choice.
 
 #include "common.h"
+#include "launch.h"
 #include "scatter.h"
 #include "wave.h"
 
@@ -442,22 +443,6 @@ __global__ __launch_bounds__(256) void nerf_encode_kernel(nsamd_points P, int64_
   if (include_input && f == 0) o[2 * per + d] = xd;
 }
 
-static int check_points(const nsamd_points& P, int64_t M) {
-  if (M < 0) return NSAMD_ERR_INVALID_ARG;
-  if (P.positions == nullptr) {
-    if (P.origins == nullptr || P.directions == nullptr || P.t_bins == nullptr || P.samples_per_ray <= 0)
-      return NSAMD_ERR_INVALID_ARG;
-    if (M % P.samples_per_ray != 0) return NSAMD_ERR_INVALID_ARG;
-  }
-  return NSAMD_OK;
-}
-
-static int check_grid(const nsamd_grid& g) {
-  if (g.num_levels <= 0 || g.num_levels > NSAMD_MAX_LEVELS) return NSAMD_ERR_UNSUPPORTED;
-  if (g.log2_table_size < 1 || g.log2_table_size > 28) return NSAMD_ERR_UNSUPPORTED;
-  return NSAMD_OK;
-}
-
 }  // namespace nsamd
 
 using namespace nsamd;
@@ -466,10 +451,8 @@ extern "C" int nsamd_hashgrid_encode_fwd(nsamd_points pts, int64_t M, int transf
                                          const float* table, nsamd_grid grid, float* enc, int64_t stride_p,
                                          int64_t stride_k, float* selector, nsamd_stream_t stream) {
   if (M == 0) return NSAMD_OK;  // empty input: nothing to launch (empty tensors carry NULL data pointers)
-  int st = check_points(pts, M);
-  if (st) return st;
-  st = check_grid(grid);
-  if (st) return st;
+  if (const int st = check_points(pts, M)) return st;
+  if (const int st = check_grid(grid)) return st;
   NSAMD_REQUIRE(table != nullptr && enc != nullptr);
   NSAMD_REQUIRE(transform >= 0 && transform <= 2);
   if (M == 0) return NSAMD_OK;
@@ -543,16 +526,9 @@ static int hashgrid_encode_bwd_impl(nsamd_points pts, int64_t M, int transform, 
     const int slice_log2 = grid.log2_table_size < kSliceLog2Max ? grid.log2_table_size : kSliceLog2Max;
     const int slices = 1 << (grid.log2_table_size - slice_log2);
     const size_t lds = sizeof(float) * 2 * ((size_t)1 << slice_log2);
-    static bool attr_set[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return NSAMD_ERR_NO_DEVICE;
-    if (dev < 0 || dev >= 64 || !attr_set[dev]) {  // the opt-in is per device
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(&hash_encode_bwd_sliced_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 2 * sizeof(float) << kSliceLog2Max) !=
-          hipSuccess)
-        return NSAMD_ERR_LAUNCH;
-      if (dev >= 0 && dev < 64) attr_set[dev] = true;
-    }
+    static LdsOptIn opted_in;  // (for the largest slice)
+    st = lds_opt_in(opted_in, hash_encode_bwd_sliced_kernel, 2 * sizeof(float) << kSliceLog2Max);
+    if (st) return st;
     dim3 g((unsigned)slices, (unsigned)grid.num_levels, 1u);
     hash_encode_bwd_sliced_kernel<<<g, kSliceThreads, lds, (hipStream_t)stream>>>(
         pts, M, transform, aabb, grid, denc, stride_p, stride_k, dtable, 0, /*accumulate=*/1);
@@ -608,17 +584,15 @@ extern "C" int nsamd_hashgrid_encode_bwd_rays_gated(nsamd_points pts, int64_t M,
                                                     float* d_directions, int accumulate, const uint32_t* gate,
                                                     const uint8_t* ray_mask, nsamd_stream_t stream) {
   if (M == 0) return NSAMD_OK;
-  int st = check_points(pts, M);
-  if (st) return st;
-  st = check_grid(grid);
-  if (st) return st;
+  if (const int st = check_points(pts, M)) return st;
+  if (const int st = check_grid(grid)) return st;
   NSAMD_REQUIRE(pts.positions == nullptr);  // ray mode only: explicit positions have no origin / direction to credit
   NSAMD_REQUIRE(table != nullptr && denc != nullptr && d_origins != nullptr && d_directions != nullptr);
   NSAMD_REQUIRE(transform >= 0 && transform <= 2);
   const int64_t rays = M / pts.samples_per_ray;
-  const int64_t nb = (rays + 3) / 4;
-  if (nb > 0x7fffffffLL) return NSAMD_ERR_UNSUPPORTED;
-  hash_encode_bwd_rays_kernel<<<(unsigned)nb, 256, 0, (hipStream_t)stream>>>(
+  unsigned nb;
+  if (grid_blocks((rays + 3) / 4, &nb)) return NSAMD_ERR_UNSUPPORTED;
+  hash_encode_bwd_rays_kernel<<<nb, 256, 0, (hipStream_t)stream>>>(
       pts, rays, transform, aabb, reinterpret_cast<const float2*>(table), grid, denc, stride_p, stride_k, d_origins,
       d_directions, accumulate ? 1 : 0, gate, ray_mask);
   NSAMD_CHECK_LAUNCH();
@@ -657,15 +631,14 @@ extern "C" int nsamd_sh4_encode(const float* dirs, int64_t M, float* out, nsamd_
 
 extern "C" int nsamd_nerf_encode(nsamd_points pts, int64_t M, const float* freqs, int32_t num_frequencies,
                                  int32_t include_input, float* out, nsamd_stream_t stream) {
-  int st = check_points(pts, M);
-  if (st) return st;
+  if (const int st = check_points(pts, M)) return st;
   NSAMD_REQUIRE(num_frequencies > 0 && num_frequencies <= 64);
   if (M == 0) return NSAMD_OK;
   NSAMD_REQUIRE(freqs != nullptr && out != nullptr);
   const int64_t threads = M * 3 * num_frequencies;
-  const int64_t blocks = (threads + 255) / 256;
-  if (blocks > 0x7fffffffLL) return NSAMD_ERR_UNSUPPORTED;
-  nerf_encode_kernel<<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>(pts, M, freqs, num_frequencies, include_input != 0, out);
+  unsigned blocks;
+  if (grid_blocks((threads + 255) / 256, &blocks)) return NSAMD_ERR_UNSUPPORTED;
+  nerf_encode_kernel<<<blocks, 256, 0, (hipStream_t)stream>>>(pts, M, freqs, num_frequencies, include_input != 0, out);
   NSAMD_CHECK_LAUNCH();
   return NSAMD_OK;
 }

@@ -12,15 +12,12 @@
 // 128 x 128 blocks of W: one launch per block, the partial sums of a row of blocks accumulate in the output and the
 // activation is applied by the last block.
 #include "common.h"
+#include "mfma_chain.h"
 
 namespace nsamd {
 
-typedef float v4f __attribute__((ext_vector_type(4)));
-
 constexpr int kLinThreads = 256;
 constexpr int kLinWaves = 4;
-
-__device__ __forceinline__ v4f mfma16l(float a, float b, v4f c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 
 __device__ __forceinline__ float act_grad(int act, float y) {
   if (act == 1) return y > 0.0f ? 1.0f : 0.0f;   // ReLU (through the post-activation value)
@@ -105,6 +102,7 @@ __global__ __launch_bounds__(kLinThreads) void linear_chain_kernel(LinBlock B, i
         }
       }
     }
+    // (chain_gemm<NT, KT> of mfma_chain.h, spelled out: through the call, the instantiations with NT >= 2 compile to other code)
 #pragma unroll
     for (int t = 0; t < KT; ++t) {
       v4f a[NT];
@@ -113,7 +111,7 @@ __global__ __launch_bounds__(kLinThreads) void linear_chain_kernel(LinBlock B, i
 #pragma unroll
       for (int r = 0; r < 4; ++r)
 #pragma unroll
-        for (int n = 0; n < NT; ++n) acc[n] = mfma16l(a[n][r], x[t][r], acc[n]);
+        for (int n = 0; n < NT; ++n) acc[n] = mfma16(a[n][r], x[t][r], acc[n]);
     }
     if (live) {
       float* orow = B.out + p * (int64_t)B.out_ld;
@@ -168,7 +166,7 @@ __global__ __launch_bounds__(kLinThreads) void linear_dw_kernel(const float* __r
       if (i < K) b = x[p * K + i];
     }
     bsum += a;
-    acc = mfma16l(a, b, acc);
+    acc = mfma16(a, b, acc);
   }
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
@@ -182,6 +180,9 @@ __global__ __launch_bounds__(kLinThreads) void linear_dw_kernel(const float* __r
   }
 }
 
+constexpr int kLinMaxTiles = 8;  // blocks of up to 128 x 128: the largest fragment block fits the LDS a kernel gets unasked
+static_assert(sizeof(float) * kLinMaxTiles * kLinMaxTiles * 256 <= 64 * 1024, "linear_chain_kernel would need the dynamic-LDS opt-in");
+
 static int pad_tiles(int dim) {  // tiles of 16, rounded up to 1, 2, 4, 8 (widths up to 128)
   const int t = (dim + 15) / 16;
   int p = 1;
@@ -193,14 +194,11 @@ template <bool TR>
 static int launch_block(const LinBlock& B, int64_t M, hipStream_t st) {
   const int NT = pad_tiles(B.out_cols), KT = pad_tiles(B.in_cols);
   const size_t lds = sizeof(float) * (size_t)NT * KT * 256;
-  if (NT > 8 || KT > 8) return NSAMD_ERR_UNSUPPORTED;  // blocks of up to 128 x 128
+  if (NT > kLinMaxTiles || KT > kLinMaxTiles) return NSAMD_ERR_UNSUPPORTED;
   const int64_t tiles = (M + 15) / 16;
   const unsigned blocks = (unsigned)min((int64_t)1024, (tiles + kLinWaves - 1) / kLinWaves);
 #define NSAMD_LIN_CASE(nt, kt)                                                                                          \
   if (NT == nt && KT == kt) {                                                                                          \
-    if (lds > 64 * 1024)                                                                                               \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&linear_chain_kernel<nt, kt, TR>),                       \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                 \
     linear_chain_kernel<nt, kt, TR><<<blocks, kLinThreads, lds, st>>>(B, M);                                           \
     NSAMD_CHECK_LAUNCH();                                                                                              \
     return NSAMD_OK;                                                                                                   \

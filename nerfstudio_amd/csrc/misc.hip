@@ -2,6 +2,7 @@
 #include <string.h>
 
 #include "common.h"
+#include "launch.h"
 #include "lens.h"
 
 namespace nsamd {
@@ -395,8 +396,7 @@ extern "C" int nsamd_device_info(int32_t* num_cus, int32_t* wavefront_size, int3
                                  char* arch_name, int32_t arch_name_len) {
   int dev = 0;
   hipDeviceProp_t prop;
-  if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess)
-    return NSAMD_ERR_NO_DEVICE;
+  if (!device_properties(&dev, &prop)) return NSAMD_ERR_NO_DEVICE;
   if (num_cus) *num_cus = prop.multiProcessorCount;
   if (wavefront_size) *wavefront_size = prop.warpSize;
   if (lds_bytes_per_cu) *lds_bytes_per_cu = (int32_t)prop.maxSharedMemoryPerMultiProcessor;

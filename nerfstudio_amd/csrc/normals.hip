@@ -23,11 +23,11 @@
 // nsamd_normals_composite. One wavefront per ray: pred = normalize(tanh(x)) per sample, the weighted sums of both normal
 // channels (double partial sums, the DPP scan of wave.h: a fixed order), r = s / (|s| + 1e-10), shaded (r + 1) / 2.
 #include "common.h"
+#include "launch.h"
+#include "mfma_chain.h"
 #include "wave.h"
 
 namespace nsamd {
-
-typedef float v4f __attribute__((ext_vector_type(4)));
 
 constexpr int kNrmWaves = 4;
 constexpr int kNrmThreads = 64 * kNrmWaves;
@@ -41,23 +41,6 @@ constexpr int kNrmB1 = kNrmB0 + 64;        // [16]
 constexpr int kNrmW1Row0 = kNrmB1 + 16;    // [64]  W1[0, :]
 constexpr int kNrmScale = kNrmW1Row0 + 64; // [16]  grid.scalings
 constexpr int kNrmLds = kNrmScale + 16;
-
-__device__ __forceinline__ v4f mfma16n(float a, float b, v4f c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-
-template <int NT, int KT>
-__device__ __forceinline__ void nrm_gemm(const float* frag, const v4f* in, v4f* out, int lane) {
-#pragma unroll
-  for (int t = 0; t < KT; ++t) {
-    v4f a[NT];
-#pragma unroll
-    for (int n = 0; n < NT; ++n) a[n] = *reinterpret_cast<const v4f*>(frag + ((n * KT + t) * 64 + lane) * 4);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-#pragma unroll
-      for (int n = 0; n < NT; ++n) out[n] = mfma16n(a[n][r], in[t][r], out[n]);
-    }
-  }
-}
 
 __global__ __launch_bounds__(kNrmThreads, 2) void field_normals_kernel(
     nsamd_points P, int64_t M, int transform, nsamd_aabb box, const float2* __restrict__ table, nsamd_grid grid,
@@ -118,9 +101,8 @@ __global__ __launch_bounds__(kNrmThreads, 2) void field_normals_kernel(
       for (int k = 0; k < 8; ++k) v[i][k] = tl[corner_index(c, k, mask)];
     }
     v4f z[4], s[4], o16[1], ge[2];
-#pragma unroll
-    for (int n = 0; n < 4; ++n) z[n] = *reinterpret_cast<const v4f*>(lds + kNrmB0 + 16 * n + 4 * g);
-    nrm_gemm<4, 2>(lds + kNrmW0, x, z, lane);
+    load_bias<4>(lds + kNrmB0, z, g);
+    chain_gemm<4, 2>(lds + kNrmW0, x, z, lane);
 #pragma unroll
     for (int n = 0; n < 4; ++n) {
       const v4f w1 = *reinterpret_cast<const v4f*>(lds + kNrmW1Row0 + 16 * n + 4 * g);
@@ -130,11 +112,10 @@ __global__ __launch_bounds__(kNrmThreads, 2) void field_normals_kernel(
         z[n][r] = fmaxf(z[n][r], 0.0f);
       }
     }
-    o16[0] = *reinterpret_cast<const v4f*>(lds + kNrmB1 + 4 * g);
-    nrm_gemm<1, 4>(lds + kNrmW1, z, o16, lane);
-    ge[0] = v4f{0.f, 0.f, 0.f, 0.f};
-    ge[1] = v4f{0.f, 0.f, 0.f, 0.f};
-    nrm_gemm<2, 4>(lds + kNrmW0T, s, ge, lane);
+    load_bias<1>(lds + kNrmB1, o16, g);
+    chain_gemm<1, 4>(lds + kNrmW1, z, o16, lane);
+    zero_tiles<2>(ge);
+    chain_gemm<2, 4>(lds + kNrmW0T, s, ge, lane);
     if (geo != nullptr && live) {  // neuron 4 g + r of the base output; neuron 0 is the density pre-activation
       float* o = geo + p * geo_stride + geo_offset + (4 * g - 1);
 #pragma unroll
@@ -237,13 +218,10 @@ extern "C" int nsamd_field_normals(nsamd_points pts, int64_t M, int transform, n
                                    const float* base_W1, const float* base_b1, float* normals, float* gradient, float* geo,
                                    int64_t geo_stride, int64_t geo_offset, nsamd_stream_t stream) {
   NSAMD_REQUIRE(M >= 0);
-  if (grid.num_levels != 16 || grid.log2_table_size < 1 || grid.log2_table_size > 28) return NSAMD_ERR_UNSUPPORTED;
+  if (grid.num_levels != 16 || check_grid(grid) != NSAMD_OK) return NSAMD_ERR_UNSUPPORTED;  // 32 features = the K of layer 0
   if (M > ((int64_t)1 << 31)) return NSAMD_ERR_UNSUPPORTED;
   if (M == 0) return NSAMD_OK;
-  if (pts.positions == nullptr) {
-    NSAMD_REQUIRE(pts.origins != nullptr && pts.directions != nullptr && pts.t_bins != nullptr && pts.samples_per_ray > 0);
-    NSAMD_REQUIRE(M % pts.samples_per_ray == 0);
-  }
+  if (const int st = check_points(pts, M)) return st;
   NSAMD_REQUIRE(transform >= 0 && transform <= 2);
   NSAMD_REQUIRE(table != nullptr && enc != nullptr && base_W0 != nullptr && base_b0 != nullptr && base_W1 != nullptr &&
                 base_b1 != nullptr);
@@ -263,13 +241,13 @@ extern "C" int nsamd_normals_composite(const float* weights, const float* normal
                                        int32_t S, float* normals_out, float* pred_out, nsamd_stream_t stream) {
   NSAMD_REQUIRE(num_rays >= 0 && S > 0);
   if (S > 4096) return NSAMD_ERR_UNSUPPORTED;
-  const int64_t blocks = (num_rays + kNrmRays - 1) / kNrmRays;
-  if (blocks > 0x7fffffffLL) return NSAMD_ERR_UNSUPPORTED;
+  unsigned blocks;
+  if (grid_blocks((num_rays + kNrmRays - 1) / kNrmRays, &blocks)) return NSAMD_ERR_UNSUPPORTED;
   if (num_rays == 0) return NSAMD_OK;
   NSAMD_REQUIRE(weights != nullptr);
   NSAMD_REQUIRE((normals_out == nullptr || normals != nullptr) && (pred_out == nullptr || pred_pre != nullptr));
   if (normals_out == nullptr && pred_out == nullptr) return NSAMD_OK;
-  normals_composite_kernel<<<(unsigned)blocks, 64 * kNrmRays, 0, (hipStream_t)stream>>>(
+  normals_composite_kernel<<<blocks, 64 * kNrmRays, 0, (hipStream_t)stream>>>(
       weights, normals_out ? normals : nullptr, pred_out ? pred_pre : nullptr, num_rays, S, normals_out, pred_out);
   NSAMD_CHECK_LAUNCH();
   return NSAMD_OK;

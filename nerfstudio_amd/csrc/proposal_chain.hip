@@ -11,6 +11,7 @@
 // level, every workgroup runs the unchanged per-level body): twelve launches become six, and two latency chains run side
 // by side. Same bits as the per-level entry points, call by call. Whether two calls of a stage can share its launches is the
 // stage's own launcher's business (proposal_chain.h, scatter.h); where they cannot, it runs them one after the other.
+#include "launch.h"
 #include "proposal_chain.h"
 #include "scatter.h"
 
@@ -23,7 +24,7 @@ static int level_checks(const nsamd_proposal_level_bwd& l) {
   NSAMD_REQUIRE(l.origins && l.directions && l.table && l.dtable && l.scatter_workspace);
   NSAMD_REQUIRE(l.transform >= 0 && l.transform <= 2);
   NSAMD_REQUIRE(l.grid.num_levels > 0 && l.grid.num_levels <= NSAMD_MAX_LEVELS && 2 * l.grid.num_levels == l.mlp.in_dim);
-  if (l.grid.log2_table_size < 1 || l.grid.log2_table_size > 28) return NSAMD_ERR_UNSUPPORTED;
+  if (!table_size_ok(l.grid)) return NSAMD_ERR_UNSUPPORTED;
   return NSAMD_OK;
 }
 

@@ -28,6 +28,7 @@
 #include <type_traits>
 
 #include "field_reduce.h"
+#include "launch.h"
 #include "scatter.h"
 
 NSAMD_PROBE_DEFINE(scatter)
@@ -895,20 +896,9 @@ ScatterBufs scatter_bufs(float* workspace, const ScatterPlan& p) {
 
 // 128 KiB of dynamic LDS need the opt-in, per device
 static int apply_lds_attribute() {
-  static bool attr_done[64] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return NSAMD_ERR_NO_DEVICE;
-  if (dev < 0 || dev >= 64 || !attr_done[dev]) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&scatter_apply_kernel<false>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)(16u << kSliceLog2Max)) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&scatter_apply_kernel<true>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)(16u << kSliceLog2Max)) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&scatter_apply_pair_kernel),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)(16u << kSliceLog2Max)) != hipSuccess)
-      return NSAMD_ERR_LAUNCH;
-    if (dev >= 0 && dev < 64) attr_done[dev] = true;
-  }
-  return NSAMD_OK;
+  static LdsOptIn opted_in;
+  const size_t bytes = (size_t)16 << kSliceLog2Max;
+  return lds_opt_in(opted_in, scatter_apply_kernel<false>, bytes, scatter_apply_kernel<true>, bytes, scatter_apply_pair_kernel, bytes);
 }
 
 // threads of an apply-pass workgroup for tiles of 2^slice_log2 entries
