@@ -22,7 +22,7 @@ constexpr int kLinWaves = 4;
 __device__ __forceinline__ float act_grad(int act, float y) {
   if (act == 1) return y > 0.0f ? 1.0f : 0.0f;   // ReLU (through the post-activation value)
   if (act == 2) return y * (1.0f - y);            // Sigmoid
-  if (act == 3) return 1.0f - expf(-y);           // Softplus: sigmoid(x) = 1 - exp(-softplus(x))
+  if (act == 3) return -expm1f(-y);               // Softplus: sigmoid(x) = 1 - exp(-softplus(x)), no cancellation for small y
   return 1.0f;
 }
 
@@ -141,6 +141,7 @@ __global__ __launch_bounds__(kLinThreads) void linear_chain_kernel(LinBlock B, i
 }
 
 // dW[16n.., 16m..] += sum_p dpre[p][.] x[p][.]; one wave per (tile, chunk); db from the m == 0 tiles
+// (dW == nullptr: db alone, the host launches the m == 0 tiles only, KT = 1)
 __global__ __launch_bounds__(kLinThreads) void linear_dw_kernel(const float* __restrict__ x, const float* __restrict__ y,
                                                                const float* __restrict__ dy, int64_t M, int K, int N,
                                                                int act, int KT, int chunks, float* __restrict__ dW,
@@ -163,15 +164,17 @@ __global__ __launch_bounds__(kLinThreads) void linear_dw_kernel(const float* __r
         a = dy[p * N + o];
         if (act != 0) a *= act_grad(act, y[p * N + o]);
       }
-      if (i < K) b = x[p * K + i];
+      if (dW != nullptr && i < K) b = x[p * K + i];
     }
     bsum += a;
     acc = mfma16(a, b, acc);
   }
+  if (dW != nullptr) {
 #pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int row = 16 * n + 4 * g + r, col = 16 * m + j;
-    if (row < N && col < K) unsafeAtomicAdd(dW + (int64_t)row * K + col, acc[r]);
+    for (int r = 0; r < 4; ++r) {
+      const int row = 16 * n + 4 * g + r, col = 16 * m + j;
+      if (row < N && col < K) unsafeAtomicAdd(dW + (int64_t)row * K + col, acc[r]);
+    }
   }
   if (db != nullptr && m == 0) {
     bsum += __shfl_xor(bsum, 16);
@@ -272,8 +275,8 @@ extern "C" int nsamd_linear_bwd(const float* x, const float* W, const float* y, 
     const int s = linear_data_grad(W, y, dy, M, K, N, activation, dx, st);
     if (s) return s;
   }
-  if (dW != nullptr) {
-    const int NT = (N + 15) / 16, KT = (K + 15) / 16;
+  if (dW != nullptr || db != nullptr) {
+    const int NT = (N + 15) / 16, KT = dW != nullptr ? (K + 15) / 16 : 1;
     int chunks = (int)min((int64_t)256, max((int64_t)1, M / 1024));
     while ((int64_t)NT * KT * chunks > 16384 && chunks > 1) chunks >>= 1;
     const int64_t units = (int64_t)NT * KT * chunks;

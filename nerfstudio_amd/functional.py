@@ -505,11 +505,9 @@ class _LinearFn(torch.autograd.Function):
         dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
         dW = torch.zeros_like(W) if ctx.needs_input_grad[1] else None
         db = torch.zeros((Nout,), device=x.device, dtype=torch.float32) if (ctx.has_bias and ctx.needs_input_grad[2]) else None
-        if dW is None and db is not None:
-            dW = torch.zeros_like(W)
         N.check(N.load().nsamd_linear_bwd(N.ptr(x), N.ptr(W), N.ptr(y), N.ptr(gy), M, K, Nout, ctx.act, N.ptr(dx), N.ptr(dW),
                                           N.ptr(db), N.stream()), "linear_bwd")
-        return dx, (dW if ctx.needs_input_grad[1] else None), db, None
+        return dx, dW, db, None
 
 
 def linear(x: Tensor, weight: Tensor, bias: Optional[Tensor], activation: Optional[str] = None) -> Tensor:
