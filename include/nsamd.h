@@ -710,6 +710,26 @@ int nsamd_select_batch(const float* slot_dev, int32_t slots, int64_t num_rays, c
                        const float* directions_pool, const int64_t* cameras_pool, const float* target_pool,
                        float* origins, float* directions, int64_t* cameras, float* target, nsamd_stream_t stream);
 
+/* The step's ray batch SAMPLED on the device from images resident in HBM — what VanillaDataManager.next_train does on the host
+ * (base_datamanager.py:506-515): PixelSampler.sample_method's uniform draw of (image, row, col) (data/pixel_samplers.py:137-174:
+ * floor(rand(n,3) * [N,H,W]), as an fp32 product), the colour gather (:305-309; uint8 / 255 as base_dataset.py:107) and
+ * RayGenerator (ray_generators.py:41-56) in ONE launch. images [N,H,W,3] uint8, mask [N,H,W] uint8 or NULL, the cameras as for
+ * nsamd_raygen_lens (one camera per image; camera_type [N] int32, every entry 1 - 3 checked by the caller; distortion [N,6] or
+ * NULL). Ray i draws from Philox-4x32-10 with counter (i, attempt, draw) and a key derived from `seed` (not the key of
+ * nsamd_step_prologue under the same seed), draw = draw_counter[0] + draw_offset: draw_counter is DEVICE memory and only
+ * read, so a captured hipGraph replays with a new batch every step once somebody else advances it. With a mask a lane redraws
+ * (attempt + 1) while its pixel is masked out, at most max_attempts times (rejection_sample_mask, :82-119); a lane that runs
+ * out keeps its last draw and adds 1 to *failed (int32, device; required with a mask). Outputs: origins, directions [n,3],
+ * pixel_area, directions_norm [n] (each nullable) — the bits of nsamd_raygen_lens over the drawn indices —, camera_indices
+ * [n] int64, target [n,3], indices [n,3] int64 = (image, row, col) (nullable; the reference's batch["indices"]).
+ * N, H, W >= 2^24 or more than 2^32 rays: NSAMD_ERR_UNSUPPORTED. */
+int nsamd_sample_batch(const uint8_t* images, const uint8_t* mask, int32_t num_images, int32_t height, int32_t width,
+                       const float* c2w, const float* fx, const float* fy, const float* cx, const float* cy,
+                       const int32_t* camera_type, const float* distortion, const int64_t* draw_counter, int64_t draw_offset,
+                       uint64_t seed, int32_t max_attempts, int64_t num_rays, float* origins, float* directions,
+                       float* pixel_area, float* directions_norm, int64_t* camera_indices, float* target, int64_t* indices,
+                       int32_t* failed, nsamd_stream_t stream);
+
 /* nsamd_select_batch + nsamd_piecewise_bins in one launch (the head of a training iteration over a pool of batches: the
  * hand-over of base_datamanager.py:506-515 and the initial sampler of ProposalNetworkSampler, ray_samplers.py:78-128, 586).
  * Same numbers as the two launches; arguments as theirs. */

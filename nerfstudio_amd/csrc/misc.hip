@@ -1,6 +1,7 @@
 // Ray generation (pinhole and lens cameras), fused Adam and library introspection for gfx950.
 #include <string.h>
 
+#include "batch_sample.h"
 #include "common.h"
 #include "launch.h"
 #include "lens.h"
@@ -135,13 +136,7 @@ __global__ void rows_scatter_kernel(float* __restrict__ rows, const int64_t* __r
 //     (seed, counter[1]) — a counter-based generator needs no state beyond the step number, so eager launches and replays of
 //     the same step draw the same numbers.
 // One workgroup: the counters are read by every thread before thread 0 advances them.
-__device__ __forceinline__ void philox_round(uint32_t (&c)[4], uint32_t (&k)[2]) {
-  const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
-  const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k[0], n1 = (uint32_t)p1, n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k[1], n3 = (uint32_t)p0;
-  c[0] = n0, c[1] = n1, c[2] = n2, c[3] = n3;
-  k[0] += 0x9E3779B9u, k[1] += 0xBB67AE85u;
-}
-
+// (philox4x32_10 and the word -> uniform conversion: batch_sample.h, shared with the batch sampler of batch.hip)
 __global__ __launch_bounds__(1024) void step_prologue_kernel(int64_t* __restrict__ counter, const float* __restrict__ table,
                                                              int rows, float* __restrict__ hyper, float* __restrict__ out0,
                                                              int64_t n0, float* __restrict__ out1, int64_t n1, uint64_t seed) {
@@ -154,12 +149,11 @@ __global__ __launch_bounds__(1024) void step_prologue_kernel(int64_t* __restrict
   for (int64_t q = threadIdx.x; 4 * q < total; q += 1024) {
     uint32_t c[4] = {(uint32_t)q, (uint32_t)(q >> 32), (uint32_t)draw, (uint32_t)(draw >> 32)};
     uint32_t k[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
-#pragma unroll
-    for (int r = 0; r < 10; ++r) philox_round(c, k);
+    philox4x32_10(c, k);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int64_t i = 4 * q + j;
-      const float u = (float)(c[j] >> 8) * 5.9604644775390625e-8f;  // 24 random bits: uniform on [0, 1)
+      const float u = batch_uniform(c[j]);  // 24 random bits: uniform on [0, 1)
       if (i < n0) out0[i] = u;
       else if (i < total) out1[i - n0] = u;
     }

@@ -24,6 +24,11 @@ gradient accumulation, mixed precision, RGBA targets over a random background, C
 `get_train_loss_dict` body over the module path — with one rank; with more the pipeline refuses loudly, because neither DDP
 nor the arena would then reduce the gradients.
 
+`HipPipelineConfig.device_batches` (off by default): the training images live in HBM and every iteration samples its own batch
+on the device (device_batches.py; inside the captured iteration where trainer.HipTrainer can hold it), so `get_train_loss_dict`
+does not call `datamanager.next_train`; a dataset the sampler does not cover is declined with a logged reason and keeps the
+datamanager. Evaluation data always stay the datamanager's.
+
 `HipDynamicBatchPipeline` is the same seam for `instant-ngp-hip`: the reference's `DynamicBatchPipeline`
 (pipelines/dynamic_batch.py:40-108 — it resizes the ray batch after every iteration from the number of samples the last one
 kept) with `get_train_loss_dict` on the explicit packed-sample schedule (ngp_trainer.NgpTrainer over ngp_step.NgpTrainStep:
@@ -38,6 +43,7 @@ nerfstudio itself is imported lazily (`pipeline_classes()`, `ngp_pipeline_classe
 from __future__ import annotations
 
 import os
+import sys
 from typing import Any, Dict, Optional
 
 import torch
@@ -96,6 +102,7 @@ class TrainEngine:
         self.runner_factory = runner_factory  # tests: a CPU stand-in for train_step.NerfactoTrainStep
         self.on_build = on_build  # tests: called with the HipTrainer right after it was built (inject jitter draws)
         self.trainer = None  # trainer.HipTrainer, built on the first batch
+        self.source = None  # device_batches.DeviceBatchSource: the trainer samples its own batches (EngineSeam hands it over)
         self.arena = None
         self.reason: Optional[str] = None
         self._lr_hist: Dict[str, Dict[int, float]] = {}
@@ -229,7 +236,7 @@ class TrainEngine:
             self.trainer.finish()
 
     def train_iteration(self, step: int, ray_bundle, batch):
-        if ray_bundle.origins.reshape(-1, 3).shape[0] != self.trainer.runner.n:
+        if self.source is None and ray_bundle.origins.reshape(-1, 3).shape[0] != self.trainer.runner.n:
             self.flush()  # a datamanager that changes its batch size: new static buffers, new graphs
             self.build_trainer_only(ray_bundle, batch)
         t = self.trainer
@@ -245,7 +252,8 @@ class TrainEngine:
             t._capture_tried = True
             t.try_capture(warm=False)
         self._eager_done += 1
-        t.set_batch(ray_bundle, {"image": self._target(batch)})
+        if self.source is None:  # (with a source the iteration samples its own batch: trainer.HipTrainer)
+            t.set_batch(ray_bundle, {"image": self._target(batch)})
         t.train_iteration()
         r = t.runner
         model = self.pipeline.model
@@ -281,8 +289,8 @@ class TrainEngine:
         runner = self.runner_factory(model, o.shape[0], o.device) if self.runner_factory is not None else None
         rb = ray_bundle.reshape(-1) if ray_bundle.origins.dim() > 2 else ray_bundle
         self.trainer = HipTrainer(model, self.arena, rb, {"image": self._target(batch)}, world=int(self.pipeline.world_size),
-                                  use_graph=True, use_runner=True, pool=None, lr_source=self._lr, drive_callbacks=False,
-                                  runner=runner)
+                                  use_graph=True, use_runner=True, pool=None, source=self.source, lr_source=self._lr,
+                                  drive_callbacks=False, runner=runner)
         if hasattr(self.trainer.runner, "want_loss_vals"):
             self.trainer.runner.want_loss_vals = True  # the reference's trainer reads the loss dictionary every iteration
         if self.on_build is not None:
@@ -387,6 +395,39 @@ class EngineSeam:
     _engine: Optional[TrainEngine] = None
     _engine_off: bool = False
     _engine_class = TrainEngine
+    _batch_source = None  # device_batches.DeviceBatchSource while device-resident batches are active (`setup_device_batches`)
+    batch_source_reason: Optional[str] = None  # why they are not, where they were asked for
+
+    def setup_device_batches(self, device, rank: int = 0, max_bytes: Optional[int] = None, launch_fn=None) -> Optional[str]:
+        """`device_batches=True`: the training images into HBM (device_batches.DeviceImageStore over
+        `datamanager.train_dataset`) and a source the engine's trainer samples from, instead of `datamanager.next_train`.
+        -> None, or the reason the dataset was declined — logged once; training then keeps today's path."""
+        from . import device_batches as DB
+
+        dm = self.datamanager
+        cfg = getattr(dm, "config", None)
+        sampler_cfg = getattr(cfg, "pixel_sampler", None)
+        reason = None
+        if torch.device(device).type != "cuda" and launch_fn is None:
+            reason = f"device {device} (the sampler is a HIP kernel)"
+        store = None
+        if reason is None:
+            store = DB.DeviceImageStore.from_dataset(dm.train_dataset, device, DB.DEFAULT_MAX_BYTES if max_bytes is None else max_bytes,
+                                                     patch_size=int(getattr(cfg, "patch_size", 1) or 1))
+            if isinstance(store, str):
+                reason, store = store, None
+        if store is not None and store.mask is not None:
+            if getattr(sampler_cfg, "ignore_mask", False):
+                store.mask = None
+            elif not getattr(sampler_cfg, "rejection_sample_mask", True):
+                reason = "rejection_sample_mask off (the sampler then draws from the list of valid pixels, pixel_samplers.py:164-167)"
+        if reason is not None:
+            self.batch_source_reason = reason
+            print(f"[nerfstudio_amd.pipeline] device_batches declined: {reason}; batches come from the datamanager", file=sys.stderr)
+            return reason
+        num_rays = int(dm.get_train_rays_per_batch())
+        self._batch_source = DB.DeviceBatchSource(store, num_rays, int(torch.initial_seed()), rank, launch_fn=launch_fn)
+        return None
 
     def attach_optimizers(self, optimizers, trainer=None, **engine_kwargs) -> None:
         """The trainer's `Optimizers` (engine/trainer.py:196-204 hands them to `get_training_callbacks`)."""
@@ -403,6 +444,18 @@ class EngineSeam:
         eng = self._engine
         if eng is None or eng.reason is not None:
             return self._module_path(step, *self.datamanager.next_train(step))
+        src = self._batch_source
+        if src is not None:
+            # the iteration samples its own batch on the device: `next_train` is not called (its bookkeeping is kept)
+            if eng.trainer is None:
+                eng.source = src
+                if eng.build(*src.next_batch(advance=False)) is not None:  # (a batch for the shapes; the trainer draws it again)
+                    self._batch_source = eng.source = None
+                    self.batch_source_reason = f"the captured schedule cannot run this setup ({eng.reason})"
+                    print(f"[nerfstudio_amd.pipeline] device_batches declined: {self.batch_source_reason}", file=sys.stderr)
+                    return self._module_path(step, *self.datamanager.next_train(step))
+            self.datamanager.train_count += 1
+            return eng.train_iteration(step, None, None)
         ray_bundle, batch = self.datamanager.next_train(step)
         if eng.trainer is None and eng.build(ray_bundle, batch) is not None:
             return self._module_path(step, ray_bundle, batch)
@@ -483,6 +536,8 @@ def pipeline_classes():
             self.world_size = world_size
             self._engine = None
             self._engine_off = not getattr(config, "graph_train_step", True) or unsupported_model_reason(self.model) is not None
+            if getattr(config, "device_batches", False) and not self._engine_off:
+                self.setup_device_batches(device, rank=local_rank)
             if world_size > 1:
                 if self._engine_off:
                     raise NotImplementedError(
@@ -510,6 +565,12 @@ def pipeline_classes():
         graph_train_step: bool = True
         """Training iterations as replayed hipGraphs with the arena's fused Adam (nerfstudio_amd/trainer.py); False: the
         module path under the trainer's own optimisers."""
+        device_batches: bool = False
+        """Keep the training images in HBM (uint8, `N * H * W * 3` bytes, + `N * H * W` with masks) and sample every batch on
+        the device inside the captured iteration (nerfstudio_amd/device_batches.py, `nsamd_sample_batch`): pixels, colours and
+        rays of a step come from one launch instead of `datamanager.next_train`'s CPU pixel sampler. Covers the default pixel
+        sampler over same-sized RGB images of perspective / fisheye cameras; anything else (and a store above 16 GiB) is
+        declined with a logged reason and trains through the datamanager. Evaluation data stay the datamanager's."""
 
     _publish(HipPipelineConfig, HipPipeline)
     return HipPipelineConfig, HipPipeline

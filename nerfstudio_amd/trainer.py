@@ -62,12 +62,18 @@ class HipTrainer:
     pool: {"origins" [slots,n,3], "directions", "cameras" [slots,n], "target" [slots,n,3]} resident in HBM — iteration i
     trains on slot i % slots, selected on the device (replayable); None: the caller fills the runner's static buffers
     (`set_batch`) before every iteration.
+    source: a device_batches.DeviceBatchSource (instead of a pool): every iteration SAMPLES its batch from the source's image
+    store. With the device prologue supplying the step's scalars (`prologue_ring`: N = 1, the camera parts inside the body) the
+    source's launch is a node of the body where `nsamd_select_batch` is for a pool — its draw number is the prologue's own
+    counter — and is captured with the rest: a replay needs nothing from the host for its batch. Otherwise (no prologue, the
+    camera parts outside the body, the data-parallel segments) the trainer calls `source.next_batch()` EAGERLY ahead of the
+    iteration and copies it into the static buffers as `set_batch` does: still no CPU work per pixel, but not the captured path.
     lr_source(group, iteration) -> learning rate of that iteration (default: the nerfacto recipe's schedulers over arena.lr).
     drive_callbacks: call the model's BEFORE/AFTER_TRAIN_ITERATION callbacks here (False when a trainer does: HipPipeline).
     runner: a train_step.NerfactoTrainStep stand-in (CPU tests of the schedule's host logic)."""
 
     def __init__(self, model, arena, ray_bundle, batch, world: int = 1, use_graph: bool = True, use_runner: bool = True,
-                 pool=None, force_dp: bool = False, dp_mode: str = "allreduce",
+                 pool=None, source=None, force_dp: bool = False, dp_mode: str = "allreduce",
                  lr_source: Optional[Callable[[str, int], float]] = None, drive_callbacks: bool = True, runner=None) -> None:
         if hasattr(getattr(model, "config", None), "depth_loss_type"):
             # its iteration (and the graphs captured from it) carries no depth target, sigma decay or depth batch
@@ -78,7 +84,13 @@ class HipTrainer:
         # replicated optimiser behind an all-reduce (the reference's DDP semantics, and the default)
         self.dp_sharded = self.dp and dp_mode == "sharded"
         self.dp_fork = False  # set below: proposal backward chains beside the main chain in the data-parallel schedule
+        if source is not None and pool is not None:
+            raise ValueError("HipTrainer: `pool` and `source` are mutually exclusive (one owner of the step's batch)")
+        if source is not None and not (use_runner or runner is not None):
+            raise ValueError("HipTrainer: a batch source needs the explicit kernel schedule (use_runner)")
         self.pool = pool
+        self.source = source
+        self.source_inside = False  # set below: the source's launch is part of the (captured) iteration body
         self.slots = int(pool["origins"].shape[0]) if pool is not None else 1
         self.step = 0
         self.opt_step = 0
@@ -187,6 +199,11 @@ class HipTrainer:
                     self.ring_np = self.ring_host.numpy()
                     self._ring_pos = 0                 # rows written so far == the device's row counter at the next launch
                     self._ring_events = [None] * 4     # recorded every 64 rows
+            if source is not None:
+                assert source.num_rays == r.n, "the source and the static buffers must agree on the rays per batch"
+                # as the jitter's counter: a trainer built in the middle of a run does not replay the pixels of steps 0, 1, ...
+                source.set_draw(int(getattr(model, "step", 0) or 0))
+                self.source_inside = self.prologue_ring
             if self.dp:
                 from .dp_schedule import PipelinedExchange
 
@@ -207,6 +224,7 @@ class HipTrainer:
         """The next iteration's rays and targets (a trainer's `datamanager.next_train`, base_datamanager.py:506-515), copied
         into the static buffers the captured graphs read. Stream-ordered: no host synchronisation."""
         assert self.pool is None, "this trainer rotates its own pool of batches"
+        assert self.source is None, "this trainer samples its own batches"
         o = ray_bundle.origins.reshape(-1, 3)
         if self.runner is not None:
             assert o.shape[0] == self.runner.n, "the captured schedule is built for a fixed number of rays per batch"
@@ -388,6 +406,14 @@ class HipTrainer:
     def _select_batch(self):
         """This step's rays out of the HBM-resident pool (slot index in device memory: replayable) — the hand-over the
         reference's datamanager does each iteration (base_datamanager.py:506-515)."""
+        if self.source is not None:
+            if self.source_inside:
+                # sampled here, inside the body: the prologue (first node) has already advanced the draw counter, hence -1
+                r = self.runner
+                co = getattr(r, "cam_opt", None) is not None  # the kernels read the pose-corrected copies
+                o, d = (r.raw_origins, r.raw_directions) if co else (r.origins, r.directions)
+                self.source.launch(o, d, r.camera_indices, r.target, self.step_counter[1:], -1)
+            return  # (else: `_source_batch` has filled the buffers ahead of the iteration)
         if self.pool is None:
             return
         from . import _native as N
@@ -407,6 +433,11 @@ class HipTrainer:
         N.check(N.load().nsamd_select_batch(N.ptr(self.hyper[_HYPER_SLOT:_HYPER_SLOT + 1]), self.slots, o.shape[0],
                                             N.ptr(p["origins"]), N.ptr(p["directions"]), N.ptr(p["cameras"]), N.ptr(p["target"]),
                                             N.ptr(o), N.ptr(d), N.ptr(c), N.ptr(t), N.stream()), "select_batch")
+
+    def _source_batch(self):
+        """The eager form of a source (class docstring): `next_batch()` into the static buffers, ahead of the iteration."""
+        rb, batch = self.source.next_batch()
+        self.runner.set_batch(rb.origins, rb.directions, rb.camera_indices.reshape(-1), batch["image"])
 
     # -- camera optimiser: the host-side halves around the captured part ---------------------------------------------------
     @property
@@ -574,6 +605,8 @@ class HipTrainer:
         if self.drive_callbacks:
             self.model.set_step(self.step)  # BEFORE_TRAIN_ITERATION callback: proposal weight anneal
         self._push_hyper()
+        if self.source is not None and not self.source_inside:
+            self._source_batch()
         if self._cams_outside:
             self._cameras_before()
         if self.pipelined:
