@@ -279,6 +279,43 @@ NSAMD_HD uint32_t corner_index(const Cell& c, int corner, uint32_t mask) {
                      (corner & 4) ? c.hi[2] : c.lo[2], mask);
 }
 
+// One feature of a level: the blend of its eight corner values q(k), x then y then z exactly as encodings.py:446-456
+// ((wx, wy, wz): the ceil-corner weights of the cell). THE operation order of the hash grid: every forward goes through here.
+template <class Q>
+NSAMD_HD float trilinear_blend(Q q, float wx, float wy, float wz) {
+  const float ux = 1.0f - wx, uy = 1.0f - wy, uz = 1.0f - wz;
+  const float yc_zc = q(7) * wx + q(6) * ux;
+  const float yf_zc = q(5) * wx + q(4) * ux;
+  const float yf_zf = q(1) * wx + q(0) * ux;
+  const float yc_zf = q(3) * wx + q(2) * ux;
+  const float zc = yc_zc * wy + yf_zc * uy;
+  const float zf = yc_zf * wy + yf_zf * uy;
+  return zc * wz + zf * uz;
+}
+
+// (lx, ly, lz) += g * d trilinear_blend / d (wx, wy, wz): the blend's derivative with respect to the three cell offsets, the
+// upstream gradient pushed back through z, y, x in turn. The caller multiplies by the level's scale (offset = scaled - floor).
+template <class Q>
+NSAMD_HD void trilinear_blend_grad(Q q, float g, float wx, float wy, float wz, float& lx, float& ly, float& lz) {
+  const float ux = 1.0f - wx, uy = 1.0f - wy, uz = 1.0f - wz;
+  const float yc_zc = q(7) * wx + q(6) * ux, yf_zc = q(5) * wx + q(4) * ux;
+  const float yf_zf = q(1) * wx + q(0) * ux, yc_zf = q(3) * wx + q(2) * ux;
+  const float zc = yc_zc * wy + yf_zc * uy, zf = yc_zf * wy + yf_zf * uy;
+  lz += g * (zc - zf);
+  const float g_zc = g * wz, g_zf = g * uz;
+  ly += g_zc * (yc_zc - yf_zc) + g_zf * (yc_zf - yf_zf);
+  const float g_yczc = g_zc * wy, g_yfzc = g_zc * uy, g_yczf = g_zf * wy, g_yfzf = g_zf * uy;
+  lx += g_yczc * (q(7) - q(6)) + g_yfzc * (q(5) - q(4)) + g_yfzf * (q(1) - q(0)) + g_yczf * (q(3) - q(2));
+}
+
+// Corner k's share of the gradient g of a blended feature, in autograd's order ((g * wz) * wy) * wx.
+NSAMD_HD float corner_share(const Cell& c, int k, float g) {
+  const float bz = (k & 4) ? c.w[2] : 1.0f - c.w[2];
+  const float by = (k & 2) ? c.w[1] : 1.0f - c.w[1];
+  const float bx = (k & 1) ? c.w[0] : 1.0f - c.w[0];
+  return ((g * bz) * by) * bx;
+}
+
 // ---- piecewise spacing function (ray_samplers.py:244-245) -----------------------------------------------------
 NSAMD_HD float spacing_fn(float x) { return (x < 1.0f) ? (x / 2.0f) : (1.0f - 1.0f / (2.0f * x)); }
 NSAMD_HD float spacing_fn_inv(float x) { return (x < 0.5f) ? (2.0f * x) : (1.0f / (2.0f - 2.0f * x)); }

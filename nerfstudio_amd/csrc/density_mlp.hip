@@ -15,7 +15,6 @@
 // density_dw_reduce_kernel sums in a fixed order (bit-reproducible; without scratch: <= kMaxBlocks float atomics per
 // weight element).
 #include "common.h"
-#include "density_point.h"
 #include "launch.h"
 #include "mfma_chain.h"
 #include "proposal_chain.h"
@@ -68,6 +67,53 @@ __global__ __launch_bounds__(kMlpBlock) void density_mlp_fwd_kernel(const float*
 // (The lane-pair arrangement that takes the main grid's forward from 76 to 63 us is SLOWER here — 37.2 -> 46.6 us on the 256-sample
 // level, profiles/r05_s16_*: the proposal grids are coarse against the sample spacing and adjacent lanes already share their
 // lines; csrc/experiments/rounds2to5_opt_in_variants.patch.)
+// (x, y, z): the sample's world position; p: its index in the level's [M] arrays. enc_out / selector_out / pre_out nullable.
+template <int LEVELS, int H>
+__device__ __forceinline__ void density_point(float x, float y, float z, int64_t p, int64_t M, int transform, const nsamd_aabb& box,
+                                              const float2* __restrict__ table, const nsamd_grid& grid,
+                                              const nsamd_density_mlp& mlp, float* __restrict__ enc_out,
+                                              float* __restrict__ selector_out, float* __restrict__ density,
+                                              float* __restrict__ pre_out) {
+  constexpr int IN = 2 * LEVELS;
+  const float sel = normalise_position(transform, box, x, y, z);
+  const uint32_t mask = (1u << grid.log2_table_size) - 1u;
+  float2 v[LEVELS][8];
+  float w[LEVELS][3];
+#pragma unroll
+  for (int l = 0; l < LEVELS; ++l) {  // all gathers in flight before the first blend
+    const Cell c = locate_cell(x, y, z, grid.scalings[l]);
+    w[l][0] = c.w[0]; w[l][1] = c.w[1]; w[l][2] = c.w[2];
+    const float2* __restrict__ tl = table + ((size_t)l << grid.log2_table_size);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) v[l][k] = tl[corner_index(c, k, mask)];
+  }
+  float feat[IN];
+#pragma unroll
+  for (int l = 0; l < LEVELS; ++l) {
+#pragma unroll
+    for (int f = 0; f < 2; ++f)
+      feat[2 * l + f] = trilinear_blend([&](int k) { return f == 0 ? v[l][k].x : v[l][k].y; }, w[l][0], w[l][1], w[l][2]);
+  }
+  if (enc_out != nullptr) {
+#pragma unroll
+    for (int k = 0; k < IN; ++k) enc_out[(int64_t)k * M + p] = feat[k];
+  }
+  if (selector_out != nullptr) selector_out[p] = sel;
+  const float* __restrict__ W0 = mlp.W0;
+  const float* __restrict__ b0 = mlp.b0;
+  const float* __restrict__ W1 = mlp.W1;
+  float out = mlp.b1[0];
+#pragma unroll
+  for (int j = 0; j < H; ++j) {
+    float a = b0[j];
+#pragma unroll
+    for (int k = 0; k < IN; ++k) a = fmaf(W0[j * IN + k], feat[k], a);
+    out = fmaf(W1[j], fmaxf(a, 0.0f), out);
+  }
+  if (pre_out != nullptr) pre_out[p] = out;
+  density[p] = mlp.average_init_density * expf(out) * sel;
+}
+
 template <int LEVELS, int H>
 __global__ __launch_bounds__(kMlpBlock) void density_field_fwd_kernel(nsamd_points P, int64_t M, int transform,
                                                                       nsamd_aabb box, const float2* __restrict__ table,

@@ -743,18 +743,16 @@ __device__ __noinline__ void route_record_slow(RouteLds* L, float x, float y, fl
   const Cell c = locate_cell(x, y, z, L->lv[level].scal);
   const PairHash h = pair_hash(c, q, mask);
   const uint32_t bin = h.ia >> sl, tile0 = (uint32_t)level << lb;
-  const float bz = (q & 2) ? c.w[2] : 1.0f - c.w[2];
-  const float by = (q & 1) ? c.w[1] : 1.0f - c.w[1];
-  const float a0 = (g0 * bz) * by, a1 = (g1 * bz) * by;
+  float a0, a1;
+  pair_share(c, q, g0, g1, a0, a1);
   if ((h.ib >> sl) != bin) {
     const float omx = 1.0f - c.w[0];
-    route_spill(L, tile0 + bin, make_uint4(__float_as_uint(a0 * omx), __float_as_uint(a1 * omx), 0u, h.ia & local_mask));
-    route_spill(L, tile0 + (h.ib >> sl), make_uint4(__float_as_uint(a0 * c.w[0]), __float_as_uint(a1 * c.w[0]), 0u, h.ib & local_mask));
+    route_spill(L, tile0 + bin, single_record(a0 * omx, a1 * omx, h.ia & local_mask));
+    route_spill(L, tile0 + (h.ib >> sl), single_record(a0 * c.w[0], a1 * c.w[0], h.ib & local_mask));
     return;
   }
   if (!segment_full) return;
-  const uint4 rec = make_uint4(__float_as_uint(a0), __float_as_uint(a1), __float_as_uint(c.w[0]),
-                               (h.ia & local_mask) | ((h.ib & local_mask) << 14) | 0x80000000u);
+  const uint4 rec = pair_record(a0, a1, c.w[0], h.ia & local_mask, h.ib & local_mask);
   const uint32_t Q = L->level_cap, static_end = L->static_end;
   const uint32_t pos = atomicAdd(L->dyn_cursor + (tile0 + bin), 1u);
   if (pos < Q - static_end) rec_store(L->queues + (L->lv[level].loff + bin * Q + static_end + pos), rec);
@@ -798,14 +796,14 @@ __device__ __forceinline__ void route_level(RouteLds* L, const float (*stash)[64
   for (int q = 0; q < 4; ++q) {
     const uint32_t bin = h[q].ia >> sl;
     const bool straddle = (h[q].ib >> sl) != bin;
-    // autograd order ((g * wz) * wy) * wx; the x factor is applied by pass 2
+    // (a straddling pair has taken a rank like any other: its slot gets a record that adds zero — zero WORDS, an integer select
+    //  whose other arm alone evaluates the share —, the two halves leave through the slow path. The share is pair_share's
+    //  (scatter.h) written out: evaluated ahead of the select, this kernel's register allocation and SGPR spills shift.)
     const float bz = (q & 2) ? c.w[2] : 1.0f - c.w[2];
     const float by = (q & 1) ? c.w[1] : 1.0f - c.w[1];
-    // (a straddling pair has taken a rank like any other: its slot gets a record that adds zero, the two halves leave
-    //  through the slow path)
-    const uint4 rec = make_uint4(straddle ? 0u : __float_as_uint((g0 * bz) * by), straddle ? 0u : __float_as_uint((g1 * bz) * by),
-                                 __float_as_uint(c.w[0]),
-                                 (h[q].ia & local_mask) | ((straddle ? h[q].ia : h[q].ib) & local_mask) << 14 | 0x80000000u);
+    const uint32_t a0 = straddle ? 0u : __float_as_uint((g0 * bz) * by), a1 = straddle ? 0u : __float_as_uint((g1 * bz) * by);
+    const uint4 rec = pair_record(__uint_as_float(a0), __uint_as_float(a1), c.w[0], h[q].ia & local_mask,
+                                  (straddle ? h[q].ia : h[q].ib) & local_mask);
     full[q] = rank[q] >= C;
     slow[q] = straddle || full[q];
     // (record indices fit 32 bits: the plan checks queue_records < 2^31)

@@ -10,6 +10,10 @@
 // (stride_p = 1) makes the 8-B-per-point result store one coalesced 256-B row per wavefront and feature; the [M, 2L]
 // row-major layout of the stand-alone Encoding API is the strided variant.
 //
+// The arithmetic is shared, one copy each (common.h): every forward blends through trilinear_blend, the position gradients
+// go through trilinear_blend_grad, a corner's share of a gradient is corner_share; the x-pair form of that share (pair_share)
+// and the 16-B queue record (pair_record / single_record and its accessors) are scatter.h's.
+//
 // HBM-bound integer/gather work, no MFMA. Algorithmic bytes: 8 corners x 8 B per point and level (fwd),
 // 8 corners x 16 B read-modify-write (bwd).
 //
@@ -71,21 +75,10 @@ __global__ __launch_bounds__(kHashBlock) void hash_encode_fwd_kernel(nsamd_point
   for (int i = 0; i < kLevels; ++i) {
     const int level = level0 + i;
     if (level >= grid.num_levels) break;
-    const float wx = w[i][0], wy = w[i][1], wz = w[i][2];
-    const float ux = 1.0f - wx, uy = 1.0f - wy, uz = 1.0f - wz;
     float r[2];
 #pragma unroll
-    for (int f = 0; f < 2; ++f) {
-      auto g = [&](int k) { return f == 0 ? v[i][k].x : v[i][k].y; };
-      // blend order x, y, z exactly as encodings.py:446-456
-      const float yc_zc = g(7) * wx + g(6) * ux;
-      const float yf_zc = g(5) * wx + g(4) * ux;
-      const float yf_zf = g(1) * wx + g(0) * ux;
-      const float yc_zf = g(3) * wx + g(2) * ux;
-      const float zc = yc_zc * wy + yf_zc * uy;
-      const float zf = yc_zf * wy + yf_zf * uy;
-      r[f] = zc * wz + zf * uz;
-    }
+    for (int f = 0; f < 2; ++f)
+      r[f] = trilinear_blend([&](int k) { return f == 0 ? v[i][k].x : v[i][k].y; }, w[i][0], w[i][1], w[i][2]);
     float* o = enc + p * stride_p + (int64_t)(2 * level) * stride_k;
     o[0] = r[0];
     o[stride_k] = r[1];
@@ -145,7 +138,7 @@ __global__ __launch_bounds__(kHashBlock) void hash_encode_fwd_v3_kernel(nsamd_po
   // round E: the even lane's point (own for even lanes, the neighbour's for odd ones); round O: the odd lane's point
   const uint32_t ex = odd ? nx : own_x, ey0 = odd ? ny0 : hy0, ey1 = odd ? ny1 : hy1, ez0 = odd ? nz0 : hz0, ez1 = odd ? nz1 : hz1;
   const uint32_t ox = odd ? own_x : nx, oy0 = odd ? hy0 : ny0, oy1 = odd ? hy1 : ny1, oz0 = odd ? hz0 : nz0, oz1 = odd ? hz1 : nz1;
-  // corner pair q: (y, z) = (lo, lo), (hi, lo), (lo, hi), (hi, hi) — v0/v1, v2/v3, v4/v5, v6/v7 of the kernel above
+  // corner pair q: (y, z) = (lo, lo), (hi, lo), (lo, hi), (hi, hi) — corners 0/1, 2/3, 4/5, 6/7 of the kernel above
   const float2 e0 = tl[(ex ^ ey0 ^ ez0) & mask], e1 = tl[(ex ^ ey1 ^ ez0) & mask], e2 = tl[(ex ^ ey0 ^ ez1) & mask],
                e3 = tl[(ex ^ ey1 ^ ez1) & mask];
   const float2 o0 = tl[(ox ^ oy0 ^ oz0) & mask], o1 = tl[(ox ^ oy1 ^ oz0) & mask], o2 = tl[(ox ^ oy0 ^ oz1) & mask],
@@ -157,24 +150,11 @@ __global__ __launch_bounds__(kHashBlock) void hash_encode_fwd_v3_kernel(nsamd_po
   };
   const float2 r0 = swap2(e0, o0), r1 = swap2(e1, o1), r2 = swap2(e2, o2), r3 = swap2(e3, o3);
   // own point's corners: even lane = (lo-x: own round E, hi-x: received), odd lane = (lo-x: received, hi-x: own round O)
-  const float2 v0 = odd ? r0 : e0, v1 = odd ? o0 : r0;
-  const float2 v2 = odd ? r1 : e1, v3 = odd ? o1 : r1;
-  const float2 v4 = odd ? r2 : e2, v5 = odd ? o2 : r2;
-  const float2 v6 = odd ? r3 : e3, v7 = odd ? o3 : r3;
-  const float wx = c.w[0], wy = c.w[1], wz = c.w[2];
-  const float ux = 1.0f - wx, uy = 1.0f - wy, uz = 1.0f - wz;
+  const float2 v[8] = {odd ? r0 : e0, odd ? o0 : r0, odd ? r1 : e1, odd ? o1 : r1,
+                       odd ? r2 : e2, odd ? o2 : r2, odd ? r3 : e3, odd ? o3 : r3};
   float r[2];
 #pragma unroll
-  for (int f = 0; f < 2; ++f) {
-    auto g = [&](const float2& a) { return f == 0 ? a.x : a.y; };
-    const float yc_zc = g(v7) * wx + g(v6) * ux;  // blend order x, y, z exactly as encodings.py:446-456
-    const float yf_zc = g(v5) * wx + g(v4) * ux;
-    const float yf_zf = g(v1) * wx + g(v0) * ux;
-    const float yc_zf = g(v3) * wx + g(v2) * ux;
-    const float zc = yc_zc * wy + yf_zc * uy;
-    const float zf = yc_zf * wy + yf_zf * uy;
-    r[f] = zc * wz + zf * uz;
-  }
+  for (int f = 0; f < 2; ++f) r[f] = trilinear_blend([&](int k) { return f == 0 ? v[k].x : v[k].y; }, c.w[0], c.w[1], c.w[2]);
   if (!live) return;
   float* o = enc + p * stride_p + (int64_t)(2 * level) * stride_k;
   o[0] = r[0];
@@ -200,13 +180,9 @@ __global__ __launch_bounds__(kHashBlock) void hash_encode_bwd_table_kernel(
   float* tl = dtable + (((size_t)level << grid.log2_table_size) << 1);
 #pragma unroll
   for (int k = 0; k < 8; ++k) {
-    // autograd order: ((g * wz) * wy) * wx
-    const float bz = (k & 4) ? c.w[2] : 1.0f - c.w[2];
-    const float by = (k & 2) ? c.w[1] : 1.0f - c.w[1];
-    const float bx = (k & 1) ? c.w[0] : 1.0f - c.w[0];
     const uint32_t idx = corner_index(c, k, mask);
-    unsafeAtomicAdd(tl + 2 * (size_t)idx + 0, ((g0 * bz) * by) * bx);
-    unsafeAtomicAdd(tl + 2 * (size_t)idx + 1, ((g1 * bz) * by) * bx);
+    unsafeAtomicAdd(tl + 2 * (size_t)idx + 0, corner_share(c, k, g0));
+    unsafeAtomicAdd(tl + 2 * (size_t)idx + 1, corner_share(c, k, g1));
   }
 }
 
@@ -234,18 +210,16 @@ constexpr int kSliceThreads = 1024;
 
 __global__ __launch_bounds__(kSliceThreads) void hash_encode_bwd_sliced_kernel(
     nsamd_points P, int64_t M, int transform, nsamd_aabb box, nsamd_grid grid, const float* __restrict__ denc,
-    int64_t stride_p, int64_t stride_k, float* __restrict__ dst, int64_t dst_chunk_stride, int accumulate) {
+    int64_t stride_p, int64_t stride_k, float* __restrict__ dtable) {
   extern __shared__ __attribute__((aligned(16))) float acc[];  // [slice_entries][2]
-  const int slice = blockIdx.x, level = blockIdx.y, chunk = blockIdx.z, chunks = gridDim.z;
+  const int slice = blockIdx.x, level = blockIdx.y;
   const int slice_log2 = min(grid.log2_table_size, kSliceLog2Max);
   const int slice_entries = 1 << slice_log2;
   for (int e = threadIdx.x; e < 2 * slice_entries; e += kSliceThreads) acc[e] = 0.0f;
   __syncthreads();
-  const int64_t per = (M + chunks - 1) / chunks;
-  const int64_t p_end = min(M, (int64_t)(chunk + 1) * per);
   const uint32_t mask = (1u << grid.log2_table_size) - 1u;
   const float scale = grid.scalings[level];
-  for (int64_t p = (int64_t)chunk * per + threadIdx.x; p < p_end; p += kSliceThreads) {
+  for (int64_t p = threadIdx.x; p < M; p += kSliceThreads) {
     const float* gptr = denc + p * stride_p + (int64_t)(2 * level) * stride_k;
     const float g0 = gptr[0], g1 = gptr[stride_k];
     if (g0 == 0.0f && g1 == 0.0f) continue;
@@ -257,22 +231,14 @@ __global__ __launch_bounds__(kSliceThreads) void hash_encode_bwd_sliced_kernel(
     for (int k = 0; k < 8; ++k) {
       const uint32_t idx = corner_index(c, k, mask);
       if ((int)(idx >> slice_log2) == slice) {
-        const float bz = (k & 4) ? c.w[2] : 1.0f - c.w[2];
-        const float by = (k & 2) ? c.w[1] : 1.0f - c.w[1];
-        const float bx = (k & 1) ? c.w[0] : 1.0f - c.w[0];
         const uint32_t local = idx & (uint32_t)(slice_entries - 1);
-        lds_add_pair(acc + 2 * local, ((g0 * bz) * by) * bx, ((g1 * bz) * by) * bx);
+        lds_add_pair(acc + 2 * local, corner_share(c, k, g0), corner_share(c, k, g1));
       }
     }
   }
   __syncthreads();
-  float* out = dst + (int64_t)chunk * dst_chunk_stride +
-               ((((size_t)level << grid.log2_table_size) + ((size_t)slice << slice_log2)) << 1);
-  if (accumulate) {
-    for (int e = threadIdx.x; e < 2 * slice_entries; e += kSliceThreads) out[e] += acc[e];  // sole owner of the tile
-  } else {
-    for (int e = threadIdx.x; e < 2 * slice_entries; e += kSliceThreads) out[e] = acc[e];
-  }
+  float* out = dtable + ((((size_t)level << grid.log2_table_size) + ((size_t)slice << slice_log2)) << 1);
+  for (int e = threadIdx.x; e < 2 * slice_entries; e += kSliceThreads) out[e] += acc[e];  // sole owner of the tile
 }
 
 // dL/d(raw position) of one point: back through the trilinear blend (offset = scaled - floor(scaled), slope
@@ -297,22 +263,10 @@ __device__ __forceinline__ void position_gradient(const nsamd_points& P, int64_t
     for (int k = 0; k < 8; ++k) v[k] = tl[corner_index(c, k, mask)];
     const float* gptr = denc + p * stride_p + (int64_t)(2 * level) * stride_k;
     const float gf[2] = {gptr[0], gptr[stride_k]};
-    const float wx = c.w[0], wy = c.w[1], wz = c.w[2];
-    const float ux = 1.0f - wx, uy = 1.0f - wy, uz = 1.0f - wz;
     float lx = 0.0f, ly = 0.0f, lz = 0.0f;
 #pragma unroll
-    for (int f = 0; f < 2; ++f) {
-      auto q = [&](int k) { return f == 0 ? v[k].x : v[k].y; };
-      const float yc_zc = q(7) * wx + q(6) * ux, yf_zc = q(5) * wx + q(4) * ux;
-      const float yf_zf = q(1) * wx + q(0) * ux, yc_zf = q(3) * wx + q(2) * ux;
-      const float zc = yc_zc * wy + yf_zc * uy, zf = yc_zf * wy + yf_zf * uy;
-      const float g = gf[f];
-      lz += g * (zc - zf);
-      const float g_zc = g * wz, g_zf = g * uz;
-      ly += g_zc * (yc_zc - yf_zc) + g_zf * (yc_zf - yf_zf);
-      const float g_yczc = g_zc * wy, g_yfzc = g_zc * uy, g_yczf = g_zf * wy, g_yfzf = g_zf * uy;
-      lx += g_yczc * (q(7) - q(6)) + g_yfzc * (q(5) - q(4)) + g_yfzf * (q(1) - q(0)) + g_yczf * (q(3) - q(2));
-    }
+    for (int f = 0; f < 2; ++f)
+      trilinear_blend_grad([&](int k) { return f == 0 ? v[k].x : v[k].y; }, gf[f], c.w[0], c.w[1], c.w[2], lx, ly, lz);
     gx += lx * scale;
     gy += ly * scale;
     gz += lz * scale;
@@ -529,9 +483,9 @@ static int hashgrid_encode_bwd_impl(nsamd_points pts, int64_t M, int transform, 
     static LdsOptIn opted_in;  // (for the largest slice)
     st = lds_opt_in(opted_in, hash_encode_bwd_sliced_kernel, 2 * sizeof(float) << kSliceLog2Max);
     if (st) return st;
-    dim3 g((unsigned)slices, (unsigned)grid.num_levels, 1u);
-    hash_encode_bwd_sliced_kernel<<<g, kSliceThreads, lds, (hipStream_t)stream>>>(
-        pts, M, transform, aabb, grid, denc, stride_p, stride_k, dtable, 0, /*accumulate=*/1);
+    dim3 g((unsigned)slices, (unsigned)grid.num_levels);
+    hash_encode_bwd_sliced_kernel<<<g, kSliceThreads, lds, (hipStream_t)stream>>>(pts, M, transform, aabb, grid, denc,
+                                                                                   stride_p, stride_k, dtable);
     NSAMD_CHECK_LAUNCH();
   }
   if (dpositions != nullptr) {

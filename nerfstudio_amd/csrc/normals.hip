@@ -122,26 +122,15 @@ __global__ __launch_bounds__(kNrmThreads, 2) void field_normals_kernel(
       for (int r = 0; r < 4; ++r)
         if (4 * g + r > 0) o[r] = o16[0][r];
     }
-    // position gradient of the lane's four levels (the derivative of the x -> y -> z blend, encodings.py:446-456)
+    // position gradient of the lane's four levels (trilinear_blend_grad: the derivative of the x -> y -> z blend)
     float gx = 0.0f, gy = 0.0f, gz = 0.0f;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      const float wx = w[i][0], wy = w[i][1], wz = w[i][2];
-      const float ux = 1.0f - wx, uy = 1.0f - wy, uz = 1.0f - wz;
       float lx = 0.0f, ly = 0.0f, lz = 0.0f;
 #pragma unroll
-      for (int f = 0; f < 2; ++f) {
-        auto q = [&](int k) { return f == 0 ? v[i][k].x : v[i][k].y; };
-        const float gf = ge[i >> 1][2 * (i & 1) + f];
-        const float yc_zc = q(7) * wx + q(6) * ux, yf_zc = q(5) * wx + q(4) * ux;
-        const float yf_zf = q(1) * wx + q(0) * ux, yc_zf = q(3) * wx + q(2) * ux;
-        const float zc = yc_zc * wy + yf_zc * uy, zf = yc_zf * wy + yf_zf * uy;
-        lz += gf * (zc - zf);
-        const float g_zc = gf * wz, g_zf = gf * uz;
-        ly += g_zc * (yc_zc - yf_zc) + g_zf * (yc_zf - yf_zf);
-        const float g_yczc = g_zc * wy, g_yfzc = g_zc * uy, g_yczf = g_zf * wy, g_yfzf = g_zf * uy;
-        lx += g_yczc * (q(7) - q(6)) + g_yfzc * (q(5) - q(4)) + g_yfzf * (q(1) - q(0)) + g_yczf * (q(3) - q(2));
-      }
+      for (int f = 0; f < 2; ++f)
+        trilinear_blend_grad([&](int k) { return f == 0 ? v[i][k].x : v[i][k].y; }, ge[i >> 1][2 * (i & 1) + f], w[i][0],
+                             w[i][1], w[i][2], lx, ly, lz);
       gx += lx * scale[i];
       gy += ly * scale[i];
       gz += lz * scale[i];

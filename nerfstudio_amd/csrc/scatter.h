@@ -91,6 +91,27 @@ constexpr int kHdrEvtLost = 42;      // sticky: records that found no room at al
 constexpr int kProducerMaxLog2Bins = 6;  // producer kernels keep [levels][2^log2_bins] rank counters in LDS (4 KiB)
 constexpr uint32_t kSpillFold = 8192;  // spill records pass 2 folds into its tiles (exact, order-independent)
 
+// ---- x-pairs: the two corners of a cell edge along x (pair q: bit0 = y is ceil, bit1 = z is ceil) leave pass 1 as ONE record.
+// Plain arithmetic, so the host check compiles it too.
+struct PairHash {
+  uint32_t ia, ib;
+};
+
+// hashes of the x-pair q of a cell
+__device__ __forceinline__ PairHash pair_hash(const Cell& c, int q, uint32_t mask) {
+  const uint32_t yz = ((uint32_t)((q & 1) ? c.hi[1] : c.lo[1]) * kPrimeY) ^ ((uint32_t)((q & 2) ? c.hi[2] : c.lo[2]) * kPrimeZ);
+  return PairHash{((uint32_t)c.lo[0] ^ yz) & mask, ((uint32_t)c.hi[0] ^ yz) & mask};
+}
+
+// (a0, a1) = the x-pair q's share of the gradients (g0, g1) of a level's two features: autograd's ((g * wz) * wy) * wx
+// (corner_share, common.h) without its x factor, which pass 2 applies to either end of the pair.
+__device__ __forceinline__ void pair_share(const Cell& c, int q, float g0, float g1, float& a0, float& a1) {
+  const float bz = (q & 2) ? c.w[2] : 1.0f - c.w[2];
+  const float by = (q & 1) ? c.w[1] : 1.0f - c.w[1];
+  a0 = (g0 * bz) * by;
+  a1 = (g1 * bz) * by;
+}
+
 #if defined(__HIPCC__)
 // ---- device helpers shared by the route kernels (scatter.hip) and the field backward's record emission (field_mlp.hip) ----
 // Queue records are written once (pass 1) and read once (pass 2, another launch): streaming accesses, kept out of the way of
@@ -107,6 +128,40 @@ __device__ __forceinline__ void rec_store(uint4* dst, const uint4& r) {
 __device__ __forceinline__ uint4 rec_load(const uint4* src) {
   const rec_vec v = __builtin_nontemporal_load(global_ptr(reinterpret_cast<const rec_vec*>(src)));
   return make_uint4(v.x, v.y, v.z, v.w);
+}
+
+// The 16-byte queue record: .x, .y = the two values; a PAIR record (an x-pair within one tile) carries wx in .z and, in .w,
+// the tile-local index of the lo-x entry, that of the hi-x entry 14 bits up (a tile has at most 2^14 entries) and the top bit;
+// a SINGLE record has .z = 0 and .w = its local index. Written and read through these functions only.
+__device__ __forceinline__ uint4 pair_record(float a0, float a1, float wx, uint32_t local_a, uint32_t local_b) {
+  return make_uint4(__float_as_uint(a0), __float_as_uint(a1), __float_as_uint(wx), local_a | (local_b << 14) | 0x80000000u);
+}
+__device__ __forceinline__ uint4 single_record(float f0, float f1, uint32_t local) {
+  return make_uint4(__float_as_uint(f0), __float_as_uint(f1), 0u, local);
+}
+__device__ __forceinline__ uint32_t rec_is_pair(const uint4& r) { return r.w & 0x80000000u; }  // (non-zero: a pair record)
+__device__ __forceinline__ float rec_f0(const uint4& r) { return __uint_as_float(r.x); }
+__device__ __forceinline__ float rec_f1(const uint4& r) { return __uint_as_float(r.y); }
+__device__ __forceinline__ float rec_wx(const uint4& r) { return __uint_as_float(r.z); }
+__device__ __forceinline__ uint32_t rec_local_a(const uint4& r) { return r.w & 0x3fffu; }  // (a single record's only index)
+__device__ __forceinline__ uint32_t rec_local_b(const uint4& r) { return (r.w >> 14) & 0x3fffu; }
+
+// A record added to its tile `t` of the gradient with float atomics: exact, but in no fixed order.
+__device__ __forceinline__ void rec_add_unordered(float* t, const uint4& rec) {
+  const float f0 = rec_f0(rec), f1 = rec_f1(rec);
+  if (rec_is_pair(rec)) {
+    const float wx = rec_wx(rec), omx = 1.0f - wx;
+    float* a = t + 2 * (size_t)rec_local_a(rec);
+    float* b = t + 2 * (size_t)rec_local_b(rec);
+    unsafeAtomicAdd(a, f0 * omx);
+    unsafeAtomicAdd(a + 1, f1 * omx);
+    unsafeAtomicAdd(b, f0 * wx);
+    unsafeAtomicAdd(b + 1, f1 * wx);
+  } else {
+    float* a = t + 2 * (size_t)rec_local_a(rec);
+    unsafeAtomicAdd(a, f0);
+    unsafeAtomicAdd(a + 1, f1);
+  }
 }
 
 // Append a record that found no room in its tile (or an x-pair straddling two tiles). One returning atomic per
@@ -129,22 +184,9 @@ static __device__ __noinline__ bool spill_list_append(uint32_t* hdr, uint4* spil
 }
 
 // Last resort of an ACCUMULATING call whose (bounded) spill list is full: float atomics straight into the gradient —
-// exact, but in no fixed order (counted). `table_level_tile` = start of the tile in the gradient.
+// exact, but in no fixed order (counted). `t` = start of the tile in the gradient.
 static __device__ __noinline__ void spill_direct(float* t, uint32_t* hdr, uint4 rec) {
-  const float f0 = __uint_as_float(rec.x), f1 = __uint_as_float(rec.y);
-  if (rec.w & 0x80000000u) {
-    const float wx = __uint_as_float(rec.z), omx = 1.0f - wx;
-    float* a = t + 2 * (size_t)(rec.w & 0x3fffu);
-    float* b = t + 2 * (size_t)((rec.w >> 14) & 0x3fffu);
-    unsafeAtomicAdd(a, f0 * omx);
-    unsafeAtomicAdd(a + 1, f1 * omx);
-    unsafeAtomicAdd(b, f0 * wx);
-    unsafeAtomicAdd(b + 1, f1 * wx);
-  } else {
-    float* a = t + 2 * (size_t)(rec.w & 0x3fffu);
-    unsafeAtomicAdd(a, f0);
-    unsafeAtomicAdd(a + 1, f1);
-  }
+  rec_add_unordered(t, rec);
   atomicAdd(hdr + kHdrEvtUnordered, 1u);
 }
 
@@ -157,16 +199,6 @@ __device__ __forceinline__ void spill_append(const ScatterBufs& buf, uint32_t ca
   } else {
     atomicAdd(buf.hdr + kHdrEvtLost, 1u);  // cannot happen: write-only calls size the list for the worst case
   }
-}
-
-struct PairHash {
-  uint32_t ia, ib;
-};
-
-// hashes of the x-pair q (bit0: y is ceil, bit1: z is ceil) of a cell
-__device__ __forceinline__ PairHash pair_hash(const Cell& c, int q, uint32_t mask) {
-  const uint32_t yz = ((uint32_t)((q & 1) ? c.hi[1] : c.lo[1]) * kPrimeY) ^ ((uint32_t)((q & 2) ? c.hi[2] : c.lo[2]) * kPrimeZ);
-  return PairHash{((uint32_t)c.lo[0] ^ yz) & mask, ((uint32_t)c.hi[0] ^ yz) & mask};
 }
 
 #endif  // __HIPCC__

@@ -169,10 +169,8 @@ __global__ __launch_bounds__(kThreads) void scatter_route_fine_kernel(
           const uint32_t tile = ((uint32_t)lvl[i] << G.log2_bins) + bin;
           const uint32_t Q = G.level_cap[lvl[i]];
           uint4* const queue = buf.queues + ((size_t)G.level_off[lvl[i]] + (size_t)bin * Q);
-          // autograd order ((g * wz) * wy) * wx; the x factor is applied by pass 2
-          const float bz = (q & 2) ? c.w[2] : 1.0f - c.w[2];
-          const float by = (q & 1) ? c.w[1] : 1.0f - c.w[1];
-          const float a0 = (g0[j][i] * bz) * by, a1 = (g1[j][i] * bz) * by;
+          float a0, a1;
+          pair_share(c, q, g0[j][i], g1[j][i], a0, a1);
           if ((h.ib >> sl) != bin) {
             // the pair straddles two tiles (needs a carry past bit slice_log2: only when res >= 2^slice_log2, which the
             // host avoids whenever the table allows): two single records through the spill list, in the second sweep
@@ -180,15 +178,13 @@ __global__ __launch_bounds__(kThreads) void scatter_route_fine_kernel(
               over |= 1u << (slot + q);
             } else {
               spill_append(buf, G.spill_cap, tile,
-                           make_uint4(__float_as_uint(a0 * (1.0f - c.w[0])), __float_as_uint(a1 * (1.0f - c.w[0])), 0u,
-                                      h.ia & local_mask));
+                           single_record(a0 * (1.0f - c.w[0]), a1 * (1.0f - c.w[0]), h.ia & local_mask));
               spill_append(buf, G.spill_cap, ((uint32_t)lvl[i] << G.log2_bins) + (h.ib >> sl),
-                           make_uint4(__float_as_uint(a0 * c.w[0]), __float_as_uint(a1 * c.w[0]), 0u, h.ib & local_mask));
+                           single_record(a0 * c.w[0], a1 * c.w[0], h.ib & local_mask));
             }
             continue;
           }
-          const uint4 rec = make_uint4(__float_as_uint(a0), __float_as_uint(a1), __float_as_uint(c.w[0]),
-                                       (h.ia & local_mask) | ((h.ib & local_mask) << 14) | 0x80000000u);
+          const uint4 rec = pair_record(a0, a1, c.w[0], h.ia & local_mask, h.ib & local_mask);
           if (SW == 0) {
             const uint32_t rank = atomicAdd(cnt + (i << G.log2_bins) + bin, 1u);  // ds_add_rtn_u32
             if (rank < C) rec_store(queue + (blockIdx.x * C + rank), rec);
@@ -350,25 +346,20 @@ __device__ __forceinline__ void scatter_route_runs_body(
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
               const PairHash h = pair_hash(cur, q, mask);
-              const float bz = (q & 2) ? cur.w[2] : 1.0f - cur.w[2];
-              const float by = (q & 1) ? cur.w[1] : 1.0f - cur.w[1];
-              const float v0 = (f0 * bz) * by, v1 = (f1 * bz) * by;
+              float v0, v1;
+              pair_share(cur, q, f0, f1, v0, v1);
               if ((h.ib >> sl) == (h.ia >> sl)) {
-                emit(i, h.ia >> sl,
-                     make_uint4(__float_as_uint(v0), __float_as_uint(v1), __float_as_uint(cur.w[0]),
-                                (h.ia & local_mask) | ((h.ib & local_mask) << 14) | 0x80000000u));
+                emit(i, h.ia >> sl, pair_record(v0, v1, cur.w[0], h.ia & local_mask, h.ib & local_mask));
               } else {  // straddling pair: two singles
-                emit(i, h.ia >> sl, make_uint4(__float_as_uint(v0 * (1.0f - cur.w[0])),
-                                               __float_as_uint(v1 * (1.0f - cur.w[0])), 0u, h.ia & local_mask));
-                emit(i, h.ib >> sl, make_uint4(__float_as_uint(v0 * cur.w[0]), __float_as_uint(v1 * cur.w[0]), 0u,
-                                               h.ib & local_mask));
+                emit(i, h.ia >> sl, single_record(v0 * (1.0f - cur.w[0]), v1 * (1.0f - cur.w[0]), h.ia & local_mask));
+                emit(i, h.ib >> sl, single_record(v0 * cur.w[0], v1 * cur.w[0], h.ib & local_mask));
               }
             }
           } else {
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
               const uint32_t idx = corner_index(cur, k, mask);
-              emit(i, idx >> sl, make_uint4(__float_as_uint(a0[k]), __float_as_uint(a1[k]), 0u, idx & local_mask));
+              emit(i, idx >> sl, single_record(a0[k], a1[k], idx & local_mask));
             }
           }
           len = 0;
@@ -382,20 +373,14 @@ __device__ __forceinline__ void scatter_route_runs_body(
             if (len == 1) {  // second sample of the run: open the per-corner sums with the first one (cell weights of cur)
 #pragma unroll
               for (int k = 0; k < 8; ++k) {
-                const float bz = (k & 4) ? cur.w[2] : 1.0f - cur.w[2];
-                const float by = (k & 2) ? cur.w[1] : 1.0f - cur.w[1];
-                const float bx = (k & 1) ? cur.w[0] : 1.0f - cur.w[0];
-                a0[k] = ((f0 * bz) * by) * bx;
-                a1[k] = ((f1 * bz) * by) * bx;
+                a0[k] = corner_share(cur, k, f0);
+                a1[k] = corner_share(cur, k, f1);
               }
             }
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
-              const float bz = (k & 4) ? c.w[2] : 1.0f - c.w[2];
-              const float by = (k & 2) ? c.w[1] : 1.0f - c.w[1];
-              const float bx = (k & 1) ? c.w[0] : 1.0f - c.w[0];
-              a0[k] += ((g0[s][i] * bz) * by) * bx;
-              a1[k] += ((g1[s][i] * bz) * by) * bx;
+              a0[k] += corner_share(c, k, g0[s][i]);
+              a1[k] += corner_share(c, k, g1[s][i]);
             }
             len += 1;
           } else {
@@ -537,17 +522,17 @@ __device__ __forceinline__ void scatter_apply_body(const nsamd_grid& grid, const
   const uint4* q = buf.queues + ((size_t)G.level_off[level] + (size_t)bin * Q);
   const int kk = fs.k;
   auto add_rec = [&](const uint4& r) {
-    const float f0 = __uint_as_float(r.x), f1 = __uint_as_float(r.y);
-    if (r.w & 0x80000000u) {  // x-pair: the x factor of the product ((g*wz)*wy)*wx is applied here
-      const float wx = __uint_as_float(r.z), omx = 1.0f - wx;
-      unsigned long long* a = acc + 2 * (r.w & 0x3fffu);
-      unsigned long long* b = acc + 2 * ((r.w >> 14) & 0x3fffu);
+    const float f0 = rec_f0(r), f1 = rec_f1(r);
+    if (rec_is_pair(r)) {  // x-pair: the x factor of the product ((g*wz)*wy)*wx is applied here
+      const float wx = rec_wx(r), omx = 1.0f - wx;
+      unsigned long long* a = acc + 2 * rec_local_a(r);
+      unsigned long long* b = acc + 2 * rec_local_b(r);
       atomicAdd(a, to_fixed(f0 * omx, kk));  // ds_add_u64, no return
       atomicAdd(a + 1, to_fixed(f1 * omx, kk));
       atomicAdd(b, to_fixed(f0 * wx, kk));
       atomicAdd(b + 1, to_fixed(f1 * wx, kk));
     } else {
-      unsigned long long* a = acc + 2 * (r.w & 0x3fffu);
+      unsigned long long* a = acc + 2 * rec_local_a(r);
       atomicAdd(a, to_fixed(f0, kk));
       atomicAdd(a + 1, to_fixed(f1, kk));
     }
@@ -702,20 +687,7 @@ __device__ __forceinline__ void scatter_finish_body(const nsamd_grid& grid, cons
     const uint32_t tile = buf.spill_tile[e];
     const uint32_t level = tile >> G.log2_bins, bin = tile & ((1u << G.log2_bins) - 1u);
     float* t = dtable + ((((size_t)level << grid.log2_table_size) + ((size_t)bin << G.slice_log2)) << 1);
-    const float f0 = __uint_as_float(r.x), f1 = __uint_as_float(r.y);
-    if (r.w & 0x80000000u) {
-      const float wx = __uint_as_float(r.z), omx = 1.0f - wx;
-      float* a = t + 2 * (size_t)(r.w & 0x3fffu);
-      float* b = t + 2 * (size_t)((r.w >> 14) & 0x3fffu);
-      unsafeAtomicAdd(a, f0 * omx);
-      unsafeAtomicAdd(a + 1, f1 * omx);
-      unsafeAtomicAdd(b, f0 * wx);
-      unsafeAtomicAdd(b + 1, f1 * wx);
-    } else {
-      float* a = t + 2 * (size_t)(r.w & 0x3fffu);
-      unsafeAtomicAdd(a, f0);
-      unsafeAtomicAdd(a + 1, f1);
-    }
+    rec_add_unordered(t, r);
   }
   __syncthreads();
   // the last workgroup to finish (every workgroup has read the counter by then) resets the per-call state

@@ -1,5 +1,5 @@
 // TEST INFRASTRUCTURE (tests/test_kernel_helpers_cpu.py): compiles the per-point arithmetic the HIP kernels share
-// (nerfstudio_amd/csrc/common.h: NSAMD_HD host+device functions; scatter.h: the fixed-point accumulation) with the HOST
+// (nerfstudio_amd/csrc/common.h: NSAMD_HD host+device functions; scatter.h: the fixed-point accumulation, the x-pairs) with the HOST
 // compiler, so that `pytest -m "not gpu"` can pin those functions to the reference's known answers and to the oracle
 // without a GPU. Nothing in the product loads this library; the kernels themselves run these functions on the device.
 #include <math.h>
@@ -29,6 +29,44 @@ void hc_cell_weights(const float* xyz, int64_t n, float scale, float* w /* [n,3]
   for (int64_t p = 0; p < n; ++p) {
     const Cell c = locate_cell(xyz[3 * p], xyz[3 * p + 1], xyz[3 * p + 2], scale);
     for (int a = 0; a < 3; ++a) w[3 * p + a] = c.w[a];
+  }
+}
+
+// HashEncoding.pytorch_fwd from the kernels' own parts (locate_cell, corner_index, trilinear_blend per level and feature) and
+// its dL/dx for the upstream gradient `gout`, summed as position_gradient (csrc/hashgrid.hip) sums it: per level both features
+// through trilinear_blend_grad into (lx, ly, lz), times the level's scale, levels in order
+void hc_hash_forward_and_gradient(const float* xyz, int64_t n, const float* table /* [levels << log2T][2] */,
+                                  const float* scalings, int levels, int log2_table_size, const float* gout /* [n, 2 levels] */,
+                                  float* out /* [n, 2 levels] */, float* dx /* [n,3] */) {
+  const uint32_t mask = (1u << log2_table_size) - 1u;
+  for (int64_t p = 0; p < n; ++p) {
+    dx[3 * p] = dx[3 * p + 1] = dx[3 * p + 2] = 0.0f;
+    for (int l = 0; l < levels; ++l) {
+      const Cell c = locate_cell(xyz[3 * p], xyz[3 * p + 1], xyz[3 * p + 2], scalings[l]);
+      const float* tl = table + 2 * ((size_t)l << log2_table_size);
+      float lx = 0.0f, ly = 0.0f, lz = 0.0f;
+      for (int f = 0; f < 2; ++f) {
+        auto q = [&](int k) { return tl[2 * (size_t)corner_index(c, k, mask) + f]; };
+        out[p * 2 * levels + 2 * l + f] = trilinear_blend(q, c.w[0], c.w[1], c.w[2]);
+        trilinear_blend_grad(q, gout[p * 2 * levels + 2 * l + f], c.w[0], c.w[1], c.w[2], lx, ly, lz);
+      }
+      dx[3 * p] += lx * scalings[l];
+      dx[3 * p + 1] += ly * scalings[l];
+      dx[3 * p + 2] += lz * scalings[l];
+    }
+  }
+}
+
+// the shares of one level's two feature gradients g [n,2]: corner_share for the 8 corners, pair_share for the 4 x-pairs
+void hc_gradient_shares(const float* xyz, int64_t n, float scale, const float* g, float* corner /* [n,8,2] */,
+                        float* pair /* [n,4,2] */) {
+  for (int64_t p = 0; p < n; ++p) {
+    const Cell c = locate_cell(xyz[3 * p], xyz[3 * p + 1], xyz[3 * p + 2], scale);
+    for (int k = 0; k < 8; ++k)
+      for (int f = 0; f < 2; ++f) corner[(8 * p + k) * 2 + f] = corner_share(c, k, g[2 * p + f]);
+    for (int q = 0; q < 4; ++q) {
+      pair_share(c, q, g[2 * p], g[2 * p + 1], pair[(4 * p + q) * 2], pair[(4 * p + q) * 2 + 1]);
+    }
   }
 }
 

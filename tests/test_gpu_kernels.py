@@ -157,6 +157,29 @@ def test_hashgrid_main_table_bit_exact_vs_oracle(F):
     exact(out, o, "main-table hash features are not bit-identical to the oracle")
 
 
+def test_hashgrid_large_table_odd_level_count_bit_exact_vs_oracle(F):
+    """The lane-pair forward WITHOUT the XCD level sweep (hash_encode_fwd_v3_kernel<false>, csrc/hashgrid.hip): a large table
+    whose level count is no multiple of 8. L = 5, 16 .. 512, T = 2^18 — the smallest table that leaves the four-levels-per-thread
+    kernel (8 B x 2^18 = 2 MiB) — on 1003 points: an odd count, so the last lane pair works with a dead lane. Lattice planes and
+    the box's faces as in the main-table test; features bit-identical to the oracle."""
+    from nerfstudio_amd.field_components.encodings import HashEncoding
+
+    L, lo, hi, log2T = 5, 16, 512, 18
+    enc = HashEncoding(num_levels=L, min_res=lo, max_res=hi, log2_hashmap_size=log2T).cuda()
+    rs = np.random.RandomState(12)
+    table = (rs.standard_normal((L * 2**log2T, 2)) * 0.1).astype(np.float32)
+    with torch.no_grad():
+        enc.hash_table.copy_(dev(table))
+    x = rs.uniform(0, 1, (1003, 3)).astype(np.float32)
+    x[:64] = np.round(x[:64] * 16) / 16          # on lattice planes of the coarsest level (lo == hi there)
+    x[64:96] = rs.randint(0, 2, (32, 3))          # the box's corners and faces
+    x[96:128, 0] = 1.0
+    out = enc(dev(x))
+    assert out.shape == (1003, 2 * L)
+    o = orc.hashgrid_encode(T(x), T(table), orc.hash_level_scalings(L, lo, hi), 2**log2T)
+    exact(out, o, "large-table, 5-level hash features are not bit-identical to the oracle")
+
+
 def test_hashgrid_shapes_and_edges(F):
     """Reference test contract (tests/field_components/test_encodings.py:143-169): shape (10,16) for L=8,F=2; plus
     empty input and batch-shape preservation."""

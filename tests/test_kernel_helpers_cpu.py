@@ -1,5 +1,6 @@
 """CPU tests of the arithmetic the HIP kernels share (nerfstudio_amd/csrc/common.h, scatter.h), compiled for the host by
-tests/hostcheck/helpers.cc: spatial hash, cell location and blend weights, scene contraction and its backward, position
+tests/hostcheck/helpers.cc: spatial hash, cell location and blend weights, the trilinear blend, its position gradient and
+the corner / x-pair shares of the table gradient, scene contraction and its backward, position
 normalisation + selector, spherical harmonics, the piecewise spacing functions, Frustums.get_positions, nan_to_num, and
 the 64-bit fixed-point accumulation of the table scatter. Pinned to the reference's known answers (tests/golden/kat.npz,
 hashgrid.npz — written by the reference itself) and to the oracle. The library built here is test infrastructure: the
@@ -30,6 +31,8 @@ def hc(tmp_path_factory):
     lib = C.CDLL(out)
     lib.hc_hash_corners.argtypes = [F32P, C.c_int64, C.c_float, C.c_int, I64P]
     lib.hc_cell_weights.argtypes = [F32P, C.c_int64, C.c_float, F32P]
+    lib.hc_hash_forward_and_gradient.argtypes = [F32P, C.c_int64, F32P, F32P, C.c_int, C.c_int, F32P, F32P, F32P]
+    lib.hc_gradient_shares.argtypes = [F32P, C.c_int64, C.c_float, F32P, F32P, F32P]
     lib.hc_hash_fn.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int]
     lib.hc_hash_fn.restype = C.c_uint32
     lib.hc_contract.argtypes = [F32P, C.c_int64]
@@ -65,21 +68,40 @@ def test_hash_fn_known_answers(hc):
         assert hc.hc_hash_fn(ix, iy, iz, 19) == ref
 
 
-def test_hash_forward_from_the_kernel_helpers_reproduces_the_reference_fixture(hc):
-    """hashgrid.npz holds HashEncoding.pytorch_fwd of the reference on 240 points: rebuilding it from locate_cell /
-    corner_index / the blend weights (the functions every hash kernel is made of) must give the same features, and the
-    corner indices must equal the oracle's bit for bit."""
+def _fixture_grid():
+    """hashgrid.npz (HashEncoding.pytorch_fwd and its autograd backward, written by the reference on 240 points) ->
+    (arrays, levels, T, log2 T)."""
     g = load_golden("hashgrid")
+    levels = len(g["scalings"])
+    T = g["table"].shape[0] // levels
+    return g, levels, T, int(math.log2(T))
+
+
+def _cells(hc, x, scale, log2_T):
+    """corner indices [n,8] within the level and blend weights [n,3] of locate_cell / corner_index."""
+    idx, w = np.zeros((x.shape[0], 8), np.int64), np.zeros((x.shape[0], 3), np.float32)
+    hc.hc_hash_corners(x, x.shape[0], float(scale), log2_T, idx)
+    hc.hc_cell_weights(x, x.shape[0], float(scale), w)
+    return idx, w
+
+
+def _forward_and_gradient(hc, g, levels, log2_T):
+    """(features [n, 2 L], dL/dx [n, 3] for the fixture's upstream gradient) of tests/hostcheck's hc_hash_forward_and_gradient."""
+    n = g["x"].shape[0]
+    out, dx = np.zeros((n, 2 * levels), np.float32), np.zeros((n, 3), np.float32)
+    hc.hc_hash_forward_and_gradient(g["x"], n, np.ascontiguousarray(g["table"]), np.ascontiguousarray(g["scalings"]), levels,
+                                    log2_T, np.ascontiguousarray(g["gout"]), out, dx)
+    return out, dx
+
+
+def test_hash_forward_from_the_kernel_helpers_reproduces_the_reference_fixture(hc):
+    """hashgrid.npz holds HashEncoding.pytorch_fwd of the reference on 240 points: locate_cell / corner_index /
+    trilinear_blend (the functions every hash forward is made of) must give the same features BIT FOR BIT — the blend is the
+    reference's operation order —, and the corner indices must equal the oracle's bit for bit."""
+    g, levels, T, log2_T = _fixture_grid()
     x, table, scalings = g["x"], g["table"], g["scalings"]
-    levels = len(scalings)
-    T = table.shape[0] // levels
-    log2_T = int(math.log2(T))
-    out = np.zeros((x.shape[0], 2 * levels), np.float32)
     for lvl, scale in enumerate(scalings):
-        idx = np.zeros((x.shape[0], 8), np.int64)
-        w = np.zeros((x.shape[0], 3), np.float32)
-        hc.hc_hash_corners(x, x.shape[0], float(scale), log2_T, idx)
-        hc.hc_cell_weights(x, x.shape[0], float(scale), w)
+        idx, _ = _cells(hc, x, scale, log2_T)
         sx = x * np.float32(scale)
         lo, hi = np.floor(sx).astype(np.int64), np.ceil(sx).astype(np.int64)
         for k in range(8):
@@ -87,14 +109,103 @@ def test_hash_forward_from_the_kernel_helpers_reproduces_the_reference_fixture(h
             cy = np.where(k & 2, hi[:, 1], lo[:, 1])
             cz = np.where(k & 4, hi[:, 2], lo[:, 2])
             np.testing.assert_array_equal(idx[:, k] + lvl * T, O.hash_corner_index(cx, cy, cz, lvl, T))
-        acc = np.zeros((x.shape[0], 2), np.float64)
+    out, _ = _forward_and_gradient(hc, g, levels, log2_T)
+    assert out.size == 2880
+    np.testing.assert_array_equal(out.view(np.uint32), g["out"].view(np.uint32))
+
+
+def _position_gradient64(hc, g, levels, T, log2_T, variant=None):
+    """dL/dx of the fixture's forward in float64 on the fp32 inputs (cell weights, table rows, scalings, upstream gradient),
+    written as the derivative of the x -> y -> z blend, and A, the same sum over the absolute values of its terms
+    scale * |g| * (weights of the two other axes) * |corner value|. `variant`: a deliberately wrong restatement."""
+    x, table = g["x"], g["table"].astype(np.float64)
+    dx, A = np.zeros((x.shape[0], 3)), np.zeros((x.shape[0], 3))
+    for lvl, scale in enumerate(g["scalings"]):
+        idx, w32 = _cells(hc, x, scale, log2_T)
+        w = w32.astype(np.float64)
+        wx, wy, wz = (w[:, a, None] for a in range(3))
+        if variant == "wx_ux_exchanged":
+            wx = 1.0 - wx
+        ux, uy, uz = 1.0 - wx, 1.0 - wy, 1.0 - wz
+        q = [table[idx[:, k] + lvl * T] for k in range(8)]  # [n, 2] per corner
+        gf = g["gout"][:, 2 * lvl:2 * lvl + 2].astype(np.float64)
+        yc_zc, yf_zc = q[7] * wx + q[6] * ux, q[5] * wx + q[4] * ux
+        yf_zf, yc_zf = q[1] * wx + q[0] * ux, q[3] * wx + q[2] * ux
+        zc, zf = yc_zc * wy + yf_zc * uy, yc_zf * wy + yf_zf * uy
+        lz = gf * (zc - zf)
+        ly = gf * (wz * (yc_zc - yf_zc) + uz * (yc_zf - yf_zf))
+        d = [q[7] - q[6], q[5] - q[4], q[1] - q[0], q[3] - q[2]]
+        if variant == "corner_pairs_exchanged":
+            d[0], d[1] = d[1], d[0]
+        lx = gf * (wz * wy * d[0] + wz * uy * d[1] + uz * uy * d[2] + uz * wy * d[3])
+        s = 1.0 if variant == "scale_dropped" else float(scale)
+        dx += s * np.stack([lx.sum(1), ly.sum(1), lz.sum(1)], axis=1)
+        a = [np.abs(v) for v in q]
+        az = (a[7] * wx + a[6] * ux) * wy + (a[5] * wx + a[4] * ux) * uy + (a[3] * wx + a[2] * ux) * wy + (a[1] * wx + a[0] * ux) * uy
+        ay = wz * (a[7] * wx + a[6] * ux + a[5] * wx + a[4] * ux) + uz * (a[3] * wx + a[2] * ux + a[1] * wx + a[0] * ux)
+        ax = wz * wy * (a[7] + a[6]) + wz * uy * (a[5] + a[4]) + uz * uy * (a[1] + a[0]) + uz * wy * (a[3] + a[2])
+        A += float(scale) * np.stack([(np.abs(gf) * ax).sum(1), (np.abs(gf) * ay).sum(1), (np.abs(gf) * az).sum(1)], axis=1)
+    return dx, A
+
+
+def test_position_gradient_from_the_kernel_helpers_vs_float64(hc):
+    """trilinear_blend_grad summed as position_gradient (csrc/hashgrid.hip) sums it, against a float64 restatement on the same
+    fp32 inputs, entry by entry.
+
+    Bound (the style of tests/linear_reference.py): every term scale * g * (two weights) * (corner value) of an entry reaches
+    the result through at most D fp32 roundings, so |got - ref| <= gamma_D * A with gamma_D = D u / (1 - D u), u = 2^-24, A the
+    float64 sum of the absolute terms. D = 13 + L, the longest of the three chains, that of dx: 1 - wz, g * wz, 1 - wy,
+    (g wz) * wy, q(7) - q(6), their product, 3 additions of the four products, 2 additions into lx over the features, the product
+    with the scale, L additions over the levels (dy: 12 + L, dz: 11 + L). The weights themselves (scaled - floor(scaled)) are
+    inputs of both sides.
+
+    The bound hides nothing: the fixture's own dx — autograd's sums, in another order, which differ from position_gradient's in
+    477 of 720 entries' bits — has to pass the same bound, and three wrong gradients must each fail it."""
+    g, levels, T, log2_T = _fixture_grid()
+    ref, A = _position_gradient64(hc, g, levels, T, log2_T)
+    D = 13 + levels
+    bound = D * 2.0 ** -24 / (1.0 - D * 2.0 ** -24) * A
+
+    def outside(v):
+        err = np.abs(np.asarray(v, np.float32).astype(np.float64) - ref)
+        return int((~(err <= bound)).sum())
+
+    _, got = _forward_and_gradient(hc, g, levels, log2_T)
+    assert got.size == 720 and np.abs(ref).max() > 100.0
+    assert (got.view(np.uint32) != g["dx"].view(np.uint32)).sum() > 0  # (two summation orders: not the same bits)
+    assert outside(got) == 0
+    assert outside(g["dx"]) == 0  # the reference's autograd result, under the same bound
+    for variant in ("wx_ux_exchanged", "scale_dropped", "corner_pairs_exchanged"):
+        wrong, _ = _position_gradient64(hc, g, levels, T, log2_T, variant)
+        assert outside(wrong.astype(np.float32)) > 0, variant
+
+
+def test_gradient_shares_from_the_kernel_helpers(hc):
+    """corner_share (common.h) and pair_share (scatter.h) on the fixture's 240 points x 6 levels: bit-identical to their fp32
+    restatement ((g * bz) * by) * bx and (g * bz) * by in numpy; a pair's share times the x weight IS the corner's share (what
+    pass 2 of the scatter does with a pair record); and the corner shares, accumulated in float64, are the reference's table
+    gradient to test_hashgrid_golden's tolerance."""
+    g, levels, T, log2_T = _fixture_grid()
+    x = g["x"]
+    n = x.shape[0]
+    dtable = np.zeros(g["table"].shape, np.float64)
+    one = np.float32(1.0)
+    for lvl, scale in enumerate(g["scalings"]):
+        idx, w = _cells(hc, x, scale, log2_T)
+        gl = np.ascontiguousarray(g["gout"][:, 2 * lvl:2 * lvl + 2])
+        corner, pair = np.zeros((n, 8, 2), np.float32), np.zeros((n, 4, 2), np.float32)
+        hc.hc_gradient_shares(x, n, float(scale), gl, corner, pair)
         for k in range(8):
-            wk = np.ones(x.shape[0], np.float64)
-            for a, bit in enumerate((1, 2, 4)):
-                wk = wk * np.where(k & bit, w[:, a], 1.0 - w[:, a])
-            acc += wk[:, None] * table[idx[:, k] + lvl * T]
-        out[:, 2 * lvl:2 * lvl + 2] = acc
-    np.testing.assert_allclose(out, g["out"], rtol=0, atol=2e-6)
+            bz = (w[:, 2] if k & 4 else one - w[:, 2])[:, None]
+            by = (w[:, 1] if k & 2 else one - w[:, 1])[:, None]
+            bx = (w[:, 0] if k & 1 else one - w[:, 0])[:, None]
+            want_pair = (gl * bz) * by
+            assert want_pair.dtype == np.float32
+            np.testing.assert_array_equal(pair[:, k >> 1].view(np.uint32), want_pair.view(np.uint32))
+            np.testing.assert_array_equal(corner[:, k].view(np.uint32), (want_pair * bx).view(np.uint32))
+            np.testing.assert_array_equal(corner[:, k].view(np.uint32), (pair[:, k >> 1] * bx).view(np.uint32))
+            np.add.at(dtable, idx[:, k] + lvl * T, corner[:, k].astype(np.float64))
+    np.testing.assert_allclose(dtable, g["dtable"], rtol=1e-3, atol=1e-5 * float(np.abs(g["dtable"]).max()))
 
 
 def test_contraction_known_answers_and_backward(hc):
