@@ -255,9 +255,10 @@ def scatter_events(ws: Tensor) -> Tuple[int, int, int]:
 
 
 # ---------------------------------------------------------------------------------------------------------------
-# launch records and launches shared by the autograd functions below and the explicit schedules (train_step,
-# eval_render, ngp_step). Records are built at launch time, never cached: they hold raw addresses, and an arena built
-# later re-homes the parameters.
+# launch records and launches shared by the autograd Functions below and the explicit schedules (train_step,
+# eval_render, ngp_step): `hash_forward`, `table_scatter`, `ray_terms_launch`, `field_forward`, `field_backward` and
+# `density_backward` take tensors and records, never a module, and are the only callers of their entry points. Records
+# are built at launch time, never cached: they hold raw addresses, and an arena built later re-homes the parameters.
 # ---------------------------------------------------------------------------------------------------------------
 def density_mlp(W0: Tensor, b0: Tensor, W1: Tensor, b1: Tensor, average_init_density: float) -> N.DensityMlp:
     """nsamd_density_mlp of a proposal network's MLP (HashMLPDensityField: `mlp_base[1].param_tensors()`)."""
@@ -286,6 +287,14 @@ def field_mlp_grads(params: Sequence[Tensor], appearance: Optional[Tensor], grad
     return N.FieldMlpGrads(*(N.ptr(grad_of(p)) for p in params), N.ptr(grad_of(appearance)) if appearance is not None else None)
 
 
+def hash_forward(pts: N.Points, M: int, transform: int, box: N.Aabb, table: Tensor, grid: HashGridSpec, enc: Tensor,
+                 stride_p: int, stride_k: int, sel: Optional[Tensor]) -> None:
+    """nsamd_hashgrid_encode_fwd on the current stream: the hash features of M points after the position normalisation
+    `transform` / `box` into `enc` (point p, feature k at p * stride_p + k * stride_k) and, unless None, the selector `sel`."""
+    N.check(N.load().nsamd_hashgrid_encode_fwd(pts, M, transform, box, N.ptr(table), grid.native(), N.ptr(enc), stride_p,
+                                               stride_k, N.ptr(sel), N.stream()), "hashgrid_encode_fwd")
+
+
 def table_scatter(pts: N.Points, M: int, transform: int, box: N.Aabb, table: Tensor, grid: HashGridSpec, denc: Tensor,
                   stride_p: int, stride_k: int, dtable: Optional[Tensor], dpos: Optional[Tensor] = None,
                   write_only: bool = False) -> None:
@@ -299,36 +308,47 @@ def table_scatter(pts: N.Points, M: int, transform: int, box: N.Aabb, table: Ten
                N.ptr(ws), ws_n, N.stream()), "hashgrid_encode_bwd")
 
 
-def field_forward(fld, pts: N.Points, M: int, enc: Tensor, sel: Tensor, dirs: Tensor, cams: Optional[Tensor],
-                  app_const: Optional[Tensor], dir_group: int, mlp: N.FieldMlp, density: Tensor, rgb: Optional[Tensor]) -> None:
+def ray_terms_apply(dir_group: int, M: int) -> bool:
+    """The ray-terms rule (include/nsamd.h, nsamd_field_mlp.ray_terms): samples grouped by ray, whole 16-sample tiles per ray."""
+    return dir_group % 16 == 0 and M % dir_group == 0 and M > 0
+
+
+def ray_terms_launch(dirs: Tensor, cams: Optional[Tensor], app_const: Optional[Tensor], rays: int, mlp: N.FieldMlp,
+                     terms: Tensor, inputs: Optional[Tensor]) -> None:
+    """nsamd_field_ray_terms on the current stream: head layer 0's share of the 48 per-ray inputs (SH of the view direction,
+    appearance row) into `terms` `[rays, 64]`, the inputs themselves into `inputs` `[rays, 48 | 16]` (None: not kept)."""
+    N.check(N.load().nsamd_field_ray_terms(N.ptr(dirs), N.ptr(cams), N.ptr(app_const), rays, mlp, N.ptr(terms), N.ptr(inputs),
+                                           N.stream()), "field_ray_terms")
+
+
+def field_forward(table: Tensor, grid: HashGridSpec, transform: int, box: N.Aabb, pts: N.Points, M: int, enc: Tensor,
+                  sel: Tensor, dirs: Tensor, cams: Optional[Tensor], app_const: Optional[Tensor], dir_group: int,
+                  mlp: N.FieldMlp, density: Tensor, rgb: Optional[Tensor]) -> None:
     """Hash grid + MLPs of a NerfactoField on M points, on the current stream: encoded features `enc` (feature-major) and
     selector `sel`, then density and rgb (None: density only). Point p takes direction / camera row p // dir_group;
     cams None -> the appearance row `app_const` for every point."""
-    lib, st = N.load(), N.stream()
-    tbl = fld.mlp_base.encoding
-    N.check(lib.nsamd_hashgrid_encode_fwd(pts, M, fld._transform, fld._box, N.ptr(tbl.hash_table), tbl.spec.native(), N.ptr(enc),
-                                          1, M, N.ptr(sel), st), "hashgrid_encode_fwd")
-    N.check(lib.nsamd_field_mlp_fwd(N.ptr(enc), N.ptr(sel), N.ptr(dirs), N.ptr(cams), N.ptr(app_const), dir_group, M, mlp,
-                                    N.ptr(density), N.ptr(rgb), st), "field_mlp_fwd")
+    hash_forward(pts, M, transform, box, table, grid, enc, 1, M, sel)
+    N.check(N.load().nsamd_field_mlp_fwd(N.ptr(enc), N.ptr(sel), N.ptr(dirs), N.ptr(cams), N.ptr(app_const), dir_group, M, mlp,
+                                         N.ptr(density), N.ptr(rgb), N.stream()), "field_mlp_fwd")
 
 
-def field_backward(fld, pts: N.Points, M: int, enc: Tensor, sel: Tensor, dirs: Tensor, cams: Optional[Tensor],
-                   app_const: Optional[Tensor], dir_group: int, mlp: N.FieldMlp, ddens: Tensor, drgb: Tensor, denc: Tensor,
-                   grads: N.FieldMlpGrads, fws: Tensor, dtable: Tensor, write_only: bool, fuse: bool = True,
-                   keep_denc: bool = False, on_denc=None, fused_launch=None) -> None:
+def field_backward(table: Tensor, grid: HashGridSpec, transform: int, box: N.Aabb, pts: N.Points, M: int, enc: Tensor,
+                   sel: Tensor, dirs: Tensor, cams: Optional[Tensor], app_const: Optional[Tensor], dir_group: int,
+                   mlp: N.FieldMlp, ddens: Tensor, drgb: Tensor, denc: Tensor, grads: N.FieldMlpGrads, fws: Tensor,
+                   dtable: Optional[Tensor], write_only: bool, fuse: bool = True, keep_denc: bool = False, on_denc=None,
+                   fused_launch=None, dpos: Optional[Tensor] = None) -> None:
     """Backward of `field_forward` from the density / rgb gradients: the MLPs' gradients into `grads` (`fws`: the
     field_bwd_workspace), the table's into `dtable`. When the table gradient is written (write_only), the grid has 16
     levels and the library plans a producer workspace, the MLP backward emits the table scatter's records itself
     (nsamd_field_mlp_bwd_scatter: no `denc` round trip, no route launch; `denc` is stored only with keep_denc) —
     `fused_launch(args)` issues it instead of the single launch when given (args: the entry point's arguments before the
-    phase and the stream). Otherwise nsamd_field_mlp_bwd writes `denc`, then `on_denc()` runs, then the table scatter."""
+    phase and the stream). Otherwise, and always with `dpos` (dL/dposition, which only the scatter can return),
+    nsamd_field_mlp_bwd writes `denc`, then `on_denc()` runs, then the table scatter unless `dtable` and `dpos` are None."""
     lib, st = N.load(), N.stream()
-    tbl = fld.mlp_base.encoding
-    grid = tbl.spec
-    if fuse and write_only and grid.num_levels == 16:
+    if fuse and write_only and dpos is None and grid.num_levels == 16:
         sws, sws_n = _producer_scatter_workspace(grid, denc.device, M)
         if sws is not None:
-            args = (pts, fld._transform, fld._box, grid.native(), N.ptr(enc), N.ptr(sel), N.ptr(dirs), N.ptr(cams),
+            args = (pts, transform, box, grid.native(), N.ptr(enc), N.ptr(sel), N.ptr(dirs), N.ptr(cams),
                     N.ptr(app_const), dir_group, M, mlp, N.ptr(ddens), N.ptr(drgb), N.ptr(denc) if keep_denc else None, grads,
                     N.ptr(fws), fws.numel(), N.ptr(dtable), N.ptr(sws), sws_n)
             if fused_launch is not None:
@@ -340,17 +360,38 @@ def field_backward(fld, pts: N.Points, M: int, enc: Tensor, sel: Tensor, dirs: T
                                     N.ptr(ddens), N.ptr(drgb), N.ptr(denc), grads, N.ptr(fws), fws.numel(), st), "field_mlp_bwd")
     if on_denc is not None:
         on_denc()
-    table_scatter(pts, M, fld._transform, fld._box, tbl.hash_table, grid, denc, 1, M, dtable, write_only=write_only)
+    if dtable is not None or dpos is not None:
+        table_scatter(pts, M, transform, box, table, grid, denc, 1, M, dtable, dpos, write_only=write_only)
 
 
-def _position_grads(spec: PointSpec, dpos: Tensor):
-    """dL/dpositions [M,3] -> gradients of whatever the spec was built from."""
+def density_backward(enc: Tensor, sel: Tensor, pre: Tensor, ddens: Tensor, M: int, mlp: N.DensityMlp, denc: Tensor,
+                     grads: Sequence[Tensor], ws: Tensor) -> None:
+    """The ungated nsamd_density_mlp_bwd on the current stream: from the density gradient `ddens` the encoded-feature gradient
+    `denc` (feature-major) and the gradients of W0, b0, W1, b1 accumulated into `grads`; `ws`: a density_bwd_workspace."""
+    N.check(N.load().nsamd_density_mlp_bwd(N.ptr(enc), N.ptr(sel), N.ptr(pre), N.ptr(ddens), M, mlp, N.ptr(denc),
+                                           *(N.ptr(g) for g in grads), N.ptr(ws), ws.numel(), N.stream()), "density_mlp_bwd")
+
+
+def _position_grads(spec: PointSpec, dpos: Optional[Tensor]):
+    """dL/dpositions [M,3] (None: not wanted) -> gradients of whatever the spec was built from."""
+    if dpos is None:
+        return None, None, None
     if not spec.ray_mode:
         return dpos, None, None
     n, s1 = spec.t_bins.shape
     d = dpos.view(n, s1 - 1, 3)
     mid = ((spec.t_bins[:, :-1] + spec.t_bins[:, 1:]) / 2)[..., None]
     return None, d.sum(dim=1), (d * mid).sum(dim=1)
+
+
+def _table_and_position_grads(ctx, spec, table, table_ref, grid, transform, box, denc, stride_p, stride_k):
+    """End of the backward of a Function whose inputs begin (positions, origins, directions, t_bins, table): the table scatter
+    from the encoded-feature gradient `denc` -> (gradients of the first three, what autograd gets for the table)."""
+    ttable, rtable = _grad_target(table_ref, ctx.needs_input_grad[4])
+    dpos = torch.empty((spec.num_points, 3), device=table.device, dtype=torch.float32) if any(ctx.needs_input_grad[:3]) else None
+    if ttable is not None or dpos is not None:
+        table_scatter(spec.native(), spec.num_points, transform, box, table, grid, denc, stride_p, stride_k, ttable, dpos)
+    return (*_position_grads(spec, dpos), rtable)
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -363,12 +404,7 @@ class _HashEncodeFn(torch.autograd.Function):
         x = _f32c(x)
         M = x.shape[0]
         out = torch.empty((M, grid.out_dim), device=x.device, dtype=torch.float32)
-        pts = N.make_points(positions=x)
-        N.check(
-            N.load().nsamd_hashgrid_encode_fwd(pts, M, N.XFORM_NONE, N.Aabb(), N.ptr(table), grid.native(), N.ptr(out),
-                                              grid.out_dim, 1, None, N.stream()),
-            "hashgrid_encode_fwd",
-        )
+        hash_forward(N.make_points(positions=x), M, N.XFORM_NONE, N.Aabb(), table, grid, out, grid.out_dim, 1, None)
         ctx.save_for_backward(x, table)
         ctx.grid = grid
         return out
@@ -377,12 +413,11 @@ class _HashEncodeFn(torch.autograd.Function):
     def backward(ctx, gout: Tensor):
         x, table = ctx.saved_tensors
         grid: HashGridSpec = ctx.grid
-        gout = _f32c(gout)
-        M = x.shape[0]
         dtable = torch.zeros_like(table) if ctx.needs_input_grad[1] else None
         dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
         if dtable is not None or dx is not None:
-            table_scatter(N.make_points(positions=x), M, N.XFORM_NONE, N.Aabb(), table, grid, gout, grid.out_dim, 1, dtable, dx)
+            table_scatter(N.make_points(positions=x), x.shape[0], N.XFORM_NONE, N.Aabb(), table, grid, _f32c(gout),
+                          grid.out_dim, 1, dtable, dx)
         return dx, dtable, None
 
 
@@ -404,8 +439,7 @@ class _SpecEncodeFn(torch.autograd.Function):
         enc = torch.empty((M, grid.out_dim), device=table.device, dtype=torch.float32)
         sel = torch.empty((M,), device=table.device, dtype=torch.float32)
         box = aabb if isinstance(aabb, N.Aabb) else N.make_aabb(aabb)
-        N.check(N.load().nsamd_hashgrid_encode_fwd(spec.native(), M, transform, box, N.ptr(table), grid.native(), N.ptr(enc),
-                                                   grid.out_dim, 1, N.ptr(sel), N.stream()), "hashgrid_encode_fwd")
+        hash_forward(spec.native(), M, transform, box, table, grid, enc, grid.out_dim, 1, sel)
         ctx.spec, ctx.grid, ctx.transform, ctx.box, ctx.table_ref = spec, grid, transform, box, table
         ctx.save_for_backward(table)
         ctx.mark_non_differentiable(sel)
@@ -414,15 +448,8 @@ class _SpecEncodeFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, genc: Tensor, _gsel):
         (table,) = ctx.saved_tensors
-        spec: PointSpec = ctx.spec
-        M = spec.num_points
-        genc = _f32c(genc)
-        need_pos = any(ctx.needs_input_grad[:3])
-        ttable, rtable = _grad_target(ctx.table_ref, ctx.needs_input_grad[4])
-        dpos = torch.empty((M, 3), device=table.device, dtype=torch.float32) if need_pos else None
-        if ttable is not None or dpos is not None:
-            table_scatter(spec.native(), M, ctx.transform, ctx.box, table, ctx.grid, genc, ctx.grid.out_dim, 1, ttable, dpos)
-        gp, go, gd = _position_grads(spec, dpos) if dpos is not None else (None, None, None)
+        gp, go, gd, rtable = _table_and_position_grads(ctx, ctx.spec, table, ctx.table_ref, ctx.grid, ctx.transform, ctx.box,
+                                                       _f32c(genc), ctx.grid.out_dim, 1)
         return gp, go, gd, None, rtable, None, None, None
 
 
@@ -527,19 +554,16 @@ class _DensityFieldFn(torch.autograd.Function):
                 transform: int, aabb, avg_density: float):
         spec = _spec_from_flat(positions, origins, directions, t_bins)
         N.require_cuda(table, W0, b0, W1, b1)
-        lib = N.load()
         M = spec.num_points
         dev = table.device
         enc = torch.empty((grid.out_dim, M), device=dev, dtype=torch.float32)  # feature-major
         sel = torch.empty((M,), device=dev, dtype=torch.float32)
-        g = grid.native()
         box = aabb if isinstance(aabb, N.Aabb) else N.make_aabb(aabb)
-        N.check(lib.nsamd_hashgrid_encode_fwd(spec.native(), M, transform, box, N.ptr(table), g, N.ptr(enc), 1, M,
-                                              N.ptr(sel), N.stream()), "hashgrid_encode_fwd")
+        hash_forward(spec.native(), M, transform, box, table, grid, enc, 1, M, sel)
         mlp = density_mlp(W0, b0, W1, b1, avg_density)
         density = torch.empty((M,), device=dev, dtype=torch.float32)
         pre = torch.empty((M,), device=dev, dtype=torch.float32)
-        N.check(lib.nsamd_density_mlp_fwd(N.ptr(enc), N.ptr(sel), M, mlp, N.ptr(density), N.ptr(pre), N.stream()),
+        N.check(N.load().nsamd_density_mlp_fwd(N.ptr(enc), N.ptr(sel), M, mlp, N.ptr(density), N.ptr(pre), N.stream()),
                 "density_mlp_fwd")
         ctx.spec, ctx.grid, ctx.transform, ctx.box, ctx.avg = spec, grid, transform, box, avg_density
         ctx.param_refs = (table, W0, b0, W1, b1)
@@ -550,24 +574,13 @@ class _DensityFieldFn(torch.autograd.Function):
     def backward(ctx, gdens: Tensor):
         table, W0, b0, W1, b1, enc, sel, pre = ctx.saved_tensors
         spec: PointSpec = ctx.spec
-        lib = N.load()
         M = spec.num_points
-        gdens = _f32c(gdens)
         denc = torch.empty_like(enc)
         refs = ctx.param_refs
         (tW0, rW0), (tb0, rb0), (tW1, rW1), (tb1, rb1) = (_grad_target(r, True) for r in refs[1:])
-        mlp = density_mlp(W0, b0, W1, b1, ctx.avg)
-        dws = density_bwd_workspace(table.device)
-        N.check(lib.nsamd_density_mlp_bwd(N.ptr(enc), N.ptr(sel), N.ptr(pre), N.ptr(gdens), M, mlp, N.ptr(denc),
-                                          N.ptr(tW0), N.ptr(tb0), N.ptr(tW1), N.ptr(tb1), N.ptr(dws), dws.numel(),
-                                          N.stream()),
-                "density_mlp_bwd")
-        need_pos = any(ctx.needs_input_grad[:3])
-        ttable, rtable = _grad_target(refs[0], ctx.needs_input_grad[4])
-        dpos = torch.empty((M, 3), device=table.device, dtype=torch.float32) if need_pos else None
-        if ttable is not None or dpos is not None:
-            table_scatter(spec.native(), M, ctx.transform, ctx.box, table, ctx.grid, denc, 1, M, ttable, dpos)
-        gp, go, gd = _position_grads(spec, dpos) if dpos is not None else (None, None, None)
+        density_backward(enc, sel, pre, _f32c(gdens), M, density_mlp(W0, b0, W1, b1, ctx.avg), denc, (tW0, tb0, tW1, tb1),
+                         density_bwd_workspace(table.device))
+        gp, go, gd, rtable = _table_and_position_grads(ctx, spec, table, refs[0], ctx.grid, ctx.transform, ctx.box, denc, 1, M)
         return gp, go, gd, None, rtable, rW0, rb0, rW1, rb1, None, None, None, None
 
 
@@ -595,7 +608,6 @@ class _NerfactoFieldFn(torch.autograd.Function):
                 "nsamd main-field kernels are built for the nerfacto shape: L=16,F=2 -> 64 -> 16, head 31|63 -> 64 -> 64 "
                 f"-> 3; got base {tuple(bW0.shape)}/{tuple(bW1.shape)}, head {tuple(hW0.shape)}/{tuple(hW1.shape)}/"
                 f"{tuple(hW2.shape)}")
-        lib = N.load()
         M = spec.num_points
         dev = table.device
         view_dirs = _f32c(view_dirs)
@@ -603,25 +615,19 @@ class _NerfactoFieldFn(torch.autograd.Function):
         enc = torch.empty((grid.out_dim, M), device=dev, dtype=torch.float32)
         sel = torch.empty((M,), device=dev, dtype=torch.float32)
         box = aabb if isinstance(aabb, N.Aabb) else N.make_aabb(aabb)
-        N.check(lib.nsamd_hashgrid_encode_fwd(spec.native(), M, transform, box, N.ptr(table), grid.native(),
-                                              N.ptr(enc), 1, M, N.ptr(sel), N.stream()), "hashgrid_encode_fwd")
         mlp = field_mlp(params, appearance, avg_density)
         density = torch.empty((M,), device=dev, dtype=torch.float32)
         rgb = torch.empty((M, 3), device=dev, dtype=torch.float32)
-        # samples grouped by ray, a whole number of 16-sample tiles per ray: head layer 0's share of the 48 per-ray inputs once
-        # per ray (include/nsamd.h, nsamd_field_mlp.ray_terms)
         ctx.ray_terms = ctx.ray_inputs = None
-        if dir_group % 16 == 0 and M % dir_group == 0 and M > 0:
+        if ray_terms_apply(dir_group, M):
             rays = M // dir_group
             has_app = cams is not None or appearance_const is not None
             ctx.ray_terms = torch.empty((rays, 64), device=dev, dtype=torch.float32)
             ctx.ray_inputs = torch.empty((rays, 48 if has_app else 16), device=dev, dtype=torch.float32)
-            N.check(lib.nsamd_field_ray_terms(N.ptr(view_dirs), N.ptr(cams), N.ptr(appearance_const), rays, mlp,
-                                              N.ptr(ctx.ray_terms), N.ptr(ctx.ray_inputs), N.stream()), "field_ray_terms")
+            ray_terms_launch(view_dirs, cams, appearance_const, rays, mlp, ctx.ray_terms, ctx.ray_inputs)
             mlp.ray_terms, mlp.ray_inputs = N.ptr(ctx.ray_terms), N.ptr(ctx.ray_inputs)
-        N.check(lib.nsamd_field_mlp_fwd(N.ptr(enc), N.ptr(sel), N.ptr(view_dirs), N.ptr(cams),
-                                        N.ptr(appearance_const), dir_group, M, mlp, N.ptr(density), N.ptr(rgb),
-                                        N.stream()), "field_mlp_fwd")
+        field_forward(table, grid, transform, box, spec.native(), M, enc, sel, view_dirs, cams, appearance_const, dir_group,
+                      mlp, density, rgb)
         ctx.spec, ctx.grid, ctx.transform, ctx.box, ctx.avg, ctx.dir_group = spec, grid, transform, box, avg_density, dir_group
         ctx.cams, ctx.app_const, ctx.has_app = cams, appearance_const, appearance is not None
         ctx.param_refs = (table, *params, appearance)
@@ -631,32 +637,24 @@ class _NerfactoFieldFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gdens: Tensor, grgb: Tensor):
-        saved = ctx.saved_tensors
-        table, params, appearance, enc, sel, view_dirs = saved[0], saved[1:11], saved[11], saved[12], saved[13], saved[14]
-        if not ctx.has_app:
-            appearance = None
+        table, *params, appearance, enc, sel, view_dirs = ctx.saved_tensors
+        appearance = appearance if ctx.has_app else None
         spec: PointSpec = ctx.spec
-        lib = N.load()
         M = spec.num_points
         gdens = _f32c(gdens) if gdens is not None else torch.zeros((M,), device=table.device)
         grgb = _f32c(grgb) if grgb is not None else torch.zeros((M, 3), device=table.device)
         denc = torch.empty_like(enc)
         refs = ctx.param_refs
-        targets = [_grad_target(r, True) for r in refs[1:11]]
-        tparams, gparams = [t for t, _ in targets], [r for _, r in targets]
+        tparams, gparams = zip(*(_grad_target(r, True) for r in refs[1:11]))
         tapp, gapp = _grad_target(refs[11], True) if (appearance is not None and ctx.cams is not None) else (None, None)
         mlp = field_mlp(params, appearance, ctx.avg, ctx.ray_terms, ctx.ray_inputs)
         grads = field_mlp_grads(tparams, tapp, lambda g: g)  # (the targets themselves)
-        fws, fws_n = field_bwd_workspace(table.device)
-        N.check(lib.nsamd_field_mlp_bwd(N.ptr(enc), N.ptr(sel), N.ptr(view_dirs), N.ptr(ctx.cams),
-                                        N.ptr(ctx.app_const), ctx.dir_group, M, mlp, N.ptr(gdens), N.ptr(grgb),
-                                        N.ptr(denc), grads, N.ptr(fws), fws_n, N.stream()), "field_mlp_bwd")
-        need_pos = any(ctx.needs_input_grad[:3])
         ttable, dtable = _grad_target(refs[0], ctx.needs_input_grad[4])
-        dpos = torch.empty((M, 3), device=table.device, dtype=torch.float32) if need_pos else None
-        if ttable is not None or dpos is not None:
-            table_scatter(spec.native(), M, ctx.transform, ctx.box, table, ctx.grid, denc, 1, M, ttable, dpos)
-        gp, go, gd = _position_grads(spec, dpos) if dpos is not None else (None, None, None)
+        dpos = torch.empty((M, 3), device=table.device, dtype=torch.float32) if any(ctx.needs_input_grad[:3]) else None
+        field_backward(table, ctx.grid, ctx.transform, ctx.box, spec.native(), M, enc, sel, view_dirs, ctx.cams, ctx.app_const,
+                       ctx.dir_group, mlp, gdens, grgb, denc, grads, field_bwd_workspace(table.device)[0], ttable,
+                       write_only=False, fuse=False, dpos=dpos)
+        gp, go, gd = _position_grads(spec, dpos)
         return (gp, go, gd, None, dtable, *gparams, gapp, None, None, None, None, None, None, None, None)
 
 

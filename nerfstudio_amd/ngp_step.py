@@ -182,6 +182,7 @@ class NgpTrainStep:
         self.num_candidates = mc
         fld = m.field
         fm = F.field_mlp(*F.field_params(fld), fld.average_init_density)
+        tbl = (fld.mlp_base.encoding.hash_table, fld.mlp_base.encoding.spec, fld._transform, fld._box)  # (field_forward's)
         mk = 0
         if mc:
             if mc > self.cap_c:
@@ -192,8 +193,8 @@ class NgpTrainStep:
             # -- sigma_fn (ray_samplers.py:420-429): density of the candidates; no direction, a constant appearance row
             ck(lib.nsamd_packed_positions(o, d, N.ptr(self.c_ri), N.ptr(self.c_ts), N.ptr(self.c_te), mc, N.ptr(self.c_pos), st),
                "packed_positions")
-            F.field_forward(fld, N.make_points(positions=self.c_pos), mc, self.c_enc, self.c_sel, self.view0, None, self.app0, mc, fm,
-                            self.c_sigma, None)  # (rgb NULL: density only)
+            F.field_forward(*tbl, N.make_points(positions=self.c_pos), mc, self.c_enc, self.c_sel, self.view0, None, self.app0, mc,
+                            fm, self.c_sigma, None)  # (rgb NULL: density only)
             # -- visibility-ordered early termination + alpha threshold, then compaction (OccGridEstimator.sampling)
             alpha = float(cfg.alpha_thre)
             if alpha > 0.0:
@@ -228,7 +229,7 @@ class NgpTrainStep:
         if self.app0 is not None and not train_app:  # eval semantics of the embedding (nerfacto_field.py:253-261)
             emb = fld.embedding_appearance.embedding.weight
             self._app_const = (emb.mean(dim=0) if fld.use_average_appearance_embedding else torch.zeros_like(emb[0])).contiguous()
-        F.field_forward(fld, N.make_points(positions=self.k_pos), mk, self.k_enc, self.k_sel, self.k_dirs,
+        F.field_forward(*tbl, N.make_points(positions=self.k_pos), mk, self.k_enc, self.k_sel, self.k_dirs,
                         self.k_cams if train_app else None, self._app_const, 1, fm, self.k_dens, self.k_rgb)
         self._train_app = train_app
         # -- packed weights and the three renderers in one launch (models/instant_ngp.py:191-214)
@@ -303,11 +304,12 @@ class NgpTrainStep:
         grad_of = (lambda p: gl[id(p)]) if gl is not None else (lambda p: p.grad)  # noqa: E731
         # as the nerfacto schedule does (train_step.backward_field_and_table): while the table's gradient is written, the field
         # backward emits the table scatter's pass-1 records from its registers (`fuse_route` False: the two entry points)
-        F.field_backward(fld, N.make_points(positions=self.k_pos), mk, self.k_enc, self.k_sel, self.k_dirs,
-                         self.k_cams if self._train_app else None, self._app_const, 1,
+        tbl = fld.mlp_base.encoding
+        F.field_backward(tbl.hash_table, tbl.spec, fld._transform, fld._box, N.make_points(positions=self.k_pos), mk, self.k_enc,
+                         self.k_sel, self.k_dirs, self.k_cams if self._train_app else None, self._app_const, 1,
                          F.field_mlp(params, emb, fld.average_init_density), self.k_dsigma, self.k_drgb, self.k_denc,
                          F.field_mlp_grads(params, emb if self._train_app else None, grad_of), F.field_bwd_workspace(self.dev)[0],
-                         grad_of(fld.mlp_base.encoding.hash_table), not self.accumulate_table, fuse=self.fuse_route)
+                         grad_of(tbl.hash_table), not self.accumulate_table, fuse=self.fuse_route)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

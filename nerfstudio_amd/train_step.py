@@ -114,7 +114,7 @@ class NerfactoTrainStep:
         self._pl_S = (C.c_int32 * self.n_prop)(*self.counts[: self.n_prop])
         # Ray terms (include/nsamd.h, nsamd_field_mlp.ray_terms): head layer 0's share of the 48 per-ray inputs (SH of the view
         # direction, appearance row) once per ray instead of once per sample (a 16-point tile must lie inside one ray).
-        self.ray_terms_on = self.counts[-1] % 16 == 0
+        self.ray_terms_on = F.ray_terms_apply(self.counts[-1], mm)
         self.ray_terms = e(n, 64) if self.ray_terms_on else None
         self.ray_inputs = e(n, 16 + (32 if fld.embedding_appearance is not None else 0)) \
             if (self.ray_terms_on and not forward_only) else None  # (the backward's: weight gradient of the 48 per-ray columns)
@@ -504,9 +504,8 @@ class NerfactoTrainStep:
                 N.ptr(self.p_dens[lvl]), N.ptr(self.p_pre[lvl]) if need_enc else None, st)
             if fused == N.ERR_UNSUPPORTED:
                 self.ensure_proposal_features(lvl)
-                ck(lib.nsamd_hashgrid_encode_fwd(self._points(lvl), m, net._transform, net._box, N.ptr(net.encoding.hash_table),
-                                                 net.encoding.spec.native(), N.ptr(self.p_enc[lvl]), 1, m,
-                                                 N.ptr(self.p_sel[lvl]), st), "hashgrid_encode_fwd")
+                F.hash_forward(self._points(lvl), m, net._transform, net._box, net.encoding.hash_table, net.encoding.spec,
+                               self.p_enc[lvl], 1, m, self.p_sel[lvl])
                 ck(lib.nsamd_density_mlp_fwd(N.ptr(self.p_enc[lvl]), N.ptr(self.p_sel[lvl]), m, dm, N.ptr(self.p_dens[lvl]),
                                              None if self.forward_only else N.ptr(self.p_pre[lvl]), st), "density_mlp_fwd")
             else:
@@ -553,10 +552,8 @@ class NerfactoTrainStep:
         batch's (pose-corrected) directions and camera indices and the CURRENT head_W0 / head_b0 / appearance table — i.e. it
         runs after batch selection and after the main-field Adam of the previous iteration. On torch's current stream.
         app_const: see forward_main (the per-ray inputs are then not kept: no backward reads them)."""
-        inputs = self.ray_inputs if app_const is None else None
-        N.check(N.load().nsamd_field_ray_terms(N.ptr(self.directions), N.ptr(self._cams(app_const)), N.ptr(app_const), self.n,
-                                               fm if fm is not None else self._field_mlp(), N.ptr(self.ray_terms), N.ptr(inputs),
-                                               N.stream()), "field_ray_terms")
+        F.ray_terms_launch(self.directions, self._cams(app_const), app_const, self.n, fm if fm is not None else self._field_mlp(),
+                           self.ray_terms, self.ray_inputs if app_const is None else None)
 
     @profiler.time_function
     def forward_main(self, terms_ready: bool = False, app_const: Optional[Tensor] = None) -> None:
@@ -570,8 +567,10 @@ class NerfactoTrainStep:
                 self.ray_terms_launch(fm, app_const)
             fm.ray_terms = N.ptr(self.ray_terms)
             fm.ray_inputs = N.ptr(self.ray_inputs if app_const is None else None)
-        F.field_forward(self.model.field, self._points(L), self.m_main, self.f_enc, self.f_sel, self.directions,
-                        self._cams(app_const), app_const, self.counts[L], fm, self.f_dens, self.f_rgb)
+        fld = self.model.field
+        tbl = fld.mlp_base.encoding
+        F.field_forward(tbl.hash_table, tbl.spec, fld._transform, fld._box, self._points(L), self.m_main, self.f_enc, self.f_sel,
+                        self.directions, self._cams(app_const), app_const, self.counts[L], fm, self.f_dens, self.f_rgb)
 
     @profiler.time_function
     def losses(self, updated: bool) -> None:
@@ -643,10 +642,11 @@ class NerfactoTrainStep:
         # (the ray terms are what forward_main computed for this batch and these parameters)
         fm = F.field_mlp(params, emb, fld.average_init_density, self.ray_terms, self.ray_inputs)
         cam = self.cam_opt is not None  # the camera optimiser's share needs the encoded-feature gradient as well
-        F.field_backward(fld, self._points(L), self.m_main, self.f_enc, self.f_sel, self.directions, self._cams(None), None,
-                         self.counts[L], fm, self.d_dens_main, self.d_rgb_s, self.f_denc, F.field_mlp_grads(params, emb, self._grad),
-                         self.field_ws, self._grad(fld.mlp_base.encoding.hash_table), self.main_table_write_only,
-                         fuse=self.fuse_route, keep_denc=cam or self.keep_denc,
+        tbl = fld.mlp_base.encoding
+        F.field_backward(tbl.hash_table, tbl.spec, fld._transform, fld._box, self._points(L), self.m_main, self.f_enc, self.f_sel,
+                         self.directions, self._cams(None), None, self.counts[L], fm, self.d_dens_main, self.d_rgb_s, self.f_denc,
+                         F.field_mlp_grads(params, emb, self._grad), self.field_ws, self._grad(tbl.hash_table),
+                         self.main_table_write_only, fuse=self.fuse_route, keep_denc=cam or self.keep_denc,
                          on_denc=(lambda: self._rays_backward(L, fld, self.f_denc)) if cam else None,
                          fused_launch=self._field_bwd_phases if (cam or N.PROFILE is not None) else None)
 
@@ -698,13 +698,12 @@ class NerfactoTrainStep:
             dws = self.density_ws[lvl]
             spec = net.encoding.spec
             ws, ws_n = F._scatter_workspace(spec, self.f_enc.device, m)
-            grads = (N.ptr(self._grad(W0)), N.ptr(self._grad(b0)), N.ptr(self._grad(W1)), N.ptr(self._grad(b1)))
+            grads = [self._grad(p) for p in (W0, b0, W1, b1)]
             if gate is None or ws is None:  # ungated chain (`gate_proposals` off, or no binned-scatter workspace for this shape)
                 ck(lib.nsamd_weights_bwd(N.ptr(self.t_bins[lvl]), N.ptr(self.p_dens[lvl]), N.ptr(self.dw_prop[lvl]),
                                          n, S, N.ptr(self.p_ddens[lvl]), st), "weights_bwd")
-                ck(lib.nsamd_density_mlp_bwd(N.ptr(self.p_enc[lvl]), N.ptr(self.p_sel[lvl]), N.ptr(self.p_pre[lvl]),
-                                             N.ptr(self.p_ddens[lvl]), m, dm, N.ptr(self.p_denc[lvl]), *grads,
-                                             N.ptr(dws), dws.numel(), st), "density_mlp_bwd")
+                F.density_backward(self.p_enc[lvl], self.p_sel[lvl], self.p_pre[lvl], self.p_ddens[lvl], m, dm, self.p_denc[lvl],
+                                   grads, dws)
                 if self.cam_opt is not None:
                     self._rays_backward(lvl, net, self.p_denc[lvl])
                 F.table_scatter(self._points(lvl), m, net._transform, net._box, net.encoding.hash_table, spec, self.p_denc[lvl],
@@ -717,7 +716,7 @@ class NerfactoTrainStep:
                                           n, S, N.ptr(self.p_ddens[lvl]), gate, mask, int(self.gates_precleared), st),
                "weights_bwd_gate")
             ck(lib.nsamd_density_mlp_bwd_gated(N.ptr(self.p_enc[lvl]), N.ptr(self.p_sel[lvl]), N.ptr(self.p_pre[lvl]),
-                                               N.ptr(self.p_ddens[lvl]), m, dm, N.ptr(self.p_denc[lvl]), *grads,
+                                               N.ptr(self.p_ddens[lvl]), m, dm, N.ptr(self.p_denc[lvl]), *map(N.ptr, grads),
                                                N.ptr(dws), dws.numel(), gate, mask, S, st), "density_mlp_bwd_gated")
             if self.cam_opt is not None:
                 self._rays_backward(lvl, net, self.p_denc[lvl], gate, mask)

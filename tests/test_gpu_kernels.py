@@ -415,6 +415,117 @@ def test_field_ray_terms_equal_the_plain_kernels(F, S, appearance):
         gclose(e1, e0, 2e-5, "appearance embedding")
 
 
+@pytest.mark.parametrize("field,S,appearance", [("nerfacto", 16, "cameras"), ("nerfacto", 6, "cameras"), ("nerfacto", 16, "const"),
+                                                ("nerfacto", 6, "const"), ("density", 10, None), ("spec", 10, None)])
+def test_autograd_fields_direct_grad_and_returned_grad_agree(F, field, S, appearance):
+    """F.nerfacto_field, F.density_field and F.spec_encode on rays whose origins and directions require grad (so the table
+    scatter returns dL/dposition and `_position_grads` runs): every parameter, origin and direction gradient with
+    F.DIRECT_GRAD off (autograd receives fresh buffers) against on (the kernels accumulate into pre-zeroed `.grad`), and each
+    against the same launches issued here through the C ABI, 2e-5 of the largest entry as in
+    test_train_step_runner_matches_autograd_path (the launches are the same, so the results are expected to be equal).
+    Five rays: the ray-terms kernel's only 16-ray tile and the fields' last wave are ragged; main field: S = 16 (M = 80, one
+    16-sample tile per ray: ray terms) and S = 6 (M = 30: none), with camera indices and with one appearance row; proposal
+    field and bare encoding: five levels at S = 10."""
+    from nerfstudio_amd import _native as N
+
+    lib, st = N.load(), N.stream()
+    rs = np.random.RandomState(100 * S + len(field))
+    R, ncam = 5, 4
+    M = R * S
+    g = lambda *shape, s=1.0: torch.from_numpy((rs.standard_normal(shape) * s).astype(np.float32)).cuda()  # noqa: E731
+    e = lambda *shape: torch.empty(*shape, device="cuda")  # noqa: E731
+    cfg = small_cfg(12, 10, ncam)
+    gc = cfg.main_grid if field == "nerfacto" else cfg.prop_grids[1]
+    grid = F.HashGridSpec(gc.num_levels, gc.min_res, gc.max_res, gc.log2_hashmap_size)
+    table = g(grid.num_levels * grid.table_size, 2, s=0.5)
+    o, d = g(R, 3, s=0.7), torch.nn.functional.normalize(g(R, 3), dim=-1).contiguous()
+    o[R // 2:] *= 3.0  # (samples on both branches of the contraction)
+    _, t_bins = F.piecewise_bins(torch.full((R,), 0.05).cuda(), torch.full((R,), 1000.0).cuda(), S, None)
+    mid = ((t_bins[:, :-1] + t_bins[:, 1:]) / 2)[..., None]
+    xf, box, L2 = N.XFORM_CONTRACT, N.Aabb(), grid.out_dim
+    cams = app_const = None
+    if field == "nerfacto":
+        prm = [g(64, 32, s=0.3), g(64, s=0.1), g(16, 64, s=0.2), g(16, s=0.1), g(64, 63, s=0.2), g(64, s=0.1), g(64, 64, s=0.2),
+               g(64, s=0.1), g(3, 64, s=0.2), g(3, s=0.1), g(ncam, 32)]  # (the last: the appearance table)
+        names = ["base_W0", "base_b0", "base_W1", "base_b1", "head_W0", "head_b0", "head_W1", "head_b1", "head_W2", "head_b2",
+                 "appearance"]
+        cams = torch.from_numpy(rs.randint(0, ncam, (R,)).astype(np.int64)).cuda() if appearance == "cameras" else None
+        app_const = g(32) if appearance == "const" else None
+        gouts = [g(M, s=0.1), g(M, 3)]
+    elif field == "density":
+        prm, names = [g(16, L2, s=0.4), g(16, s=0.1), g(1, 16, s=0.4), g(1)], ["W0", "b0", "W1", "b1"]
+        gouts = [g(M, s=0.1)]
+    else:
+        prm, names, gouts = [], [], [g(M, L2)]
+    names = ["table"] + names + ["origins", "directions"]
+
+    def through_autograd(direct):
+        leaves = [t.clone().requires_grad_(True) for t in [table, *prm, o, d]]
+        tb, ps, (o_, d_) = leaves[0], leaves[1:-2], leaves[-2:]
+        if direct:
+            for p in leaves[:-2]:
+                p.grad = torch.zeros_like(p)
+        spec = F.PointSpec(origins=o_, directions=d_, t_bins=t_bins)
+        F.DIRECT_GRAD = direct
+        try:
+            if field == "nerfacto":
+                outs = F.nerfacto_field(spec, tb, ps[:4], ps[4:10], ps[10], d_.detach(), cams, app_const, S, grid, xf, None, 1.0)
+            elif field == "density":
+                outs = [F.density_field(spec, tb, *ps, grid, xf, None, 1.0)]
+            else:
+                outs = [F.spec_encode(spec, tb, grid, xf, None)[0]]
+            sum((y * gy).sum() for y, gy in zip(outs, gouts)).backward()
+        finally:
+            F.DIRECT_GRAD = False
+        # (an input without gradient — the appearance table under one constant row — is None, or its zero-filled buffer)
+        return [p.grad if p.grad is not None else torch.zeros_like(p) for p in leaves]
+
+    def through_the_abi():
+        pts = N.make_points(None, o, d, t_bins, S)
+        gp = [torch.zeros_like(p) for p in prm]
+        if field == "spec":
+            enc, sel, denc, sp, sk = e(M, L2), e(M), gouts[0], L2, 1
+        else:
+            enc, sel, denc, sp, sk = e(L2, M), e(M), e(L2, M), 1, M
+        N.check(lib.nsamd_hashgrid_encode_fwd(pts, M, xf, box, N.ptr(table), grid.native(), N.ptr(enc), sp, sk, N.ptr(sel), st),
+                "hashgrid_encode_fwd")
+        if field == "nerfacto":
+            fm = N.FieldMlp(*(N.ptr(p) for p in prm), ncam, 1.0)
+            if S % 16 == 0:
+                terms, xin = e(R, 64), e(R, 48)
+                N.check(lib.nsamd_field_ray_terms(N.ptr(d), N.ptr(cams), N.ptr(app_const), R, fm, N.ptr(terms), N.ptr(xin), st),
+                        "field_ray_terms")
+                fm.ray_terms, fm.ray_inputs = N.ptr(terms), N.ptr(xin)
+            dens, rgb = e(M), e(M, 3)
+            N.check(lib.nsamd_field_mlp_fwd(N.ptr(enc), N.ptr(sel), N.ptr(d), N.ptr(cams), N.ptr(app_const), S, M, fm, N.ptr(dens),
+                                            N.ptr(rgb), st), "field_mlp_fwd")
+            ws, ws_n = F.field_bwd_workspace(torch.device("cuda"))
+            gfm = N.FieldMlpGrads(*(N.ptr(x) for x in gp[:10]), N.ptr(gp[10]) if cams is not None else None)
+            N.check(lib.nsamd_field_mlp_bwd(N.ptr(enc), N.ptr(sel), N.ptr(d), N.ptr(cams), N.ptr(app_const), S, M, fm,
+                                            N.ptr(gouts[0]), N.ptr(gouts[1]), N.ptr(denc), gfm, N.ptr(ws), ws_n, st), "field_mlp_bwd")
+        elif field == "density":
+            dm = N.DensityMlp(*(N.ptr(p) for p in prm), L2, 16, 1.0)
+            dens, pre = e(M), e(M)
+            N.check(lib.nsamd_density_mlp_fwd(N.ptr(enc), N.ptr(sel), M, dm, N.ptr(dens), N.ptr(pre), st), "density_mlp_fwd")
+            ws = F.density_bwd_workspace(torch.device("cuda"))
+            N.check(lib.nsamd_density_mlp_bwd(N.ptr(enc), N.ptr(sel), N.ptr(pre), N.ptr(gouts[0]), M, dm, N.ptr(denc),
+                                              *(N.ptr(x) for x in gp), N.ptr(ws), ws.numel(), st), "density_mlp_bwd")
+        dtable, dpos = torch.zeros_like(table), e(M, 3)
+        ws, ws_n = F._scatter_workspace(grid, torch.device("cuda"), M)
+        N.check(lib.nsamd_hashgrid_encode_bwd(pts, M, xf, box, N.ptr(table), grid.native(), N.ptr(denc), sp, sk, N.ptr(dtable),
+                                              N.ptr(dpos), N.ptr(ws), ws_n, st), "hashgrid_encode_bwd")
+        dpos = dpos.view(R, S, 3)
+        return [dtable, *gp, dpos.sum(dim=1), (dpos * mid).sum(dim=1)]
+
+    returned, direct, ref = through_autograd(False), through_autograd(True), through_the_abi()
+    torch.cuda.synchronize()
+    for name, a, b, c in zip(names, returned, direct, ref):
+        assert torch.isfinite(c).all() and (float(c.abs().max()) > 0 or (name == "appearance" and cams is None)), name
+        gclose(b, a, 2e-5, f"{name}: DIRECT_GRAD on against off")
+        gclose(a, c, 2e-5, f"{name}: DIRECT_GRAD off against the launches through the C ABI")
+        gclose(b, c, 2e-5, f"{name}: DIRECT_GRAD on against the launches through the C ABI")
+
+
 # ---------------------------------------------------------------- samplers ------------------------------------------
 @pytest.mark.parametrize("mode", ["train", "eval"])
 def test_samplers_golden_bit_exact(F, golden, mode):
