@@ -253,6 +253,11 @@ def ptr(t: Optional[torch.Tensor]):
     return t.data_ptr()
 
 
+def ptr_array(tensors):
+    """Host array of the device pointers of `tensors` (None -> NULL), for the entry points that take one pointer per level."""
+    return (vp * len(tensors))(*[ptr(t) for t in tensors])
+
+
 # torch.cuda.current_stream() / `with torch.cuda.stream(s)` with no device argument resolve "the current device" through
 # torch._utils._get_available_device_type -> torch.cuda.is_available() -> a device-count query of the driver: ~20 us per call on
 # this ROCm build, 14 - 16 of them per eagerly launched iteration = a third of the host's share of an eager / data-parallel step
@@ -261,11 +266,13 @@ _RAW_STREAM = getattr(torch._C, "_cuda_getCurrentRawStream", None)  # (private t
 _GET_DEVICE = getattr(torch._C, "_cuda_getDevice", None)
 
 
-def stream() -> int:
-    """The raw hipStream_t of torch's current stream (kernels must run on it, SURVEY.md §8b threading)."""
-    if _RAW_STREAM is None or _GET_DEVICE is None:
+if _RAW_STREAM is None or _GET_DEVICE is None:
+    def stream() -> int:
         return torch.cuda.current_stream().cuda_stream
-    return _RAW_STREAM(_GET_DEVICE())
+else:
+    def stream() -> int:
+        """The raw hipStream_t of torch's current stream (kernels must run on it, SURVEY.md §8b threading)."""
+        return _RAW_STREAM(_GET_DEVICE())
 
 
 def current_stream() -> "torch.cuda.Stream":

@@ -15,7 +15,9 @@ the mean (or zero) appearance embedding for every sample (fields/nerfacto_field.
 a clamp of the composited colour (renderers.py:225-231), expected depth clipped to the CHUNK's min / max sample midpoint
 (the reference clips per forward call, i.e. per chunk, renderers.py:380-383). A last, shorter chunk is padded with copies
 of its last ray (which leaves that min / max untouched) and only its valid rows are copied out.
-Same kernels, same order as the module path: the outputs are equal bit for bit (tests/test_gpu_kernels.py).
+Same kernels, same order as the module path, launched through the same helpers (functional.weights_launch, composite_launch,
+field_normals_launch, nerf_encode_launch, linear_launch, normals_composite_launch): the outputs are equal bit for bit
+(tests/test_gpu_kernels.py).
 """
 from __future__ import annotations
 
@@ -26,7 +28,7 @@ import torch
 from torch import Tensor
 
 from . import _native as N
-from . import functional as F  # noqa: F401
+from . import functional as F
 from .utils import profiler
 
 
@@ -40,19 +42,17 @@ def pred_normals_mlp_launch(fld, pts: N.Points, M: int, freqs: Tensor, pn_enc: T
     raw positions (`pn_enc` [M, 12], copied into columns 0..11), then the MLP's three layers (ReLU, ReLU, none) and the 64 -> 3
     head with no activation — nsamd_normals_composite applies tanh and the normalisation — into `pn_pre` [M, 3], in blocks of
     the rows `pn_a` / `pn_b` [block, 64] hold."""
-    lib, st = N.load(), N.stream()
-    pe = fld.position_encoding
-    N.check(lib.nsamd_nerf_encode(pts, M, N.ptr(freqs), pe.num_frequencies, 0, N.ptr(pn_enc), st), "nerf_encode")
+    F.nerf_encode_launch(pts, M, freqs, False, pn_enc)
     pn_in[:, :12].copy_(pn_enc)  # (the encoder writes dense 12-wide rows)
     W0, b0, W1, b1, W2, b2 = fld.mlp_pred_normals.param_tensors()
     head = fld.field_head_pred_normals.net
     block = pn_a.shape[0]
     for a in range(0, M, block):
         k = min(a + block, M) - a
-        layers = ((pn_in[a:a + k], W0, b0, 27, 64, 1, pn_a), (pn_a, W1, b1, 64, 64, 1, pn_b), (pn_b, W2, b2, 64, 64, 0, pn_a),
-                  (pn_a, head.weight, head.bias, 64, 3, 0, pn_pre[a:a + k]))
-        for x, W, b, K, n_out, act, y in layers:
-            N.check(lib.nsamd_linear_fwd(N.ptr(x), N.ptr(W), N.ptr(b), k, K, n_out, act, N.ptr(y), st), "linear_fwd")
+        layers = ((pn_in[a:a + k], W0, b0, 1, pn_a), (pn_a, W1, b1, 1, pn_b), (pn_b, W2, b2, 0, pn_a),
+                  (pn_a, head.weight, head.bias, 0, pn_pre[a:a + k]))  # 27 -> 64 -> 64 -> 64 -> 3
+        for x, W, b, act, y in layers:
+            F.linear_launch(x, W, b, k, act, y)
 
 
 class EvalRenderer:
@@ -111,15 +111,13 @@ class EvalRenderer:
     def _launch_chunk(self) -> None:
         """The kernel schedule of one chunk (all arguments are static buffers: capturable): the training runner's forward in
         eval mode, then weights + compositing with the clamp."""
-        s, lib, st, n = self.step, N.load(), N.stream(), self.chunk
+        s = self.step
         s.forward_proposals(need_enc=False, stratified=False)
         s.forward_main(app_const=self.app_const)
         L = s.n_prop
-        S = s.counts[L]
-        N.check(lib.nsamd_weights_fwd(N.ptr(s.t_bins[L]), N.ptr(s.f_dens), n, S, N.ptr(s.weights[L]), st), "weights_fwd")
-        N.check(lib.nsamd_composite_fwd(N.ptr(s.f_rgb), N.ptr(s.weights[L]), N.ptr(s.t_bins[L]), n, S, self.bg_mode, self.bg_vals,
-                                        1, N.ptr(s.rgb), N.ptr(s.acc), N.ptr(s.depth_exp), N.ptr(s.depth_med[L]), None,
-                                        N.ptr(s.minmax_ws), st), "composite_fwd")
+        F.weights_launch(s.t_bins[L], s.f_dens, s.weights[L])
+        F.composite_launch(s.f_rgb, s.weights[L], s.t_bins[L], self.bg_mode, self.bg_vals, True, s.rgb, s.acc, s.depth_exp,
+                           s.depth_med[L], None, s.minmax_ws)
         if self.normals:
             self._launch_normals()
 

@@ -256,9 +256,13 @@ def scatter_events(ws: Tensor) -> Tuple[int, int, int]:
 
 # ---------------------------------------------------------------------------------------------------------------
 # launch records and launches shared by the autograd Functions below and the explicit schedules (train_step,
-# eval_render, ngp_step): `hash_forward`, `table_scatter`, `ray_terms_launch`, `field_forward`, `field_backward` and
-# `density_backward` take tensors and records, never a module, and are the only callers of their entry points. Records
-# are built at launch time, never cached: they hold raw addresses, and an arena built later re-homes the parameters.
+# eval_render, ngp_step, trainer): `hash_forward`, `table_scatter`, `ray_terms_launch`, `field_forward`, `field_backward`,
+# `density_forward`, `density_backward` here and every `*_launch` further down take tensors and records, never a module, and
+# are the only callers of their entry points: outputs are the caller's, counts that no shape gives are integers, nothing is
+# allocated, copied or waited for (each is a node of a captured iteration), and the one check is the contiguity assert of
+# `N.ptr` / `N.ptr_array` on each argument. `_f32c` / `N.require_cuda` (device, dtype, making contiguous) stay with
+# the allocating wrappers, the only callers that receive foreign tensors. Records are built at launch time, never cached:
+# they hold raw addresses, and an arena built later re-homes the parameters.
 # ---------------------------------------------------------------------------------------------------------------
 def density_mlp(W0: Tensor, b0: Tensor, W1: Tensor, b1: Tensor, average_init_density: float) -> N.DensityMlp:
     """nsamd_density_mlp of a proposal network's MLP (HashMLPDensityField: `mlp_base[1].param_tensors()`)."""
@@ -362,6 +366,13 @@ def field_backward(table: Tensor, grid: HashGridSpec, transform: int, box: N.Aab
         on_denc()
     if dtable is not None or dpos is not None:
         table_scatter(pts, M, transform, box, table, grid, denc, 1, M, dtable, dpos, write_only=write_only)
+
+
+def density_forward(enc: Tensor, sel: Tensor, M: int, mlp: N.DensityMlp, density: Tensor, pre: Optional[Tensor]) -> None:
+    """nsamd_density_mlp_fwd on the current stream: density `[M]` of the feature-major features `enc` and selector `sel`; `pre`:
+    the pre-activation the backward reads (None: not kept)."""
+    N.check(N.load().nsamd_density_mlp_fwd(N.ptr(enc), N.ptr(sel), M, mlp, N.ptr(density), N.ptr(pre), N.stream()),
+            "density_mlp_fwd")
 
 
 def density_backward(enc: Tensor, sel: Tensor, pre: Tensor, ddens: Tensor, M: int, mlp: N.DensityMlp, denc: Tensor,
@@ -473,6 +484,12 @@ def sh4_encode(directions: Tensor) -> Tensor:
 _FREQS: dict = {}
 
 
+def nerf_encode_launch(pts: N.Points, M: int, freqs: Tensor, include_input: bool, out: Tensor) -> None:
+    """nsamd_nerf_encode on the current stream: M points at the frequencies `freqs` -> dense rows `[M, 6 F (+3)]` of `out`."""
+    N.check(N.load().nsamd_nerf_encode(pts, M, N.ptr(freqs), freqs.shape[0], int(bool(include_input)), N.ptr(out), N.stream()),
+            "nerf_encode")
+
+
 def nerf_encode(spec: PointSpec, num_frequencies: int, min_freq_exp: float, max_freq_exp: float,
                 include_input: bool = False) -> Tensor:
     """NeRFEncoding.forward (encodings.py:148-189, no covariances) on the points of `spec` -> `[M, 6 F (+3)]`. The
@@ -488,8 +505,7 @@ def nerf_encode(spec: PointSpec, num_frequencies: int, min_freq_exp: float, max_
     spec = _spec_from_flat(*spec.tensors())
     M = spec.num_points
     out = torch.empty((M, 6 * num_frequencies + (3 if include_input else 0)), device=dev, dtype=torch.float32)
-    N.check(N.load().nsamd_nerf_encode(spec.native(), M, N.ptr(_FREQS[key]), num_frequencies, int(bool(include_input)),
-                                       N.ptr(out), N.stream()), "nerf_encode")
+    nerf_encode_launch(spec.native(), M, _FREQS[key], include_input, out)
     return out
 
 
@@ -510,6 +526,12 @@ def contract_linf(x: Tensor) -> Tensor:
 _ACT = {None: 0, "relu": 1, "sigmoid": 2, "softplus": 3}
 
 
+def linear_launch(x: Tensor, W: Tensor, b: Optional[Tensor], M: int, act: int, y: Tensor) -> None:
+    """nsamd_linear_fwd on the current stream: y = act(x W^T + b) on the first M rows of `x` `[., K]`, `W` `[N, K]`."""
+    N.check(N.load().nsamd_linear_fwd(N.ptr(x), N.ptr(W), N.ptr(b), M, W.shape[1], W.shape[0], act, N.ptr(y), N.stream()),
+            "linear_fwd")
+
+
 class _LinearFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x: Tensor, W: Tensor, b: Optional[Tensor], act: int):
@@ -518,7 +540,7 @@ class _LinearFn(torch.autograd.Function):
         M, K = x.shape
         Nout = W.shape[0]
         y = torch.empty((M, Nout), device=x.device, dtype=torch.float32)
-        N.check(N.load().nsamd_linear_fwd(N.ptr(x), N.ptr(W), N.ptr(b), M, K, Nout, act, N.ptr(y), N.stream()), "linear_fwd")
+        linear_launch(x, W, b, M, act, y)
         ctx.save_for_backward(x, W, y)
         ctx.act, ctx.has_bias = act, b is not None
         return y
@@ -563,8 +585,7 @@ class _DensityFieldFn(torch.autograd.Function):
         mlp = density_mlp(W0, b0, W1, b1, avg_density)
         density = torch.empty((M,), device=dev, dtype=torch.float32)
         pre = torch.empty((M,), device=dev, dtype=torch.float32)
-        N.check(N.load().nsamd_density_mlp_fwd(N.ptr(enc), N.ptr(sel), M, mlp, N.ptr(density), N.ptr(pre), N.stream()),
-                "density_mlp_fwd")
+        density_forward(enc, sel, M, mlp, density, pre)
         ctx.spec, ctx.grid, ctx.transform, ctx.box, ctx.avg = spec, grid, transform, box, avg_density
         ctx.param_refs = (table, W0, b0, W1, b1)
         ctx.save_for_backward(table, W0, b0, W1, b1, enc, sel, pre)
@@ -694,6 +715,15 @@ def _linspace(kind: str, num_samples: int, device) -> Tensor:
     return t
 
 
+def piecewise_bins_launch(nears: Tensor, fars: Tensor, edges: Tensor, jitter: Optional[Tensor], per_edge: int, spacing: int,
+                          s_bins: Tensor, t_bins: Tensor) -> None:
+    """nsamd_piecewise_bins on the current stream: the initial sampler's `[n, S+1]` spacing and Euclidean edges from `nears` /
+    `fars` `[n]`, the linspace table `edges` and the draws `jitter` (None: bin centres; per_edge 1: one draw per edge)."""
+    n, s1 = s_bins.shape
+    N.check(N.load().nsamd_piecewise_bins(N.ptr(nears), N.ptr(fars), N.ptr(edges), N.ptr(jitter), per_edge, n, s1 - 1, spacing,
+                                          N.ptr(s_bins), N.ptr(t_bins), N.stream()), "piecewise_bins")
+
+
 @torch.no_grad()
 def piecewise_bins(nears: Tensor, fars: Tensor, num_samples: int, jitter: Optional[Tensor], spacing: int = 0
                    ) -> Tuple[Tensor, Tensor]:
@@ -708,8 +738,7 @@ def piecewise_bins(nears: Tensor, fars: Tensor, num_samples: int, jitter: Option
     s_bins = torch.empty((n, num_samples + 1), device=nears.device, dtype=torch.float32)
     t_bins = torch.empty_like(s_bins)
     edges = _linspace("edges", num_samples, nears.device)
-    N.check(N.load().nsamd_piecewise_bins(N.ptr(nears), N.ptr(fars), N.ptr(edges), N.ptr(jitter), per_edge, n, num_samples,
-                                          int(spacing), N.ptr(s_bins), N.ptr(t_bins), N.stream()), "piecewise_bins")
+    piecewise_bins_launch(nears, fars, edges, jitter, per_edge, int(spacing), s_bins, t_bins)
     return s_bins, t_bins
 
 
@@ -723,31 +752,54 @@ def _jitter_layout(jitter: Optional[Tensor], num_rays: int, num_edges: int) -> i
     return 1
 
 
+def weights_launch(t_bins: Tensor, density: Tensor, weights: Tensor) -> None:
+    """nsamd_weights_fwd on the current stream: `weights` `[n, S]` from the edges `[n, S+1]` and the densities (n * S values)."""
+    n, s = weights.shape
+    N.check(N.load().nsamd_weights_fwd(N.ptr(t_bins), N.ptr(density), n, s, N.ptr(weights), N.stream()), "weights_fwd")
+
+
+def weights_backward_launch(t_bins: Tensor, density: Tensor, dweights: Tensor, ddensity: Tensor) -> None:
+    """nsamd_weights_bwd on the current stream: the density gradient (n * S values) from `dweights` `[n, S]`."""
+    n, s = dweights.shape
+    N.check(N.load().nsamd_weights_bwd(N.ptr(t_bins), N.ptr(density), N.ptr(dweights), n, s, N.ptr(ddensity), N.stream()),
+            "weights_bwd")
+
+
 class _WeightsFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, t_bins: Tensor, density: Tensor):
         N.require_cuda(t_bins, density)
         t_bins, density = _f32c(t_bins), _f32c(density)
-        n, s = density.shape
         w = torch.empty_like(density)
-        N.check(N.load().nsamd_weights_fwd(N.ptr(t_bins), N.ptr(density), n, s, N.ptr(w), N.stream()), "weights_fwd")
+        weights_launch(t_bins, density, w)
         ctx.save_for_backward(t_bins, density)
         return w
 
     @staticmethod
     def backward(ctx, gw: Tensor):
         t_bins, density = ctx.saved_tensors
-        n, s = density.shape
-        gw = _f32c(gw)
         gd = torch.empty_like(density)
-        N.check(N.load().nsamd_weights_bwd(N.ptr(t_bins), N.ptr(density), N.ptr(gw), n, s, N.ptr(gd), N.stream()),
-                "weights_bwd")
+        weights_backward_launch(t_bins, density, _f32c(gw), gd)
         return None, gd
 
 
 def weights_from_density(t_bins: Tensor, density: Tensor) -> Tensor:
     """RaySamples.get_weights (cameras/rays.py:129-152): `[N,S+1]`, `[N,S]` -> `[N,S]`."""
     return _WeightsFn.apply(t_bins, density)
+
+
+def pdf_resample_launch(s_bins_prev: Tensor, weights: Tensor, u_base: Tensor, jitter: Optional[Tensor], nears: Tensor,
+                        fars: Tensor, anneal: float, anneal_dev: Optional[Tensor], histogram_padding: float, eps: float,
+                        spacing: int, per_edge: int, include_original: bool, num_samples: int, s_bins: Tensor, t_bins: Tensor,
+                        inds: Optional[Tensor]) -> None:
+    """nsamd_pdf_resample on the current stream: `num_samples` + 1 new edges per ray drawn from the histogram `weights`
+    `[n, S_prev]` over `s_bins_prev` into `s_bins` / `t_bins` (with include_original merged into the existing edges), the
+    searchsorted result into `inds` (None: not kept). `anneal_dev`: the anneal exponent in device memory instead of `anneal`."""
+    n, s_prev = weights.shape
+    N.check(N.load().nsamd_pdf_resample(N.ptr(s_bins_prev), N.ptr(weights), s_prev, N.ptr(u_base), N.ptr(jitter), N.ptr(nears),
+                                        N.ptr(fars), anneal, N.ptr(anneal_dev), histogram_padding, eps,
+                                        1.0 / (2 * (num_samples + 1)), spacing, per_edge, int(include_original), n, num_samples,
+                                        N.ptr(s_bins), N.ptr(t_bins), N.ptr(inds), N.stream()), "pdf_resample")
 
 
 @torch.no_grad()
@@ -771,12 +823,17 @@ def pdf_resample(s_bins_prev: Tensor, weights: Tensor, num_samples: int, jitter:
     t_bins = torch.empty_like(s_bins)
     inds = torch.empty((n, nb), device=dev, dtype=torch.int32) if return_indices else None
     u_base = _linspace("u", num_samples, dev)
-    N.check(N.load().nsamd_pdf_resample(N.ptr(s_bins_prev), N.ptr(weights), s_prev, N.ptr(u_base), N.ptr(jitter),
-                                        N.ptr(nears), N.ptr(fars), float(anneal), N.ptr(anneal_dev),
-                                        float(histogram_padding), float(eps),
-                                        1.0 / (2 * nb), int(spacing), per_edge, int(bool(include_original)), n, num_samples,
-                                        N.ptr(s_bins), N.ptr(t_bins), N.ptr(inds), N.stream()), "pdf_resample")
+    pdf_resample_launch(s_bins_prev, weights, u_base, jitter, nears, fars, float(anneal), anneal_dev, float(histogram_padding),
+                        float(eps), int(spacing), per_edge, bool(include_original), num_samples, s_bins, t_bins, inds)
     return (s_bins, t_bins, inds) if return_indices else (s_bins, t_bins)
+
+
+def distance_gradient_scale_launch(t_bins: Tensor, d_density: Optional[Tensor], d_rgb: Optional[Tensor]) -> None:
+    """nsamd_distance_gradient_scale on the current stream: the per-sample gradients of the samples between the edges `t_bins`
+    `[n, S+1]` multiplied in place by clamp(((start + end) / 2)^2, 0, 1)."""
+    n, s1 = t_bins.shape
+    N.check(N.load().nsamd_distance_gradient_scale(N.ptr(t_bins), n, s1 - 1, N.ptr(d_density), N.ptr(d_rgb), N.stream()),
+            "distance_gradient_scale")
 
 
 class _DistanceGradientScaleFn(torch.autograd.Function):
@@ -791,11 +848,9 @@ class _DistanceGradientScaleFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_density, g_rgb):
         (t_bins,) = ctx.saved_tensors
-        n, s1 = t_bins.shape
         gd = _f32c(g_density).clone() if g_density is not None else None
         gr = _f32c(g_rgb).clone() if g_rgb is not None else None
-        N.check(N.load().nsamd_distance_gradient_scale(N.ptr(t_bins), n, s1 - 1, N.ptr(gd), N.ptr(gr), N.stream()),
-                "distance_gradient_scale")
+        distance_gradient_scale_launch(t_bins, gd, gr)
         return gd, gr, None
 
 
@@ -825,6 +880,19 @@ def _bg_args(background, device):
     return N.BG_CONSTANT, (C.c_float * 3)(*vals)
 
 
+def composite_launch(rgb: Optional[Tensor], weights: Tensor, t_bins: Optional[Tensor], bg_mode: int, bg_vals, eval_clamp: bool,
+                     out_rgb: Optional[Tensor], acc: Optional[Tensor], depth: Optional[Tensor], median: Optional[Tensor],
+                     median_index: Optional[Tensor], minmax_ws: Optional[Tensor]) -> None:
+    """nsamd_composite_fwd on the current stream over `weights` `[n, S]`; every output is optional: the composited colour
+    (eval_clamp: nan_to_num on the samples, clamp to [0, 1]), the accumulation, the expected depth (needs `minmax_ws`, 2 + 2
+    ceil(n / 4) floats, for the global clip), the median depth and its int32 sample index."""
+    n, s = weights.shape
+    N.check(N.load().nsamd_composite_fwd(N.ptr(rgb), N.ptr(weights), N.ptr(t_bins), n, s, bg_mode, bg_vals, int(eval_clamp),
+                                         N.ptr(out_rgb), N.ptr(acc), N.ptr(depth), N.ptr(median), N.ptr(median_index),
+                                         N.ptr(minmax_ws), N.stream()),
+            "composite_fwd" if out_rgb is not None else "composite_fwd(median)" if median is not None else "composite_fwd(acc)")
+
+
 class _CompositeFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, rgb: Tensor, weights: Tensor, t_bins: Optional[Tensor], bg_mode: int, bg_vals, want_depth: bool):
@@ -837,9 +905,7 @@ class _CompositeFn(torch.autograd.Function):
         acc = torch.empty((n,), device=dev, dtype=torch.float32)
         depth = torch.empty((n,), device=dev, dtype=torch.float32) if want_depth else None
         ws = torch.empty((2 + 2 * ((n + 3) // 4),), device=dev, dtype=torch.float32) if want_depth else None
-        N.check(N.load().nsamd_composite_fwd(N.ptr(rgb), N.ptr(weights), N.ptr(t_bins) if want_depth else None, n, s,
-                                             bg_mode, bg_vals, 0, N.ptr(out), N.ptr(acc), N.ptr(depth), None, None,
-                                             N.ptr(ws), N.stream()), "composite_fwd")
+        composite_launch(rgb, weights, t_bins if want_depth else None, bg_mode, bg_vals, False, out, acc, depth, None, None, ws)
         ctx.save_for_backward(rgb, weights, t_bins if want_depth else None, ws)
         ctx.bg_mode, ctx.bg_vals, ctx.want_depth = bg_mode, bg_vals, want_depth
         if want_depth:
@@ -883,9 +949,7 @@ def composite_eval(rgb: Tensor, weights: Tensor, t_bins: Tensor, background="las
     dexp = torch.empty((n,), device=dev, dtype=torch.float32)
     dmed = torch.empty((n,), device=dev, dtype=torch.float32)
     ws = torch.empty((2 + 2 * ((n + 3) // 4),), device=dev, dtype=torch.float32)
-    N.check(N.load().nsamd_composite_fwd(N.ptr(rgb), N.ptr(weights), N.ptr(t_bins), n, s, mode, vals, 1, N.ptr(out),
-                                         N.ptr(acc), N.ptr(dexp), N.ptr(dmed), None, N.ptr(ws), N.stream()),
-            "composite_fwd")
+    composite_launch(rgb, weights, t_bins, mode, vals, True, out, acc, dexp, dmed, None, ws)
     return out, acc, dexp, dmed
 
 
@@ -897,8 +961,7 @@ def depth_median(weights: Tensor, t_bins: Tensor, return_index: bool = False):
     n, s = weights.shape
     d = torch.empty((n,), device=weights.device, dtype=torch.float32)
     idx = torch.empty((n,), device=weights.device, dtype=torch.int32) if return_index else None
-    N.check(N.load().nsamd_composite_fwd(None, N.ptr(weights), N.ptr(t_bins), n, s, N.BG_NONE, None, 0, None, None,
-                                         None, N.ptr(d), N.ptr(idx), None, N.stream()), "composite_fwd(median)")
+    composite_launch(None, weights, t_bins, N.BG_NONE, None, False, None, None, None, d, idx, None)
     return (d, idx) if return_index else d
 
 
@@ -909,8 +972,7 @@ def accumulation(weights: Tensor) -> Tensor:
     weights = _f32c(weights)
     n, s = weights.shape
     acc = torch.empty((n,), device=weights.device, dtype=torch.float32)
-    N.check(N.load().nsamd_composite_fwd(None, N.ptr(weights), None, n, s, N.BG_NONE, None, 0, None, N.ptr(acc), None,
-                                         None, None, None, N.stream()), "composite_fwd(acc)")
+    composite_launch(None, weights, None, N.BG_NONE, None, False, None, acc, None, None, None, None)
     return acc
 
 
@@ -981,7 +1043,7 @@ def depth_loss_launch(weights: Sequence[Tensor], t_bins: Sequence[Tensor], termi
                       d_predicted: Optional[Tensor], accumulate: bool = False) -> None:
     """nsamd_depth_loss on dense fp32 device tensors (weights `[n,S_l]`, bins `[n,S_l+1]`, per-ray vectors `[n]`)."""
     levels, n = len(weights), termination_depth.shape[0]
-    parr = lambda ts: (C.c_void_p * levels)(*[N.ptr(t) for t in ts])  # noqa: E731
+    parr = N.ptr_array
     counts = (C.c_int32 * levels)(*[int(w.shape[1]) for w in weights])
     N.check(N.load().nsamd_depth_loss(levels, parr(t_bins), parr(weights), counts, n, N.ptr(termination_depth),
                                       N.ptr(directions_norm), N.ptr(predicted_depth), float(sigma), int(loss_type),
@@ -1105,6 +1167,29 @@ def normals_composite(weights: Tensor, normals: Tensor, pred_pre: Tensor) -> Tup
 CAMERA_MODES = {"SO3xR3": 1, "SE3": 2}
 
 
+def camera_apply_launch(pose: Tensor, mode: int, raw_origins: Tensor, raw_directions: Tensor, cams: Tensor, origins: Tensor,
+                        directions: Tensor) -> None:
+    """nsamd_camera_apply on the current stream: origins + t(c), R(c) directions of the `[n, 3]` raw rays for the camera c =
+    `cams[ray]` (int64) under the pose corrections `pose` `[num_cameras, 6]`, `mode` a CAMERA_MODES value."""
+    N.check(N.load().nsamd_camera_apply(N.ptr(pose), mode, pose.shape[0], N.ptr(raw_origins), N.ptr(raw_directions), N.ptr(cams),
+                                        raw_origins.shape[0], N.ptr(origins), N.ptr(directions), N.stream()), "camera_apply")
+
+
+def camera_backward_launch(pose: Tensor, mode: int, raw_directions: Tensor, cams: Tensor, d_origins: Sequence[Tensor],
+                           d_directions: Sequence[Tensor], trans_penalty: float, rot_penalty: float, dpose: Tensor,
+                           reg_out: Optional[Tensor]) -> None:
+    """nsamd_camera_backward on the current stream: the per-ray gradients dL/d(origins, directions) of up to four sampling
+    levels (one `[n, 3]` pair per level) summed per camera and taken through the exponential map into `dpose`, plus the
+    gradient of the L2 pose regulariser with the two penalties, whose value goes to `reg_out` (None: not wanted)."""
+    up = N.RayGrads()
+    for k, (go, gd) in enumerate(zip(d_origins, d_directions)):
+        up.d_origins[k], up.d_directions[k] = N.ptr(go), N.ptr(gd)
+    up.count = len(d_origins)
+    N.check(N.load().nsamd_camera_backward(N.ptr(pose), mode, pose.shape[0], N.ptr(raw_directions), N.ptr(cams),
+                                           raw_directions.shape[0], up, trans_penalty, rot_penalty, N.ptr(dpose), N.ptr(reg_out),
+                                           N.stream()), "camera_backward")
+
+
 class _CameraRaysFn(torch.autograd.Function):
     """CameraOptimizer.apply_to_raybundle (cameras/camera_optimizers.py:148-153) on the pose parameter: one launch forward
     (nsamd_camera_apply), one launch backward (nsamd_camera_backward: per-camera sums of dL/d(origins, directions) in double
@@ -1117,10 +1202,8 @@ class _CameraRaysFn(torch.autograd.Function):
         raw_o, raw_d = _f32c(origins.reshape(-1, 3)), _f32c(directions.reshape(-1, 3))
         idx = cams.reshape(-1).contiguous().to(torch.int64)
         p = _f32c(pose)
-        n = raw_o.shape[0]
         o, d = torch.empty_like(raw_o), torch.empty_like(raw_d)
-        N.check(N.load().nsamd_camera_apply(N.ptr(p), mode, p.shape[0], N.ptr(raw_o), N.ptr(raw_d), N.ptr(idx), n, N.ptr(o),
-                                            N.ptr(d), N.stream()), "camera_apply")
+        camera_apply_launch(p, mode, raw_o, raw_d, idx, o, d)
         ctx.save_for_backward(p, raw_d, idx)
         ctx.mode = mode
         ctx.pose_param = pose
@@ -1129,14 +1212,10 @@ class _CameraRaysFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_o: Optional[Tensor], g_d: Optional[Tensor]):
         p, raw_d, idx = ctx.saved_tensors
-        n = raw_d.shape[0]
         g_o = torch.zeros_like(raw_d) if g_o is None else _f32c(g_o.reshape(-1, 3))
         g_d = torch.zeros_like(raw_d) if g_d is None else _f32c(g_d.reshape(-1, 3))
         buf, ret = _grad_target(ctx.pose_param, True)
-        up = N.RayGrads()
-        up.d_origins[0], up.d_directions[0], up.count = N.ptr(g_o), N.ptr(g_d), 1
-        N.check(N.load().nsamd_camera_backward(N.ptr(p), ctx.mode, p.shape[0], N.ptr(raw_d), N.ptr(idx), n, up, 0.0, 0.0,
-                                               N.ptr(buf), None, N.stream()), "camera_backward")
+        camera_backward_launch(p, ctx.mode, raw_d, idx, [g_o], [g_d], 0.0, 0.0, buf, None)
         return ret, None, None, None, None
 
 
@@ -1144,6 +1223,15 @@ def camera_correct_rays(pose: Tensor, mode: str, origins: Tensor, directions: Te
     """origins + t(c), R(c) directions for the camera c of every ray; `pose` [num_cameras, 6] = (translation, rotation
     vector), mode "SO3xR3" / "SE3" (cameras/lie_groups.py:25-117). The rays themselves are treated as constants."""
     return _CameraRaysFn.apply(pose, origins, directions, camera_indices, CAMERA_MODES[mode])
+
+
+def select_batch_launch(slot: Tensor, slots: int, pool_origins: Tensor, pool_directions: Tensor, pool_cameras: Tensor,
+                        pool_target: Tensor, origins: Tensor, directions: Tensor, camera_indices: Tensor, target: Tensor) -> None:
+    """nsamd_select_batch on the current stream: batch number `slot[0]` (a device value, so that a captured launch follows it) of
+    a pool of `slots` batches of `origins.shape[0]` rays each into the four static buffers a schedule reads."""
+    N.check(N.load().nsamd_select_batch(N.ptr(slot), slots, origins.shape[0], N.ptr(pool_origins), N.ptr(pool_directions),
+                                        N.ptr(pool_cameras), N.ptr(pool_target), N.ptr(origins), N.ptr(directions),
+                                        N.ptr(camera_indices), N.ptr(target), N.stream()), "select_batch")
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -1285,6 +1373,91 @@ def occgrid_binarise(occs: Tensor, binaries: Tensor, coarse: Optional[Tensor], o
                                             N.ptr(scratch), N.ptr(threshold_out), N.stream()), "occgrid_binarise")
 
 
+def packed_info_launch(counts: Tensor, n: int, info: Tensor, total: Tensor) -> None:
+    """nsamd_packed_info on the current stream: `info` `[n, 2]` int64 (start, count) from per-ray `counts` `[n]` int32, their sum
+    into the one-element int64 `total`. Here and below `n` is the number of rays: a schedule's buffers may be larger."""
+    N.check(N.load().nsamd_packed_info(N.ptr(counts), n, N.ptr(info), N.ptr(total), N.stream()), "packed_info")
+
+
+def occgrid_march_count_launch(origins: Tensor, directions: Tensor, t_min: Optional[Tensor], t_max: Optional[Tensor], n: int,
+                               near: float, far: float, grid: N.OccGrid, step_size: float, cone_angle: float, jitter: Optional[Tensor],
+                               counts: Tensor, stash: Optional[Tensor], stash_cap: int) -> None:
+    """nsamd_occgrid_march_count_stash on the current stream: the count pass of the marcher over `[n, 3]` rays -> kept steps per
+    ray in `counts`, the first `stash_cap` of them in `stash` `[n, stash_cap, 2]` (None / 0: nothing stashed)."""
+    N.check(N.load().nsamd_occgrid_march_count_stash(N.ptr(origins), N.ptr(directions), N.ptr(t_min), N.ptr(t_max),
+                                                     n, near, far, grid, step_size, cone_angle, N.ptr(jitter),
+                                                     N.ptr(counts), N.ptr(stash), stash_cap, N.stream()),
+            "occgrid_march_count_stash")
+
+
+def occgrid_march_write_launch(origins: Tensor, directions: Tensor, t_min: Optional[Tensor], t_max: Optional[Tensor], n: int,
+                               near: float, far: float, grid: N.OccGrid, step_size: float, cone_angle: float, jitter: Optional[Tensor],
+                               info: Tensor, stash: Optional[Tensor], stash_cap: int, ray_indices: Tensor, t_starts: Tensor,
+                               t_ends: Tensor) -> None:
+    """nsamd_occgrid_march_write_stashed on the current stream: the write pass behind `occgrid_march_count_launch` and
+    `packed_info_launch` — every ray's samples at its `info` offset of the packed outputs (sized for the total or larger)."""
+    N.check(N.load().nsamd_occgrid_march_write_stashed(N.ptr(origins), N.ptr(directions), N.ptr(t_min), N.ptr(t_max),
+                                                       n, near, far, grid, step_size, cone_angle, N.ptr(jitter),
+                                                       N.ptr(info), N.ptr(stash), stash_cap, N.ptr(ray_indices), N.ptr(t_starts),
+                                                       N.ptr(t_ends), N.stream()), "occgrid_march_write_stashed")
+
+
+def packed_positions_launch(origins: Tensor, directions: Tensor, ray_indices: Tensor, t_starts: Tensor, t_ends: Tensor,
+                            count: int, out: Tensor) -> None:
+    """nsamd_packed_positions on the current stream: o[ray] + d[ray] (t_start + t_end) / 2 of the first `count` packed samples."""
+    N.check(N.load().nsamd_packed_positions(N.ptr(origins), N.ptr(directions), N.ptr(ray_indices), N.ptr(t_starts), N.ptr(t_ends),
+                                            count, N.ptr(out), N.stream()), "packed_positions")
+
+
+def packed_visibility_launch(t_starts: Tensor, t_ends: Tensor, sigmas: Tensor, packed_info: Tensor, n: int, early_stop_eps: float,
+                             alpha_thre: float, mask: Tensor, kept: Tensor) -> None:
+    """nsamd_packed_visibility on the current stream: per packed sample of the `[n, 2]` rays of `packed_info` whether it is kept
+    (uint8 `mask`), per ray how many are (int32 `kept`)."""
+    N.check(N.load().nsamd_packed_visibility(N.ptr(t_starts), N.ptr(t_ends), N.ptr(sigmas), N.ptr(packed_info),
+                                             n, early_stop_eps, alpha_thre, N.ptr(mask), N.ptr(kept),
+                                             N.stream()), "packed_visibility")
+
+
+def packed_compact_launch(mask: Tensor, packed_info: Tensor, kept_info: Tensor, n: int, t_starts: Tensor, t_ends: Tensor,
+                          ray_indices_out: Tensor, t_starts_out: Tensor, t_ends_out: Tensor) -> None:
+    """nsamd_packed_compact on the current stream: the samples `mask` keeps, moved to their `kept_info` offsets."""
+    N.check(N.load().nsamd_packed_compact(N.ptr(mask), N.ptr(packed_info), N.ptr(kept_info), n, N.ptr(t_starts),
+                                          N.ptr(t_ends), N.ptr(ray_indices_out), N.ptr(t_starts_out), N.ptr(t_ends_out),
+                                          N.stream()), "packed_compact")
+
+
+def packed_weights_launch(t_starts: Tensor, t_ends: Tensor, sigmas: Tensor, packed_info: Tensor, n: int, weights: Tensor) -> None:
+    """nsamd_packed_weights_fwd on the current stream: rendering weights of the packed samples of the rays of `packed_info`."""
+    N.check(N.load().nsamd_packed_weights_fwd(N.ptr(t_starts), N.ptr(t_ends), N.ptr(sigmas), N.ptr(packed_info),
+                                              n, N.ptr(weights), None, N.stream()), "packed_weights_fwd")
+
+
+def packed_weights_backward_launch(t_starts: Tensor, t_ends: Tensor, sigmas: Tensor, dweights: Tensor, packed_info: Tensor,
+                                   n: int, dsigmas: Tensor) -> None:
+    """nsamd_packed_weights_bwd on the current stream: the density gradient of `packed_weights_launch` from `dweights`."""
+    N.check(N.load().nsamd_packed_weights_bwd(N.ptr(t_starts), N.ptr(t_ends), N.ptr(sigmas), N.ptr(dweights), N.ptr(packed_info),
+                                              n, N.ptr(dsigmas), N.stream()), "packed_weights_bwd")
+
+
+def packed_composite_launch(rgb: Tensor, weights: Tensor, t_starts: Optional[Tensor], t_ends: Optional[Tensor],
+                            packed_info: Tensor, n: int, bg_mode: int, bg_vals, eval_mode: bool, out_rgb: Tensor, acc: Tensor,
+                            depth: Optional[Tensor]) -> None:
+    """nsamd_packed_composite_fwd on the current stream: colour `[n, 3]`, accumulation `[n]` and (with the sample intervals)
+    expected depth `[n]` of the rays of `packed_info`; `bg_mode` / `bg_vals` as `_packed_bg` returns them."""
+    N.check(N.load().nsamd_packed_composite_fwd(N.ptr(rgb), N.ptr(weights), N.ptr(t_starts), N.ptr(t_ends), N.ptr(packed_info),
+                                                n, bg_mode, bg_vals, int(eval_mode), N.ptr(out_rgb),
+                                                N.ptr(acc), N.ptr(depth), N.stream()), "packed_composite_fwd")
+
+
+def packed_composite_backward_launch(rgb: Tensor, weights: Tensor, ray_indices: Tensor, count: int, bg_mode: int, bg_vals,
+                                     g_rgb: Tensor, g_acc: Optional[Tensor], d_rgb: Optional[Tensor], d_weights: Tensor) -> None:
+    """nsamd_packed_composite_bwd on the current stream: gradients of the first `count` packed samples' colours (None: not
+    wanted) and weights from the per-ray gradients of the composited colour and (None: none) the accumulation."""
+    N.check(N.load().nsamd_packed_composite_bwd(N.ptr(rgb), N.ptr(weights), N.ptr(ray_indices), count, bg_mode, bg_vals,
+                                                N.ptr(g_rgb), N.ptr(g_acc), N.ptr(d_rgb), N.ptr(d_weights), N.stream()),
+            "packed_composite_bwd")
+
+
 @torch.no_grad()
 def packed_info_from_counts(counts: Tensor) -> Tuple[Tensor, int]:
     """nerfacc.pack_info from per-ray counts (int32 `[N]`) -> (`[N,2]` int64 (start, count), total). The total is read
@@ -1293,7 +1466,7 @@ def packed_info_from_counts(counts: Tensor) -> Tuple[Tensor, int]:
     n = counts.shape[0]
     info = torch.empty((n, 2), device=counts.device, dtype=torch.int64)
     total = torch.zeros((1,), device=counts.device, dtype=torch.int64)
-    N.check(N.load().nsamd_packed_info(N.ptr(counts), n, N.ptr(info), N.ptr(total), N.stream()), "packed_info")
+    packed_info_launch(counts, n, info, total)
     return info, int(total.item())
 
 
@@ -1316,21 +1489,15 @@ def occgrid_march(origins: Tensor, directions: Tensor, binaries: Tensor, roi_aab
     tmax = None if t_max is None else _f32c(t_max.reshape(-1))
     jit = None if jitter is None else _f32c(jitter.reshape(-1))
     counts = torch.empty((n,), device=dev, dtype=torch.int32)
-    lib = N.load()
-    far = min(float(far_plane), 3.0e38)
+    march = (o, d, tmin, tmax, n, float(near_plane), min(float(far_plane), 3.0e38), grid, float(step_size), float(cone_angle), jit)
     stash = torch.empty((n, int(stash_cap), 2), device=dev, dtype=torch.float32) if stash_cap > 0 else None
-    N.check(lib.nsamd_occgrid_march_count_stash(N.ptr(o), N.ptr(d), N.ptr(tmin), N.ptr(tmax), n, float(near_plane), far, grid,
-                                                float(step_size), float(cone_angle), N.ptr(jit), N.ptr(counts), N.ptr(stash),
-                                                int(stash_cap), N.stream()), "occgrid_march_count_stash")
+    occgrid_march_count_launch(*march, counts, stash, int(stash_cap))
     info, total = packed_info_from_counts(counts)
     ray_indices = torch.empty((total,), device=dev, dtype=torch.int64)
     t_starts = torch.empty((total,), device=dev, dtype=torch.float32)
     t_ends = torch.empty((total,), device=dev, dtype=torch.float32)
     if total:
-        N.check(lib.nsamd_occgrid_march_write_stashed(N.ptr(o), N.ptr(d), N.ptr(tmin), N.ptr(tmax), n, float(near_plane), far,
-                                                      grid, float(step_size), float(cone_angle), N.ptr(jit), N.ptr(info),
-                                                      N.ptr(stash), int(stash_cap), N.ptr(ray_indices), N.ptr(t_starts),
-                                                      N.ptr(t_ends), N.stream()), "occgrid_march_write_stashed")
+        occgrid_march_write_launch(*march, info, stash, int(stash_cap), ray_indices, t_starts, t_ends)
     return ray_indices, t_starts, t_ends, info
 
 
@@ -1339,9 +1506,7 @@ def packed_positions(origins: Tensor, directions: Tensor, ray_indices: Tensor, t
     """o[ray] + d[ray] (t_start + t_end) / 2 for packed samples -> `[n,3]`."""
     N.require_cuda(origins, directions, ray_indices, t_starts, t_ends)
     out = torch.empty((ray_indices.shape[0], 3), device=origins.device, dtype=torch.float32)
-    N.check(N.load().nsamd_packed_positions(N.ptr(_f32c(origins)), N.ptr(_f32c(directions)), N.ptr(ray_indices),
-                                            N.ptr(t_starts), N.ptr(t_ends), ray_indices.shape[0], N.ptr(out), N.stream()),
-            "packed_positions")
+    packed_positions_launch(_f32c(origins), _f32c(directions), ray_indices, t_starts, t_ends, ray_indices.shape[0], out)
     return out
 
 
@@ -1355,17 +1520,14 @@ def packed_visibility_compact(ray_indices: Tensor, t_starts: Tensor, t_ends: Ten
     dev = t_starts.device
     mask = torch.empty((t_starts.shape[0],), device=dev, dtype=torch.uint8)
     kept = torch.empty((n_rays,), device=dev, dtype=torch.int32)
-    lib = N.load()
-    N.check(lib.nsamd_packed_visibility(N.ptr(t_starts), N.ptr(t_ends), N.ptr(_f32c(sigmas)), N.ptr(packed_info), n_rays,
-                                        float(early_stop_eps), float(alpha_thre), N.ptr(mask), N.ptr(kept), N.stream()),
-            "packed_visibility")
+    packed_visibility_launch(t_starts, t_ends, _f32c(sigmas), packed_info, n_rays, float(early_stop_eps), float(alpha_thre), mask,
+                             kept)
     info2, total = packed_info_from_counts(kept)
     ri = torch.empty((total,), device=dev, dtype=torch.int64)
     ts = torch.empty((total,), device=dev, dtype=torch.float32)
     te = torch.empty((total,), device=dev, dtype=torch.float32)
     if total:
-        N.check(lib.nsamd_packed_compact(N.ptr(mask), N.ptr(packed_info), N.ptr(info2), n_rays, N.ptr(t_starts), N.ptr(t_ends),
-                                         N.ptr(ri), N.ptr(ts), N.ptr(te), N.stream()), "packed_compact")
+        packed_compact_launch(mask, packed_info, info2, n_rays, t_starts, t_ends, ri, ts, te)
     return ri, ts, te, info2, mask
 
 
@@ -1375,8 +1537,7 @@ class _PackedWeightsFn(torch.autograd.Function):
         N.require_cuda(sigmas, t_starts, t_ends, packed_info)
         sigmas = _f32c(sigmas)
         w = torch.empty_like(sigmas)
-        N.check(N.load().nsamd_packed_weights_fwd(N.ptr(t_starts), N.ptr(t_ends), N.ptr(sigmas), N.ptr(packed_info),
-                                                  packed_info.shape[0], N.ptr(w), None, N.stream()), "packed_weights_fwd")
+        packed_weights_launch(t_starts, t_ends, sigmas, packed_info, packed_info.shape[0], w)
         ctx.save_for_backward(sigmas, t_starts, t_ends, packed_info)
         return w
 
@@ -1384,8 +1545,7 @@ class _PackedWeightsFn(torch.autograd.Function):
     def backward(ctx, gw: Tensor):
         sigmas, t_starts, t_ends, info = ctx.saved_tensors
         ds = torch.empty_like(sigmas)
-        N.check(N.load().nsamd_packed_weights_bwd(N.ptr(t_starts), N.ptr(t_ends), N.ptr(sigmas), N.ptr(_f32c(gw)), N.ptr(info),
-                                                  info.shape[0], N.ptr(ds), N.stream()), "packed_weights_bwd")
+        packed_weights_backward_launch(t_starts, t_ends, sigmas, _f32c(gw), info, info.shape[0], ds)
         return ds, None, None, None
 
 
@@ -1417,9 +1577,7 @@ class _PackedCompositeFn(torch.autograd.Function):
         out = torch.empty((n_rays, 3), device=dev, dtype=torch.float32)
         acc = torch.empty((n_rays,), device=dev, dtype=torch.float32)
         depth = torch.empty((n_rays,), device=dev, dtype=torch.float32) if t_starts is not None else None
-        N.check(N.load().nsamd_packed_composite_fwd(N.ptr(rgb), N.ptr(weights), N.ptr(t_starts), N.ptr(t_ends),
-                                                    N.ptr(packed_info), n_rays, bg_mode, bg_vals, 1 if eval_mode else 0,
-                                                    N.ptr(out), N.ptr(acc), N.ptr(depth), N.stream()), "packed_composite_fwd")
+        packed_composite_launch(rgb, weights, t_starts, t_ends, packed_info, n_rays, bg_mode, bg_vals, eval_mode, out, acc, depth)
         ctx.save_for_backward(rgb, weights, ray_indices)
         ctx.bg = (bg_mode, bg_vals)
         ctx.mark_non_differentiable(*([depth] if depth is not None else []))
@@ -1432,9 +1590,7 @@ class _PackedCompositeFn(torch.autograd.Function):
         d_rgb = torch.empty_like(rgb) if ctx.needs_input_grad[0] else None
         d_w = torch.empty_like(weights)
         g_rgb = _f32c(g_rgb) if g_rgb is not None else torch.zeros((int(ray_indices.max()) + 1 if n else 0, 3), device=rgb.device)
-        N.check(N.load().nsamd_packed_composite_bwd(N.ptr(rgb), N.ptr(weights), N.ptr(ray_indices), n, ctx.bg[0], ctx.bg[1],
-                                                    N.ptr(g_rgb), N.ptr(_f32c(g_acc) if g_acc is not None else None),
-                                                    N.ptr(d_rgb), N.ptr(d_w), N.stream()), "packed_composite_bwd")
+        packed_composite_backward_launch(rgb, weights, ray_indices, n, ctx.bg[0], ctx.bg[1], g_rgb, _f32c(g_acc), d_rgb, d_w)
         return d_rgb, d_w, None, None, None, None, None, None, None
 
 

@@ -12,8 +12,11 @@ Through this package's nn.Module / autograd classes that is the same kernels plu
 the frustums, elementwise position arithmetic, allocations of every intermediate, bincount, the loss) between TWO host
 reads of a sample count, and the step is host-bound: 1.52 ms against 0.85 ms of kernel time (profiles/r03_final_bench_ngp*).
 Here every intermediate lives in a buffer sized for a CAPACITY of candidates / kept samples (grown 1.5 x when a batch exceeds
-it — the only allocation after warm-up), the kernels are launched back to back through the C ABI, and the two counts are the
-only host reads (the packed arrays are data-dependent in size, as in nerfacc; the kernels take their sizes by value).
+it — the only allocation after warm-up), the kernels are launched back to back through the launch helpers the module path's
+wrappers use (functional.occgrid_march_count_launch / occgrid_march_write_launch, packed_info_launch, packed_positions_launch,
+packed_visibility_launch, packed_compact_launch, packed_weights[_backward]_launch, packed_composite[_backward]_launch,
+field_forward / field_backward), and the two counts are the only host reads (the packed arrays are data-dependent in size, as
+in nerfacc; the helpers take the candidate / kept counts by value, the ray count off the per-ray views).
 
 Same kernels, same order as the module path. What differs is rounding only: the positions of the kept samples come from
 nsamd_packed_positions (an fma) instead of the torch expression `o + d * (t0 + t1) / 2`, and the gradient of the MSE is
@@ -162,7 +165,6 @@ class NgpTrainStep:
     def forward(self, jitter: Optional[Tensor] = None) -> None:
         """Sampling + field + compositing. `jitter [n]`: injected lattice offsets (tests); None draws them on the device."""
         m, cfg, n = self.model, self.cfg, self.n
-        lib, st, ck = N.load(), N.stream(), N.check
         grid = m.occupancy_grid
         grid.ensure_derived()
         og = F._occgrid_native(grid.binaries, grid._roi, grid._coarse)
@@ -170,14 +172,13 @@ class NgpTrainStep:
             self.jitter.uniform_()  # stratified training (ray_samplers.py:489); same draws as torch.rand(n)
         else:
             self.jitter.copy_(jitter.reshape(-1))
-        o, d = N.ptr(self.origins), N.ptr(self.directions)
-        near, far, step, cone = float(cfg.near_plane), min(float(cfg.far_plane), 3.0e38), float(cfg.render_step_size), float(cfg.cone_angle)
+        o, d = self.origins, self.directions
         # -- candidates: count -> prefix -> (host read) -> write
-        tmin, tmax = (N.ptr(self.t_min), N.ptr(self.t_max)) if self.has_bounds else (None, None)
-        stash = N.ptr(self.stash)
-        ck(lib.nsamd_occgrid_march_count_stash(o, d, tmin, tmax, n, near, far, og, step, cone, N.ptr(self.jitter), N.ptr(self.counts),
-                                               stash, STASH_CAP, st), "occgrid_march_count_stash")
-        ck(lib.nsamd_packed_info(N.ptr(self.counts), n, N.ptr(self.info), N.ptr(self.totals[0:1]), st), "packed_info")
+        tmin, tmax = (self.t_min, self.t_max) if self.has_bounds else (None, None)
+        march = (o, d, tmin, tmax, n, float(cfg.near_plane), min(float(cfg.far_plane), 3.0e38), og, float(cfg.render_step_size),
+                 float(cfg.cone_angle), self.jitter)
+        F.occgrid_march_count_launch(*march, self.counts, self.stash, STASH_CAP)
+        F.packed_info_launch(self.counts, n, self.info, self.totals[0:1])
         mc = self._read_total(0)
         self.num_candidates = mc
         fld = m.field
@@ -187,27 +188,23 @@ class NgpTrainStep:
         if mc:
             if mc > self.cap_c:
                 self._grow_candidates(int(1.5 * mc))
-            ck(lib.nsamd_occgrid_march_write_stashed(o, d, tmin, tmax, n, near, far, og, step, cone, N.ptr(self.jitter), N.ptr(self.info),
-                                                     stash, STASH_CAP, N.ptr(self.c_ri), N.ptr(self.c_ts), N.ptr(self.c_te), st),
-               "occgrid_march_write_stashed")
+            F.occgrid_march_write_launch(*march, self.info, self.stash, STASH_CAP, self.c_ri, self.c_ts, self.c_te)
             # -- sigma_fn (ray_samplers.py:420-429): density of the candidates; no direction, a constant appearance row
-            ck(lib.nsamd_packed_positions(o, d, N.ptr(self.c_ri), N.ptr(self.c_ts), N.ptr(self.c_te), mc, N.ptr(self.c_pos), st),
-               "packed_positions")
+            F.packed_positions_launch(o, d, self.c_ri, self.c_ts, self.c_te, mc, self.c_pos)
             F.field_forward(*tbl, N.make_points(positions=self.c_pos), mc, self.c_enc, self.c_sel, self.view0, None, self.app0, mc,
                             fm, self.c_sigma, None)  # (rgb NULL: density only)
             # -- visibility-ordered early termination + alpha threshold, then compaction (OccGridEstimator.sampling)
             alpha = float(cfg.alpha_thre)
             if alpha > 0.0:
                 alpha = min(alpha, grid._occ_mean)
-            ck(lib.nsamd_packed_visibility(N.ptr(self.c_ts), N.ptr(self.c_te), N.ptr(self.c_sigma), N.ptr(self.info), n, 1e-4, alpha,
-                                           N.ptr(self.c_mask), N.ptr(self.kept), st), "packed_visibility")
-            ck(lib.nsamd_packed_info(N.ptr(self.kept), n, N.ptr(self.info2), N.ptr(self.totals[1:2]), st), "packed_info")
+            F.packed_visibility_launch(self.c_ts, self.c_te, self.c_sigma, self.info, n, 1e-4, alpha, self.c_mask, self.kept)
+            F.packed_info_launch(self.kept, n, self.info2, self.totals[1:2])
             mk = self._read_total(1)
             if mk:
                 if mk > self.cap_k:
                     self._grow_kept(int(1.5 * mk))
-                ck(lib.nsamd_packed_compact(N.ptr(self.c_mask), N.ptr(self.info), N.ptr(self.info2), n, N.ptr(self.c_ts),
-                                            N.ptr(self.c_te), N.ptr(self.k_ri), N.ptr(self.k_ts), N.ptr(self.k_te), st), "packed_compact")
+                F.packed_compact_launch(self.c_mask, self.info, self.info2, n, self.c_ts, self.c_te, self.k_ri, self.k_ts,
+                                        self.k_te)
         if mk == 0:
             # a single fake sample (ray 0, [1, 1]) keeps every downstream shape valid (ray_samplers.py:494-500)
             mk = 1
@@ -223,8 +220,7 @@ class NgpTrainStep:
         train_app = self.app0 is not None and m.training
         if train_app:
             torch.index_select(self.cams, 0, self.k_ri[:mk], out=self.k_cams[:mk])
-        ck(lib.nsamd_packed_positions(o, d, N.ptr(self.k_ri), N.ptr(self.k_ts), N.ptr(self.k_te), mk, N.ptr(self.k_pos), st),
-           "packed_positions")
+        F.packed_positions_launch(o, d, self.k_ri, self.k_ts, self.k_te, mk, self.k_pos)
         self._app_const = None
         if self.app0 is not None and not train_app:  # eval semantics of the embedding (nerfacto_field.py:253-261)
             emb = fld.embedding_appearance.embedding.weight
@@ -233,11 +229,9 @@ class NgpTrainStep:
                         self.k_cams if train_app else None, self._app_const, 1, fm, self.k_dens, self.k_rgb)
         self._train_app = train_app
         # -- packed weights and the three renderers in one launch (models/instant_ngp.py:191-214)
-        ck(lib.nsamd_packed_weights_fwd(N.ptr(self.k_ts), N.ptr(self.k_te), N.ptr(self.k_dens), N.ptr(self.info2), n, N.ptr(self.k_w),
-                                        None, st), "packed_weights_fwd")
-        ck(lib.nsamd_packed_composite_fwd(N.ptr(self.k_rgb), N.ptr(self.k_w), N.ptr(self.k_ts), N.ptr(self.k_te), N.ptr(self.info2), n,
-                                          self.bg_mode, self.bg_vals, 0, N.ptr(self.rgb), N.ptr(self.acc), N.ptr(self.depth), st),
-           "packed_composite_fwd")
+        F.packed_weights_launch(self.k_ts, self.k_te, self.k_dens, self.info2, n, self.k_w)
+        F.packed_composite_launch(self.k_rgb, self.k_w, self.k_ts, self.k_te, self.info2, n, self.bg_mode, self.bg_vals, False,
+                                  self.rgb, self.acc, self.depth)
         # expected depth clipped to the batch's range of sample midpoints (renderers.py:381-383)
         torch.add(self.k_ts[:mk], self.k_te[:mk], out=self.k_mid[:mk])
         self.k_mid[:mk].mul_(0.5)
@@ -290,15 +284,11 @@ class NgpTrainStep:
     @profiler.time_function
     @torch.no_grad()
     def backward(self) -> None:
-        m, n, mk = self.model, self.n, self.num_kept
-        lib, st, ck = N.load(), N.stream(), N.check
-        fld = m.field
+        mk, fld = self.num_kept, self.model.field
         self.prepare_grads()
-        ck(lib.nsamd_packed_composite_bwd(N.ptr(self.k_rgb), N.ptr(self.k_w), N.ptr(self.k_ri), mk, self.bg_mode, self.bg_vals,
-                                          N.ptr(self.g_rgb), N.ptr(self.g_acc) if self.random_bg else None, N.ptr(self.k_drgb),
-                                          N.ptr(self.k_dw), st), "packed_composite_bwd")
-        ck(lib.nsamd_packed_weights_bwd(N.ptr(self.k_ts), N.ptr(self.k_te), N.ptr(self.k_dens), N.ptr(self.k_dw), N.ptr(self.info2), n,
-                                        N.ptr(self.k_dsigma), st), "packed_weights_bwd")
+        F.packed_composite_backward_launch(self.k_rgb, self.k_w, self.k_ri, mk, self.bg_mode, self.bg_vals, self.g_rgb,
+                                           self.g_acc if self.random_bg else None, self.k_drgb, self.k_dw)
+        F.packed_weights_backward_launch(self.k_ts, self.k_te, self.k_dens, self.k_dw, self.info2, self.n, self.k_dsigma)
         params, emb = F.field_params(fld)
         gl = self.grad_lookup
         grad_of = (lambda p: gl[id(p)]) if gl is not None else (lambda p: p.grad)  # noqa: E731

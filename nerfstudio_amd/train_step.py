@@ -17,6 +17,11 @@ measured slower — csrc/experiments/rounds2to5_opt_in_variants.patch, DESIGN.md
 accumulate directly into `param.grad` (the views of arena.ParamArena). Nothing here depends on host-side values that change from step to step (the jitter is drawn on the
 device, the anneal exponent lives in device memory), so the whole iteration can be captured in a hipGraph once per
 schedule variant and replayed. Numerically identical to the autograd path (tests/test_gpu_kernels.py compares them).
+
+The launches this schedule shares with the module path (or with trainer / eval_render) go through the helpers of functional.py
+— piecewise_bins_launch, density_forward, weights_launch, composite_launch, pdf_resample_launch, depth_loss_launch,
+distance_gradient_scale_launch, weights_backward_launch, camera_apply_launch, camera_backward_launch, select_batch_launch
+and the field helpers — with this runner's static buffers; the entry points only this schedule launches are called here.
 """
 from __future__ import annotations
 
@@ -104,13 +109,10 @@ class NerfactoTrainStep:
         self.dw_prop = [t(n, self.counts[lvl]) for lvl in range(self.n_prop)]
         self.d_rgb_s, self.d_dens_main = t(mm, 3), t(mm)
         # host arrays of device pointers for nsamd_proposal_losses (the buffers are static, so built once)
-        def parr(ts):
-            return (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
-
-        self._pl_s_bins = parr(self.s_bins[: self.n_prop])
-        self._pl_weights = parr(self.weights[: self.n_prop])
-        self._pl_per_ray = parr(self.inter_per_ray)
-        self._pl_dw = parr(self.dw_prop)
+        self._pl_s_bins = N.ptr_array(self.s_bins[: self.n_prop])
+        self._pl_weights = N.ptr_array(self.weights[: self.n_prop])
+        self._pl_per_ray = N.ptr_array(self.inter_per_ray)
+        self._pl_dw = N.ptr_array(self.dw_prop)
         self._pl_S = (C.c_int32 * self.n_prop)(*self.counts[: self.n_prop])
         # Ray terms (include/nsamd.h, nsamd_field_mlp.ray_terms): head layer 0's share of the 48 per-ray inputs (SH of the view
         # direction, appearance row) once per ray instead of once per sample (a 16-point tile must lie inside one ray).
@@ -184,7 +186,7 @@ class NerfactoTrainStep:
                                 and co.config.mode in ("SO3xR3", "SE3")
                                 and len(self.counts) <= 4  # nsamd_ray_grads has four level slots
                                 and getattr(co, "non_trainable_camera_indices", None) is None)
-            self.cam_mode = {"SO3xR3": 1, "SE3": 2}.get(co.config.mode, 0)
+            self.cam_mode = F.CAMERA_MODES.get(co.config.mode, 0)
             self.raw_origins, self.raw_directions = e(n, 3), e(n, 3)
             self.d_origins = [e(n, 3) for _ in self.counts]
             self.d_directions = [e(n, 3) for _ in self.counts]
@@ -213,9 +215,7 @@ class NerfactoTrainStep:
             if self._slot0 is None:
                 self._slot0 = torch.zeros(1, device=self.origins.device)
             o, d = (self.raw_origins, self.raw_directions) if self.cam_opt is not None else (self.origins, self.directions)
-            N.check(N.load().nsamd_select_batch(N.ptr(self._slot0), 1, self.n, N.ptr(origins), N.ptr(directions), N.ptr(cams),
-                                                N.ptr(target_rgb), N.ptr(o), N.ptr(d), N.ptr(self.camera_indices),
-                                                N.ptr(self.target), N.stream()), "select_batch")
+            F.select_batch_launch(self._slot0, 1, origins, directions, cams, target_rgb, o, d, self.camera_indices, self.target)
             return
         if self.cam_opt is not None:  # the kernels see the pose-corrected rays (apply_camera_corrections)
             self.raw_origins.copy_(origins)
@@ -248,16 +248,9 @@ class NerfactoTrainStep:
             raise ValueError("a depth that is not Euclidean needs directions_norm")
         d = self._depth_buffers
         if d is None:
-            dev, levels = self.origins.device, len(self.counts)
-            f32 = dict(device=dev, dtype=torch.float32)
-            parr = lambda ts: (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])  # noqa: E731
+            f32 = dict(device=self.origins.device, dtype=torch.float32)
             d = self._depth_buffers = {"target": torch.empty(self.n, **f32), "norm": torch.empty(self.n, **f32),
-                              "per_ray": torch.empty(levels, self.n, **f32), "value": torch.zeros((), **f32),
-                              "t_bins": parr(self.t_bins), "weights": parr(self.weights),
-                              "S": (C.c_int32 * levels)(*self.counts),
-                              # the final level always; the proposal levels on update steps only
-                              "dw_all": parr(self.dw_prop + [self.dw_dist]),
-                              "dw_final": (C.c_void_p * levels)(*([None] * self.n_prop + [self.dw_dist.data_ptr()]))}
+                                       "per_ray": torch.empty(len(self.counts), self.n, **f32), "value": torch.zeros((), **f32)}
         d["target"].copy_(termination_depth.reshape(-1))
         if not is_euclidean:
             d["norm"].copy_(directions_norm.reshape(-1))
@@ -375,10 +368,8 @@ class NerfactoTrainStep:
         if self.cam_opt is None:
             return
         if self.cam_kernels:
-            pose = self.cam_opt.pose_adjustment
-            N.check(N.load().nsamd_camera_apply(N.ptr(pose), self.cam_mode, pose.shape[0], N.ptr(self.raw_origins),
-                                                N.ptr(self.raw_directions), N.ptr(self.camera_indices), self.n,
-                                                N.ptr(self.origins), N.ptr(self.directions), N.stream()), "camera_apply")
+            F.camera_apply_launch(self.cam_opt.pose_adjustment, self.cam_mode, self.raw_origins, self.raw_directions,
+                                  self.camera_indices, self.origins, self.directions)
             return
         if hasattr(self.cam_opt, "corrected_rays"):
             o, d = self.cam_opt.corrected_rays(self.raw_origins, self.raw_directions, self.camera_indices)
@@ -419,16 +410,12 @@ class NerfactoTrainStep:
                     pose.grad = torch.zeros_like(pose)
                 g = pose.grad
             levels = (list(range(L)) if updated else []) + [L]  # the proposal networks saw the rays too (interlevel loss)
-            up = N.RayGrads()
-            for k, lvl in enumerate(levels):
-                up.d_origins[k], up.d_directions[k] = N.ptr(self.d_origins[lvl]), N.ptr(self.d_directions[lvl])
-            up.count = len(levels)
             cfg = self.cam_opt.config
             reg = self.reg_in_backward  # (else the caller differentiates the regulariser itself — fused_step.FusedTrainStep)
-            N.check(N.load().nsamd_camera_backward(
-                N.ptr(pose), self.cam_mode, pose.shape[0], N.ptr(self.raw_directions), N.ptr(self.camera_indices), self.n, up,
-                float(cfg.trans_l2_penalty) if reg else 0.0, float(cfg.rot_l2_penalty) if reg else 0.0, N.ptr(g),
-                N.ptr(self.camera_reg) if reg else None, N.stream()), "camera_backward")
+            F.camera_backward_launch(pose, self.cam_mode, self.raw_directions, self.camera_indices,
+                                     [self.d_origins[lvl] for lvl in levels], [self.d_directions[lvl] for lvl in levels],
+                                     float(cfg.trans_l2_penalty) if reg else 0.0, float(cfg.rot_l2_penalty) if reg else 0.0, g,
+                                     self.camera_reg if reg else None)
             return
         d_o, d_d = self.d_origins[L], self.d_directions[L]
         if updated:  # the proposal networks saw the rays too (interlevel loss)
@@ -487,8 +474,8 @@ class NerfactoTrainStep:
                                      N.ptr(self.edges), N.ptr(jit0), int(per_edge), S0, self.spacing, N.ptr(self.s_bins[0]),
                                      N.ptr(self.t_bins[0]), st), "select_bins")
         else:
-            ck(lib.nsamd_piecewise_bins(N.ptr(self.nears), N.ptr(self.fars), N.ptr(self.edges), N.ptr(jit0), int(per_edge), n,
-                                        S0, self.spacing, N.ptr(self.s_bins[0]), N.ptr(self.t_bins[0]), st), "piecewise_bins")
+            F.piecewise_bins_launch(self.nears, self.fars, self.edges, jit0, int(per_edge), self.spacing, self.s_bins[0],
+                                    self.t_bins[0])
         if after_bins is not None:  # (trainer.HipTrainer: the ray terms, behind the batch selection)
             after_bins()
         # ---- proposal levels ----
@@ -506,23 +493,21 @@ class NerfactoTrainStep:
                 self.ensure_proposal_features(lvl)
                 F.hash_forward(self._points(lvl), m, net._transform, net._box, net.encoding.hash_table, net.encoding.spec,
                                self.p_enc[lvl], 1, m, self.p_sel[lvl])
-                ck(lib.nsamd_density_mlp_fwd(N.ptr(self.p_enc[lvl]), N.ptr(self.p_sel[lvl]), m, dm, N.ptr(self.p_dens[lvl]),
-                                             None if self.forward_only else N.ptr(self.p_pre[lvl]), st), "density_mlp_fwd")
+                F.density_forward(self.p_enc[lvl], self.p_sel[lvl], m, dm, self.p_dens[lvl],
+                                  None if self.forward_only else self.p_pre[lvl])
             else:
                 ck(fused, "density_field_fwd")
             S2 = self.counts[lvl + 1]
             if per_edge:
                 # one draw per new bin edge: the fused launch below draws per ray, so this (non-default) configuration takes
                 # its three constituents — same numbers (nsamd.h)
-                ck(lib.nsamd_weights_fwd(N.ptr(self.t_bins[lvl]), N.ptr(self.p_dens[lvl]), n, S, N.ptr(self.weights[lvl]), st),
-                   "weights_fwd")
+                F.weights_launch(self.t_bins[lvl], self.p_dens[lvl], self.weights[lvl])
                 if self.compute_depths:
-                    ck(lib.nsamd_composite_fwd(None, N.ptr(self.weights[lvl]), N.ptr(self.t_bins[lvl]), n, S, N.BG_NONE, None, 0,
-                                               None, None, None, N.ptr(self.depth_med[lvl]), None, None, st), "composite_fwd(median)")
-                ck(lib.nsamd_pdf_resample(N.ptr(self.s_bins[lvl]), N.ptr(self.weights[lvl]), S, N.ptr(self.u_base[lvl + 1]),
-                                          N.ptr(self.jitter_edges[lvl + 1]), N.ptr(self.nears), N.ptr(self.fars), 1.0,
-                                          N.ptr(self.anneal_dev), 0.01, 1e-5, 1.0 / (2 * (S2 + 1)), self.spacing, 1, 0, n, S2,
-                                          N.ptr(self.s_bins[lvl + 1]), N.ptr(self.t_bins[lvl + 1]), None, st), "pdf_resample")
+                    F.composite_launch(None, self.weights[lvl], self.t_bins[lvl], N.BG_NONE, None, False, None, None, None,
+                                       self.depth_med[lvl], None, None)
+                F.pdf_resample_launch(self.s_bins[lvl], self.weights[lvl], self.u_base[lvl + 1], self.jitter_edges[lvl + 1],
+                                      self.nears, self.fars, 1.0, self.anneal_dev, 0.01, 1e-5, self.spacing, 1, False, S2,
+                                      self.s_bins[lvl + 1], self.t_bins[lvl + 1], None)
                 continue
             # weights of this level, its median depth (prop_depth_i, models/nerfacto.py:346-347) and the PDF resampling
             ck(lib.nsamd_proposal_resample(N.ptr(self.t_bins[lvl]), N.ptr(self.s_bins[lvl]), N.ptr(self.p_dens[lvl]), S,
@@ -599,11 +584,11 @@ class NerfactoTrainStep:
             if torch.cuda.is_current_stream_capturing():
                 raise NotImplementedError("explicit schedule: a depth target inside a captured graph; depth supervision in "
                                           "captured iterations is only on the module path")
-            levels = len(self.counts)
-            scale = d["mult"] / (n * levels)
-            ck(lib.nsamd_depth_loss(levels, d["t_bins"], d["weights"], d["S"], n, N.ptr(d["target"]),
-                                    None if d["euclidean"] else N.ptr(d["norm"]), None, d["sigma"], F.DEPTH_DS_NERF, scale, 1,
-                                    N.ptr(d["per_ray"]), d["dw_all"] if updated else d["dw_final"], None, st), "depth_loss")
+            scale = d["mult"] / (n * len(self.counts))
+            # the final level always; the proposal levels on update steps only
+            dws = (self.dw_prop if updated else [None] * self.n_prop) + [self.dw_dist]
+            F.depth_loss_launch(self.weights, self.t_bins, d["target"], None if d["euclidean"] else d["norm"], None, d["sigma"],
+                                F.DEPTH_DS_NERF, scale, d["per_ray"], dws, None, accumulate=True)
             torch.sum(d["per_ray"], dim=(0, 1), out=d["value"])
             d["value"].mul_(scale)
         if self.want_loss_vals:
@@ -627,8 +612,7 @@ class NerfactoTrainStep:
                                       N.ptr(self.d_rgb_s), N.ptr(self.d_dens_main), N.ptr(self.bg_rays), st),
            "render_train_bwd")
         if self.gradient_scaling:  # scale_gradients_by_distance_squared on the field's outputs (models/nerfacto.py:321-322)
-            ck(lib.nsamd_distance_gradient_scale(N.ptr(self.t_bins[L]), n, S, N.ptr(self.d_dens_main), N.ptr(self.d_rgb_s), st),
-               "distance_gradient_scale")
+            F.distance_gradient_scale_launch(self.t_bins[L], self.d_dens_main, self.d_rgb_s)
         if field:
             self.backward_field_and_table()
 
@@ -653,25 +637,29 @@ class NerfactoTrainStep:
     def _field_bwd_phases(self, args) -> None:
         """The fused main-field backward (nsamd_field_mlp_bwd_scatter) as separate phases: under N.PROFILE one launch group at
         a time (the per-kernel table, utils/roofline.py; same bits), else for the camera optimiser's share."""
-        lib, st, ck = N.load(), N.stream(), N.check
+        lib, st = N.load(), N.stream()
         L, fld = self.n_prop, self.model.field
+
+        def launch(phase: int) -> None:
+            N.check(lib.nsamd_field_mlp_bwd_scatter_phase(*args, phase, st), "field_mlp_bwd_scatter_phase")
+
         if N.PROFILE is not None:
             for phase in (1, 2, 4):
-                ck(lib.nsamd_field_mlp_bwd_scatter_phase(*args, phase, st), "field_mlp_bwd_scatter_phase")
+                launch(phase)
             if self.cam_opt is not None:
                 self._rays_backward(L, fld, self.f_denc)
             return
         # camera optimiser: the rays' gradient through the main grid (a gather pass over the table, 96 us) needs the
         # encoded-feature gradient the kernel has just written and nothing of the table scatter's apply pass (LDS
         # atomics, latency-bound): beside it on the second stream instead of behind it
-        ck(lib.nsamd_field_mlp_bwd_scatter_phase(*args, 1, st), "field_mlp_bwd_scatter_phase")
+        launch(1)
         main = N.current_stream()
         self._red_fork.record(main)
         self.reduce_stream.wait_event(self._red_fork)
         with N.on_stream(self.reduce_stream):
             self._rays_backward(L, fld, self.f_denc)
             self._red_join.record(self.reduce_stream)
-        ck(lib.nsamd_field_mlp_bwd_scatter_phase(*args, 6, st), "field_mlp_bwd_scatter_phase")  # (the reduce rides the apply pass)
+        launch(6)  # (the reduce rides the apply pass)
         main.wait_event(self._red_join)
 
     @profiler.time_function
@@ -700,8 +688,7 @@ class NerfactoTrainStep:
             ws, ws_n = F._scatter_workspace(spec, self.f_enc.device, m)
             grads = [self._grad(p) for p in (W0, b0, W1, b1)]
             if gate is None or ws is None:  # ungated chain (`gate_proposals` off, or no binned-scatter workspace for this shape)
-                ck(lib.nsamd_weights_bwd(N.ptr(self.t_bins[lvl]), N.ptr(self.p_dens[lvl]), N.ptr(self.dw_prop[lvl]),
-                                         n, S, N.ptr(self.p_ddens[lvl]), st), "weights_bwd")
+                F.weights_backward_launch(self.t_bins[lvl], self.p_dens[lvl], self.dw_prop[lvl], self.p_ddens[lvl])
                 F.density_backward(self.p_enc[lvl], self.p_sel[lvl], self.p_pre[lvl], self.p_ddens[lvl], m, dm, self.p_denc[lvl],
                                    grads, dws)
                 if self.cam_opt is not None:

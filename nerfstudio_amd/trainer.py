@@ -416,7 +416,7 @@ class HipTrainer:
             return  # (else: `_source_batch` has filled the buffers ahead of the iteration)
         if self.pool is None:
             return
-        from . import _native as N
+        from . import functional as F
 
         p = self.pool
         if self.runner is not None:
@@ -430,9 +430,8 @@ class HipTrainer:
             c, t = r.camera_indices, r.target
         else:
             o, d, c, t = self.rb.origins, self.rb.directions, self.rb.camera_indices, self.batch["image"]
-        N.check(N.load().nsamd_select_batch(N.ptr(self.hyper[_HYPER_SLOT:_HYPER_SLOT + 1]), self.slots, o.shape[0],
-                                            N.ptr(p["origins"]), N.ptr(p["directions"]), N.ptr(p["cameras"]), N.ptr(p["target"]),
-                                            N.ptr(o), N.ptr(d), N.ptr(c), N.ptr(t), N.stream()), "select_batch")
+        F.select_batch_launch(self.hyper[_HYPER_SLOT:_HYPER_SLOT + 1], self.slots, p["origins"], p["directions"], p["cameras"],
+                              p["target"], o, d, c, t)
 
     def _source_batch(self):
         """The eager form of a source (class docstring): `next_batch()` into the static buffers, ahead of the iteration."""

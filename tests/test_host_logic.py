@@ -435,6 +435,25 @@ def test_environment_switches_match_the_design_table():
     assert read == listed, (sorted(read - listed), sorted(listed - read))
 
 
+def test_every_entry_point_is_launched_from_one_place():
+    """Each entry point of `_native._SIGNATURES` has at most one attribute reference `.nsamd_<name>` in the package outside
+    _native.py: the allocating wrappers, the autograd Functions and the explicit schedules share one launch helper per entry
+    point, so a signature change is made once."""
+    import glob
+    import os
+    import re
+
+    from nerfstudio_amd import _native as N
+
+    pkg = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "nerfstudio_amd")
+    files = [p for p in glob.glob(os.path.join(pkg, "**", "*.py"), recursive=True) if os.path.basename(p) != "_native.py"]
+    assert len(files) > 10
+    text = "\n".join(open(p).read() for p in files)
+    counts = {name: len(re.findall(r"\." + name + r"(?!\w)", text)) for name in N._SIGNATURES}
+    assert max(counts.values()) == 1  # (the pattern does find the launches)
+    assert not {name: c for name, c in counts.items() if c > 1}
+
+
 def test_kernel_sources_have_one_build_configuration():
     """The only NSAMD_* name a preprocessor conditional of csrc/ tests is NSAMD_PROBE_CLOCKS (the instrumented `make probe`
     build): a decided A/B arm is deleted, not kept behind a macro that nothing sets."""
