@@ -444,7 +444,11 @@ int nsamd_proposal_levels_bwd(const nsamd_proposal_level_bwd* levels, int32_t nu
  * bins are bit-exact on every test seed.
  * anneal_dev (nullable): device copy of the anneal exponent; overrides `anneal` so that a captured hipGraph of the
  * training step can be replayed while the schedule advances. spacing: as in nsamd_piecewise_bins (the s -> t map of
- * the initial sampler, ray_samplers.py:112-116). */
+ * the initial sampler, ray_samplers.py:112-116).
+ * LIMITS: S_prev <= 1024 and S <= 4096, with or without include_original; beyond either NSAMD_ERR_UNSUPPORTED, no output
+ * written. The kernel keeps 4 rays x (3 S_prev + 2 [+ S + 1 with include_original]) floats in LDS: up to 114 736 B at
+ * (1024, 4096) with include_original. Requests beyond 64 KiB opt the kernel in to the larger size (once per device);
+ * NSAMD_ERR_LAUNCH if the runtime refuses that. */
 int nsamd_pdf_resample(const float* s_bins_prev, const float* weights, int32_t S_prev, const float* u_base,
                        const float* jitter, const float* nears, const float* fars, float anneal,
                        const float* anneal_dev, float histogram_padding, float eps, float u_offset, int spacing,
@@ -454,7 +458,8 @@ int nsamd_pdf_resample(const float* s_bins_prev, const float* weights, int32_t S
 /* One proposal level of ProposalNetworkSampler.generate_ray_samples (ray_samplers.py:576-617) in a single launch:
  * weights = RaySamples.get_weights(density) of the level's samples (t_bins_prev), its median depth (nullable;
  * models/nerfacto.py:346-347 renders prop_depth_i for every level), then nsamd_pdf_resample on those weights.
- * Same numbers as nsamd_weights_fwd + nsamd_composite_fwd(median) + nsamd_pdf_resample. */
+ * Same numbers as nsamd_weights_fwd + nsamd_composite_fwd(median) + nsamd_pdf_resample. S_prev <= 1024
+ * (NSAMD_ERR_UNSUPPORTED beyond, no output written). */
 int nsamd_proposal_resample(const float* t_bins_prev, const float* s_bins_prev, const float* density, int32_t S_prev,
                             const float* u_base, const float* jitter, const float* nears, const float* fars,
                             float anneal, const float* anneal_dev, float histogram_padding, float eps, float u_offset,

@@ -10,6 +10,7 @@
 // Layout: 4 rays per 256-thread workgroup (N = 4096 -> 1024 workgroups); rows are read/written coalesced.
 #include <stdlib.h>
 
+#include "launch.h"
 #include "proposal_chain.h"
 #include "ray_bodies.h"
 
@@ -72,6 +73,16 @@ __global__ __launch_bounds__(kThreads) void select_bins_kernel(
 // bit-exactly on their seeds). The previous one-lane-per-ray loop was 5x slower (profiles/).
 // ---------------------------------------------------------------------------------------------------------------
 constexpr int kWaves = 4;  // rays per 256-thread workgroup
+
+// nsamd_pdf_resample's accepted range (include/nsamd.h) and the LDS row of one wave of pdf_resample_kernel
+constexpr int kPdfMaxPrev = 1024;
+constexpr int kPdfMaxNew = 4096;
+constexpr size_t pdf_row_floats(size_t S_prev, size_t S, bool include_original) {
+  return 3 * S_prev + 2 + (include_original ? S + 1 : 0);
+}
+// the largest request, include_original at the limits: 114 736 B of gfx950's 160 KiB
+constexpr size_t kPdfLdsMax = sizeof(float) * kWaves * pdf_row_floats(kPdfMaxPrev, kPdfMaxNew, true);
+static_assert(kPdfLdsMax <= 160 * 1024, "pdf_resample_kernel: the accepted range must fit the LDS of a workgroup");
 
 // (wave.h: DPP scans - the shuffle-based Hillis-Steele version spent ~1.5 k clocks per scan in ds_bpermute round trips)
 __device__ __forceinline__ double wave_scan_inclusive(double v, int /*lane*/) { return wave_scan_inclusive_f64(v); }
@@ -146,7 +157,7 @@ __global__ __launch_bounds__(kThreads) void pdf_resample_kernel(
   extern __shared__ float lds[];  // (ray_bodies.h: pdf_resample_body)
   const int64_t ray = (int64_t)blockIdx.x * kWaves + wave_index();
   if (ray >= num_rays) return;  // wave-uniform; no workgroup barrier in the body
-  const int row_floats = 3 * S_prev + 2 + (include_original ? S + 1 : 0);
+  const size_t row_floats = pdf_row_floats((size_t)S_prev, (size_t)S, include_original != 0);
   pdf_resample_body<kFused>(lds + (size_t)wave_index() * row_floats, ray, s_bins_prev, weights, S_prev, u_base, jitter, nears,
                             fars, anneal_host, anneal_dev, hist_pad, eps, u_offset, spacing, num_rays, S, s_bins, t_bins, inds,
                             t_bins_prev, density, weights_out, depth_median, jitter_per_edge, include_original);
@@ -259,8 +270,13 @@ extern "C" int nsamd_pdf_resample(const float* s_bins_prev, const float* weights
   NSAMD_REQUIRE(num_rays >= 0 && S > 0 && S_prev > 0 && (spacing == 0 || spacing == 1));
   if (num_rays == 0) return NSAMD_OK;
   NSAMD_REQUIRE(s_bins_prev && weights && u_base && nears && fars && s_bins && t_bins);
-  if (S_prev > 1024 || S > 4096) return NSAMD_ERR_UNSUPPORTED;
-  const size_t lds = sizeof(float) * kWaves * (3 * (size_t)S_prev + 2 + (include_original ? (size_t)S + 1 : 0));
+  if (S_prev > kPdfMaxPrev || S > kPdfMaxNew) return NSAMD_ERR_UNSUPPORTED;
+  const size_t lds = sizeof(float) * kWaves * pdf_row_floats((size_t)S_prev, (size_t)S, include_original != 0);
+  if (lds > 64 * 1024) {  // include_original with long rows: beyond the default dynamic-LDS limit (launch.h)
+    static LdsOptIn opted_in;  // (once per device, for the largest accepted request)
+    const int rc = lds_opt_in(opted_in, pdf_resample_kernel<false>, kPdfLdsMax);
+    if (rc) return rc;
+  }
   pdf_resample_kernel<false><<<ray_blocks(num_rays), kThreads, lds, (hipStream_t)stream>>>(
       s_bins_prev, weights, S_prev, u_base, jitter, nears, fars, anneal, anneal_dev, histogram_padding, eps, u_offset,
       spacing, num_rays, S, s_bins, t_bins, inds, nullptr, nullptr, nullptr, nullptr, jitter_per_edge != 0,
@@ -278,8 +294,8 @@ extern "C" int nsamd_proposal_resample(const float* t_bins_prev, const float* s_
   NSAMD_REQUIRE(num_rays >= 0 && S > 0 && S_prev > 0 && (spacing == 0 || spacing == 1));
   if (num_rays == 0) return NSAMD_OK;
   NSAMD_REQUIRE(t_bins_prev && s_bins_prev && density && u_base && nears && fars && weights && s_bins && t_bins);
-  if (S_prev > 1024) return NSAMD_ERR_UNSUPPORTED;
-  const size_t lds = sizeof(float) * kWaves * (3 * (size_t)S_prev + 2);
+  if (S_prev > kPdfMaxPrev) return NSAMD_ERR_UNSUPPORTED;
+  const size_t lds = sizeof(float) * kWaves * pdf_row_floats((size_t)S_prev, (size_t)S, false);
   pdf_resample_kernel<true><<<ray_blocks(num_rays), kThreads, lds, (hipStream_t)stream>>>(
       s_bins_prev, nullptr, S_prev, u_base, jitter, nears, fars, anneal, anneal_dev, histogram_padding, eps, u_offset,
       spacing, num_rays, S, s_bins, t_bins, nullptr, t_bins_prev, density, weights, depth_median, 0, 0);

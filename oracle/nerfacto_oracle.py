@@ -496,6 +496,31 @@ def weights_from_density(t_bins: Tensor, density: Tensor) -> Tensor:
 
 
 
+def _weights_parts64(t_bins: Tensor, density: Tensor) -> Dict[str, Tensor]:
+    """The forward quantities of `weights_from_density` in float64 (shared by weights64 and weights_bwd64)."""
+    t, dens = t_bins.double(), density.double()
+    delta = t[:, 1:] - t[:, :-1]
+    dd = delta * dens
+    e = torch.exp(-dd)
+    alpha = 1 - e
+    X = torch.cat([torch.zeros_like(dd[:, :1]), torch.cumsum(dd[:, :-1], dim=-1)], dim=-1)
+    E = torch.exp(-X)
+    return dict(delta=delta, dd=dd, e=e, alpha=alpha, X=X, E=E, w=alpha * E)
+
+
+def weights64(t_bins: Tensor, density: Tensor) -> Dict[str, Tensor]:
+    """Float64 `weights_from_density` on fp32 (or float64) inputs. Returns float64 `[N,S]` tensors: w = alpha * E after
+    nan_to_num with fp32's limits (nan -> 0, +-inf -> +-FLT_MAX, as the fp32 pipeline stores it), w_raw before it, X = the
+    optical depth in front of the sample, Xabs = the same sum over |dd|, dd = delta * density, delta, e = exp(-dd),
+    alpha = 1 - e, E = exp(-X)."""
+    r = _weights_parts64(t_bins, density)
+    ddabs = r["dd"].abs()
+    r["Xabs"] = torch.cat([torch.zeros_like(ddabs[:, :1]), torch.cumsum(ddabs[:, :-1], dim=-1)], dim=-1)
+    r["w_raw"] = r["w"]
+    r["w"] = torch.nan_to_num(r["w"], nan=0.0, posinf=FLT_MAX, neginf=-FLT_MAX)
+    return r
+
+
 def weights_bwd64(t_bins: Tensor, density: Tensor, dweights: Tensor) -> Dict[str, Tensor]:
     """Float64 backward of `weights_from_density` on fp32 (or float64) inputs: autograd's own sequence of operations
     (nan_to_num passes the gradient where the weight is finite, as grad * isfinite(w); the cumsum's backward is the
@@ -503,14 +528,9 @@ def weights_bwd64(t_bins: Tensor, density: Tensor, dweights: Tensor) -> Dict[str
     ddensity; suf = sum_{i>j} g_i w_i (the exclusive suffix sum of the masked gradient times the weight) and suf_abs =
     sum_{i>j} |g_i w_i|; X = the optical depth in front of sample j, dd = delta_j * density_j, delta, E = exp(-X),
     e = exp(-dd), alpha = 1 - e, w = alpha * E (before nan_to_num), g = the masked upstream gradient."""
-    t, dens, gw = t_bins.double(), density.double(), dweights.double()
-    delta = t[:, 1:] - t[:, :-1]
-    dd = delta * dens
-    e = torch.exp(-dd)
-    alpha = 1 - e
-    X = torch.cat([torch.zeros_like(dd[:, :1]), torch.cumsum(dd[:, :-1], dim=-1)], dim=-1)
-    E = torch.exp(-X)
-    w = alpha * E
+    gw = dweights.double()
+    p = _weights_parts64(t_bins, density)
+    delta, dd, e, alpha, X, E, w = (p[k] for k in ("delta", "dd", "e", "alpha", "X", "E", "w"))
     g = gw * torch.isfinite(w)
     d_acc = -((g * alpha) * E)  # d loss / d X_i
     rev = torch.flip(torch.cumsum(torch.flip(d_acc[:, 1:], [-1]), dim=-1), [-1])  # sum_{i>j} d_acc_i, j < S-1
@@ -522,16 +542,102 @@ def weights_bwd64(t_bins: Tensor, density: Tensor, dweights: Tensor) -> Dict[str
     return dict(ddensity=d_dd * delta, suf=suf, suf_abs=suf_abs, X=X, dd=dd, delta=delta, E=E, e=e, alpha=alpha, w=w, g=g)
 
 
-def composite_bwd64(rgb: Tensor, weights: Tensor, d_rgb_out: Tensor, background: int, bg_color=None,
-                    bg_rays: Optional[Tensor] = None, d_weights_add: Optional[Tensor] = None) -> Dict[str, Tensor]:
+FLT_MAX = 3.4028234663852886e38
+DEPTH_EPS = float(np.float32(1e-10))  # renderers.py:379, as the fp32 pipeline holds it
+
+
+def _midpoints64(t_bins: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
+    """Sample midpoints of the edges `[N,S+1]` in float64, and the batch-global clip range of the expected depth: the min / max
+    of the midpoints AS THE PIPELINE HOLDS THEM (rounded to the edges' own precision, renderers.py:378-381)."""
+    held = (t_bins[:, :-1] + t_bins[:, 1:]) / 2
+    t = t_bins.double()
+    return (t[:, :-1] + t[:, 1:]) / 2, held.min().double(), held.max().double()
+
+
+def composite64(rgb: Optional[Tensor], weights: Tensor, t_bins: Optional[Tensor], background: int, bg_color=None,
+                bg_rays: Optional[Tensor] = None, eval_mode: bool = False, target: Optional[Tensor] = None,
+                grad_scale: float = 1.0) -> Dict[str, Tensor]:
+    """Float64 compositing of one batch (renderers.py: combine_rgb :72-119, the eval nan_to_num / clamp :225-231,
+    accumulation :293-317, expected depth :365-383, and MSELoss on the loss blend :194-196) on fp32 (or float64) inputs.
+    background as in composite_bwd64 (3: rgb is composited without a background, the loss is taken on rgb + bg_rays (1 - acc)).
+    Returns float64 tensors, each summed quantity with the sum of its |terms|: acc, acc_abs `[N]`; with rgb: rgb `[N,3]` (after
+    the clamp in eval mode), rgb_raw (before it), rgb_sum_abs = sum |w c|, bg `[N,3]` (the blended colour, zeros without one),
+    rem = 1 - acc; with t_bins: depth_raw = num / (acc + eps), depth (clipped to [lo, hi]), num, num_abs, lo, hi; with target:
+    pred (the colour the loss is taken on), sq_err `[N]`, d_rgb_out `[N,3]` = 2 (pred - target) grad_scale."""
+    w = weights.double()
+    N, S = w.shape
+    out: Dict[str, Tensor] = {}
+    acc = w.sum(-1)
+    out["acc"], out["acc_abs"], out["rem"] = acc, w.abs().sum(-1), 1.0 - acc
+    if rgb is not None:
+        c = rgb.double()
+        if eval_mode:
+            c = torch.nan_to_num(c, nan=0.0, posinf=FLT_MAX, neginf=-FLT_MAX)
+        comp = (w[..., None] * c).sum(-2)
+        out["rgb_sum_abs"] = (w[..., None] * c).abs().sum(-2)
+        if background == 1:
+            bg = c[:, -1, :]
+        elif background == 2:
+            bg = torch.tensor([float(v) for v in bg_color], dtype=torch.float64).expand(N, 3)
+        else:
+            bg = torch.zeros(N, 3, dtype=torch.float64)
+        out["bg"] = bg
+        out["rgb_sum"] = comp
+        if background in (1, 2):
+            comp = comp + bg * out["rem"][:, None]
+        out["rgb_raw"] = comp
+        out["rgb"] = comp.clamp(0.0, 1.0) if eval_mode else comp
+        if target is not None:
+            pred = out["rgb"]
+            if background == 3:
+                pred = pred + bg_rays.double() * out["rem"][:, None]
+            gs = float(np.float32(grad_scale))
+            d = pred - target.double()
+            out["pred"], out["diff"] = pred, d
+            out["sq_err"] = (d * d).sum(-1)
+            out["d_rgb_out"] = 2.0 * d * gs
+    if t_bins is not None:
+        mid, lo, hi = _midpoints64(t_bins)
+        num = (w * mid).sum(-1)
+        out["num"], out["num_abs"] = num, (w * mid).abs().sum(-1)
+        out["depth_raw"] = num / (acc + DEPTH_EPS)
+        out["lo"], out["hi"] = lo, hi
+        out["depth"] = torch.minimum(torch.maximum(out["depth_raw"], lo), hi)
+    return out
+
+
+def mse64(pred: Tensor, target: Tensor, grad_scale: float) -> Dict[str, Tensor]:
+    """Float64 sum of squared errors (nn.MSELoss before its mean) and the gradient 2 (pred - target) grad_scale."""
+    d = pred.double() - target.double()
+    return dict(loss_sum=(d * d).sum(), dpred=2.0 * d * float(np.float32(grad_scale)))
+
+
+def distance_scale64(t_bins: Tensor, d_density: Optional[Tensor], d_rgb: Optional[Tensor]) -> Tuple[Optional[Tensor], Optional[Tensor]]:
+    """Float64 backward of scale_gradients_by_distance_squared (losses.py:534-569): the gradients `[N,S]` / `[N,S,3]` times
+    clamp(midpoint^2, 0, 1)."""
+    t = t_bins.double()
+    scale = (((t[:, :-1] + t[:, 1:]) / 2) ** 2).clamp(0.0, 1.0)
+    return (None if d_density is None else d_density.double() * scale,
+            None if d_rgb is None else d_rgb.double() * scale[..., None])
+
+
+def composite_bwd64(rgb: Tensor, weights: Tensor, d_rgb_out: Optional[Tensor], background: int, bg_color=None,
+                    bg_rays: Optional[Tensor] = None, d_weights_add: Optional[Tensor] = None, d_acc: Optional[Tensor] = None,
+                    d_depth: Optional[Tensor] = None, t_bins: Optional[Tensor] = None) -> Dict[str, Tensor]:
     """Float64 gradient of the training composite (`composite_rgb` in training mode, the loss blend of background
     "random") with respect to the per-sample colours and weights, for the upstream gradient d_rgb_out `[N,3]` of the
     composited colour: the `nsamd_render_train_bwd` contract. background: 0 none, 1 last_sample, 2 the constant colour
     bg_color (3 floats), 3 the per-ray colours bg_rays `[N,3]` of the loss blend. d_weights_add `[N,S]` (nullable) is
     added to the weights' gradient. Returns d_rgb `[N,S,3]`, d_weights `[N,S]` and their abs companions: d_rgb_abs (the
-    terms of the last sample's d_rgb under last_sample: |g| (w + |1 - acc|)), dw_abs = sum |terms| of d_weights."""
-    c, w, g = rgb.double(), weights.double(), d_rgb_out.double()
+    terms of the last sample's d_rgb under last_sample: |g| (w + |1 - acc|)), dw_abs = sum |terms| of d_weights.
+    The `nsamd_composite_bwd` contract adds the upstream gradients d_acc `[N]` of the accumulation and d_depth `[N]` of the
+    expected depth clip(num / (acc + eps), lo, hi) over the edges t_bins (eps = 1e-10; the clip passes gradient inside
+    [lo, hi] inclusive; lo / hi as in composite64); d_rgb_out may then be None (zeros). With d_depth the result also holds
+    depth_raw, depth_mask (bool `[N]`), gd = the masked d_depth, g_num = d depth / d num and g_den = d depth / d acc (both
+    times gd), the midpoints mid, num, num_abs and den = acc + eps."""
+    c, w = rgb.double(), weights.double()
     N, S = w.shape
+    g = d_rgb_out.double() if d_rgb_out is not None else torch.zeros(N, 3, dtype=torch.float64)
     if background == 1:
         bg = c[:, -1, :]
     elif background == 2:
@@ -545,6 +651,22 @@ def composite_bwd64(rgb: Tensor, weights: Tensor, d_rgb_out: Tensor, background:
     if d_weights_add is not None:
         dw = dw + d_weights_add.double()
         dw_abs = dw_abs + d_weights_add.double().abs()
+    extra: Dict[str, Tensor] = {}
+    if d_acc is not None:
+        dw = dw + d_acc.double()[:, None]
+        dw_abs = dw_abs + d_acc.double().abs()[:, None]
+    if d_depth is not None:
+        mid, lo, hi = _midpoints64(t_bins)
+        den = w.sum(-1) + DEPTH_EPS
+        num = (w * mid).sum(-1)
+        raw = num / den
+        mask = (raw >= lo) & (raw <= hi)
+        gd = d_depth.double() * mask
+        g_num, g_den = gd / den, -gd * num / (den * den)
+        dw = dw + g_den[:, None] + g_num[:, None] * mid
+        dw_abs = dw_abs + g_den.abs()[:, None] + (g_num[:, None] * mid).abs()
+        extra = dict(depth_raw=raw, depth_mask=mask, gd=gd, g_num=g_num, g_den=g_den, lo=lo, hi=hi, mid=mid, num=num,
+                     num_abs=(w * mid).abs().sum(-1), den=den)
     e = w.clone()
     e_abs = w.abs()
     if background == 1:
@@ -552,7 +674,7 @@ def composite_bwd64(rgb: Tensor, weights: Tensor, d_rgb_out: Tensor, background:
         e[:, -1] += rem
         e_abs[:, -1] += rem.abs()
     d_rgb = g[:, None, :] * e[..., None]
-    return dict(d_rgb=d_rgb, d_rgb_abs=g.abs()[:, None, :] * e_abs[..., None], d_weights=dw, dw_abs=dw_abs)
+    return dict(d_rgb=d_rgb, d_rgb_abs=g.abs()[:, None, :] * e_abs[..., None], d_weights=dw, dw_abs=dw_abs, **extra)
 
 
 # ---------------------------------------------------------------------------------------------------------------
