@@ -31,6 +31,7 @@ from torch import Tensor
 
 from . import _native as N
 from . import functional as F
+from .runner_interface import PackedStepRunner
 from .utils import profiler
 
 
@@ -39,9 +40,11 @@ from .utils import profiler
 STASH_CAP = 128
 
 
-class NgpTrainStep:
+class NgpTrainStep(PackedStepRunner):
     """forward() -> backward() on static buffers; the caller owns the optimiser (param.grad is accumulated into, the main
     table's gradient is WRITTEN — nsamd_hashgrid_encode_bwd_set — unless `accumulate_table`)."""
+
+    writes_arena_grads = True  # through `grad_lookup`, where the caller sets one
 
     def __init__(self, model, num_rays: int, device, cap_candidates: int = 0, cap_kept: int = 0) -> None:
         N.require_cuda(torch.empty(0, device=device))

@@ -105,6 +105,7 @@ class TrainEngine:
         self.source = None  # device_batches.DeviceBatchSource: the trainer samples its own batches (EngineSeam hands it over)
         self.arena = None
         self.reason: Optional[str] = None
+        self._eager_done = 0  # iterations the current trainer has run (the first EAGER_ITERATIONS are a capture's warm-up)
         self._lr_hist: Dict[str, Dict[int, float]] = {}
         self._anchor = None
 
@@ -244,11 +245,10 @@ class TrainEngine:
         t.step = step
         # the first iterations run eagerly (they are the warm-up a capture needs, and every one of them is a real training
         # iteration on its own batch); then the schedule variants are captured once and replayed from there on
-        self._eager_done = getattr(self, "_eager_done", 0)
         # More than one rank: eager segments unless NSAMD_DP_GRAPH=1 — captured segments with RCCL collectives between them
         # have only been rehearsed on a one-rank communicator (trainer.py docstring)
         may_capture = t.use_graph and (not t.dp or os.environ.get("NSAMD_DP_GRAPH", "0") == "1")
-        if t.graphs is None and may_capture and self._eager_done >= self.EAGER_ITERATIONS and not getattr(t, "_capture_tried", False):
+        if t.graphs is None and may_capture and self._eager_done >= self.EAGER_ITERATIONS and not t._capture_tried:
             t._capture_tried = True
             t.try_capture(warm=False)
         self._eager_done += 1
@@ -258,7 +258,7 @@ class TrainEngine:
         r = t.runner
         model = self.pipeline.model
         outputs = r.outputs()
-        if getattr(r, "_loss_vals_fresh", False) and model.config.background_color != "random":
+        if r._loss_vals_fresh and model.config.background_color != "random":
             # nsamd_train_loss_values left the loss values and the training metrics in five floats (include/nsamd.h): one clone
             # per iteration instead of a dozen reduction launches
             rgb, inter, dist, psnr, dmetric = _LossValuesBackpropagated.apply(self._anchor, r.loss_vals)
@@ -291,8 +291,7 @@ class TrainEngine:
         self.trainer = HipTrainer(model, self.arena, rb, {"image": self._target(batch)}, world=int(self.pipeline.world_size),
                                   use_graph=True, use_runner=True, pool=None, source=self.source, lr_source=self._lr,
                                   drive_callbacks=False, runner=runner)
-        if hasattr(self.trainer.runner, "want_loss_vals"):
-            self.trainer.runner.want_loss_vals = True  # the reference's trainer reads the loss dictionary every iteration
+        self.trainer.runner.want_loss_vals = True  # the reference's trainer reads the loss dictionary every iteration
         if self.on_build is not None:
             self.on_build(self.trainer)
 
@@ -303,6 +302,11 @@ class NgpEngine(TrainEngine):
     parameters' `.grad` stay None — the packed kernels write into the arena's gradient views (`NgpTrainStep.grad_lookup`) — so that
     the trainer's own optimiser finds nothing to step (engine/optimizers.py:160-172).
     The occupancy refresh stays the model's BEFORE_TRAIN_ITERATION callback, run by the trainer."""
+
+    def __init__(self, *args, **kwargs) -> None:
+        super().__init__(*args, **kwargs)
+        self._grad_views = []     # (parameter, the arena's gradient view of it): built with the arena
+        self._bind_grads = False  # the views become `param.grad` for the duration of an iteration (`build_trainer_only`)
 
     def build(self, ray_bundle, batch) -> Optional[str]:
         from .arena import ParamArena
@@ -347,7 +351,7 @@ class NgpEngine(TrainEngine):
         self.trainer = NgpTrainer(model, self.arena, o.shape[0], o.device, refresh=False, runner=runner)
         # the kernel schedule writes into the arena's gradient views directly; a stand-in runner (tests: autograd over the module
         # path) needs them as `param.grad` for the duration of the iteration
-        self._bind_grads = not hasattr(self.trainer.runner, "grad_lookup")
+        self._bind_grads = not self.trainer.runner.writes_arena_grads
         if not self._bind_grads:
             self.trainer.runner.grad_lookup = self.arena.grad_lookup()
         if self.on_build is not None:

@@ -35,10 +35,11 @@ from torch import Tensor
 from . import _native as N
 from . import functional as F
 from .nerfacto import NerfactoModel
+from .runner_interface import TrainStepRunner
 from .utils import profiler
 
 
-class NerfactoTrainStep:
+class NerfactoTrainStep(TrainStepRunner):
     def __init__(self, model: NerfactoModel, num_rays: int, device, compute_depths: bool = True,
                  forward_only: bool = False) -> None:
         """forward_only: no gradient / saved-activation buffers (eval_render.EvalRenderer: at 32 768 rays per chunk they
@@ -164,6 +165,7 @@ class NerfactoTrainStep:
         # chains in line on the main stream 0.674 / 0.736 — same bits in all three).
         self.side_stream = torch.cuda.Stream(device=device)
         self._fork, self._join = torch.cuda.Event(), torch.cuda.Event()
+        self._open_branches = []  # the proposal_branches() `backward_fork` has started and `backward_join` has yet to wait for
         # camera optimiser: the rays' gradient through the main grid on its own stream, beside the table scatter's apply pass
         # (see backward_field_and_table)
         self.reduce_stream = torch.cuda.Stream(device=device)
@@ -337,7 +339,7 @@ class NerfactoTrainStep:
     def backward_join(self, updated: bool) -> None:
         """Second half of backward_all: wait for the proposal chains, then the camera optimiser's share."""
         main = N.current_stream()
-        for _, join, _ in getattr(self, "_open_branches", []):
+        for _, join, _ in self._open_branches:
             main.wait_event(join)
         self._open_branches = []
         self.backward_cameras(updated)
@@ -752,15 +754,11 @@ class NerfactoTrainStep:
             # iterations (a trainer's logging history) must not see them all change to the latest values
             v = self.loss_vals[:3].clone()
             out = {"rgb_loss": v[0], "distortion_loss": v[2], "interlevel_loss": v[1]}
-            if self.cam_opt is not None:
-                out["camera_opt_regularizer"] = self.camera_reg
-            if self.depth is not None:
-                out["depth_loss"] = self.depth["value"].clone()
-            return out
-        out = {"rgb_loss": self.sq_err.sum() / (3 * n),
-               "distortion_loss": self.cfg.distortion_loss_mult * self.dist_per_ray.sum() / n}
-        inter = sum(p.sum() for p in self.inter_per_ray) / (n * S)
-        out["interlevel_loss"] = self.cfg.interlevel_loss_mult * inter
+        else:
+            out = {"rgb_loss": self.sq_err.sum() / (3 * n),
+                   "distortion_loss": self.cfg.distortion_loss_mult * self.dist_per_ray.sum() / n}
+            inter = sum(p.sum() for p in self.inter_per_ray) / (n * S)
+            out["interlevel_loss"] = self.cfg.interlevel_loss_mult * inter
         if self.cam_opt is not None:
             out["camera_opt_regularizer"] = self.camera_reg
         if self.depth is not None:

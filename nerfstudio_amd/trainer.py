@@ -38,21 +38,72 @@ forward, autograd backward and optimiser alike) — launched eagerly around the 
 against 0.76, profiles/r04_camera_optimizer.txt). N > 1 (eager segments) or NSAMD_CAMERAS_OUTSIDE=1: batch selection and pose
 corrections before the segments, the rays' share of `pose_adjustment.grad`, the group's exchange and Adam after them; the
 kernels read the corrected rays and leave dL/d(origins, directions) per ray either way.
+
+Which of these arrangements a construction gets is decided in one place, `plan_schedule` (a pure function of the arguments, the
+runner's capabilities and two switches); what the drivers ask of a runner is stated in runner_interface.TrainStepRunner.
 """
 from __future__ import annotations
 
 import os
 import sys
-from typing import Callable, Dict, Optional
+from typing import Callable, Dict, NamedTuple, Optional
 
 import torch
 
 from . import _native as N
+from .runner_interface import TrainStepRunner
 
 BATCH_SLOTS = 8  # default number of pre-generated ray batches of a pool (bench.py)
 
 _HYPER = {"fields": 0, "proposal_networks": 2, "camera_opt": 6}  # offsets of (step size, 1/sqrt(bc2)) per optimiser group
 _HYPER_ANNEAL, _HYPER_SLOT, _HYPER_FLOATS = 4, 5, 8
+
+
+class SchedulePlan(NamedTuple):
+    dp: bool                # the data-parallel segments (N > 1, or force_dp: the same over a one-rank communicator)
+    dp_sharded: bool        # reduce-scatter -> Adam on the rank's 1/N arena shard -> all-gather; else the reference's DDP semantics
+    dp_fork: bool           # the proposal backward chains beside the main chain (eager data-parallel segments: `capture` clears it)
+    use_graph: bool
+    defer: bool             # the main-field Adam of iteration k at the head of iteration k+1
+    cam_inside: bool        # the camera optimiser's torch ops and Adam are part of the (captured) iteration body
+    cameras_outside: bool   # ... or run around it (the runner's attribute)
+    prologue: bool          # nsamd_step_prologue is the body's first launch (the step's draws)
+    prologue_ring: bool     # ... and fetches the step's scalars from the ring in host memory (else: the upload)
+    source_inside: bool     # the batch source's launch is part of the (captured) iteration body
+    gates_precleared: bool  # `_zero` clears the proposal levels' gradient flags with the gradients (the runner's attribute)
+
+
+def plan_schedule(*, runner: Optional[TrainStepRunner], own_runner: bool, world: int, force_dp: bool, dp_mode: str, use_graph: bool,
+                  on_gpu: bool, cam_group: bool, has_source: bool, cameras_outside_switch: bool,
+                  defer_switch: Optional[bool]) -> SchedulePlan:
+    """The schedule of one HipTrainer construction: a function of its arguments alone (no device, no tensor, no environment).
+    runner: None (the module path: nothing beyond dp / dp_sharded / use_graph) or the runner, of which only the capabilities of
+    runner_interface.TrainStepRunner are read; own_runner: the trainer built it (none was injected); cam_group: the arena has
+    a "camera_opt" group; cameras_outside_switch: NSAMD_CAMERAS_OUTSIDE=1; defer_switch: NSAMD_DEFER_MAIN_ADAM (None: unset)."""
+    dp = world > 1 or force_dp
+    use_graph = use_graph and on_gpu
+    if runner is None:
+        return SchedulePlan(dp, dp and dp_mode == "sharded", False, use_graph, *[False] * 7)
+    cam_on = runner.cam_opt is not None
+    cam_inside = cam_on and cam_group and not dp and not cameras_outside_switch
+    cameras_outside = cam_on and not cam_inside  # see the module docstring
+    # N = 1: the main-field Adam of iteration k (470 MB of HBM streaming) runs BESIDE the proposal forward of iteration k+1
+    # (L2-resident gathers and per-ray scans that read only proposal-network parameters) — the single-GPU form of the
+    # pipelined schedule; same dependencies, same bits. Measured on three MI355X boxes (profiles/r02_schedule_ab.txt): 1.3 / 3
+    # / 4.5 % faster than Adam at the end of the iteration when replayed from hipGraphs, neutral with eager launches — so it
+    # is the default with graphs. NSAMD_DEFER_MAIN_ADAM=0/1: A/B.
+    defer = not dp and on_gpu and (use_graph if defer_switch is None else defer_switch)
+    prologue = on_gpu and own_runner and bool(runner.single_jitter) and runner.jitter is not None
+    # The batch slot must be read INSIDE the iteration body: with the camera parts outside the graph the batch is selected
+    # eagerly ahead of the replay, i.e. before the prologue would have written the slot (then: the upload for the scalars, the
+    # prologue for the draws only). The data-parallel segments keep the upload as well — their Adam launches are segments of
+    # their own, ordered by the exchange — and take the DRAWS from the prologue: one generator for every schedule, so that a
+    # one-rank data-parallel run trains through the bits of the single-GPU one.
+    prologue_ring = prologue and not cameras_outside and not dp
+    return SchedulePlan(dp=dp, dp_sharded=dp and dp_mode == "sharded", dp_fork=dp and runner.side_stream is not None,
+                        use_graph=use_graph, defer=defer, cam_inside=cam_inside, cameras_outside=cameras_outside, prologue=prologue,
+                        prologue_ring=prologue_ring, source_inside=has_source and prologue_ring,
+                        gates_precleared=runner.prop_gates is not None)
 
 
 class HipTrainer:
@@ -70,7 +121,7 @@ class HipTrainer:
     iteration and copies it into the static buffers as `set_batch` does: still no CPU work per pixel, but not the captured path.
     lr_source(group, iteration) -> learning rate of that iteration (default: the nerfacto recipe's schedulers over arena.lr).
     drive_callbacks: call the model's BEFORE/AFTER_TRAIN_ITERATION callbacks here (False when a trainer does: HipPipeline).
-    runner: a train_step.NerfactoTrainStep stand-in (CPU tests of the schedule's host logic)."""
+    runner: a runner_interface.TrainStepRunner standing in for train_step.NerfactoTrainStep (CPU tests of the host logic)."""
 
     def __init__(self, model, arena, ray_bundle, batch, world: int = 1, use_graph: bool = True, use_runner: bool = True,
                  pool=None, source=None, force_dp: bool = False, dp_mode: str = "allreduce",
@@ -78,22 +129,16 @@ class HipTrainer:
         if hasattr(getattr(model, "config", None), "depth_loss_type"):
             # its iteration (and the graphs captured from it) carries no depth target, sigma decay or depth batch
             raise NotImplementedError("HipTrainer: depth supervision (depth-nerfacto) is only on the module path")
-        self.model, self.arena, self.rb, self.batch, self.world = model, arena, ray_bundle, batch, world
-        self.dp = world > 1 or force_dp  # force_dp: the data-parallel schedule with a one-rank communicator
-        # "sharded": reduce-scatter -> Adam on the rank's 1/N arena shard -> all-gather (dp_schedule.py); "allreduce": the
-        # replicated optimiser behind an all-reduce (the reference's DDP semantics, and the default)
-        self.dp_sharded = self.dp and dp_mode == "sharded"
-        self.dp_fork = False  # set below: proposal backward chains beside the main chain in the data-parallel schedule
         if source is not None and pool is not None:
             raise ValueError("HipTrainer: `pool` and `source` are mutually exclusive (one owner of the step's batch)")
         if source is not None and not (use_runner or runner is not None):
             raise ValueError("HipTrainer: a batch source needs the explicit kernel schedule (use_runner)")
-        self.pool = pool
-        self.source = source
-        self.source_inside = False  # set below: the source's launch is part of the (captured) iteration body
+        if runner is not None and not isinstance(runner, TrainStepRunner):
+            raise TypeError(f"HipTrainer: the runner must be a runner_interface.TrainStepRunner, got {type(runner).__name__}")
+        self.model, self.arena, self.rb, self.batch, self.world = model, arena, ray_bundle, batch, world
+        self.pool, self.source = pool, source
         self.slots = int(pool["origins"].shape[0]) if pool is not None else 1
-        self.step = 0
-        self.opt_step = 0
+        self.step = self.opt_step = 0
         self.drive_callbacks = drive_callbacks
         self._true_steps = dict(arena.step_counts)
         dev = ray_bundle.origins.device
@@ -119,6 +164,42 @@ class HipTrainer:
             lr_source = lambda group, it: sched[group].get_lr(max(it, 0), base[group])  # noqa: E731
         self.lr_source = lr_source
         self.exchange = None  # dp_schedule.PipelinedExchange (N > 1 with the runner)
+        self.ring_rows = 256
+        self.hyper_views = {g: self.hyper[o:o + 2] for g, o in _HYPER.items()}
+        self.loss_buf = torch.zeros((), device=dev)
+        model.proposal_sampler.anneal_dev = self.hyper[_HYPER_ANNEAL:_HYPER_ANNEAL + 1]
+        self.graphs = None
+        self._capture_tried = False  # pipeline.TrainEngine: one capture attempt per trainer
+        self.defer_scatter = False  # read by bench.py: the main table scatter is never deferred to the next iteration
+        self.opt_parallel = True  # False: the deferred Adam runs on the main stream (per-kernel timing)
+        # False: the jitter buffer of the runner is filled by the caller before every iteration (parity tests inject the
+        # draws the CPU oracle uses; the default draws them on the device inside the iteration, graph-safe Philox)
+        self.draw_jitter = True
+        self._pending_main = False  # deferred schedule: the main-field Adam of the previous iteration is still to run
+        self.cam_group = "camera_opt" if "camera_opt" in arena.groups else None
+        own_runner = runner is None
+        if use_runner and own_runner:  # explicit kernel schedule over static buffers (train_step.py); default
+            from .train_step import NerfactoTrainStep
+
+            runner = NerfactoTrainStep(model, ray_bundle.origins.shape[0], dev)
+        self.runner = r = runner
+        defer_env = os.environ.get("NSAMD_DEFER_MAIN_ADAM")
+        plan = plan_schedule(runner=r, own_runner=own_runner, world=world, force_dp=force_dp, dp_mode=dp_mode, use_graph=use_graph,
+                             on_gpu=self.on_gpu, cam_group=self.cam_group is not None, has_source=source is not None,
+                             cameras_outside_switch=os.environ.get("NSAMD_CAMERAS_OUTSIDE", "0") == "1",
+                             defer_switch=None if defer_env is None else defer_env == "1")
+        # (plain attributes: tests, bench.py and utils/roofline.py read and assign them; `capture` clears dp_fork)
+        (self.dp, self.dp_sharded, self.dp_fork, self.use_graph, self.defer, self.cam_inside, cameras_outside, self.prologue,
+         self.prologue_ring, self.source_inside, gates_precleared) = plan
+        if r is None:
+            return
+        r.grad_lookup = arena.grad_lookup()
+        r.gates_precleared, r.cameras_outside = gates_precleared, cameras_outside
+        r.set_batch(ray_bundle.origins, ray_bundle.directions, ray_bundle.camera_indices, batch["image"])
+        r.anneal_dev = self.hyper[_HYPER_ANNEAL:_HYPER_ANNEAL + 1]
+        if self.defer:
+            self.opt_stream = torch.cuda.Stream(device=dev)
+            self._opt_fork, self._opt_join, self._batch_ready = torch.cuda.Event(), torch.cuda.Event(), torch.cuda.Event()
         # ---- device-side head of the iteration (nsamd_step_prologue), on the GPU with the trainer's own runner ----
         # A replayed graph had two host-issued operations in front of it every iteration — the 32-byte upload of `hyper` and the
         # offset fill of torch's graph-safe generator (for the jitter's uniform_) — and each eager -> graph hand-over leaves the
@@ -129,95 +210,40 @@ class HipTrainer:
         # it serves a trainer whose learning rates come from outside (pipeline.TrainEngine) as well. An event every 64 rows
         # keeps the host from lapping the device. (A table of rows predicted ahead in device memory measured the same, the
         # per-iteration upload 3 % slower: profiles/r05_s11_ab_step_prologue.txt.)
-        self.prologue = False          # set below
-        self.prologue_ring = False     # the scalars come from the ring in host memory (else: the upload)
-        self.ring_rows = 256
-        self.hyper_views = {g: self.hyper[o:o + 2] for g, o in _HYPER.items()}
-        self.loss_buf = torch.zeros((), device=dev)
-        model.proposal_sampler.anneal_dev = self.hyper[_HYPER_ANNEAL:_HYPER_ANNEAL + 1]
-        self.graphs = None
-        self.use_graph = use_graph and self.on_gpu
-        self.runner = runner
-        self.defer = False
-        self.defer_scatter = False  # read by bench.py: the main table scatter is never deferred to the next iteration
-        self.opt_parallel = True  # False: the deferred Adam runs on the main stream (per-kernel timing)
-        # False: the jitter buffer of the runner is filled by the caller before every iteration (parity tests inject the
-        # draws the CPU oracle uses; the default draws them on the device inside the iteration, graph-safe Philox)
-        self.draw_jitter = True
-        self._pending_main = False  # deferred schedule: the main-field Adam of the previous iteration is still to run
-        self.cam_group = "camera_opt" if "camera_opt" in arena.groups else None
-        self.cam_inside = False  # the camera optimiser's torch ops and Adam are part of the (captured) iteration body
-        if use_runner or runner is not None:  # explicit kernel schedule over static buffers (train_step.py); default
-            if self.runner is None:
-                from .train_step import NerfactoTrainStep
+        if self.prologue:
+            self.step_counter = torch.zeros(2, device=dev, dtype=torch.int64)  # [row, draw]
+            # The draws are keyed by (seed, draw counter). The counter starts at the model's training step, so that a trainer
+            # built in the middle of a run (a resumed checkpoint, an engine rebuilt for another batch size) does not replay
+            # the jitter and background draws of steps 0, 1, ...; the rank is mixed into the seed, so that data-parallel
+            # ranks that share torch's seed still draw different numbers (the reference: one generator per process).
+            self.step_counter[1] = int(getattr(model, "step", 0) or 0)
+            rank = 0
+            if world > 1 and os.environ.get("NSAMD_BENCH_SAME_RAYS") != "1":  # (the functional check: every rank the same rays AND draws)
+                import torch.distributed as dist
 
-                self.runner = NerfactoTrainStep(model, ray_bundle.origins.shape[0], dev)
-            r = self.runner
-            r.grad_lookup = arena.grad_lookup()
-            if hasattr(r, "prop_gates"):
-                r.gates_precleared = True  # `_zero` clears the proposal levels' gradient flags with the gradients
-            r.set_batch(ray_bundle.origins, ray_bundle.directions, ray_bundle.camera_indices, batch["image"])
-            r.anneal_dev = self.hyper[_HYPER_ANNEAL:_HYPER_ANNEAL + 1]
-            cam_on = getattr(r, "cam_opt", None) is not None
-            self.cam_inside = cam_on and self.cam_group is not None and not self.dp and os.environ.get("NSAMD_CAMERAS_OUTSIDE", "0") != "1"
-            r.cameras_outside = cam_on and not self.cam_inside  # see the module docstring
-            # N = 1: the main-field Adam of iteration k (470 MB of HBM streaming) runs BESIDE the proposal forward of
-            # iteration k+1 (L2-resident gathers and per-ray scans that read only proposal-network parameters) — the
-            # single-GPU form of the pipelined schedule above; same dependencies, same bits. Measured on three MI355X boxes
-            # (profiles/r02_schedule_ab.txt): 1.3 / 3 / 4.5 % faster than Adam at the end of the iteration when replayed
-            # from hipGraphs, neutral with eager launches — so it is the default with graphs. NSAMD_DEFER_MAIN_ADAM=0/1: A/B.
-            self.defer = (not self.dp and self.on_gpu and
-                          os.environ.get("NSAMD_DEFER_MAIN_ADAM", "1" if self.use_graph else "0") == "1")
-            if self.defer:
-                self.opt_stream = torch.cuda.Stream(device=dev)
-                self._opt_fork, self._opt_join = torch.cuda.Event(), torch.cuda.Event()
-                self._batch_ready = torch.cuda.Event()
-            if self.on_gpu and runner is None and getattr(r, "single_jitter", False) and hasattr(r, "jitter"):
-                self.prologue = True
-                self.step_counter = torch.zeros(2, device=dev, dtype=torch.int64)  # [row, draw]
-                # The draws are keyed by (seed, draw counter). The counter starts at the model's training step, so that a trainer
-                # built in the middle of a run (a resumed checkpoint, an engine rebuilt for another batch size) does not replay
-                # the jitter and background draws of steps 0, 1, ...; the rank is mixed into the seed, so that data-parallel
-                # ranks that share torch's seed still draw different numbers (the reference: one generator per process).
-                self.step_counter[1] = int(getattr(model, "step", 0) or 0)
-                rank = 0
-                if world > 1 and os.environ.get("NSAMD_BENCH_SAME_RAYS") != "1":  # (the functional check: every rank the same rays AND draws)
-                    import torch.distributed as dist
+                rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+            self.rng_seed = ((int(torch.initial_seed()) + 0x632BE59BD9B4E019 * rank) * 0x9E3779B97F4A7C15
+                             + 0x5851F42D4C957F2D) & 0xFFFFFFFFFFFFFFFF
+        if self.prologue_ring:
+            self.ring_host = torch.zeros(self.ring_rows, _HYPER_FLOATS).pin_memory()  # (device-visible: hipHostMalloc)
+            self.ring_np = self.ring_host.numpy()
+            self._ring_pos = 0                 # rows written so far == the device's row counter at the next launch
+            self._ring_events = [None] * 4     # recorded every 64 rows
+        if source is not None:
+            assert source.num_rays == r.n, "the source and the static buffers must agree on the rays per batch"
+            # as the jitter's counter: a trainer built in the middle of a run does not replay the pixels of steps 0, 1, ...
+            source.set_draw(int(getattr(model, "step", 0) or 0))
+        if self.dp:
+            from .dp_schedule import PipelinedExchange
 
-                    rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
-                self.rng_seed = ((int(torch.initial_seed()) + 0x632BE59BD9B4E019 * rank) * 0x9E3779B97F4A7C15
-                                 + 0x5851F42D4C957F2D) & 0xFFFFFFFFFFFFFFFF
-                # the batch slot must be read INSIDE the iteration body: with the camera parts outside the graph the batch is
-                # selected eagerly ahead of the replay, i.e. before the prologue would have written the slot (then: the upload
-                # for the scalars, the prologue for the draws only)
-                # (the data-parallel segments keep the upload as well — their Adam launches are segments of their own, ordered by
-                #  the exchange — and take the DRAWS from the prologue: one generator for every schedule, so that a one-rank
-                #  data-parallel run trains through the bits of the single-GPU one)
-                if not r.cameras_outside and not self.dp:
-                    self.prologue_ring = True
-                    self.ring_host = torch.zeros(self.ring_rows, _HYPER_FLOATS).pin_memory()  # (device-visible: hipHostMalloc)
-                    self.ring_np = self.ring_host.numpy()
-                    self._ring_pos = 0                 # rows written so far == the device's row counter at the next launch
-                    self._ring_events = [None] * 4     # recorded every 64 rows
-            if source is not None:
-                assert source.num_rays == r.n, "the source and the static buffers must agree on the rays per batch"
-                # as the jitter's counter: a trainer built in the middle of a run does not replay the pixels of steps 0, 1, ...
-                source.set_draw(int(getattr(model, "step", 0) or 0))
-                self.source_inside = self.prologue_ring
-            if self.dp:
-                from .dp_schedule import PipelinedExchange
-
-                self.exchange = PipelinedExchange(arena, self._run, before_main_update=self._push_hyper,
-                                                  sharded=self.dp_sharded)
-                # eager segments only (a captured segment must end with its streams joined)
-                self.dp_fork = getattr(r, "side_stream", None) is not None
-                # the coarse levels of the main table can only ever touch 288 k of their 2.6 M rows: exchange those
-                # compactly (2.3 MB instead of 21 MB of the 67 MB main-field all-reduce)
-                enc = model.field.mlp_base.encoding
-                if hasattr(enc, "spec"):
-                    rows, index = enc.spec.reachable_prefix()
-                    if index.numel() and index.numel() < rows // 2 and not self.dp_sharded:
-                        arena.register_compact(enc.hash_table, rows, index)  # (the reduce-scatter takes the slice as it lies)
+            self.exchange = PipelinedExchange(arena, self._run, before_main_update=self._push_hyper, sharded=self.dp_sharded)
+            # the coarse levels of the main table can only ever touch 288 k of their 2.6 M rows: exchange those
+            # compactly (2.3 MB instead of 21 MB of the 67 MB main-field all-reduce)
+            enc = model.field.mlp_base.encoding
+            if hasattr(enc, "spec"):
+                rows, index = enc.spec.reachable_prefix()
+                if index.numel() and index.numel() < rows // 2 and not self.dp_sharded:
+                    arena.register_compact(enc.hash_table, rows, index)  # (the reduce-scatter takes the slice as it lies)
 
     # -- the batch ---------------------------------------------------------------------------------------------------
     def set_batch(self, ray_bundle, batch) -> None:
@@ -308,7 +334,7 @@ class HipTrainer:
     def _clear_gates(self):
         # (instead of one 4-byte memset node per level ahead of its weights backward; BEFORE the losses launch, which raises
         # the flags when it also runs the levels' weights backward)
-        if getattr(self.runner, "gates_precleared", False):
+        if self.runner.gates_precleared:
             self.runner.prop_gates.zero_()
 
     def _stepped(self, updated, pending):
@@ -333,7 +359,7 @@ class HipTrainer:
         # the selected batch, nothing else: beside a pending Adam they go on its branch, behind an event the main branch
         # records once the batch is in place — off the critical path instead of a launch (and a dependent-launch gap) in
         # front of the hash forward.
-        terms_beside = beside and getattr(r, "ray_terms_on", False)
+        terms_beside = beside and r.ray_terms_on
 
         def terms_behind_batch():  # (runs inside forward_proposals, right behind the launch that selects the batch)
             self._batch_ready.record(main)
@@ -363,20 +389,12 @@ class HipTrainer:
             # the main table's gradient is written, not accumulated; the proposal group's gradients are neither produced nor
             # consumed on a step that does not update it (ray_samplers.py:590-599), so its 10 MB need no zero-fill then
             self._zero(updated)
-        # (the ray-terms keywords only when the terms ride the Adam branch: a runner without ray terms keeps the plain calls)
-        draw = self.draw_jitter and not self.prologue
-        if terms_beside:
-            r.forward_proposals(draw, need_enc=updated, after_bins=terms_behind_batch)
-        else:
-            r.forward_proposals(draw, need_enc=updated)
+        r.forward_proposals(self.draw_jitter and not self.prologue, need_enc=updated, after_bins=terms_behind_batch if terms_beside else None)
         if beside:
             main.wait_event(self._opt_join)
         elif self.defer:
             self._zero(updated)
-        if terms_beside:
-            r.forward_main_and_losses(updated, terms_ready=True)
-        else:
-            r.forward_main_and_losses(updated)
+        r.forward_main_and_losses(updated, terms_ready=terms_beside)
         r.backward_all(updated)  # the backward chains run as parallel branches
         late = self._stepped(updated, pending=False)  # (a pending main-field update has run at the head)
         if late:
@@ -410,7 +428,7 @@ class HipTrainer:
             if self.source_inside:
                 # sampled here, inside the body: the prologue (first node) has already advanced the draw counter, hence -1
                 r = self.runner
-                co = getattr(r, "cam_opt", None) is not None  # the kernels read the pose-corrected copies
+                co = r.cam_opt is not None  # the kernels read the pose-corrected copies
                 o, d = (r.raw_origins, r.raw_directions) if co else (r.origins, r.directions)
                 self.source.launch(o, d, r.camera_indices, r.target, self.step_counter[1:], -1)
             return  # (else: `_source_batch` has filled the buffers ahead of the iteration)
@@ -421,8 +439,8 @@ class HipTrainer:
         p = self.pool
         if self.runner is not None:
             r = self.runner
-            co = getattr(r, "cam_opt", None) is not None  # the kernels read the pose-corrected copies
-            if not co and getattr(r, "fuse_select", False):
+            co = r.cam_opt is not None  # the kernels read the pose-corrected copies
+            if not co and r.fuse_select:
                 # the runner's next `forward_proposals` selects the batch in the launch that writes the initial bins
                 r.pending_select = (N.ptr(self.hyper[_HYPER_SLOT:_HYPER_SLOT + 1]), self.slots, p)
                 return
@@ -441,7 +459,7 @@ class HipTrainer:
     # -- camera optimiser: the host-side halves around the captured part ---------------------------------------------------
     @property
     def _cams_outside(self):
-        return self.runner is not None and getattr(self.runner, "cameras_outside", False)
+        return self.runner is not None and self.runner.cameras_outside
 
     def _cameras_before(self):
         """Batch selection + pose corrections (cameras/camera_optimizers.py:148-153), eagerly, ahead of the replay."""

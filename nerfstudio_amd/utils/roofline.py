@@ -172,7 +172,7 @@ def measure_roofline(trainer, arena, steps, main_points):
     along, table rows sorted by time per step)."""
     graphs, trainer.graphs = trainer.graphs, None  # per-kernel events need eager launches
     runner = getattr(trainer, "runner", None)
-    side = getattr(runner, "side_stream", None)
+    side = runner.side_stream if runner is not None else None
     if runner is not None:
         runner.side_stream = None
     trainer.opt_parallel = False
@@ -201,7 +201,7 @@ def measure_roofline(trainer, arena, steps, main_points):
                       "bound": bound, "work": work})
     table.sort(key=lambda r: -r["ms_per_step"])
     ranked = [r for r in table if r["bound"] is not None and r["work"]]
-    rt = bool(getattr(runner, "ray_terms_on", False))
+    rt = runner is not None and bool(runner.ray_terms_on)
     roof = roofline_entry(ranked[0]["kernel"], ranked[0]["mean_ms"], ranked[0]["bound"], ranked[0]["work"], main_points, rt) if ranked else None
     # The main-field MLP backward and the main-table scatter are within a few percent of each other per step: which one is
     # "the dominant kernel" flips between runs. The runner-up rides along so that both are in every line.

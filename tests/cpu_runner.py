@@ -6,6 +6,8 @@ autograd forward / backward per iteration, the gradients handed out in the runne
 this; on a GPU box the real runner launches the kernels."""
 import torch
 
+from nerfstudio_amd.runner_interface import PackedStepRunner, TrainStepRunner
+
 
 def cpu_adam(params, grads, exp_avg, exp_avg_sq, step, lr, betas=(0.9, 0.999), eps=1e-15, grad_scale=1.0, hyper_dev=None):
     """torch.optim.Adam's update on arena slices with the device-resident step scalars of functional.adam_hyper
@@ -24,13 +26,10 @@ def cpu_adam(params, grads, exp_avg, exp_avg_sq, step, lr, betas=(0.9, 0.999), e
     params.addcdiv_(exp_avg, denom, value=-step_size)
 
 
-class CpuRunner:
+class CpuRunner(TrainStepRunner):
     """The runner interface HipTrainer drives (train_step.NerfactoTrainStep): static batch buffers, forward phases, backward
-    phases that ACCUMULATE into the arena's gradient views (`grad_lookup`), loss / output views."""
-
-    side_stream = None
-    cam_opt = None
-    cameras_outside = False
+    phases that ACCUMULATE into the arena's gradient views (`grad_lookup`), loss / output views. Every optional capability is
+    at the interface's default."""
 
     def __init__(self, model, num_rays, device, seed_base=0):
         self.model, self.n = model, int(num_rays)
@@ -41,7 +40,6 @@ class CpuRunner:
         self.jitter = torch.zeros(3, self.n)
         self.dist_per_ray = torch.zeros(self.n)
         self.anneal_dev = torch.ones(1)
-        self.grad_lookup = None
         self.seed_base, self.iterations = seed_base, 0
         self.calls = []
         self._losses = self._out = self._grads = None
@@ -124,11 +122,13 @@ class CpuRunner:
         return {"rgb": self._out["rgb"], "accumulation": self._out["accumulation"], "depth": self._out["depth"]}
 
 
-class CpuNgpRunner:
+class CpuNgpRunner(PackedStepRunner):
     """The runner interface ngp_trainer.NgpTrainer drives (ngp_step.NgpTrainStep): set_batch with ANY number of rays, forward,
     loss, backward into the parameters' `.grad` (the engine binds views of the arena's gradient; the table's gradient is
     WRITTEN, the others accumulate), outputs, `num_kept`, `target`. The numbers come from the module path of the same model
     (plugin.HipNGPModel under the reference's Model.forward / get_loss_dict) over tests/cpu_kernels.py."""
+
+    writes_arena_grads = False  # autograd fills `param.grad`
 
     def __init__(self, model, num_rays, device, bundle_cls, seed_base=0):
         self.model, self.n, self.bundle_cls = model, int(num_rays), bundle_cls

@@ -24,6 +24,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 import batch_reference as BR  # noqa: E402
 
+from nerfstudio_amd.runner_interface import TrainStepRunner  # noqa: E402
+
 U32P = np.ctypeslib.ndpointer(np.uint32, flags="C_CONTIGUOUS")
 I32P = np.ctypeslib.ndpointer(np.int32, flags="C_CONTIGUOUS")
 F32P = np.ctypeslib.ndpointer(np.float32, flags="C_CONTIGUOUS")
@@ -259,17 +261,15 @@ class _ToyModel(torch.nn.Module):
         return {"fields": [self.w], "proposal_networks": [self.pw]}
 
 
-class _ToyRunner:
+class _ToyRunner(TrainStepRunner):
     """The runner interface trainer.HipTrainer drives, reduced to a loss of the batch it was handed."""
-    side_stream = cam_opt = None
-    cameras_outside = False
 
     def __init__(self, model, n, device):
         self.model, self.n = model, n
         self.origins, self.directions, self.target = torch.zeros(n, 3), torch.zeros(n, 3), torch.zeros(n, 3)
         self.camera_indices = torch.zeros(n, dtype=torch.int64)
         self.dist_per_ray = torch.zeros(n)
-        self.batches, self.grad_lookup = [], None
+        self.batches = []
 
     def set_batch(self, origins, directions, camera_indices, target=None):
         self.origins.copy_(origins), self.directions.copy_(directions), self.camera_indices.copy_(camera_indices.reshape(-1))

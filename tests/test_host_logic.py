@@ -435,6 +435,38 @@ def test_environment_switches_match_the_design_table():
     assert read == listed, (sorted(read - listed), sorted(listed - read))
 
 
+def test_no_driver_probes_the_runner_interface_or_the_schedule_flags():
+    """No `getattr` / `hasattr` in the package names an attribute of runner_interface.TrainStepRunner / PackedStepRunner, a field
+    of trainer.SchedulePlan, a trainer attribute tests and bench.py assign, or an attribute a constructor now creates: the
+    drivers read them plainly, so a renamed or misspelt capability is an AttributeError instead of a slower path with the same
+    bits. (`getattr` on objects the project does not own — the reference's trainer, configs, cameras, a model's `step` —
+    names none of these.)"""
+    import ast
+    import glob
+    import os
+
+    from nerfstudio_amd.runner_interface import PackedStepRunner, TrainStepRunner
+    from nerfstudio_amd.trainer import SchedulePlan
+
+    names = {k for cls in (TrainStepRunner, PackedStepRunner) for k in vars(cls) if not k.startswith("__")}
+    names |= set(SchedulePlan._fields) | {"pipelined", "graphs", "opt_parallel", "draw_jitter", "defer_scatter"}
+    names |= {"_eager_done", "_capture_tried", "_open_branches", "_bind_grads", "_grad_views"}
+    assert {"ray_terms_on", "prop_gates", "fuse_select", "want_loss_vals", "grad_lookup", "prologue_ring", "defer"} <= names
+    pkg = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "nerfstudio_amd")
+    files = glob.glob(os.path.join(pkg, "**", "*.py"), recursive=True)
+    assert len(files) > 10
+    probes, seen = [], 0
+    for path in files:
+        for node in ast.walk(ast.parse(open(path).read(), path)):
+            if isinstance(node, ast.Call) and isinstance(node.func, ast.Name) and node.func.id in ("getattr", "hasattr"):
+                seen += 1
+                for arg in node.args[1:2]:
+                    if isinstance(arg, ast.Constant) and arg.value in names:
+                        probes.append(f"{os.path.relpath(path, pkg)}:{node.lineno} {node.func.id}(..., {arg.value!r})")
+    assert seen > 20  # (the walk does find the calls)
+    assert not probes, probes
+
+
 def test_every_entry_point_is_launched_from_one_place():
     """Each entry point of `_native._SIGNATURES` has at most one attribute reference `.nsamd_<name>` in the package outside
     _native.py: the allocating wrappers, the autograd Functions and the explicit schedules share one launch helper per entry
