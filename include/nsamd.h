@@ -175,6 +175,17 @@ int nsamd_sh4_encode(const float* dirs, int64_t M, float* out, nsamd_stream_t st
 int nsamd_nerf_encode(nsamd_points pts, int64_t M, const float* freqs, int32_t num_frequencies, int32_t include_input,
                       float* out, nsamd_stream_t stream);
 
+/* The gradient of nsamd_nerf_encode's rows with respect to the sample positions, reduced per ray exactly as
+ * nsamd_hashgrid_encode_bwd_rays reduces the hash grid's (ray mode only: pts.positions == NULL): with g_s the position gradient of
+ * sample s — 2 pi sum_f (g[d F + f] cos(s) + g[3 F + d F + f] cos(s + pi/2)) freqs[f] on axis d, plus g[6 F + d] with
+ * include_input — d_origins[r] = sum_s g_s, d_directions[r] = sum_s g_s (t_s + t_{s+1}) / 2. Row p of the upstream gradient
+ * starts at d_out + p * d_out_stride (d_out_stride >= 6 F (+3): e.g. the 12 encoded columns at the start of the 27-wide input
+ * rows of the predicted-normals MLP, whose raw positions are functions of the camera optimiser's pose corrections). [N,3] each,
+ * written (accumulate = 0) or added to (accumulate = 1). Fixed summation order: bit-reproducible. */
+int nsamd_nerf_encode_bwd_rays(nsamd_points pts, int64_t M, const float* freqs, int32_t num_frequencies, int32_t include_input,
+                               const float* d_out, int64_t d_out_stride, float* d_origins, float* d_directions, int accumulate,
+                               nsamd_stream_t stream);
+
 /* SceneContraction(order=inf) forward on [M,3] (spatial_distortions.py:66-69). */
 int nsamd_contract_linf(const float* x, int64_t M, float* out, nsamd_stream_t stream);
 
@@ -314,7 +325,7 @@ int nsamd_field_mlp_bwd_scatter_phase(nsamd_points pts, int transform, nsamd_aab
                                       int64_t scatter_workspace_floats, int phase, nsamd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
- * Normals of the nerfacto field, forward only (the eval render of a `predict_normals` model).
+ * Normals of the nerfacto field: the forward (eval render and training of a `predict_normals` model) and the training losses.
  * nsamd_field_normals: for each of M samples (`pts` as nsamd_hashgrid_encode_fwd takes them) the gradient of the density
  * pre-activation with respect to the NORMALISED, selector-masked position (Field.get_normals, fields/base_field.py:79-99:
  * first order, no contraction Jacobian), from the encoded features `enc` [32, M] (feature-major, as the hash forward left
@@ -336,6 +347,24 @@ int nsamd_field_normals(nsamd_points pts, int64_t M, int transform, nsamd_aabb a
                         int64_t geo_offset, nsamd_stream_t stream);
 int nsamd_normals_composite(const float* weights, const float* normals, const float* pred_pre, int64_t num_rays, int32_t S,
                             float* normals_out, float* pred_out, nsamd_stream_t stream);
+
+/* The two normals losses of a `predict_normals` model in training with their gradients (models/nerfacto.py:335-344, :379-388;
+ * losses.py:201-222), per ray from weights [N,S], analytic normals [N*S,3], the predicted-normals head's pre-activation x
+ * [N*S,3] and the rays' view directions v [N,3]. Weights and normals are constants (the reference detaches both; the analytic
+ * normals come from a first-order autograd.grad, fields/base_field.py:92-99). Per sample, p = normalize(tanh(x)):
+ *   pred_per_ray[r]        = sum_s w (1 - n . p)                                   (unscaled)
+ *   d_pred_pre[r S + s]    = pred_scale * d(w (1 - n . p)) / dx                    (overwritten; through normalize — where
+ *                            |tanh(x)| < 1e-12 the clamped form, as autograd has it — and tanh)
+ *   orientation_per_ray[r] = sum_s w min(0, n . (-v))^2                            (unscaled; torch.fmin: a NaN product counts as 0)
+ *   d_directions[r]        = orientation_scale * sum_s 2 w min(0, n . (-v)) (-n)   (written, or added to when
+ *                            accumulate_directions != 0: the camera optimiser's share)
+ * Every output is nullable (pred_pre / directions may be NULL when neither of their outputs is wanted); sums are double
+ * partial sums in a fixed order, no atomics: the same bits on every run. 1 <= S <= 4096, else NSAMD_ERR_UNSUPPORTED;
+ * num_rays == 0 is a no-op. */
+int nsamd_normals_losses(const float* weights, const float* normals, const float* pred_pre, const float* directions,
+                         int64_t num_rays, int32_t S, float orientation_scale, float pred_scale, float* orientation_per_ray,
+                         float* pred_per_ray, float* d_pred_pre, float* d_directions, int32_t accumulate_directions,
+                         nsamd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Generic dense layer for the stand-alone MLP of the plugin API (MLP.pytorch_fwd, field_components/mlp.py:160-179):

@@ -85,6 +85,7 @@ _SIGNATURES = {
     "nsamd_hashgrid_scatter_events": [vp, vp, vp],
     "nsamd_sh4_encode": [vp, i64, vp, vp],
     "nsamd_nerf_encode": [Points, i64, vp, i32, i32, vp, vp],
+    "nsamd_nerf_encode_bwd_rays": [Points, i64, vp, i32, i32, vp, i64, vp, vp, C.c_int, vp],
     "nsamd_contract_linf": [vp, i64, vp, vp],
     "nsamd_density_mlp_fwd": [vp, vp, i64, DensityMlp, vp, vp, vp],
     "nsamd_density_field_fwd": [Points, i64, C.c_int, Aabb, vp, Grid, DensityMlp, vp, vp, vp, vp, vp],
@@ -101,6 +102,7 @@ _SIGNATURES = {
     "nsamd_proposal_levels_bwd": [C.POINTER(ProposalLevelBwd), i32, i32, vp],
     "nsamd_field_normals": [Points, i64, C.c_int, Aabb, vp, Grid, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, vp],
     "nsamd_normals_composite": [vp, vp, vp, i64, i32, vp, vp, vp],
+    "nsamd_normals_losses": [vp, vp, vp, vp, i64, i32, f32, f32, vp, vp, vp, vp, i32, vp],
     "nsamd_linear_fwd": [vp, vp, vp, i64, i32, i32, C.c_int, vp, vp],
     "nsamd_linear_bwd": [vp, vp, vp, vp, i64, i32, i32, C.c_int, vp, vp, vp, vp],
     "nsamd_piecewise_bins": [vp, vp, vp, vp, i32, i64, i32, C.c_int, vp, vp, vp],

@@ -397,6 +397,67 @@ __global__ __launch_bounds__(256) void nerf_encode_kernel(nsamd_points P, int64_
   if (include_input && f == 0) o[2 * per + d] = xd;
 }
 
+// The gradient of nerf_encode_kernel's rows with respect to the sample positions, reduced per RAY as
+// hash_encode_bwd_rays_kernel reduces the hash grid's: g_x[d] = 2 pi sum_f (g[k] cos(s) + g[3F + k] cos(s + pi/2)) freqs[f]
+// (+ g[6F + d] with the raw input appended), k = d F + f — autograd's order through sin, the concatenation, the product with
+// the frequencies and the scalar 2 pi. One wavefront per ray, lane l takes samples l, l + 64, ... in order; the per-sample
+// gradients are fp32, their sums double partial sums through the scan of wave.h (a fixed order, rounded once): bit-reproducible.
+// Row p of the upstream gradient starts at d_out + p * stride.
+__global__ __launch_bounds__(256) void nerf_encode_bwd_rays_kernel(nsamd_points P, int64_t num_rays,
+                                                                   const float* __restrict__ freqs, int F, bool include_input,
+                                                                   const float* __restrict__ d_out, int64_t stride,
+                                                                   float* __restrict__ d_origins,
+                                                                   float* __restrict__ d_directions, int accumulate) {
+  const int lane = threadIdx.x & 63;
+  const int64_t ray = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (ray >= num_rays) return;
+  const int S = P.samples_per_ray;
+  const int per = 3 * F;
+  double so[3] = {0.0, 0.0, 0.0}, sd[3] = {0.0, 0.0, 0.0};
+  for (int smp = lane; smp < S; smp += 64) {
+    const int64_t p = ray * S + smp;
+    float x[3], g[3];
+    load_position(P, p, x[0], x[1], x[2]);
+    const float* __restrict__ row = d_out + p * stride;
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+      const float scaled = 6.283185307179586f * x[d];
+      float acc = 0.0f;
+      for (int f = 0; f < F; ++f) {
+        const float s = scaled * freqs[f];
+        const float gs = row[d * F + f] * cosf(s) + row[per + d * F + f] * cosf(s + 1.5707963267948966f);
+        acc += gs * freqs[f];
+      }
+      g[d] = 6.283185307179586f * acc;
+      if (include_input) g[d] += row[2 * per + d];
+    }
+    const float* tb = P.t_bins + ray * (S + 1) + smp;
+    const float half = (tb[0] + tb[1]) / 2.0f;
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+      so[d] += (double)g[d];
+      sd[d] += (double)(g[d] * half);
+    }
+  }
+  float to[3], td[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    to[k] = (float)wave_read_f64<63>(wave_scan_inclusive_f64(so[k]));
+    td[k] = (float)wave_read_f64<63>(wave_scan_inclusive_f64(sd[k]));
+  }
+  if (lane < 3) {
+    const float o = lane == 0 ? to[0] : (lane == 1 ? to[1] : to[2]);
+    const float d = lane == 0 ? td[0] : (lane == 1 ? td[1] : td[2]);
+    if (accumulate) {
+      d_origins[3 * ray + lane] += o;
+      d_directions[3 * ray + lane] += d;
+    } else {
+      d_origins[3 * ray + lane] = o;
+      d_directions[3 * ray + lane] = d;
+    }
+  }
+}
+
 }  // namespace nsamd
 
 using namespace nsamd;
@@ -593,6 +654,24 @@ extern "C" int nsamd_nerf_encode(nsamd_points pts, int64_t M, const float* freqs
   unsigned blocks;
   if (grid_blocks((threads + 255) / 256, &blocks)) return NSAMD_ERR_UNSUPPORTED;
   nerf_encode_kernel<<<blocks, 256, 0, (hipStream_t)stream>>>(pts, M, freqs, num_frequencies, include_input != 0, out);
+  NSAMD_CHECK_LAUNCH();
+  return NSAMD_OK;
+}
+
+extern "C" int nsamd_nerf_encode_bwd_rays(nsamd_points pts, int64_t M, const float* freqs, int32_t num_frequencies,
+                                          int32_t include_input, const float* d_out, int64_t d_out_stride, float* d_origins,
+                                          float* d_directions, int accumulate, nsamd_stream_t stream) {
+  if (const int st = check_points(pts, M)) return st;
+  NSAMD_REQUIRE(num_frequencies > 0 && num_frequencies <= 64);
+  NSAMD_REQUIRE(d_out_stride >= 6 * (int64_t)num_frequencies + (include_input ? 3 : 0));
+  if (M == 0) return NSAMD_OK;
+  NSAMD_REQUIRE(pts.positions == nullptr);  // ray mode only: explicit positions have no origin / direction to credit
+  NSAMD_REQUIRE(freqs != nullptr && d_out != nullptr && d_origins != nullptr && d_directions != nullptr);
+  const int64_t rays = M / pts.samples_per_ray;
+  unsigned nb;
+  if (grid_blocks((rays + 3) / 4, &nb)) return NSAMD_ERR_UNSUPPORTED;
+  nerf_encode_bwd_rays_kernel<<<nb, 256, 0, (hipStream_t)stream>>>(pts, rays, freqs, num_frequencies, include_input != 0, d_out,
+                                                                   d_out_stride, d_origins, d_directions, accumulate ? 1 : 0);
   NSAMD_CHECK_LAUNCH();
   return NSAMD_OK;
 }

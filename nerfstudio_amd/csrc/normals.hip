@@ -22,9 +22,14 @@
 //
 // nsamd_normals_composite. One wavefront per ray: pred = normalize(tanh(x)) per sample, the weighted sums of both normal
 // channels (double partial sums, the DPP scan of wave.h: a fixed order), r = s / (|s| + 1e-10), shaded (r + 1) / 2.
+//
+// nsamd_normals_losses. The two training losses on those normals with their gradients (normals_loss.h), one wavefront per ray
+// as the composite: lane l takes samples l, l + 64, ..., writes their pre-activation gradients, and the ray's two loss terms and
+// its view-direction gradient are double partial sums through the same scan. No atomics, the same bits on every run.
 #include "common.h"
 #include "launch.h"
 #include "mfma_chain.h"
+#include "normals_loss.h"
 #include "wave.h"
 
 namespace nsamd {
@@ -198,6 +203,60 @@ __global__ __launch_bounds__(64 * kNrmRays) void normals_composite_kernel(
   }
 }
 
+__global__ __launch_bounds__(64 * kNrmRays) void normals_losses_kernel(
+    const float* __restrict__ weights, const float* __restrict__ normals, const float* __restrict__ pred_pre,
+    const float* __restrict__ directions, int64_t num_rays, int S, float orientation_scale, float pred_scale,
+    float* __restrict__ orientation_per_ray, float* __restrict__ pred_per_ray, float* __restrict__ d_pred_pre,
+    float* __restrict__ d_directions, int accumulate) {
+  const int lane = threadIdx.x & 63;
+  const int64_t ray = (int64_t)blockIdx.x * kNrmRays + wave_index();
+  if (ray >= num_rays) return;  // (wave-uniform)
+  float v[3] = {0.0f, 0.0f, 0.0f};
+  if (directions != nullptr) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) v[c] = directions[3 * ray + c];
+  }
+  double so = 0.0, sp = 0.0, sd[3] = {0.0, 0.0, 0.0};
+  for (int smp = lane; smp < S; smp += 64) {
+    const int64_t i = ray * S + smp;
+    const float w = weights[i];
+    const float n[3] = {normals[3 * i], normals[3 * i + 1], normals[3 * i + 2]};
+    if (pred_pre != nullptr) {
+      const float x[3] = {pred_pre[3 * i], pred_pre[3 * i + 1], pred_pre[3 * i + 2]};
+      float term, dx[3];
+      pred_normal_sample(w, n, x, pred_scale, &term, d_pred_pre != nullptr ? dx : nullptr);
+      sp += (double)term;
+      if (d_pred_pre != nullptr) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) d_pred_pre[3 * i + c] = dx[c];
+      }
+    }
+    if (directions != nullptr) {
+      float term, dv[3];
+      orientation_sample(w, n, v, &term, dv);
+      so += (double)term;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) sd[c] += (double)dv[c];
+    }
+  }
+  const float to = (float)wave_read_f64<63>(wave_scan_inclusive_f64(so));
+  const float tp = (float)wave_read_f64<63>(wave_scan_inclusive_f64(sp));
+  float td[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) td[c] = (float)wave_read_f64<63>(wave_scan_inclusive_f64(sd[c]));
+  if (lane == 0) {
+    if (orientation_per_ray != nullptr) orientation_per_ray[ray] = to;
+    if (pred_per_ray != nullptr) pred_per_ray[ray] = tp;
+    if (d_directions != nullptr) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const float g = orientation_scale * td[c];
+        d_directions[3 * ray + c] = accumulate ? d_directions[3 * ray + c] + g : g;
+      }
+    }
+  }
+}
+
 }  // namespace nsamd
 
 using namespace nsamd;
@@ -238,6 +297,27 @@ extern "C" int nsamd_normals_composite(const float* weights, const float* normal
   if (normals_out == nullptr && pred_out == nullptr) return NSAMD_OK;
   normals_composite_kernel<<<blocks, 64 * kNrmRays, 0, (hipStream_t)stream>>>(
       weights, normals_out ? normals : nullptr, pred_out ? pred_pre : nullptr, num_rays, S, normals_out, pred_out);
+  NSAMD_CHECK_LAUNCH();
+  return NSAMD_OK;
+}
+
+extern "C" int nsamd_normals_losses(const float* weights, const float* normals, const float* pred_pre, const float* directions,
+                                    int64_t num_rays, int32_t S, float orientation_scale, float pred_scale,
+                                    float* orientation_per_ray, float* pred_per_ray, float* d_pred_pre, float* d_directions,
+                                    int32_t accumulate_directions, nsamd_stream_t stream) {
+  NSAMD_REQUIRE(num_rays >= 0);
+  if (S < 1 || S > 4096) return NSAMD_ERR_UNSUPPORTED;
+  unsigned blocks;
+  if (grid_blocks((num_rays + kNrmRays - 1) / kNrmRays, &blocks)) return NSAMD_ERR_UNSUPPORTED;
+  if (num_rays == 0) return NSAMD_OK;
+  const bool want_pred = pred_per_ray != nullptr || d_pred_pre != nullptr;
+  const bool want_orientation = orientation_per_ray != nullptr || d_directions != nullptr;
+  if (!want_pred && !want_orientation) return NSAMD_OK;
+  NSAMD_REQUIRE(weights != nullptr && normals != nullptr);
+  NSAMD_REQUIRE((!want_pred || pred_pre != nullptr) && (!want_orientation || directions != nullptr));
+  normals_losses_kernel<<<blocks, 64 * kNrmRays, 0, (hipStream_t)stream>>>(
+      weights, normals, want_pred ? pred_pre : nullptr, want_orientation ? directions : nullptr, num_rays, S, orientation_scale,
+      pred_scale, orientation_per_ray, pred_per_ray, d_pred_pre, d_directions, accumulate_directions ? 1 : 0);
   NSAMD_CHECK_LAUNCH();
   return NSAMD_OK;
 }

@@ -35,6 +35,15 @@ from .utils import profiler
 _PN_BLOCK = 1 << 18  # samples per pass of the predicted-normals MLP (its two [block, 64] activation buffers: 64 MiB each)
 
 
+def pred_normals_layers(fld):
+    """The dense layers of a NerfactoField's predicted-normals branch (nerfacto_field.py:181-191) as (W, b, activation) in order:
+    the MLP's three layers (ReLU, ReLU, none) and the 64 -> 3 head without its activation — 27 -> 64 -> 64 -> 64 -> 3. The one
+    list both the eval form below and the training stage (train_step.NerfactoTrainStep) launch."""
+    W0, b0, W1, b1, W2, b2 = fld.mlp_pred_normals.param_tensors()
+    head = fld.field_head_pred_normals.net
+    return ((W0, b0, 1), (W1, b1, 1), (W2, b2, 0), (head.weight, head.bias, 0))
+
+
 def pred_normals_mlp_launch(fld, pts: N.Points, M: int, freqs: Tensor, pn_enc: Tensor, pn_in: Tensor, pn_a: Tensor, pn_b: Tensor,
                             pn_pre: Tensor) -> None:
     """The predicted-normals branch of a NerfactoField in eval (nerfacto_field.py:287-295) on M points whose geometry features
@@ -44,15 +53,13 @@ def pred_normals_mlp_launch(fld, pts: N.Points, M: int, freqs: Tensor, pn_enc: T
     the rows `pn_a` / `pn_b` [block, 64] hold."""
     F.nerf_encode_launch(pts, M, freqs, False, pn_enc)
     pn_in[:, :12].copy_(pn_enc)  # (the encoder writes dense 12-wide rows)
-    W0, b0, W1, b1, W2, b2 = fld.mlp_pred_normals.param_tensors()
-    head = fld.field_head_pred_normals.net
+    layers = pred_normals_layers(fld)
     block = pn_a.shape[0]
     for a in range(0, M, block):
         k = min(a + block, M) - a
-        layers = ((pn_in[a:a + k], W0, b0, 1, pn_a), (pn_a, W1, b1, 1, pn_b), (pn_b, W2, b2, 0, pn_a),
-                  (pn_a, head.weight, head.bias, 0, pn_pre[a:a + k]))  # 27 -> 64 -> 64 -> 64 -> 3
-        for x, W, b, act, y in layers:
-            F.linear_launch(x, W, b, k, act, y)
+        rows = (pn_in[a:a + k], pn_a, pn_b, pn_a, pn_pre[a:a + k])  # each layer's input and, one further, its output
+        for i, (W, b, act) in enumerate(layers):
+            F.linear_launch(rows[i], W, b, k, act, rows[i + 1])
 
 
 class EvalRenderer:

@@ -509,6 +509,16 @@ def nerf_encode(spec: PointSpec, num_frequencies: int, min_freq_exp: float, max_
     return out
 
 
+def nerf_encode_bwd_rays_launch(pts: N.Points, M: int, freqs: Tensor, include_input: bool, d_out: Tensor, d_out_stride: int,
+                                d_origins: Tensor, d_directions: Tensor, accumulate: bool = False) -> None:
+    """nsamd_nerf_encode_bwd_rays on the current stream: the gradient of nerf_encode_launch's rows (row p of `d_out` starts at
+    p * d_out_stride floats) with respect to the M sample positions of the rays `pts`, reduced per ray into `d_origins` /
+    `d_directions` `[n,3]` (written, or added to)."""
+    N.check(N.load().nsamd_nerf_encode_bwd_rays(pts, M, N.ptr(freqs), freqs.shape[0], int(bool(include_input)), N.ptr(d_out),
+                                                int(d_out_stride), N.ptr(d_origins), N.ptr(d_directions),
+                                                1 if accumulate else 0, N.stream()), "nerf_encode_bwd_rays")
+
+
 def contract_linf(x: Tensor) -> Tensor:
     """SceneContraction(order=inf).forward (spatial_distortions.py:66-69), forward only (the fused fields carry
     the Jacobian inside their own backward)."""
@@ -530,6 +540,14 @@ def linear_launch(x: Tensor, W: Tensor, b: Optional[Tensor], M: int, act: int, y
     """nsamd_linear_fwd on the current stream: y = act(x W^T + b) on the first M rows of `x` `[., K]`, `W` `[N, K]`."""
     N.check(N.load().nsamd_linear_fwd(N.ptr(x), N.ptr(W), N.ptr(b), M, W.shape[1], W.shape[0], act, N.ptr(y), N.stream()),
             "linear_fwd")
+
+
+def linear_backward_launch(x: Tensor, W: Tensor, y: Optional[Tensor], dy: Tensor, M: int, act: int, dx: Optional[Tensor],
+                           dW: Optional[Tensor], db: Optional[Tensor]) -> None:
+    """nsamd_linear_bwd on the current stream, on the first M rows: `dx` `[., K]` written, `dW` `[N, K]` / `db` `[N]` accumulated
+    into (each optional); `y` is the forward's output (not read without an activation: may then be None)."""
+    N.check(N.load().nsamd_linear_bwd(N.ptr(x), N.ptr(W), N.ptr(y), N.ptr(dy), M, W.shape[1], W.shape[0], act, N.ptr(dx),
+                                      N.ptr(dW), N.ptr(db), N.stream()), "linear_bwd")
 
 
 class _LinearFn(torch.autograd.Function):
@@ -554,8 +572,7 @@ class _LinearFn(torch.autograd.Function):
         dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
         dW = torch.zeros_like(W) if ctx.needs_input_grad[1] else None
         db = torch.zeros((Nout,), device=x.device, dtype=torch.float32) if (ctx.has_bias and ctx.needs_input_grad[2]) else None
-        N.check(N.load().nsamd_linear_bwd(N.ptr(x), N.ptr(W), N.ptr(y), N.ptr(gy), M, K, Nout, ctx.act, N.ptr(dx), N.ptr(dW),
-                                          N.ptr(db), N.stream()), "linear_bwd")
+        linear_backward_launch(x, W, y, gy, M, ctx.act, dx, dW, db)
         return dx, dW, db, None
 
 
@@ -1159,6 +1176,59 @@ def normals_composite(weights: Tensor, normals: Tensor, pred_pre: Tensor) -> Tup
                                                                                             dtype=torch.float32)
     normals_composite_launch(w, nr, pp, out_n, out_p)
     return out_n, out_p
+
+
+def normals_losses_launch(weights: Tensor, normals: Tensor, pred_pre: Optional[Tensor], directions: Optional[Tensor],
+                          orientation_scale: float, pred_scale: float, orientation_per_ray: Optional[Tensor],
+                          pred_per_ray: Optional[Tensor], d_pred_pre: Optional[Tensor], d_directions: Optional[Tensor],
+                          accumulate_directions: bool = False) -> None:
+    """nsamd_normals_losses on dense fp32 device tensors, on the current stream (weights `[n,S]`, per-sample `[n*S,3]`, directions
+    and `d_directions` `[n,3]`, per-ray terms `[n]`); every output is optional."""
+    n, S = weights.shape
+    N.check(N.load().nsamd_normals_losses(N.ptr(weights), N.ptr(normals), N.ptr(pred_pre), N.ptr(directions), n, S,
+                                          float(orientation_scale), float(pred_scale), N.ptr(orientation_per_ray),
+                                          N.ptr(pred_per_ray), N.ptr(d_pred_pre), N.ptr(d_directions),
+                                          1 if accumulate_directions else 0, N.stream()), "normals_losses")
+
+
+class _NormalsLossesFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, weights: Tensor, normals: Tensor, pred_pre: Tensor, directions: Tensor):
+        N.require_cuda(weights, normals, pred_pre, directions)
+        w = _f32c(weights.detach().reshape(weights.shape[0], -1))
+        n, S = w.shape
+        nr, pp = _f32c(normals.detach().reshape(n * S, 3)), _f32c(pred_pre.detach().reshape(n * S, 3))
+        v = _f32c(directions.detach().reshape(n, 3))
+        new = lambda *shape: torch.empty(shape, device=w.device, dtype=torch.float32)  # noqa: E731
+        orientation, pred = new(n), new(n)
+        d_pre = new(n * S, 3) if ctx.needs_input_grad[2] else None
+        d_dir = new(n, 3) if ctx.needs_input_grad[3] else None
+        normals_losses_launch(w, nr, pp, v, 1.0, 1.0, orientation, pred, d_pre, d_dir)
+        ctx.save_for_backward(*(t for t in (d_pre, d_dir) if t is not None))
+        ctx.have = (d_pre is not None, d_dir is not None)
+        ctx.shapes = (pred_pre.shape, directions.shape)
+        return orientation, pred
+
+    @staticmethod
+    def backward(ctx, g_orientation: Tensor, g_pred: Tensor):
+        saved = list(ctx.saved_tensors)
+        d_pre = saved.pop(0) if ctx.have[0] else None
+        d_dir = saved.pop(0) if ctx.have[1] else None
+        n = g_pred.shape[0]
+        if d_pre is not None:  # the kernel left d term / d x of every sample: times the ray's upstream gradient
+            d_pre = (d_pre.view(n, -1, 3) * g_pred.reshape(n, 1, 1)).reshape(ctx.shapes[0])
+        if d_dir is not None:
+            d_dir = (d_dir * g_orientation.reshape(n, 1)).reshape(ctx.shapes[1])
+        return None, None, d_pre, d_dir
+
+
+def normals_losses(weights: Tensor, normals: Tensor, pred_pre: Tensor, directions: Tensor) -> Tuple[Tensor, Tensor]:
+    """The two per-ray normals loss terms of a `predict_normals` model (models/nerfacto.py:335-344 over losses.py:201-222):
+    (orientation_loss(weights, normals, directions), pred_normal_loss(weights, normals, normalize(tanh(pred_pre)))), each `[n]`,
+    from weights `[n,S]` or `[n,S,1]`, per-sample analytic normals and the predicted-normals head's PRE-activation `[n,S,3]` and
+    the rays' view directions `[n,3]`. Weights and normals are constants, as the reference detaches them; gradient flows to
+    `pred_pre` and to `directions`."""
+    return _NormalsLossesFn.apply(weights, normals, pred_pre, directions)
 
 
 # ---------------------------------------------------------------------------------------------------------------

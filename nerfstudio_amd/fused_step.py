@@ -8,7 +8,8 @@ profiles/r02_module_path.txt). `FusedTrainStep` keeps the Model API and runs the
 
   get_outputs(ray_bundle)      rays -> [camera corrections] -> proposal levels -> main field -> compositing; returns the
                                reference's output dict (rgb, accumulation, depth, expected_depth, prop_depth_i,
-                               weights_list) as views of the runner's static buffers
+                               weights_list; a `predict_normals` model: normals, pred_normals and the two rendered loss
+                               terms) as views of the runner's static buffers
   get_loss_dict(outputs, batch) the three losses against batch["image"] (one more launch of the fused
                                compositing + MSE kernel with the real target, and the proposal-loss kernel); the values
                                come back as outputs of ONE autograd node whose backward launches the backward chains,
@@ -30,6 +31,7 @@ import torch
 from torch import Tensor
 
 _LOSS_KEYS = ("rgb_loss", "interlevel_loss", "distortion_loss")
+_NORMALS_KEYS = ("orientation_loss", "pred_normal_loss")  # a `predict_normals` model (models/nerfacto.py:379-388)
 
 
 def ddp_reason() -> Optional[str]:
@@ -85,7 +87,13 @@ class FusedTrainStep:
         """None, or the reason this model has to stay on the module path."""
         cfg = self.model.config
         if getattr(cfg, "predict_normals", False):
-            return "predict_normals"
+            # the runner's normals stage needs the field's modules as well as the option (the double condition of
+            # eval_render.supported(model, normals=True))
+            fld = getattr(self.model, "field", None)
+            if not getattr(fld, "use_pred_normals", False):
+                return "predict_normals"
+            if getattr(cfg, "use_gradient_scaling", False):
+                return "predict_normals together with use_gradient_scaling"
         kind = getattr(cfg, "depth_loss_type", None)  # a depth model (depth_nerfacto.py): the schedule covers DS_NERF
         if kind is not None and int(getattr(kind, "value", kind)) != 1:
             return f"depth loss type {getattr(kind, 'name', kind)}"
@@ -94,8 +102,14 @@ class FusedTrainStep:
     def is_depth_model(self) -> bool:
         return hasattr(self.model.config, "depth_loss_type")
 
+    def is_normals_model(self) -> bool:
+        """The option AND the field's modules: the condition under which the runner has its normals stage."""
+        return bool(getattr(self.model.config, "predict_normals", False)
+                    and getattr(getattr(self.model, "field", None), "use_pred_normals", False))
+
     def loss_keys(self):
-        return _LOSS_KEYS + ("depth_loss",) if self.is_depth_model() else _LOSS_KEYS
+        keys = _LOSS_KEYS + ("depth_loss",) if self.is_depth_model() else _LOSS_KEYS
+        return keys + _NORMALS_KEYS if self.is_normals_model() else keys
 
     def _runner_for(self, num_rays: int, device):
         from .train_step import NerfactoTrainStep

@@ -62,7 +62,8 @@ class NerfactoModelConfig:
     pred_normal_loss_mult: float = 0.001
     predict_normals: bool = False
     """Analytic normals from the density gradient + the predicted-normals head (models/nerfacto.py:103-120, :325-345,
-    :379-388). The field then runs as the reference composes it (fields/nerfacto_field.py here), not as the fused pipeline."""
+    :379-388). On the module path the field then runs as the reference composes it (fields/nerfacto_field.py here), not as the
+    fused pipeline; with `fused_train_step` training runs the explicit schedule's normals stage (train_step.NerfactoTrainStep)."""
     use_proposal_weight_anneal: bool = True
     use_appearance_embedding: bool = True
     use_average_appearance_embedding: bool = True

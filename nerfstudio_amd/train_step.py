@@ -20,6 +20,7 @@ schedule variant and replayed. Numerically identical to the autograd path (tests
 
 The launches this schedule shares with the module path (or with trainer / eval_render) go through the helpers of functional.py
 — piecewise_bins_launch, density_forward, weights_launch, composite_launch, pdf_resample_launch, depth_loss_launch,
+field_normals_launch, nerf_encode_launch, linear_launch, normals_losses_launch, normals_composite_launch,
 distance_gradient_scale_launch, weights_backward_launch, camera_apply_launch, camera_backward_launch, select_batch_launch
 and the field helpers — with this runner's static buffers; the entry points only this schedule launches are called here.
 """
@@ -58,6 +59,14 @@ class NerfactoTrainStep(TrainStepRunner):
         # per-level jitter buffers become [n, S+1] and the resampling goes through the unfused kernels
         self.single_jitter = bool(getattr(cfg, "use_single_jitter", True))
         self.gradient_scaling = bool(getattr(cfg, "use_gradient_scaling", False))
+        # the normals stage of a `predict_normals` model whose field carries the modules (training runners only: the eval render
+        # has its own, eval_render.EvalRenderer)
+        want_normals = (not forward_only and bool(getattr(cfg, "predict_normals", False))
+                        and bool(getattr(model.field, "use_pred_normals", False)))
+        if want_normals and self.gradient_scaling:
+            # the reference scales the predicted normals' gradient as well (models/nerfacto.py:321-322)
+            raise NotImplementedError("explicit schedule: predict_normals together with use_gradient_scaling is only on the "
+                                      "module path")
         f32 = dict(device=device, dtype=torch.float32)
         e = lambda *shape: torch.empty(shape, **f32)  # noqa: E731
         # (training-only buffers: one element each in a forward-only runner)
@@ -186,7 +195,8 @@ class NerfactoTrainStep(TrainStepRunner):
             self.cam_kernels = (os.environ.get("NSAMD_CAMERA_KERNELS", "1") == "1" and pose is not None and pose.is_cuda
                                 and pose.dtype == torch.float32 and pose.dim() == 2 and pose.shape[1] == 6
                                 and co.config.mode in ("SO3xR3", "SE3")
-                                and len(self.counts) <= 4  # nsamd_ray_grads has four level slots
+                                # nsamd_ray_grads has four slots: the levels' and the normals chain's
+                                and len(self.counts) + int(want_normals) <= 4
                                 and getattr(co, "non_trainable_camera_indices", None) is None)
             self.cam_mode = F.CAMERA_MODES.get(co.config.mode, 0)
             self.raw_origins, self.raw_directions = e(n, 3), e(n, 3)
@@ -194,6 +204,8 @@ class NerfactoTrainStep(TrainStepRunner):
             self.d_directions = [e(n, 3) for _ in self.counts]
             self._corrected = None
             self.camera_reg = torch.zeros((), **f32)
+        self.normals = self._normals_buffers(device) if want_normals else None
+        self._normals_fresh = False  # the stage's results belong to the last forward_main
         self.reg_in_backward = True  # backward_cameras also differentiates the pose regulariser
         # True: `backward_join` leaves the camera optimiser's share to the caller (`backward_cameras(updated, force=True)`
         # after a replayed graph: the exponential map's autograd graph is host-side torch and stays out of the capture)
@@ -258,6 +270,102 @@ class NerfactoTrainStep(TrainStepRunner):
             d["norm"].copy_(directions_norm.reshape(-1))
         d["euclidean"], d["sigma"], d["mult"] = bool(is_euclidean), float(sigma), float(mult)
         self.depth = d
+
+    def _normals_buffers(self, device) -> Dict[str, object]:
+        """Static buffers of the normals stage, allocated once: per-sample analytic normals, the predicted-normals MLP's 27-wide
+        input rows (12 encoded columns | 15 geometry features), the KEPT activations of its three layers and the head's
+        pre-activation, the per-ray terms and rendered channels; for the backward the pre-activation's gradient, two ping-pong
+        `[M, 64]` gradient blocks (the base MLP's recomputed hidden activations reuse one), the input rows' gradient, the base
+        output's 16-wide gradient (column 0, the density pre-activation, stays zero), the row-major hash features and their
+        gradient; with a camera optimiser the loss's view-direction gradient and one more (d_origins, d_directions) pair. The
+        accumulating table scatter's cached workspace for this sample count is taken here as well."""
+        f32 = dict(device=device, dtype=torch.float32)
+        e = lambda *shape: torch.empty(shape, **f32)  # noqa: E731
+        n, mm = self.n, self.m_main
+        fld = self.model.field
+        pe = fld.position_encoding
+        cam = self.cam_opt is not None
+        F._scatter_workspace(fld.mlp_base.encoding.spec, device, mm)  # the accumulating table scatter's workspace: here, not lazily
+        return {"freqs": (2 ** torch.linspace(pe.min_freq, pe.max_freq, pe.num_frequencies)).to(device),
+                "n_smp": e(mm, 3), "enc": e(mm, 12), "in": e(mm, 27), "act": [e(mm, 64) for _ in range(3)], "pre": e(mm, 3),
+                "orientation": e(n), "pred": e(n), "normals_img": e(n, 3), "pred_img": e(n, 3),
+                "d_pre": e(mm, 3), "d_a": e(mm, 64), "d_b": e(mm, 64), "d_in": e(mm, 27), "dy16": torch.zeros((mm, 16), **f32),
+                "enc_rows": e(mm, 32), "d_enc": e(mm, 32), "d_dir_loss": e(n, 3) if cam else None,
+                "d_origins": e(n, 3) if cam else None, "d_directions": e(n, 3) if cam else None}
+
+    def _normals_rows(self):
+        """The predicted-normals branch's row buffers: each layer's input and, one further, its output."""
+        nb = self.normals
+        return (nb["in"], *nb["act"], nb["pre"])
+
+    @profiler.time_function
+    def normals_forward(self) -> None:
+        """The normals stage of `losses` (models/nerfacto.py:325-344), behind the weights: analytic normals and the geometry
+        features from the hash features forward_main left, the predicted-normals branch with its activations kept, the two
+        loss terms with their gradients (to the head's pre-activation; to the view directions for a camera optimiser) and the
+        two rendered channels. It depends on nothing `losses` takes from the target, so a second `losses` of the same forward
+        (FusedTrainStep: once for the outputs, once with the real target) does not repeat it."""
+        from .eval_render import pred_normals_layers
+
+        if self._normals_fresh:
+            return
+        if torch.cuda.is_current_stream_capturing():
+            raise NotImplementedError("explicit schedule: predict_normals inside a captured graph; normals in captured "
+                                      "iterations are only on the module path")
+        nb, fld, cfg, n = self.normals, self.model.field, self.cfg, self.n
+        L, M = self.n_prop, self.m_main
+        pts = self._points(L)
+        enc = fld.mlp_base.encoding
+        F.field_normals_launch(pts, M, fld._transform, fld._box, enc.hash_table, enc.spec, self.f_enc,
+                               fld.mlp_base.mlp.param_tensors(), nb["n_smp"], None, nb["in"], 27, 12)
+        F.nerf_encode_launch(pts, M, nb["freqs"], False, nb["enc"])
+        nb["in"][:, :12].copy_(nb["enc"])  # (the encoder writes dense 12-wide rows)
+        rows = self._normals_rows()
+        for i, (W, b, act) in enumerate(pred_normals_layers(fld)):
+            F.linear_launch(rows[i], W, b, M, act, rows[i + 1])
+        F.normals_losses_launch(self.weights[L], nb["n_smp"], nb["pre"], self.directions,
+                                float(cfg.orientation_loss_mult) / n, float(cfg.pred_normal_loss_mult) / n, nb["orientation"],
+                                nb["pred"], nb["d_pre"], nb["d_dir_loss"])
+        F.normals_composite_launch(self.weights[L], nb["n_smp"], nb["pre"], nb["normals_img"], nb["pred_img"])
+        self._normals_fresh = True
+
+    @profiler.time_function
+    def normals_backward(self) -> None:
+        """The predicted-normal loss's gradient chain, on the current stream behind backward_main (whose table scatter writes;
+        everything here ACCUMULATES): head and the three layers of the predicted-normals MLP down to its input rows; their
+        geometry-feature columns through the base MLP (hidden activations recomputed from a row-major copy of the hash
+        features) and the table scatter; with a camera optimiser the rays' share — through the hash grid, through the
+        frequency encoding of the raw positions, and the orientation loss's view-direction gradient — into one more
+        (d_origins, d_directions) pair for backward_cameras."""
+        from .eval_render import pred_normals_layers
+
+        nb, fld = self.normals, self.model.field
+        L, M = self.n_prop, self.m_main
+        pts = self._points(L)
+        layers, rows = pred_normals_layers(fld), self._normals_rows()
+        d_rows = (nb["d_in"], nb["d_a"], nb["d_b"], nb["d_a"], nb["d_pre"])
+        for i in range(len(layers) - 1, -1, -1):
+            W, b, act = layers[i]
+            F.linear_backward_launch(rows[i], W, rows[i + 1], d_rows[i + 1], M, act, d_rows[i], self._grad(W), self._grad(b))
+        # base MLP: layer 1 (64 -> 16, no activation) from dy = [0 | d geometry features], layer 0 (32 -> 64, ReLU)
+        W0, b0, W1, b1 = fld.mlp_base.mlp.param_tensors()
+        hidden, d_hidden = nb["d_b"], nb["d_a"]
+        nb["enc_rows"].copy_(self.f_enc.t())  # (the hash forward leaves the features feature-major)
+        F.linear_launch(nb["enc_rows"], W0, b0, M, 1, hidden)
+        nb["dy16"][:, 1:].copy_(nb["d_in"][:, 12:])
+        F.linear_backward_launch(hidden, W1, None, nb["dy16"], M, 0, d_hidden, self._grad(W1), self._grad(b1))
+        F.linear_backward_launch(nb["enc_rows"], W0, hidden, d_hidden, M, 1, nb["d_enc"], self._grad(W0), self._grad(b0))
+        tbl = fld.mlp_base.encoding
+        F.table_scatter(pts, M, fld._transform, fld._box, tbl.hash_table, tbl.spec, nb["d_enc"], 32, 1,
+                        self._grad(tbl.hash_table))
+        if self.cam_opt is not None:
+            nb["d_origins"].zero_()
+            nb["d_directions"].copy_(nb["d_dir_loss"])
+            N.check(N.load().nsamd_hashgrid_encode_bwd_rays(pts, M, fld._transform, fld._box, N.ptr(tbl.hash_table),
+                                                            tbl.spec.native(), N.ptr(nb["d_enc"]), 32, 1, N.ptr(nb["d_origins"]),
+                                                            N.ptr(nb["d_directions"]), 1, N.stream()), "hashgrid_encode_bwd_rays")
+            F.nerf_encode_bwd_rays_launch(pts, M, nb["freqs"], False, nb["d_in"], 27, nb["d_origins"], nb["d_directions"],
+                                          accumulate=True)
 
     def prepare_grads(self, updated: bool) -> None:
         """For callers without a gradient arena (a trainer that runs `zero_grad(set_to_none=True)`, engine/optimizers.py:
@@ -331,8 +439,12 @@ class NerfactoTrainStep(TrainStepRunner):
                     self.backward_proposals(levels=levels)
                     join.record(stream)
             self.backward_main()
+            if self.normals is not None:
+                self.normals_backward()
         else:
             self.backward_main()
+            if self.normals is not None:
+                self.normals_backward()
             if updated:
                 self.backward_proposals()
 
@@ -350,6 +462,8 @@ class NerfactoTrainStep(TrainStepRunner):
         (interlevel-loss gradients of the proposal networks) still runs."""
         self.forward_and_losses(updated, draw_jitter)
         self.backward_main()
+        if self.normals is not None:
+            self.normals_backward()
 
     def written_params(self):
         """Parameters whose gradient this runner WRITES (hash tables, nsamd_hashgrid_encode_bwd_set): callers need not
@@ -412,10 +526,13 @@ class NerfactoTrainStep(TrainStepRunner):
                     pose.grad = torch.zeros_like(pose)
                 g = pose.grad
             levels = (list(range(L)) if updated else []) + [L]  # the proposal networks saw the rays too (interlevel loss)
+            d_os, d_ds = [self.d_origins[lvl] for lvl in levels], [self.d_directions[lvl] for lvl in levels]
+            if self.normals is not None:  # the normals chain's share of the rays' gradient (normals_backward)
+                d_os.append(self.normals["d_origins"])
+                d_ds.append(self.normals["d_directions"])
             cfg = self.cam_opt.config
             reg = self.reg_in_backward  # (else the caller differentiates the regulariser itself — fused_step.FusedTrainStep)
-            F.camera_backward_launch(pose, self.cam_mode, self.raw_directions, self.camera_indices,
-                                     [self.d_origins[lvl] for lvl in levels], [self.d_directions[lvl] for lvl in levels],
+            F.camera_backward_launch(pose, self.cam_mode, self.raw_directions, self.camera_indices, d_os, d_ds,
                                      float(cfg.trans_l2_penalty) if reg else 0.0, float(cfg.rot_l2_penalty) if reg else 0.0, g,
                                      self.camera_reg if reg else None)
             return
@@ -423,6 +540,8 @@ class NerfactoTrainStep(TrainStepRunner):
         if updated:  # the proposal networks saw the rays too (interlevel loss)
             d_o = d_o + sum(self.d_origins[:L])
             d_d = d_d + sum(self.d_directions[:L])
+        if self.normals is not None:
+            d_o, d_d = d_o + self.normals["d_origins"], d_d + self.normals["d_directions"]
         o, d = self._corrected
         outs, ups = [o, d], [d_o, d_d]
         if self.reg_in_backward:
@@ -558,6 +677,7 @@ class NerfactoTrainStep(TrainStepRunner):
         tbl = fld.mlp_base.encoding
         F.field_forward(tbl.hash_table, tbl.spec, fld._transform, fld._box, self._points(L), self.m_main, self.f_enc, self.f_sel,
                         self.directions, self._cams(app_const), app_const, self.counts[L], fm, self.f_dens, self.f_rgb)
+        self._normals_fresh = False
 
     @profiler.time_function
     def losses(self, updated: bool) -> None:
@@ -593,6 +713,8 @@ class NerfactoTrainStep(TrainStepRunner):
                                 F.DEPTH_DS_NERF, scale, d["per_ray"], dws, None, accumulate=True)
             torch.sum(d["per_ray"], dim=(0, 1), out=d["value"])
             d["value"].mul_(scale)
+        if self.normals is not None:
+            self.normals_forward()
         if self.want_loss_vals:
             # a caller that reads the loss dictionary every iteration (pipeline.TrainEngine): the values and the training metrics
             # as five floats from one small launch instead of a dozen reductions issued by the host
@@ -763,6 +885,9 @@ class NerfactoTrainStep(TrainStepRunner):
             out["camera_opt_regularizer"] = self.camera_reg
         if self.depth is not None:
             out["depth_loss"] = self.depth["value"].clone()
+        if self.normals is not None:  # models/nerfacto.py:379-388: mult * mean of the rendered per-ray terms
+            out["orientation_loss"] = self.cfg.orientation_loss_mult * self.normals["orientation"].sum() / n
+            out["pred_normal_loss"] = self.cfg.pred_normal_loss_mult * self.normals["pred"].sum() / n
         return out
 
     def outputs(self) -> Dict[str, Tensor]:
@@ -775,5 +900,9 @@ class NerfactoTrainStep(TrainStepRunner):
                 out["depth"] = self.depth_med[-1][:, None]
                 for i in range(self.n_prop):
                     out[f"prop_depth_{i}"] = self.depth_med[i][:, None]
+            if self.normals is not None:
+                nb = self.normals
+                out.update(normals=nb["normals_img"], pred_normals=nb["pred_img"], rendered_orientation_loss=nb["orientation"],
+                           rendered_pred_normal_loss=nb["pred"])
             self._outputs = out
         return dict(self._outputs)
