@@ -764,8 +764,10 @@ __device__ __noinline__ void route_record_slow(RouteLds* L, float x, float y, fl
 // record stores were FLAT instructions — each held up the wave's next LDS wait for a full L2 round trip, so they had to be
 // kept apart —; as global stores they are fire-and-forget, and what is left of a record is its chain of ~6 dependent LDS
 // round trips, which four records now share.)
+// `gmax`: the lane's running maximum of |gradient| bits on this level, kept in a register across the workgroup's tiles and
+// folded once at the end (route_publish_max) — as an LDS atomicMax here it was 64 lanes on 4 addresses per tile and level.
 template <int K>
-__device__ __forceinline__ void route_level(RouteLds* L, const float (*stash)[64], int lane) {
+__device__ __forceinline__ void route_level(RouteLds* L, const float (*stash)[64], int lane, uint32_t& gmax) {
   constexpr int t = K >> 1, rr = K & 1;
   const int g = lane >> 4;
   const int level = 8 * t + 2 * g + rr;
@@ -775,7 +777,7 @@ __device__ __forceinline__ void route_level(RouteLds* L, const float (*stash)[64
   const Cell c = locate_cell(x, y, z, L->lv[level].scal);
   {  // integer compare of |bits|: a NaN or Inf wins and marks the level non-finite
     const uint32_t b0 = __float_as_uint(g0) & 0x7fffffffu, b1 = __float_as_uint(g1) & 0x7fffffffu;
-    atomicMax(&L->lv[level].lmax, b0 > b1 ? b0 : b1);
+    gmax = max(gmax, max(b0, b1));
   }
   const uint32_t mask = (1u << L->log2_table_size) - 1u;
   const int sl = L->slice_log2;
@@ -816,11 +818,22 @@ __device__ __forceinline__ void route_level(RouteLds* L, const float (*stash)[64
 }
 
 // every record of the stashed tile at once (after the last tile of a workgroup; emission of a tile normally rides on the next one)
-__device__ __forceinline__ void route_flush(RouteLds* L, const float (*stash)[64], int lane) {
-  route_level<0>(L, stash, lane);
-  route_level<1>(L, stash, lane);
-  route_level<2>(L, stash, lane);
-  route_level<3>(L, stash, lane);
+__device__ __forceinline__ void route_flush(RouteLds* L, const float (*stash)[64], int lane, uint32_t (&gmax)[4]) {
+  route_level<0>(L, stash, lane, gmax[0]);
+  route_level<1>(L, stash, lane, gmax[1]);
+  route_level<2>(L, stash, lane, gmax[2]);
+  route_level<3>(L, stash, lane, gmax[3]);
+}
+
+// The lanes' running maxima into the workgroup's per-level maxima: the 16 lanes of a level group meet over DPP, one lane of
+// the group issues the LDS atomic — one per wave and level. All 64 lanes; before the barrier in front of the header write.
+__device__ __forceinline__ void route_publish_max(RouteLds* L, int lane, const uint32_t (&gmax)[4]) {
+#pragma unroll
+  for (int K = 0; K < 4; ++K) {
+    const int level = 8 * (K >> 1) + 2 * (lane >> 4) + (K & 1);
+    const uint32_t m = row16_max_u32(gmax[K]);
+    if ((lane & 15) == 0 && level < L->num_levels && m != 0u) atomicMax(&L->lv[level].lmax, m);
+  }
 }
 
 // Raw position of this lane's point of a tile, in two halves: `route_issue_position` puts the loads out (one phase ahead of
@@ -949,11 +962,12 @@ struct RouteBetween {
   const float (*stash)[64];
   int lane;
   bool on;
+  uint32_t* gmax;  // the kernel's four running maxima (registers: every index is a constant)
   template <int I>
   __device__ __forceinline__ void at() const {
     if (!on) return;
-    if (I == 0) route_level<0>(L, stash, lane);
-    if (I == 2) route_level<1>(L, stash, lane);
+    if (I == 0) route_level<0>(L, stash, lane, gmax[0]);
+    if (I == 2) route_level<1>(L, stash, lane, gmax[1]);
   }
 };
 
@@ -1035,6 +1049,7 @@ __global__ __launch_bounds__(kCoopThreads) void field_mlp_bwd_kernel(
   if (iters > 0)
     fetch_tile<RAYC>(nxt, (int64_t)blockIdx.x * kCoopWaves + wave, tiles, lane, M, enc, selector, directions, cams, app_table,
                      app_const, app_dim, dir_group, ddensity, drgb, mlp.ray_terms, mlp.ray_inputs);
+  uint32_t route_gmax[4] = {0u, 0u, 0u, 0u};  // ROUTE: max |gradient| bits of this lane's four levels (route_level)
   for (int64_t it = 0; it < iters; ++it) {
     PROBE_STAMP(kCoopWaves, 2 + 10 * (int)it);
     const int64_t tile = (it * gridDim.x + blockIdx.x) * kCoopWaves + wave;
@@ -1057,7 +1072,7 @@ __global__ __launch_bounds__(kCoopThreads) void field_mlp_bwd_kernel(
     const float nxt_xin = nxt.xin;
     if (ROUTE) {
       // records 0..6 of the PREVIOUS tile leave between this tile's forward GEMMs, the other nine between the phases below
-      const RouteBetween rb{RL, RL->stash[wave], lane, it > 0};
+      const RouteBetween rb{RL, RL->stash[wave], lane, it > 0, route_gmax};
       coop_forward_tile<RouteBetween, RAYC>(W, bias, dir, app_table, app_const, app_dim, ti, lane, A, app, rb, cterm);
     } else {
       coop_forward_tile<NoBetween, RAYC>(W, bias, dir, app_table, app_const, app_dim, ti, lane, A, app, NoBetween{}, cterm);
@@ -1067,7 +1082,7 @@ __global__ __launch_bounds__(kCoopThreads) void field_mlp_bwd_kernel(
 #define NSAMD_ROUTE_LEVEL(K)                                                      \
   do {                                                                           \
     if (ROUTE) {                                                                 \
-      if (emit) route_level<K>(RL, RL->stash[wave], lane);           \
+      if (emit) route_level<K>(RL, RL->stash[wave], lane, route_gmax[K]); \
     }                                                                            \
   } while (0)
 
@@ -1274,7 +1289,10 @@ __global__ __launch_bounds__(kCoopThreads) void field_mlp_bwd_kernel(
     PROBE_STAMP(kCoopWaves, 8 + 10 * (int)it);
 #undef NSAMD_ROUTE_LEVEL
   }
-  if (ROUTE && iters > 0) route_flush(RL, RL->stash[wave], lane);  // the last tile's records
+  if (ROUTE && iters > 0) {
+    route_flush(RL, RL->stash[wave], lane, route_gmax);  // the last tile's records
+    route_publish_max(RL, lane, route_gmax);
+  }
   PROBE_STAMP(kCoopWaves, 62);
 
   // ---- the two point-halves of the 1 x 4 layers meet in LDS (scratch is free now) ---------------------------------

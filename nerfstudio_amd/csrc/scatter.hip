@@ -30,6 +30,7 @@
 #include "field_reduce.h"
 #include "launch.h"
 #include "scatter.h"
+#include "wave.h"
 
 NSAMD_PROBE_DEFINE(scatter)
 
@@ -158,6 +159,11 @@ __global__ __launch_bounds__(kThreads) void scatter_route_fine_kernel(
         if (SW == 1 && ((over >> slot) & 0xfu) == 0u) continue;
         const Cell c = locate_cell(x[j], y[j], z[j], grid.scalings[lvl[i]]);
         if (SW == 0) {  // integer compare of |bits|: a NaN or Inf wins and marks the level non-finite
+          // (one LDS atomic per live thread and level, as it was: a thread has ONE point, so there is no loop to carry a
+          //  running maximum across as the field backward's producer does over its tiles (field_mlp.hip, route_publish_max),
+          //  and a fold over the wave in front of the atomic would need every lane here, inside the `continue`s of the
+          //  sweep. This kernel is not on the benchmark's step — the main table's records come from the field backward,
+          //  the proposal levels go through the run kernel —, so such a fold could not be measured there either.)
           const uint32_t b0 = __float_as_uint(g0[j][i]) & 0x7fffffffu, b1 = __float_as_uint(g1[j][i]) & 0x7fffffffu;
           atomicMax(lmax + i, b0 > b1 ? b0 : b1);
         }
@@ -393,6 +399,7 @@ __device__ __forceinline__ void scatter_route_runs_body(
       }
       // a merged record carries up to kRunLen gradients: the scale bound accounts for that
       // (exponent + 2 = x kRunLen; saturates into the non-finite range only for gradients beyond 2^125)
+      // (the running maximum of the thread's kRunLen samples is a register already: one LDS atomic per thread and level)
       if (SW == 0 && gmax != 0u) atomicMax(lmax + i, min(gmax + (2u << 23), 0x7fc00000u));
     }
   };
@@ -462,7 +469,7 @@ __global__ __launch_bounds__(kRunThreads) void scatter_route_runs_pair_kernel(Ru
 // One workgroup per (level, tile): static segments, dynamic area and the folded part of the spill list are summed into
 // an LDS tile of 2 x int64 per entry; the finished tile is converted once and stored / added with coalesced accesses.
 // kRider: the launch carries the main field's weight-gradient reduce along (its own instantiation: the rider's registers —
-// 118 against 83 — must not cost the small-tile launches of the proposal levels their occupancy).
+// 118 against 48 — must not cost the small-tile launches of the proposal levels their occupancy).
 template <bool kRider>
 __device__ __forceinline__ void scatter_apply_body(const nsamd_grid& grid, const ScatterGeom& G, const ScatterBufs& buf,
                                                    float* __restrict__ dtable, int overwrite,
@@ -485,25 +492,38 @@ __device__ __forceinline__ void scatter_apply_body(const nsamd_grid& grid, const
   PROBE_STAMP(0, 10);
   const bool coarse = (G.coarse_mask >> level) & 1u;
   const uint32_t Q = G.level_cap[level], C = G.seg_cap;
+  // Everything the tile reads before its first record is asked for HERE, together — the level's maximum, the dynamic cursor,
+  // the spill count, and the counts of the wave's first 64 static segments (wave w owns segments w, w + nw, ...; one count
+  // per lane): unconditional loads of words that always exist (a lane without a segment, and every lane of a run-routed
+  // tile, reads the tile's first count: `counts` holds tiles x segs words with segs >= 1), what must not count is selected
+  // away below. These are four-byte COUNT words, one request per wave; no lane asks for a RECORD it does not add. Under their conditions they were three memory round trips in a row in front
+  // of every tile — and a compute unit runs its four tiles of the main table one after the other (MI355X, the main table's
+  // pass eager: 85.3 -> 84.2 us, profiles/scatter_dense_stream_ab.txt).
+  const int lane = threadIdx.x & 63;
+  const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const uint32_t nw = blockDim.x >> 6;
+  const uint32_t* cnts = buf.counts + (size_t)tile * G.segs;
+  const uint32_t mine = !coarse && G.segs > wave ? (G.segs - wave + nw - 1u) / nw : 0u;  // static segments of this wave
+  const uint32_t cv_first = cnts[(uint32_t)lane < mine ? wave + (uint32_t)lane * nw : 0u];
+  const uint32_t max_bits = buf.hdr[level], cursor = buf.dyn_cursor[tile], spilled = buf.hdr[kHdrSpillCount];
   // headroom of the fixed-point sums: <= 2 summands per record (a pair whose corners coincide) over the queue and the
   // folded spill records; one more bit for the sign
   const int headroom = 2 + (32 - __clz((int)(Q + kSpillFold - 1u)));
-  const FixedScale fs = fixed_scale(buf.hdr[level], headroom);
+  const FixedScale fs = fixed_scale(max_bits, headroom);
   if (fs.empty && !overwrite) {
     // an accumulating call and nothing (or only flushed denormals) recorded on this level: the tile stays as it is
     if (threadIdx.x == 0) buf.dyn_cursor[tile] = 0u;
     return;
   }
   const uint32_t static_end = coarse ? 0u : G.segs * C;
-  const uint32_t n_dyn = min(buf.dyn_cursor[tile], Q - static_end);
-  const uint32_t n_spill = min(min(buf.hdr[kHdrSpillCount], G.spill_cap), kSpillFold);
+  const uint32_t n_dyn = min(cursor, Q - static_end);
+  const uint32_t n_spill = min(min(spilled, G.spill_cap), kSpillFold);
   if (!overwrite && n_spill == 0u) {
     // Accumulating call: a tile nothing was routed into (the proposal levels while few rays carry gradient,
     // profiles/r03_proposal_sparsity.txt) keeps its gradient as it is — no LDS fill, no conversion, no read-modify-write.
     // Static segments: one count per pass-1 workgroup, read once here (the accumulation below reads them again from L2).
     bool any = n_dyn != 0u;
     if (!coarse && !any) {
-      const uint32_t* cnts = buf.counts + (size_t)tile * G.segs;
       for (uint32_t sgi = threadIdx.x; sgi < G.segs; sgi += blockDim.x) any = any || cnts[sgi] != 0u;
     }
     if (!__syncthreads_or(any)) {
@@ -511,14 +531,6 @@ __device__ __forceinline__ void scatter_apply_body(const nsamd_grid& grid, const
       return;
     }
   }
-  {
-    uint4* z = reinterpret_cast<uint4*>(acc);
-    for (int e = threadIdx.x; e < entries; e += blockDim.x) z[e] = make_uint4(0u, 0u, 0u, 0u);
-  }
-  __syncthreads();
-  PROBE_STAMP(0, 11);
-  // self-cleaning cursor: the next call finds zeros again (the workspace state is zero-initialised once by its owner)
-  if (threadIdx.x == 0) buf.dyn_cursor[tile] = 0u;
   const uint4* q = buf.queues + ((size_t)G.level_off[level] + (size_t)bin * Q);
   const int kk = fs.k;
   auto add_rec = [&](const uint4& r) {
@@ -537,68 +549,99 @@ __device__ __forceinline__ void scatter_apply_body(const nsamd_grid& grid, const
       atomicAdd(a + 1, to_fixed(f1, kk));
     }
   };
-  if (!fs.empty && !fs.bad) {
-    const int lane = threadIdx.x & 63;
-    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const uint32_t nw = blockDim.x >> 6;
+  // Static segments, 64 of the wave's at a time (a round). The records of a round's segments are taken as ONE DENSE STREAM:
+  // with the exclusive prefix sum of the counts (DPP scan, wave.h) lane l of batch b takes stream position 64 b + l, so
+  // every batch but the round's last runs all 64 lanes through the conversions and the LDS atomics. One wave step per
+  // segment — the form this replaces — ran the main table's ~48-record segments of the field backward's producers on
+  // three quarters of the lanes, issued a second, empty step per segment for records 64 .. 127, and left nearly every
+  // lane idle on a sparse call's few-record segments. Integer sums: which lane adds which record does not reach the result.
+  // (On its own, with the loads of a trip still settled together, this took the main table's pass from 96.4 to 95.6 us: a
+  // quarter of the conversions and LDS atomics gone and next to nothing gained — the pass waits for its records, not for
+  // its VALU or the LDS pipe. What the dense stream buys is the ring below.)
+  uint32_t c0 = 0u;              // the round's first segment (among the wave's)
+  uint32_t cv, pre, total = 0u;  // per lane: the segment's count and the stream position of its first record; the stream's length
+  unsigned long long rem = 0ull; // the round's non-empty segments that the stream has not passed yet
+  uint4 r[4];
+  // (stream position -> record) is a WAVE-UNIFORM WALK over the non-empty segments (their lanes in a ballot, scalar bit
+  // scans — an accumulating call on few points leaves most of a tile's segments empty): per segment that overlaps the
+  // batch two v_readlane and four VALU (subtract, compare, add, select), against ~60 VALU and four LDS atomics per
+  // record batch. A segment that runs past the batch's end stays at the head of the walk for the next batch.
+  auto locate = [&](uint32_t first) {  // the queue index of the record at stream position first + lane (calls in stream order)
+    const uint32_t p = first + (uint32_t)lane;
+    uint32_t idx = 0u;
+    while (rem != 0ull) {
+      const int j = __builtin_ctzll(rem);
+      const uint32_t s = (uint32_t)__builtin_amdgcn_readlane((int)pre, j);
+      if (s >= first + 64u) break;
+      const uint32_t n = (uint32_t)__builtin_amdgcn_readlane((int)cv, j);
+      const uint32_t seg0 = (wave + (c0 + (uint32_t)j) * nw) * C;  // (fits 32 bits: inside the tile's queue, Q < 2^30)
+      idx = p - s < n ? seg0 - s + p : idx;
+      if (s + n > first + 64u) break;
+      rem &= rem - 1ull;
+    }
+    return idx;
+  };
+  // FULL batches need no lane predicate, so their loads are plain straight-line code: a ring of four batches per wave,
+  // each slot reloaded as soon as its record has gone through the LDS atomics — the wave waits for the OLDEST of four
+  // loads in flight (s_waitcnt vmcnt(3)), not for all of them. (Per-segment steps had a lane predicate on every load:
+  // each sat in a branch of its own, and a trip of loads was settled with vmcnt(0) before the first add. The
+  // unconditional form of THAT schedule — idle lanes re-reading a record — measured 2-3 us slower:
+  // profiles/r04_negative_results.txt; here no lane asks for anything it does not add.) MI355X, main table, eager:
+  // 96.4 -> 85.3 us per launch, three alternating repeats each way (profiles/scatter_dense_stream_ab.txt).
+  auto open_stream = [&](uint32_t counts) {  // all 64 lanes; asks for the ring's first four batches
+    cv = counts;
+    const uint32_t incl = wave_scan_inclusive_u32(cv);
+    pre = incl - cv;
+    total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+    rem = __ballot(cv != 0u);
+    if ((total >> 8) != 0u) {
+#pragma unroll
+      for (int u = 0; u < 4; ++u) r[u] = rec_load(q + locate(64u * u));
+    }
+  };
+  auto run_stream = [&]() {
+    const uint32_t groups = total >> 8;  // groups of 4 full batches
+    for (uint32_t g = 1; g < groups; ++g) {
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        add_rec(r[u]);
+        r[u] = rec_load(q + locate(256u * g + 64u * u));
+      }
+    }
+    // the stream's last, partial group (up to 3 full batches and one partly filled): predicated loads, requested
+    // before the ring's last four batches are added
+    uint4 rt[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const uint32_t first = 256u * groups + 64u * u;
+      const uint32_t idx = locate(first);
+      rt[u] = first + (uint32_t)lane < total ? rec_load(q + idx) : make_uint4(0u, 0u, 0u, 0u);
+    }
+    if (groups != 0u) {
+#pragma unroll
+      for (int u = 0; u < 4; ++u) add_rec(r[u]);
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+      if (256u * groups + 64u * u + (uint32_t)lane < total) add_rec(rt[u]);
+  };
+  const bool sums = !fs.empty && !fs.bad;
+  // the first round's first records are on their way while the tile is cleared
+  if (sums && !coarse) open_stream((uint32_t)lane < mine ? cv_first : 0u);
+  {
+    uint4* z = reinterpret_cast<uint4*>(acc);
+    for (int e = threadIdx.x; e < entries; e += blockDim.x) z[e] = make_uint4(0u, 0u, 0u, 0u);
+  }
+  __syncthreads();
+  PROBE_STAMP(0, 11);
+  // self-cleaning cursor: the next call finds zeros again (the workspace state is zero-initialised once by its owner)
+  if (threadIdx.x == 0) buf.dyn_cursor[tile] = 0u;
+  if (sums) {
     if (!coarse) {
-      // static segments: wave w owns segments w, w + nw, ...; their counts are fetched up front (one load per lane),
-      // so a trip of 4 segments has a single memory latency in front of its records, not two
-      const uint32_t* cnts = buf.counts + (size_t)tile * G.segs;
-      const uint32_t mine = G.segs > wave ? (G.segs - wave + nw - 1u) / nw : 0u;
-      for (uint32_t c0 = 0; c0 < mine; c0 += 64u) {
-        const uint32_t cv = (c0 + (uint32_t)lane < mine) ? cnts[wave + (c0 + (uint32_t)lane) * nw] : 0u;
-        // Only the NON-EMPTY segments are visited (their lanes in a ballot; wave-uniform, scalar bit scans): an accumulating
-        // call on few points (the proposal levels while few rays carry gradient) leaves most of a tile's 384 segments
-        // empty, and walking them cost ~2.2 k clocks of pure instruction issue per trip of four
-        // (scripts/probe_gated_scatter_clocks.py: 27 k clocks per tile with next to nothing to add).
-        unsigned long long rem = __ballot(cv != 0u);
-        // trips of 4 segments, software-pipelined in the source: the records of the next trip are requested before this one goes
-        // through the LDS atomics. (The ISA does not keep them in flight — lane-predicated loads sit in branches, and the
-        // compiler settles each trip with s_waitcnt vmcnt(0) —, but the unconditional form that does (clamped lanes re-reading
-        // the segment's first record) measured 2-3 us SLOWER, as did the tile as two feature planes instead of (f0, f1) pairs:
-        // with 16 waves per CU the latency is covered by the other waves, and what bounds the pass is the LDS atomic pipe plus
-        // the VALU of the fixed-point conversions. profiles/r04_negative_results.txt.)
-        uint32_t n[4], n_next[4], sg[4], sg_next[4];
-        uint4 r[4][2], r_next[4][2];
-        auto fetch = [&](uint32_t (&nn)[4], uint32_t (&ss)[4], uint4 (&rr)[4][2]) {
-#pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            nn[u] = 0u;
-            ss[u] = 0u;
-            if (rem != 0ull) {
-              const int j = __builtin_ctzll(rem);
-              rem &= rem - 1ull;
-              nn[u] = (uint32_t)__builtin_amdgcn_readlane((int)cv, j);
-              ss[u] = wave + (c0 + (uint32_t)j) * nw;
-            }
-            const uint4* seg = q + (size_t)ss[u] * C;
-#pragma unroll
-            for (int v = 0; v < 2; ++v) {
-              const uint32_t e = (uint32_t)lane + 64u * v;
-              rr[u][v] = e < nn[u] ? rec_load(seg + e) : make_uint4(0u, 0u, 0u, 0u);
-            }
-          }
-        };
-        fetch(n, sg, r);
-        while (n[0] != 0u) {  // (segments are taken in order: an empty first slot means none is left)
-          fetch(n_next, sg_next, r_next);
-#pragma unroll
-          for (int u = 0; u < 4; ++u) {
-#pragma unroll
-            for (int v = 0; v < 2; ++v)
-              if ((uint32_t)lane + 64u * v < n[u]) add_rec(r[u][v]);
-            const uint4* seg = q + (size_t)sg[u] * C;
-            for (uint32_t e = (uint32_t)lane + 128u; e < n[u]; e += 64u) add_rec(rec_load(seg + e));
-          }
-#pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            n[u] = n_next[u];
-            sg[u] = sg_next[u];
-            r[u][0] = r_next[u][0];
-            r[u][1] = r_next[u][1];
-          }
-        }
+      run_stream();
+      for (c0 = 64u; c0 < mine; c0 += 64u) {
+        open_stream(c0 + (uint32_t)lane < mine ? cnts[wave + (c0 + (uint32_t)lane) * nw] : 0u);
+        run_stream();
       }
     }
     PROBE_STAMP(0, 12);

@@ -51,6 +51,32 @@ __device__ __forceinline__ double wave_read_f64(double v) {
   return __longlong_as_double((long long)(((unsigned long long)hi << 32) | (unsigned long long)lo));
 }
 
+// inclusive prefix sum of a 32-bit count over the 64 lanes: the same six DPP steps as the double scan. All lanes active.
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ uint32_t dpp_move_u32(uint32_t v) {  // lanes without a source read 0
+  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROW_MASK, 0xf, true);
+}
+__device__ __forceinline__ uint32_t wave_scan_inclusive_u32(uint32_t v) {
+  v += dpp_move_u32<0x111, 0xf>(v);  // row_shr:1
+  v += dpp_move_u32<0x112, 0xf>(v);  // row_shr:2
+  v += dpp_move_u32<0x114, 0xf>(v);  // row_shr:4
+  v += dpp_move_u32<0x118, 0xf>(v);  // row_shr:8
+  v += dpp_move_u32<0x142, 0xa>(v);  // row_bcast:15 into rows 1 and 3
+  v += dpp_move_u32<0x143, 0xc>(v);  // row_bcast:31 into rows 2 and 3
+  return v;
+}
+
+// Maximum over the 16 lanes of a DPP row, valid in EVERY lane of the row (quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_ror:4,
+// row_ror:8: after the two quad steps a lane holds its quad's maximum, the two rotations bring in the other three quads').
+// All 16 lanes of the row active.
+__device__ __forceinline__ uint32_t row16_max_u32(uint32_t v) {
+  v = max(v, dpp_move_u32<0xB1, 0xf>(v));
+  v = max(v, dpp_move_u32<0x4E, 0xf>(v));
+  v = max(v, dpp_move_u32<0x124, 0xf>(v));  // row_ror:4
+  v = max(v, dpp_move_u32<0x128, 0xf>(v));  // row_ror:8
+  return v;
+}
+
 // Value of the neighbouring lane of the pair (2i, 2i + 1): DPP quad_perm [1, 0, 3, 2] — VALU rate, no LDS. All four lanes of
 // the quad must be active.
 __device__ __forceinline__ uint32_t pair_swap_u32(uint32_t v) {
