@@ -186,6 +186,19 @@ int nsamd_nerf_encode_bwd_rays(nsamd_points pts, int64_t M, const float* freqs, 
                                const float* d_out, int64_t d_out_stride, float* d_origins, float* d_directions, int accumulate,
                                nsamd_stream_t stream);
 
+/* NeRFEncoding.forward WITH covariances — mip-NeRF's integrated positional encoding (encodings.py:162-186, utils/math.py:124-134):
+ * out [M, 6 F (+3)] = [exp(-var freq^2 / 2) sin(s), exp(...) sin(s + pi/2), mean], s[d F + f] = (2 pi mean_d) freqs[f], var the
+ * DIAGONAL of the covariance (not multiplied by (2 pi)^2, as the reference has it); an entry whose damping factor is exactly 0 is 0.
+ *   ray mode      (pts.positions == NULL): the Gaussian of the conical frustum [t_s, t_{s+1}] of every sample
+ *                 (Frustums.get_gaussian_blob, cameras/rays.py:73-90 -> utils/math.py:95-121 and :42-67) is formed in the kernel
+ *                 from origins / directions [num_rays,3], t_bins [num_rays,S+1] and pixel_area [num_rays]; `variances` is not read.
+ *   explicit mode (pts.positions = the means [M,3]): variances [M,3] = the covariance diagonals; `pixel_area` is not read.
+ * Checks, in this order: M < 0 or a ray description that is incomplete or does not divide M -> INVALID_ARG; num_frequencies
+ * outside 1 .. 64 -> UNSUPPORTED; M == 0 -> OK, nothing launched; freqs, out or the mode's own array NULL -> INVALID_ARG.
+ * No gradient (the encoding has no parameters). */
+int nsamd_ipe_encode(nsamd_points pts, int64_t M, const float* pixel_area, const float* variances, const float* freqs,
+                     int32_t num_frequencies, int32_t include_input, float* out, nsamd_stream_t stream);
+
 /* SceneContraction(order=inf) forward on [M,3] (spatial_distortions.py:66-69). */
 int nsamd_contract_linf(const float* x, int64_t M, float* out, nsamd_stream_t stream);
 

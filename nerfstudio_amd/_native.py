@@ -86,6 +86,7 @@ _SIGNATURES = {
     "nsamd_sh4_encode": [vp, i64, vp, vp],
     "nsamd_nerf_encode": [Points, i64, vp, i32, i32, vp, vp],
     "nsamd_nerf_encode_bwd_rays": [Points, i64, vp, i32, i32, vp, i64, vp, vp, C.c_int, vp],
+    "nsamd_ipe_encode": [Points, i64, vp, vp, vp, i32, i32, vp, vp],
     "nsamd_contract_linf": [vp, i64, vp, vp],
     "nsamd_density_mlp_fwd": [vp, vp, i64, DensityMlp, vp, vp, vp],
     "nsamd_density_field_fwd": [Points, i64, C.c_int, Aabb, vp, Grid, DensityMlp, vp, vp, vp, vp, vp],

@@ -70,9 +70,10 @@ class Frustums(TensorDataclass):
 
     def get_gaussian_blob(self) -> Gaussians:
         """mip-NeRF's Gaussian approximation of the conical frustum (cameras/rays.py:66-81 -> utils/math.py:95-121: eq. 7 of
-        arXiv:2103.13415 in its stable form, c = interval centre, h = half width): for integrated encodings, which are not
-        on the nerfacto path — a few elementwise torch ops, part of the Frustums interface for completeness. The cone's radius
-        at distance 1 is the one whose disc has the pixel's area."""
+        arXiv:2103.13415 in its stable form, c = interval centre, h = half width), for integrated encodings. A few
+        elementwise torch ops: the path of frustums that come without a RayPack. For the samples of this package's samplers
+        NeRFField hands rays and bin edges to csrc/ipe.hip instead, which forms the same Gaussians (their covariance diagonals)
+        in the kernel. The cone's radius at distance 1 is the one whose disc has the pixel's area."""
         if self.offsets is not None:
             raise NotImplementedError()
         radius = torch.sqrt(self.pixel_area) / 1.7724538509055159  # sqrt(area / pi)

@@ -37,7 +37,9 @@ class Identity(Encoding):
 
 class NeRFEncoding(Encoding):
     """Frequency encoding of vanilla NeRF (encodings.py:90-189): `[sin(2 pi x 2^k), sin(... + pi/2), x]`, one kernel
-    (csrc/hashgrid.hip nerf_encode_kernel). Integrated (mip-NeRF, `covs`) encodings are not built."""
+    (csrc/hashgrid.hip nerf_encode_kernel). With covariances it is mip-NeRF's integrated encoding, every entry damped by
+    `exp(-cov_dd freq^2 / 2)` (:170-174), also one kernel (csrc/ipe.hip), which forms the Gaussians of the samples' conical
+    frustums itself when they come as rays and bin edges (`ray_forward`)."""
 
     def __init__(self, in_dim: int, num_frequencies: int, min_freq_exp: float, max_freq_exp: float,
                  include_input: bool = False, implementation: Literal["hip"] = "hip") -> None:
@@ -60,18 +62,30 @@ class NeRFEncoding(Encoding):
         """Encoding of the points of a PointSpec (rays + bin edges: the sample midpoints are formed in the kernel)."""
         return F.nerf_encode(spec, self.num_frequencies, self.min_freq, self.max_freq, self.include_input)
 
+    def ray_forward(self, spec: "F.PointSpec", pixel_area: Tensor) -> Tensor:
+        """Integrated encoding of the conical frustums of a PointSpec's samples (rays + bin edges, one pixel area per ray): the
+        Gaussians of Frustums.get_gaussian_blob are formed in the kernel."""
+        return F.ipe_encode(spec, pixel_area, None, self.num_frequencies, self.min_freq, self.max_freq, self.include_input)
+
     def forward(self, in_tensor: Tensor, covs: Optional[Tensor] = None) -> Tensor:
-        if covs is not None:
-            raise NotImplementedError("integrated (mip-NeRF) encodings are not built for the hip backend")
         shape = in_tensor.shape[:-1]
-        if in_tensor.requires_grad and torch.is_grad_enabled():
-            # the kernel has no backward; points that carry gradient (pose corrections of a camera optimiser behind the
-            # predicted-normals head) take the same arithmetic through torch (encodings.py:148-166)
+        carries_grad = in_tensor.requires_grad or (covs is not None and covs.requires_grad)
+        if carries_grad and torch.is_grad_enabled():
+            # the kernels have no backward; points that carry gradient (pose corrections of a camera optimiser behind the
+            # predicted-normals head) take the same arithmetic through torch (encodings.py:148-175)
             freqs = (2 ** torch.linspace(self.min_freq, self.max_freq, self.num_frequencies)).to(in_tensor.device)
             scaled = ((2 * torch.pi * in_tensor)[..., None] * freqs).reshape(*shape, -1)
             out = torch.sin(torch.cat([scaled, scaled + torch.pi / 2.0], dim=-1))
+            if covs is not None:
+                var = (torch.diagonal(covs, dim1=-2, dim2=-1)[..., :, None] * freqs[None, :] ** 2).reshape(*shape, -1)
+                out = torch.exp(-0.5 * torch.cat(2 * [var], dim=-1)) * out
             return torch.cat([out, in_tensor], dim=-1) if self.include_input else out
-        out = self.spec_forward(F.PointSpec(positions=in_tensor.detach().reshape(-1, 3)))
+        if covs is not None:
+            variances = torch.diagonal(covs.detach(), dim1=-2, dim2=-1).reshape(-1, 3)
+            out = F.ipe_encode(F.PointSpec(positions=in_tensor.detach().reshape(-1, 3)), None, variances, self.num_frequencies,
+                               self.min_freq, self.max_freq, self.include_input)
+        else:
+            out = self.spec_forward(F.PointSpec(positions=in_tensor.detach().reshape(-1, 3)))
         return out.view(*shape, self.get_out_dim())
 
 

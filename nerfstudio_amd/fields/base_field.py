@@ -10,14 +10,23 @@ from ..cameras.rays import Frustums, RaySamples, pack_of
 from ..field_components.field_heads import FieldHeadNames
 
 
+def ray_spec(ray_samples: RaySamples) -> Optional[F.PointSpec]:
+    """The rays and bin edges behind `ray_samples` when a nerfstudio_amd sampler produced them and nothing moved them since
+    (a per-ray pack, no offsets); None for the reference's own RaySamples and after any batch operation."""
+    pk = pack_of(ray_samples)
+    if pk is not None and ray_samples.frustums.offsets is None and pk.origins.dim() == 2:
+        return F.PointSpec(origins=pk.origins, directions=pk.directions, t_bins=pk.t_bins)
+    return None
+
+
 def point_spec(ray_samples: RaySamples) -> Tuple[F.PointSpec, Tuple[int, ...]]:
     """How the kernels should obtain the sample points of `ray_samples`: straight from the per-ray pack when a
     nerfstudio_amd sampler produced it (positions never touch HBM), otherwise from materialised frustum centres."""
     shape = tuple(ray_samples.frustums.shape)
-    pk = pack_of(ray_samples)  # None for the reference's own RaySamples: positions are materialised then
-    if pk is not None and ray_samples.frustums.offsets is None and pk.origins.dim() == 2:
-        return F.PointSpec(origins=pk.origins, directions=pk.directions, t_bins=pk.t_bins), shape
-    return F.PointSpec(positions=ray_samples.frustums.get_positions().reshape(-1, 3)), shape
+    spec = ray_spec(ray_samples)
+    if spec is None:
+        spec = F.PointSpec(positions=ray_samples.frustums.get_positions().reshape(-1, 3))
+    return spec, shape
 
 
 class Field(nn.Module):

@@ -1,7 +1,8 @@
 """Classic NeRF field (reference: nerfstudio/fields/vanilla_nerf_field.py:30-125): frequency encoding -> 8 x 256 MLP with a
 skip connection -> softplus density head; [encoded direction, features] -> 2 x 128 MLP -> sigmoid RGB head. Every dense layer
 is a csrc/linear.hip launch (fp32 MFMA, 128 x 128 blocks of W, activation fused), the encodings one kernel each; the sample
-midpoints are formed inside the encoding kernel when the samples come from this package's samplers."""
+midpoints — with `use_integrated_encoding` (mip-NeRF) the Gaussians of the samples' conical frustums — are formed inside the
+encoding kernel when the samples come from this package's samplers."""
 from typing import Dict, Optional, Tuple, Type
 
 import torch
@@ -12,13 +13,13 @@ from ..field_components.encodings import Encoding, Identity, NeRFEncoding
 from ..field_components.field_heads import DensityFieldHead, FieldHead, FieldHeadNames, RGBFieldHead
 from ..field_components.mlp import MLP
 from ..field_components.spatial_distortions import SpatialDistortion
-from .base_field import Field, point_spec
+from .base_field import Field, point_spec, ray_spec
 
 
 class NeRFField(Field):
     """The reference's constructor contract (vanilla_nerf_field.py:45-58: argument names, defaults, sub-module names — what
-    the method config and a checkpoint's state dict address). Integrated encodings and temporal / spatial distortions of the
-    sample positions are not built (the vanilla-nerf method config uses neither)."""
+    the method config and a checkpoint's state dict address). `use_integrated_encoding` (mip-NeRF) wants a NeRFEncoding for the
+    positions. Spatial distortions of the sample positions are not built (neither method config uses one)."""
 
     def __init__(self, position_encoding: Encoding = Identity(in_dim=3), direction_encoding: Encoding = Identity(in_dim=3),
                  base_mlp_num_layers: int = 8, base_mlp_layer_width: int = 256, head_mlp_num_layers: int = 2,
@@ -26,12 +27,12 @@ class NeRFField(Field):
                  field_heads: Optional[Tuple[Type[FieldHead]]] = (RGBFieldHead,), use_integrated_encoding: bool = False,
                  spatial_distortion: Optional[SpatialDistortion] = None) -> None:
         super().__init__()
-        for refused, what in ((use_integrated_encoding, "integrated (mip-NeRF) encodings are"),
-                              (spatial_distortion is not None, "NeRFField(spatial_distortion=...) is")):
-            if refused:
-                raise NotImplementedError(f"{what} not built for the hip backend")
+        if spatial_distortion is not None:
+            raise NotImplementedError("NeRFField(spatial_distortion=...) is not built for the hip backend")
+        if use_integrated_encoding and not isinstance(position_encoding, NeRFEncoding):
+            raise NotImplementedError("integrated (mip-NeRF) encodings are built for NeRFEncoding only")
         self.position_encoding, self.direction_encoding = position_encoding, direction_encoding
-        self.use_integrated_encoding, self.spatial_distortion = False, None
+        self.use_integrated_encoding, self.spatial_distortion = use_integrated_encoding, None
         width_in, width_dir = position_encoding.get_out_dim(), direction_encoding.get_out_dim()
         # trunk: frequency-encoded position -> features (ReLU on the last layer too), density read off the features
         self.mlp_base = MLP(in_dim=width_in, num_layers=base_mlp_num_layers, layer_width=base_mlp_layer_width,
@@ -48,14 +49,27 @@ class NeRFField(Field):
             head.set_in_dim(self.mlp_head.get_out_dim())
 
     def get_density(self, ray_samples: RaySamples) -> Tuple[Tensor, Tensor]:
-        spec, shape = point_spec(ray_samples)
+        shape = tuple(ray_samples.frustums.shape)
         enc = self.position_encoding
-        if isinstance(enc, NeRFEncoding):
-            x = enc.spec_forward(spec)  # midpoints o + d (s + e) / 2 formed in the kernel
+        if self.use_integrated_encoding:
+            x = self._integrated_encoding(ray_samples)
+        elif isinstance(enc, NeRFEncoding):
+            x = enc.spec_forward(point_spec(ray_samples)[0])  # midpoints o + d (s + e) / 2 formed in the kernel
         else:
             x = enc(ray_samples.frustums.get_positions().reshape(-1, 3))
         features = self.mlp_base(x)
         return self.field_output_density(features).view(*shape, 1), features.view(*shape, -1)
+
+    def _integrated_encoding(self, ray_samples: RaySamples) -> Tensor:
+        """vanilla_nerf_field.py:85-89. Samples of this package's samplers: rays, bin edges and the per-ray pixel area (the
+        frustums' is a broadcast view of the bundle's: its first sample's) go to the kernel, which forms the Gaussians.
+        Anything else: get_gaussian_blob (which raises for frustums with offsets) and its covariance diagonals."""
+        frustums = ray_samples.frustums
+        spec = ray_spec(ray_samples)
+        if spec is not None:
+            return self.position_encoding.ray_forward(spec, frustums.pixel_area[..., 0, 0])
+        blob = frustums.get_gaussian_blob()
+        return self.position_encoding(blob.mean.reshape(-1, 3), covs=blob.cov.reshape(-1, 3, 3))
 
     def get_outputs(self, ray_samples: RaySamples, density_embedding: Optional[Tensor] = None) -> Dict[FieldHeadNames, Tensor]:
         if len(self.field_heads) == 0:

@@ -499,13 +499,56 @@ def nerf_encode(spec: PointSpec, num_frequencies: int, min_freq_exp: float, max_
     if any(t is not None and t.requires_grad for t in spec.tensors()):
         raise RuntimeError("nsamd NeRFEncoding has no backward: the encoded points must not require grad")
     dev = next(t for t in spec.tensors() if t is not None).device
-    key = (num_frequencies, float(min_freq_exp), float(max_freq_exp), dev)
-    if key not in _FREQS:
-        _FREQS[key] = (2 ** torch.linspace(min_freq_exp, max_freq_exp, num_frequencies)).to(dev)
+    freqs = _frequencies(num_frequencies, min_freq_exp, max_freq_exp, dev)
     spec = _spec_from_flat(*spec.tensors())
     M = spec.num_points
     out = torch.empty((M, 6 * num_frequencies + (3 if include_input else 0)), device=dev, dtype=torch.float32)
-    nerf_encode_launch(spec.native(), M, _FREQS[key], include_input, out)
+    nerf_encode_launch(spec.native(), M, freqs, include_input, out)
+    return out
+
+
+def _frequencies(num_frequencies: int, min_freq_exp: float, max_freq_exp: float, dev) -> Tensor:
+    """The device copy of `2 ** linspace(min, max, F)`, evaluated with torch on the host once per configuration."""
+    key = (num_frequencies, float(min_freq_exp), float(max_freq_exp), dev)
+    if key not in _FREQS:
+        _FREQS[key] = (2 ** torch.linspace(min_freq_exp, max_freq_exp, num_frequencies)).to(dev)
+    return _FREQS[key]
+
+
+def ipe_encode_launch(pts: N.Points, M: int, pixel_area: Optional[Tensor], variances: Optional[Tensor], freqs: Tensor,
+                      include_input: bool, out: Tensor) -> None:
+    """nsamd_ipe_encode on the current stream: the integrated encoding of M Gaussians -> dense rows `[M, 6 F (+3)]` of `out`.
+    Ray mode (`pts` holds rays and bin edges): `pixel_area [num_rays]`, the Gaussians are formed in the kernel; explicit mode
+    (`pts.positions` = the means): `variances [M,3]`, the covariance diagonals."""
+    N.check(N.load().nsamd_ipe_encode(pts, M, N.ptr(pixel_area), N.ptr(variances), N.ptr(freqs), freqs.shape[0],
+                                      int(bool(include_input)), N.ptr(out), N.stream()), "ipe_encode")
+
+
+def ipe_encode(spec: PointSpec, pixel_area: Optional[Tensor], variances: Optional[Tensor], num_frequencies: int,
+               min_freq_exp: float, max_freq_exp: float, include_input: bool = False) -> Tensor:
+    """NeRFEncoding.forward with covariances (encodings.py:162-186) -> `[M, 6 F (+3)]`: on the conical frustums of the samples
+    of `spec`'s rays (`pixel_area`, one value per ray) or on explicit means `spec.positions` with the covariance diagonals
+    `variances [M,3]`. No gradient (mip-NeRF has none to take: no camera optimiser, no learned warp)."""
+    given = (*spec.tensors(), pixel_area, variances)
+    N.require_cuda(*given)
+    if any(t is not None and t.requires_grad for t in given):
+        raise RuntimeError("nsamd integrated NeRFEncoding has no backward: the encoded Gaussians must not require grad")
+    if (pixel_area if spec.ray_mode else variances) is None:
+        raise ValueError("ipe_encode takes pixel_area with rays and variances with explicit means")
+    dev = next(t for t in spec.tensors() if t is not None).device
+    freqs = _frequencies(num_frequencies, min_freq_exp, max_freq_exp, dev)
+    spec = _spec_from_flat(*spec.tensors())
+    M = spec.num_points
+    if spec.ray_mode:
+        pixel_area, variances = _f32c(pixel_area.reshape(-1)), None
+        if pixel_area.shape[0] != spec.t_bins.shape[0]:
+            raise ValueError("ipe_encode: one pixel area per ray")
+    else:
+        pixel_area, variances = None, _f32c(variances.reshape(-1, 3))
+        if variances.shape[0] != M:
+            raise ValueError("ipe_encode: one covariance diagonal per mean")
+    out = torch.empty((M, 6 * num_frequencies + (3 if include_input else 0)), device=dev, dtype=torch.float32)
+    ipe_encode_launch(spec.native(), M, pixel_area, variances, freqs, include_input, out)
     return out
 
 

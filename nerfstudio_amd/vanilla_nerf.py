@@ -5,7 +5,7 @@ median depth, MSE of both renders. Temporal distortion (D-NeRF) and gradient sca
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import Dict, List, Literal
+from typing import Dict, List, Literal, Tuple
 
 import torch
 from torch import Tensor, nn
@@ -62,17 +62,27 @@ class NeRFModel(nn.Module):
     def get_param_groups(self) -> Dict[str, List[Parameter]]:
         return {"fields": list(self.field_coarse.parameters()) + list(self.field_fine.parameters())}
 
+    def fields(self) -> Tuple[NeRFField, NeRFField]:
+        """The field of the uniform pass and the field of the resampled pass."""
+        return self.field_coarse, self.field_fine
+
+    def loss_scales(self) -> Tuple[float, float]:
+        """What the coarse and the fine MSE are multiplied by (models/vanilla_nerf.py:214-215: the two multipliers)."""
+        return self.config.rgb_loss_coarse_mult, self.config.rgb_loss_fine_mult
+
     def get_outputs(self, ray_bundle: RayBundle, jitters=None) -> Dict[str, Tensor]:
-        """`jitters` (optional): the two samplers' draws, `[N, 65]` and `[N, 129]` — injected by the parity tests."""
+        """`jitters` (optional): the two samplers' draws, one per bin edge (`[N, 65]` and `[N, 129]` at the default counts) —
+        injected by the parity tests."""
         j0, j1 = jitters if jitters is not None else (None, None)
+        field_coarse, field_fine = self.fields()
         ray_samples_uniform = self.sampler_uniform(ray_bundle, jitter=j0)
-        field_outputs_coarse = self.field_coarse.forward(ray_samples_uniform)
+        field_outputs_coarse = field_coarse.forward(ray_samples_uniform)
         weights_coarse = ray_samples_uniform.get_weights(field_outputs_coarse[FieldHeadNames.DENSITY])
         rgb_coarse = self.renderer_rgb(rgb=field_outputs_coarse[FieldHeadNames.RGB], weights=weights_coarse)
         accumulation_coarse = self.renderer_accumulation(weights_coarse)
         depth_coarse = self.renderer_depth(weights_coarse, ray_samples_uniform)
         ray_samples_pdf = self.sampler_pdf(ray_bundle, ray_samples_uniform, weights_coarse, jitter=j1)
-        field_outputs_fine = self.field_fine.forward(ray_samples_pdf)
+        field_outputs_fine = field_fine.forward(ray_samples_pdf)
         weights_fine = ray_samples_pdf.get_weights(field_outputs_fine[FieldHeadNames.DENSITY])
         rgb_fine = self.renderer_rgb(rgb=field_outputs_fine[FieldHeadNames.RGB], weights=weights_fine)
         accumulation_fine = self.renderer_accumulation(weights_fine)
@@ -93,5 +103,6 @@ class NeRFModel(nn.Module):
             pred_image=outputs["rgb_coarse"], pred_accumulation=outputs["accumulation_coarse"], gt_image=image)
         fine_pred, fine_image = self.renderer_rgb.blend_background_for_loss_computation(
             pred_image=outputs["rgb_fine"], pred_accumulation=outputs["accumulation_fine"], gt_image=image)
-        return {"rgb_loss_coarse": self.config.rgb_loss_coarse_mult * self.rgb_loss(coarse_image, coarse_pred),
-                "rgb_loss_fine": self.config.rgb_loss_fine_mult * self.rgb_loss(fine_image, fine_pred)}
+        scale_coarse, scale_fine = self.loss_scales()
+        return {"rgb_loss_coarse": scale_coarse * self.rgb_loss(coarse_image, coarse_pred),
+                "rgb_loss_fine": scale_fine * self.rgb_loss(fine_image, fine_pred)}
