@@ -485,6 +485,15 @@ def test_field_mlp_backward_at_bench_size_vs_float64(F):
             bad.append(k)
     print(f"\nfield MLP backward at M = 196608 against float64 ({int(ambiguous.sum())} samples = {100 * frac:.2f} % with a "
           "ReLU pre-activation within 1e-5 of zero excluded):\n" + "\n".join(rows))
+    import field_reference as fr  # (how the fixed 1e-5 relates to the running bound tests/field_reference.py derives per unit)
+
+    names = dict(zip(fr.W_KEYS, fr.ORACLE_KEYS))
+    fw = fr.forward64({**{k: params[names[k]].numpy() for k in fr.W_KEYS}, "M": enc.shape[0], "dir_group": 1,
+                       "enc": enc.t().contiguous().numpy(), "selector": sel.numpy(), "directions": dirs.numpy(),
+                       "camera_indices": cams.numpy(), "appearance_const": None, "avg": cfg.average_init_density,
+                       "appearance": params["field.embedding_appearance.embedding.weight"].numpy()})
+    print(f"  largest derived rounding bound e(pre) of a hidden unit at this shape: {fw['unit_bound_max']:.2e}; "
+          f"{100 * float(fw['undecided'].mean()):.2f} % of the samples own a unit within 2 e(pre) of zero")
     assert not bad, f"{bad}\n" + "\n".join(rows)
 
 
