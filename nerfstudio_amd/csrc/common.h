@@ -192,7 +192,8 @@ NSAMD_HD void load_positions_burst(const nsamd_points& P, const int64_t (&p)[N],
 
 // ---- L-inf scene contraction (spatial_distortions.py:66-69) ---------------------------------------------------
 NSAMD_HD void contract_linf(float& x, float& y, float& z) {
-  const float mag = fmaxf(fabsf(x), fmaxf(fabsf(y), fabsf(z)));
+  float mag = fmaxf(fabsf(x), fmaxf(fabsf(y), fabsf(z)));
+  if (x != x || y != y || z != z) mag = x + y + z;  // the norm of a row with a NaN is NaN (fmaxf drops a NaN operand)
   if (!(mag < 1.0f)) {  // torch.where(mag < 1, x, ...): NaN takes the second branch
     const float a = 2.0f - (1.0f / mag);
     x = a * (x / mag);

@@ -6,6 +6,8 @@ import torch
 U = 2.0**-24
 D53 = 2.0**-53
 E_EXP = 4 * U      # expf: 2 ulp = relative 2 * 2^-23 (assumed; test_expf_budget)
+E_SIN = 4 * U      # sinf: 2 ulp, assumed as E_EXP is (no ULP table of the device math library ships with the toolchain to take it
+                   # from); test_gpu_encoders_float64.py measures it through nsamd_nerf_encode, arguments up to ~1.6e6
 SAFE = 1 + 2.0**-6
 TINY = 2.0**-140
 

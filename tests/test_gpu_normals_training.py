@@ -87,7 +87,7 @@ def test_normals_losses_no_rays_and_too_many_samples():
 
 
 # ---------------------------------------------------------------- (b) the encoding's ray gradient -----------------------------------
-@pytest.mark.parametrize("n,S", [(5, 1), (7, 48)])
+@pytest.mark.parametrize("n,S", [(5, 1), (7, 48), (3, 64), (3, 65), (2, 130)])  # S > 64: the lane-strided loop's later trips
 @pytest.mark.parametrize("include_input", [0, 1])
 @pytest.mark.parametrize("padded", [False, True])  # rows 12 (15 with the input) floats apart, or the 27 of the MLP's input rows
 def test_nerf_encode_bwd_rays_against_float64(n, S, include_input, padded):
