@@ -278,6 +278,17 @@ typedef struct nsamd_field_mlp {
    * table / the directions / the camera indices changed. */
   const float* ray_terms;
   const float* ray_inputs;
+  /* Saved tile (nullable, both NULL = the backward recomputes every layer). nsamd_field_mlp_fwd with rgb != NULL stores head
+   * layer 1's output after the ReLU per 16-sample tile, as its wavefront holds it (lane (j, g) = sample j, register (t, r) =
+   * feature 16 t + 4 g + r; 256 B per sample):
+   *   saved_hb [tiles][4][64][4],  tiles = ceil(M / 16)
+   * The caller zero-fills it once (a partial last tile's absent samples are never written). The backward entry points given
+   * it AND `saved_rgb` (the `rgb` [M,3] that forward wrote) read both instead of recomputing head layers 1 and 2 (80 of a
+   * tile's 144 matrix instructions) — the same bits, since the forward formed them with the same operations in the same
+   * order — provided they come from a forward of the same enc / directions / cameras / parameters (/ ray terms). The forward
+   * ignores `saved_rgb`. */
+  float* saved_hb;
+  const float* saved_rgb;
 } nsamd_field_mlp;
 
 /* ray_terms [num_rays,64] (and ray_inputs [num_rays,48], nullable) of the struct above for `num_rays` rays: directions
@@ -297,7 +308,7 @@ typedef struct nsamd_field_mlp_grads {          /* all accumulated; caller zero-
   float* appearance;                            /* [num_images,32] or NULL */
 } nsamd_field_mlp_grads;
 
-/* Backward recomputes the activations from enc (nothing but enc is kept from the forward).
+/* Backward recomputes the activations from enc (nothing but enc is kept from the forward, unless mlp.saved_* are set).
  * ddensity [M], drgb [M,3] -> denc feature-major [32,M] (overwritten) + parameter gradients.
  * workspace (nullable): >= 256 CUs * 12544 floats of device scratch for per-workgroup weight-gradient partials
  * (summed by a single-writer pass); without it the workgroups flush with global atomics. */

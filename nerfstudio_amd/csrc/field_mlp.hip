@@ -9,7 +9,8 @@
 // Chain layout: mfma_chain.h (one wavefront owns 16 points; lane (j, g) holds feature 16t + 4g + r; a layer's accumulators are
 // the next layer's B operands; weight fragments Wf[n][t][lane][r] staged in LDS).
 // That is the forward kernel (4 waves per workgroup, fragments staged once, workgroups persistent over tiles). The
-// backward kernel (further down) recomputes the forward per tile, runs the data-gradient GEMMs in the same chain
+// backward kernel (further down) recomputes the forward per tile (or, given the forward's saved tile — nsamd_field_mlp.saved_hb /
+// saved_rgb —, all of it but head layers 1 and 2), runs the data-gradient GEMMs in the same chain
 // layout with W^T operands, and needs points on the k axis for the weight-gradient GEMMs: each wave transposes its
 // (Dout, X) tiles through an LDS scratch (row stride 80 floats = 16 mod 32 banks: conflict-free b32 column reads).
 // Its first version gave every wave all 48 dW accumulator tiles (424 registers, one wave per SIMD, MFMA busy 33 %);
@@ -83,6 +84,7 @@ struct FieldActs {
   v4f ha[4];      // relu
   v4f hb[4];      // relu
   v4f rgbp[1];    // rgb pre-sigmoid (rows 0..2 of tile 0)
+  float sg[3];    // backward on the saved tile: the forward's rgb of the lane's point instead of rgbp
 };
 
 // head-input tile 0: the 4 SH components 4g + r of this lane's group, from the 16 of the view direction
@@ -249,6 +251,11 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 16 ? 1 : 2) void field_mlp_fwd
     field_forward_tile<RAYC>(wf, bias, directions, app_table, app_const, dir_group, M, app_dim, ti, lane, A, 3 + 4 * probe_it,
                              rgb == nullptr);
     PROBE_STAMP(WAVES, 4 + 4 * probe_it);
+    if (rgb != nullptr && mlp.saved_hb != nullptr && ti.live) {
+      // the backward's saved tile (nsamd_field_mlp.saved_hb), as the wave holds it: four coalesced 1-KB rows
+#pragma unroll
+      for (int t = 0; t < 4; ++t) *reinterpret_cast<v4f*>(mlp.saved_hb + ((tile * 4 + t) * 64 + lane) * 4) = A.hb[t];
+    }
     if (lane < 16 && ti.live) {  // g == 0 holds neurons 0..3 of tile 0
       density[ti.p] = mlp.average_init_density * expf(A.o16[0][0]) * ti.sel;
       if (rgb != nullptr) {
@@ -480,13 +487,28 @@ __device__ __forceinline__ void rows_gemm_bwd(const float* Wrows, const v4f* in,
   }
 }
 
+// Head layer 2's data gradient. Only outputs 0..2 of its 16 padded ones exist (rows 3..15 of the staged weight are zero, and so
+// is the gradient there), so the contraction is ONE k-step with output g on lane group g: 4 MFMAs where rows_gemm_bwd<4, 1>
+// issues 16, twelve of them on zeros. `in_k`: dL/d(pre-sigmoid) of output g of the lane's point (0 for g == 3). The three
+// products are added in the order 0, 1, 2 as before and an exact zero product changes nothing: the same bits.
+template <int MT, int LD>
+__device__ __forceinline__ void rows_gemm_bwd_rgb(const float* Wrows, float in_k, v4f* out, int j, int g) {
+  float a[MT];
+#pragma unroll
+  for (int m = 0; m < MT; ++m) a[m] = Wrows[g * LD + 16 * m + j];
+#pragma unroll
+  for (int m = 0; m < MT; ++m) out[m] = mfma16(a[m], in_k, out[m]);
+}
+
 struct NoBetween {
   template <int I>
   __device__ __forceinline__ void at() const {}
 };
 
-// `between.at<I>()` runs after GEMM I (0..4) of the chain: the producer mode of the backward slots its record stores there
-template <class Between = NoBetween, bool RAYC = false>
+// `between.at<I>()` runs after GEMM I (0..4) of the chain: the producer mode of the backward slots its record stores there.
+// SAVED: A.hb holds the forward kernel's tile (nsamd_field_mlp.saved_hb) on entry and A.sg its rgb — head layers 1 and 2 are not
+// recomputed (80 of the 144 MFMAs), A.rgbp is not formed.
+template <class Between = NoBetween, bool RAYC = false, bool SAVED = false>
 __device__ __forceinline__ void coop_forward_tile(const float* W, const float* bias, const float (&dir)[3],
                                                   const float* __restrict__ app_table,
                                                   const float* __restrict__ app_const, int app_dim,
@@ -495,6 +517,11 @@ __device__ __forceinline__ void coop_forward_tile(const float* W, const float* b
   const int j = lane & 15, g = lane >> 4;
   load_bias<4>(bias + kBiasBase0, A.h1, g);
   rows_gemm_fwd<4, 2, kLd32>(W + kRowBase0, A.enc, A.h1, j, g);
+  if (SAVED) {
+    // The saved tile is waited for HERE, behind the GEMM that covered its loads and ahead of the record stores: those are
+    // conditional, so a wait at the first use further down would be `s_waitcnt vmcnt(0)` — a drain of the stores (see fetch_tile).
+    asm volatile("" : "+v"(A.hb[0]), "+v"(A.hb[1]), "+v"(A.hb[2]), "+v"(A.hb[3]), "+v"(A.sg[0]), "+v"(A.sg[1]), "+v"(A.sg[2]));
+  }
   between.template at<0>();
   relu_tiles<4>(A.h1);
   load_bias<1>(bias + kBiasBase1, A.o16, g);
@@ -523,12 +550,16 @@ __device__ __forceinline__ void coop_forward_tile(const float* W, const float* b
   }
   between.template at<2>();
   relu_tiles<4>(A.ha);
-  load_bias<4>(bias + kBiasHead1, A.hb, g);
-  rows_gemm_fwd<4, 4, kLd64>(W + kRowHead1, A.ha, A.hb, j, g);
+  if (!SAVED) {
+    load_bias<4>(bias + kBiasHead1, A.hb, g);
+    rows_gemm_fwd<4, 4, kLd64>(W + kRowHead1, A.ha, A.hb, j, g);
+  }
   between.template at<3>();
-  relu_tiles<4>(A.hb);
-  load_bias<1>(bias + kBiasHead2, A.rgbp, g);
-  rows_gemm_fwd<1, 4, kLd64>(W + kRowHead2, A.hb, A.rgbp, j, g);
+  if (!SAVED) {
+    relu_tiles<4>(A.hb);
+    load_bias<1>(bias + kBiasHead2, A.rgbp, g);
+    rows_gemm_fwd<1, 4, kLd64>(W + kRowHead2, A.hb, A.rgbp, j, g);
+  }
   between.template at<4>();
 }
 
@@ -979,7 +1010,9 @@ struct RouteBetween {
 // workgroup iteration on the k axis, dW0[:, per-ray columns] += S^T X (X = the tiles' ray_inputs rows) is 24 f32 MFMAs per
 // iteration for the whole workgroup where the per-point form took 384, and the tiles' appearance-gradient rows are
 // W0[:, appearance]^T S (32 MFMAs) — written to `app_partials` exactly as the plain kernel writes its per-tile sums.
-template <bool ROUTE, bool RAYC = false>
+// SAVED: head layer 1's output and rgb come from the forward of the same step (nsamd_field_mlp.saved_hb / saved_rgb) instead of
+// being recomputed; everything downstream of the activations is the same code.
+template <bool ROUTE, bool RAYC = false, bool SAVED = false>
 __global__ __launch_bounds__(kCoopThreads) void field_mlp_bwd_kernel(
     const float* __restrict__ enc, const float* __restrict__ selector, const float* __restrict__ directions,
     const int64_t* __restrict__ cams, const float* __restrict__ app_const, int64_t dir_group, int64_t M,
@@ -1070,12 +1103,23 @@ __global__ __launch_bounds__(kCoopThreads) void field_mlp_bwd_kernel(
     const v4f app[2] = {app_dim > 0 ? nxt.app[0] : zero4, app_dim > 0 ? nxt.app[1] : zero4};
     const v4f cterm[4] = {nxt.cterm[0], nxt.cterm[1], nxt.cterm[2], nxt.cterm[3]};
     const float nxt_xin = nxt.xin;
+    if (SAVED) {
+      // The forward's tile, straight into the registers the recomputation would have filled: 4 coalesced dwordx4 rows per
+      // wave (+ the point's rgb), issued here so that they land behind base layer 0's GEMM. Not part of TileFetch: that would
+      // keep 19 more registers live across the previous tile. (An idle wave of the last round reads the last tile.)
+      const int64_t tc = tile < tiles ? tile : tiles - 1;
+      const float* hb = mlp.saved_hb + (tc * 256 + lane) * 4;
+#pragma unroll
+      for (int t = 0; t < 4; ++t) A.hb[t] = *reinterpret_cast<const v4f*>(hb + t * 256);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) A.sg[c] = mlp.saved_rgb[3 * ti.p + c];
+    }
     if (ROUTE) {
       // records 0..6 of the PREVIOUS tile leave between this tile's forward GEMMs, the other nine between the phases below
       const RouteBetween rb{RL, RL->stash[wave], lane, it > 0, route_gmax};
-      coop_forward_tile<RouteBetween, RAYC>(W, bias, dir, app_table, app_const, app_dim, ti, lane, A, app, rb, cterm);
+      coop_forward_tile<RouteBetween, RAYC, SAVED>(W, bias, dir, app_table, app_const, app_dim, ti, lane, A, app, rb, cterm);
     } else {
-      coop_forward_tile<NoBetween, RAYC>(W, bias, dir, app_table, app_const, app_dim, ti, lane, A, app, NoBetween{}, cterm);
+      coop_forward_tile<NoBetween, RAYC, SAVED>(W, bias, dir, app_table, app_const, app_dim, ti, lane, A, app, NoBetween{}, cterm);
     }
     PROBE_STAMP(kCoopWaves, 3 + 10 * (int)it);
     const bool emit = ROUTE && it > 0;  // the previous tile's records are still going out
@@ -1092,9 +1136,15 @@ __global__ __launch_bounds__(kCoopThreads) void field_mlp_bwd_kernel(
     if (g == 0 && ti.live) {
 #pragma unroll
       for (int c = 0; c < 3; ++c) {
-        const float sg = 1.0f / (1.0f + expf(-A.rgbp[0][c]));
+        const float sg = SAVED ? A.sg[c] : 1.0f / (1.0f + expf(-A.rgbp[0][c]));  // (the forward's rgb IS sg)
         g_rgbp[0][c] = up_rgb[c] * (sg * (1.0f - sg));
       }
+    }
+    // output g's gradient on lane group g (rows_gemm_bwd_rgb): lanes g == 0 hold the three
+    float g_rgb_k;
+    {
+      const float s0 = __shfl(g_rgbp[0][0], j), s1 = __shfl(g_rgbp[0][1], j), s2 = __shfl(g_rgbp[0][2], j);
+      g_rgb_k = g == 0 ? s0 : (g == 1 ? s1 : (g == 2 ? s2 : 0.0f));
     }
     __syncthreads();  // the previous iteration's last weight-gradient reads of the scratch are done
     // Every layer: the wave stores its (Dout, X) tiles, runs its own data-gradient GEMM (registers + weights only) while
@@ -1104,7 +1154,7 @@ __global__ __launch_bounds__(kCoopThreads) void field_mlp_bwd_kernel(
     store_rows<4>(Sx, A.hb, j, g);
     v4f g_hb[4];
     zero_tiles<4>(g_hb);
-    rows_gemm_bwd<4, 1, kLd64>(W + kRowHead2, g_rgbp, g_hb, j, g);
+    rows_gemm_bwd_rgb<4, kLd64>(W + kRowHead2, g_rgb_k, g_hb, j, g);
     relu_mask<4>(g_hb, A.hb);
     __syncthreads();
     coop_dw<1>(dW_h2, &db_h2, bias_owner14, scratch, 4 * own_half, 4, 0, own_q, j, g);
@@ -1492,7 +1542,9 @@ static int field_mlp_bwd_impl(const FieldBwdCall& c, hipStream_t stream) {
   const size_t lds_route = lds + sizeof(uint32_t) * kRouteLdsWords;
   static LdsOptIn opted_in;
   st = lds_opt_in(opted_in, field_mlp_bwd_kernel<false, false>, lds, field_mlp_bwd_kernel<true, false>, lds_route,
-                  field_mlp_bwd_kernel<false, true>, lds, field_mlp_bwd_kernel<true, true>, lds_route);
+                  field_mlp_bwd_kernel<false, true>, lds, field_mlp_bwd_kernel<true, true>, lds_route,
+                  field_mlp_bwd_kernel<false, false, true>, lds, field_mlp_bwd_kernel<true, false, true>, lds_route,
+                  field_mlp_bwd_kernel<false, true, true>, lds, field_mlp_bwd_kernel<true, true, true>, lds_route);
   if (st) return st;
   const unsigned blocks = field_bwd_blocks(M);
   float* const workspace = c.workspace;
@@ -1535,10 +1587,15 @@ static int field_mlp_bwd_impl(const FieldBwdCall& c, hipStream_t stream) {
                                                       app_dim, c.ddensity, c.drgb, c.denc, c.grads, partials, app_partials,
                                                       app_rows_per_point, R);
     };
-    if (c.route != nullptr)
-      rayc ? launch(&field_mlp_bwd_kernel<true, true>, lds_route) : launch(&field_mlp_bwd_kernel<true, false>, lds_route);
-    else
-      rayc ? launch(&field_mlp_bwd_kernel<false, true>, lds) : launch(&field_mlp_bwd_kernel<false, false>, lds);
+    // saved tile (nsamd_field_mlp.saved_hb / saved_rgb): both given, else the kernels that recompute every layer
+    const bool saved = c.mlp.saved_hb != nullptr && c.mlp.saved_rgb != nullptr;
+    if (c.route != nullptr) {
+      if (saved) rayc ? launch(&field_mlp_bwd_kernel<true, true, true>, lds_route) : launch(&field_mlp_bwd_kernel<true, false, true>, lds_route);
+      else rayc ? launch(&field_mlp_bwd_kernel<true, true>, lds_route) : launch(&field_mlp_bwd_kernel<true, false>, lds_route);
+    } else {
+      if (saved) rayc ? launch(&field_mlp_bwd_kernel<false, true, true>, lds) : launch(&field_mlp_bwd_kernel<false, false, true>, lds);
+      else rayc ? launch(&field_mlp_bwd_kernel<false, true>, lds) : launch(&field_mlp_bwd_kernel<false, false>, lds);
+    }
     NSAMD_CHECK_LAUNCH();
   }
   // weight-gradient partials -> gradients, and (extra blocks, one per camera) the appearance rows -> embedding gradient

@@ -130,6 +130,12 @@ class NerfactoTrainStep(TrainStepRunner):
         self.ray_terms = e(n, 64) if self.ray_terms_on else None
         self.ray_inputs = e(n, 16 + (32 if fld.embedding_appearance is not None else 0)) \
             if (self.ray_terms_on and not forward_only) else None  # (the backward's: weight gradient of the 48 per-ray columns)
+        # Saved tile (include/nsamd.h, nsamd_field_mlp.saved_hb): the forward leaves head layer 1's output, as its wavefronts hold
+        # it, for the backward of the same step, which reads it and `f_rgb` instead of recomputing head layers 1 and 2. Whole
+        # 16-sample tiles, zeroed once: a partial last tile's absent samples are never written. A static address, so a captured
+        # iteration stays valid. `_saved_fresh`: the tile is that of the last `forward_main`.
+        self.saved_hb = None if forward_only else torch.zeros(((mm + 15) // 16, 4, 64, 4), **f32)
+        self._saved_fresh = False
         self.f_denc = t(*self.f_enc.shape)
         self.p_ddens = [t(*x.shape) for x in self.p_dens]
         self.p_denc = [t(*x.shape) for x in self.p_enc]
@@ -673,6 +679,10 @@ class NerfactoTrainStep(TrainStepRunner):
                 self.ray_terms_launch(fm, app_const)
             fm.ray_terms = N.ptr(self.ray_terms)
             fm.ray_inputs = N.ptr(self.ray_inputs if app_const is None else None)
+        # (an eval-mode forward has no backward: no tile is stored, and that of an earlier forward no longer matches f_rgb)
+        self._saved_fresh = self.saved_hb is not None and app_const is None
+        if self._saved_fresh:
+            fm.saved_hb = N.ptr(self.saved_hb)
         fld = self.model.field
         tbl = fld.mlp_base.encoding
         F.field_forward(tbl.hash_table, tbl.spec, fld._transform, fld._box, self._points(L), self.m_main, self.f_enc, self.f_sel,
@@ -749,6 +759,8 @@ class NerfactoTrainStep(TrainStepRunner):
         params, emb = F.field_params(fld)
         # (the ray terms are what forward_main computed for this batch and these parameters)
         fm = F.field_mlp(params, emb, fld.average_init_density, self.ray_terms, self.ray_inputs)
+        if self._saved_fresh:  # (and head layer 1's output, with the rgb it wrote)
+            fm.saved_hb, fm.saved_rgb = N.ptr(self.saved_hb), N.ptr(self.f_rgb)
         cam = self.cam_opt is not None  # the camera optimiser's share needs the encoded-feature gradient as well
         tbl = fld.mlp_base.encoding
         F.field_backward(tbl.hash_table, tbl.spec, fld._transform, fld._box, self._points(L), self.m_main, self.f_enc, self.f_sel,

@@ -68,13 +68,17 @@ def step_algorithmic_bytes(rays, counts=(256, 96, 48), main_levels=16, prop_leve
 # row) per 16-sample tile. The ALGORITHMIC figure stays SURVEY §8(d)'s dense 11 392.
 FIELD_MACS_RAY_TERMS_FWD = 8320 + 64
 FIELD_MACS_RAY_TERMS_BWD = (8320 + 64) + 8320 + (8320 + (64 * 48 + 64 * 32) // 16)  # recompute + data gradient + weight gradient
+# Saved tile (include/nsamd.h, nsamd_field_mlp.saved_hb / saved_rgb): the backward reads head layer 1's output and rgb from the
+# forward of the same step, so its recomputation stops in front of head layers 1 and 2.
+FIELD_MACS_SAVED_TILE = 64 * 64 + 64 * 3
 
 
-def executed_per_launch(key, main_points, ray_terms=False):
+def executed_per_launch(key, main_points, ray_terms=False, saved_tile=False):
     if key in ("nsamd_field_mlp_bwd", "nsamd_field_mlp_bwd_scatter_phase[gradients+records]"):
+        saved = FIELD_MACS_SAVED_TILE if saved_tile else 0
         if ray_terms:
-            return main_points * 2 * FIELD_MACS_RAY_TERMS_BWD
-        return main_points * 2 * FIELD_MACS * 3  # + the forward recompute
+            return main_points * 2 * (FIELD_MACS_RAY_TERMS_BWD - saved)
+        return main_points * 2 * (FIELD_MACS * 3 - saved)  # + the forward recompute
     if key == "nsamd_field_mlp_fwd" and ray_terms:
         return main_points * 2 * FIELD_MACS_RAY_TERMS_FWD
     return None
@@ -82,8 +86,8 @@ def executed_per_launch(key, main_points, ray_terms=False):
 
 # entry point -> the kernel name rocprofv3 --kernel-trace --stats lists for it (profiles/*_kernel_stats.csv)
 ROCPROF_KERNEL = {
-    "nsamd_field_mlp_bwd": "nsamd::field_mlp_bwd_kernel<false, RAYC>",
-    "nsamd_field_mlp_bwd_scatter_phase[gradients+records]": "nsamd::field_mlp_bwd_kernel<true, true> (ray terms; <true, false> without)",
+    "nsamd_field_mlp_bwd": "nsamd::field_mlp_bwd_kernel<false, RAYC, SAVED>",
+    "nsamd_field_mlp_bwd_scatter_phase[gradients+records]": "nsamd::field_mlp_bwd_kernel<true, true, true> (ray terms, saved tile; false without)",
     "nsamd_field_mlp_bwd_scatter_phase[apply]": "nsamd::scatter_apply_kernel<true> (replayed graphs: the weight-gradient reduce rides it) "
                                                 "+ nsamd::scatter_finish_kernel",
     "nsamd_field_mlp_fwd": "nsamd::field_mlp_fwd_kernel",
@@ -136,7 +140,7 @@ def profile_table(run_steps, steps):
     return prof
 
 
-def roofline_entry(kernel, mean_ms, bound, work, main_points, ray_terms=False):
+def roofline_entry(kernel, mean_ms, bound, work, main_points, ray_terms=False, saved_tile=False):
     sec = mean_ms * 1e-3
     if bound == "hbm":
         ach, peak, unit = work / sec / 1e9, HBM_PEAK_GBS, "GB/s"
@@ -155,7 +159,7 @@ def roofline_entry(kernel, mean_ms, bound, work, main_points, ray_terms=False):
                                     "roofline_min_ms": round((work / (F32_MFMA_PEAK_TFLOPS * 1e12) + rec / (HBM_PEAK_GBS * 1e9)) * 1e3, 4),
                                     "frac_of_roofline_min": round((work / (F32_MFMA_PEAK_TFLOPS * 1e12) + rec / (HBM_PEAK_GBS * 1e9)) / sec, 4)}
     ex = executed_per_launch(kernel if "[" in kernel and kernel.startswith("nsamd_field_mlp_bwd_scatter_phase") else base, main_points,
-                             ray_terms)
+                             ray_terms, saved_tile)
     if ex is not None:  # the utilisation view (work the launch executes, incl. recomputation)
         roof["executed_per_launch"] = ex
         roof["executed_frac"] = round(ex / sec / (1e9 if bound == "hbm" else 1e12) / peak, 4)
@@ -163,6 +167,9 @@ def roofline_entry(kernel, mean_ms, bound, work, main_points, ray_terms=False):
             roof["ray_terms"] = ("head layer 0's 48 per-ray inputs (SH of the view direction, appearance row) are multiplied once per "
                                  "ray instead of once per sample: executed MACs per sample 8 384 of the dense layer stack's 11 392 "
                                  "that `achieved` is counted on")
+        if saved_tile and base.startswith("nsamd_field_mlp_bwd"):
+            roof["saved_tile"] = ("head layer 1's output and rgb are read from the forward of the same step: the recomputation "
+                                  "executes 4 288 MACs per sample fewer (head layers 1 and 2)")
     return roof
 
 
@@ -202,12 +209,13 @@ def measure_roofline(trainer, arena, steps, main_points):
     table.sort(key=lambda r: -r["ms_per_step"])
     ranked = [r for r in table if r["bound"] is not None and r["work"]]
     rt = runner is not None and bool(runner.ray_terms_on)
-    roof = roofline_entry(ranked[0]["kernel"], ranked[0]["mean_ms"], ranked[0]["bound"], ranked[0]["work"], main_points, rt) if ranked else None
+    sv = runner is not None and getattr(runner, "saved_hb", None) is not None
+    roof = roofline_entry(ranked[0]["kernel"], ranked[0]["mean_ms"], ranked[0]["bound"], ranked[0]["work"], main_points, rt, sv) if ranked else None
     # The main-field MLP backward and the main-table scatter are within a few percent of each other per step: which one is
     # "the dominant kernel" flips between runs. The runner-up rides along so that both are in every line.
     if roof is not None and len(ranked) > 1:
         r1 = ranked[1]
-        roof["runner_up"] = roofline_entry(r1["kernel"], r1["mean_ms"], r1["bound"], r1["work"], main_points, rt)
+        roof["runner_up"] = roofline_entry(r1["kernel"], r1["mean_ms"], r1["bound"], r1["work"], main_points, rt, sv)
     return roof, table
 
 
