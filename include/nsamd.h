@@ -289,11 +289,20 @@ typedef struct nsamd_field_mlp {
    * ignores `saved_rgb`. */
   float* saved_hb;
   const float* saved_rgb;
+  /* Batch pool (nullable: NULL and 0 = the rays are the batch itself). Read by nsamd_field_ray_terms ONLY; every other entry
+   * point ignores both. `batch_slot` is a float in DEVICE memory, `batch_slots` the number of batches in the pool. */
+  const float* batch_slot;
+  int32_t batch_slots;
 } nsamd_field_mlp;
 
 /* ray_terms [num_rays,64] (and ray_inputs [num_rays,48], nullable) of the struct above for `num_rays` rays: directions
  * [num_rays,3]; camera_indices [num_rays] int64 or NULL (then appearance_const [32], or neither: no appearance embedding).
- * `mlp.ray_terms / ray_inputs` are ignored here. */
+ * `mlp.ray_terms / ray_inputs` are ignored here.
+ * With mlp.batch_slot set the batch still lies in a pool of mlp.batch_slots batches (nsamd_select_batch's layout):
+ * `directions` is the pool [slots,num_rays,3], `camera_indices` the pool [slots,num_rays] (or NULL), the slot is clamped to
+ * [0, slots - 1] as nsamd_select_batch clamps it, and row slot * num_rays + ray is read where the plain call reads row ray.
+ * The arithmetic is the same: the bits of nsamd_select_batch followed by the plain call, without waiting for the selection.
+ * INVALID_ARG for batch_slots != 0 without batch_slot, or batch_slot with batch_slots < 1. */
 int nsamd_field_ray_terms(const float* directions, const int64_t* camera_indices, const float* appearance_const,
                           int64_t num_rays, nsamd_field_mlp mlp, float* ray_terms, float* ray_inputs,
                           nsamd_stream_t stream);

@@ -46,7 +46,7 @@ class FieldMlp(C.Structure):
     _fields_ = [("base_W0", vp), ("base_b0", vp), ("base_W1", vp), ("base_b1", vp), ("head_W0", vp), ("head_b0", vp),
                 ("head_W1", vp), ("head_b1", vp), ("head_W2", vp), ("head_b2", vp), ("appearance", vp),
                 ("num_images", i32), ("average_init_density", f32), ("ray_terms", vp), ("ray_inputs", vp),
-                ("saved_hb", vp), ("saved_rgb", vp)]
+                ("saved_hb", vp), ("saved_rgb", vp), ("batch_slot", vp), ("batch_slots", i32)]
 
 
 class OccGrid(C.Structure):

@@ -272,11 +272,20 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 16 ? 1 : 2) void field_mlp_fwd
 
 // ray_terms [num_rays, 64] (+ ray_inputs [num_rays, 16 + 32]): head layer 0 on the 48 per-ray inputs, 16 RAYS per wavefront in
 // the chain layout (a ray where the field kernels have a point): bias, then the SH tile, then the two appearance tiles.
+// slot_dev != nullptr (nsamd_field_mlp.batch_slot / batch_slots): `directions` / `cams` are pools of `slots` batches and the rays are rows
+// slot * num_rays + ray of them, the slot clamped as select_batch_kernel (misc.hip) clamps it — the same rows that launch copies.
 __global__ __launch_bounds__(kFieldThreads) void field_ray_terms_kernel(
     const float* __restrict__ directions, const int64_t* __restrict__ cams, const float* __restrict__ app_const,
-    int64_t num_rays, nsamd_field_mlp mlp, int app_dim, float* __restrict__ terms, float* __restrict__ inputs) {
+    int64_t num_rays, nsamd_field_mlp mlp, int app_dim, float* __restrict__ terms, float* __restrict__ inputs,
+    const float* __restrict__ slot_dev, int32_t slots) {
   __shared__ __attribute__((aligned(16))) float wf[kFragHead0];
   __shared__ __attribute__((aligned(16))) float bias[64];
+  if (slot_dev != nullptr) {
+    int32_t slot = (int32_t)slot_dev[0];
+    slot = slot < 0 ? 0 : (slot >= slots ? slots - 1 : slot);
+    directions += (int64_t)slot * 3 * num_rays;
+    if (cams != nullptr) cams += (int64_t)slot * num_rays;
+  }
   {
     float v[16];
     stage_frag_load<4, 4, kFieldThreads>(v, mlp.head_W0, 64, 31 + app_dim, true, app_dim);
@@ -1476,13 +1485,16 @@ extern "C" int nsamd_field_ray_terms(const float* directions, const int64_t* cam
                                      int64_t num_rays, nsamd_field_mlp mlp, float* ray_terms, float* ray_inputs,
                                      nsamd_stream_t stream) {
   NSAMD_REQUIRE(num_rays >= 0);
+  // a batch pool comes with its slot and its size, or not at all (then `directions` / `camera_indices` are the batch itself)
+  NSAMD_REQUIRE(mlp.batch_slot != nullptr ? mlp.batch_slots >= 1 : mlp.batch_slots == 0);
   if (num_rays == 0) return NSAMD_OK;
   NSAMD_REQUIRE(directions && ray_terms && mlp.head_W0 && mlp.head_b0);
   int app_dim = 0;
   if (const int st = field_app_dim(mlp, camera_indices, appearance_const, &app_dim)) return st;
   const unsigned blocks = field_blocks((num_rays + 15) / 16, kWaves);
   field_ray_terms_kernel<<<blocks, kFieldThreads, 0, (hipStream_t)stream>>>(directions, camera_indices, appearance_const, num_rays,
-                                                                           mlp, app_dim, ray_terms, ray_inputs);
+                                                                           mlp, app_dim, ray_terms, ray_inputs, mlp.batch_slot,
+                                                                           mlp.batch_slots);
   NSAMD_CHECK_LAUNCH();
   return NSAMD_OK;
 }

@@ -318,11 +318,18 @@ def ray_terms_apply(dir_group: int, M: int) -> bool:
 
 
 def ray_terms_launch(dirs: Tensor, cams: Optional[Tensor], app_const: Optional[Tensor], rays: int, mlp: N.FieldMlp,
-                     terms: Tensor, inputs: Optional[Tensor]) -> None:
+                     terms: Tensor, inputs: Optional[Tensor], slot=None, slots: int = 0) -> None:
     """nsamd_field_ray_terms on the current stream: head layer 0's share of the 48 per-ray inputs (SH of the view direction,
-    appearance row) into `terms` `[rays, 64]`, the inputs themselves into `inputs` `[rays, 48 | 16]` (None: not kept)."""
-    N.check(N.load().nsamd_field_ray_terms(N.ptr(dirs), N.ptr(cams), N.ptr(app_const), rays, mlp, N.ptr(terms), N.ptr(inputs),
-                                           N.stream()), "field_ray_terms")
+    appearance row) into `terms` `[rays, 64]`, the inputs themselves into `inputs` `[rays, 48 | 16]` (None: not kept).
+    slot (the device address of a float) and slots: `dirs` `[slots, rays, 3]` and `cams` `[slots, rays]` are a pool of batches
+    and the rays are those of the slot, clamped as `select_batch_launch` clamps it (nsamd_field_mlp.batch_slot) — the bits of
+    the selection followed by the plain launch, without the selection in front."""
+    mlp.batch_slot, mlp.batch_slots = slot, slots
+    try:
+        N.check(N.load().nsamd_field_ray_terms(N.ptr(dirs), N.ptr(cams), N.ptr(app_const), rays, mlp, N.ptr(terms),
+                                               N.ptr(inputs), N.stream()), "field_ray_terms")
+    finally:
+        mlp.batch_slot, mlp.batch_slots = None, 0  # (the caller's struct goes on to the forward)
 
 
 def field_forward(table: Tensor, grid: HashGridSpec, transform: int, box: N.Aabb, pts: N.Points, M: int, enc: Tensor,

@@ -22,7 +22,7 @@ class TrainStepRunner:
       backward_main(), backward_proposals()               the data-parallel segments
       backward_fork(updated), backward_join(updated)      the same with `side_stream` (the proposal chains beside the exchange)
       backward_cameras(updated, force=True), camera_reg   `cam_opt` set
-      ray_terms_launch()                                  `ray_terms_on`
+      ray_terms_launch(select=...)                        `ray_terms_on` (select: the `pending_select` still to be consumed)
       loss_vals                                           `want_loss_vals`
 
     The attributes below are the optional capabilities the drivers read; a runner that does not state one has the default.

@@ -171,6 +171,9 @@ class NerfactoTrainStep(TrainStepRunner):
         self._slot0 = None  # a device zero: `set_batch` as a one-slot batch selection
         self._outputs = None
         self.fuse_select = os.environ.get("NSAMD_FUSE_SELECT", "1") == "1"
+        # update steps: the main backward chain is issued (and its graph nodes created) before the proposal chains' fork, so
+        # that a replayed graph keeps composite_bwd on the losses' hardware queue (backward_fork)
+        self.main_chain_first = True
         # Second stream for the proposal-network backward: the two backward chains are independent, and since the
         # scatter kernels were reworked (latency-bound phases, small workgroups) they overlap: 3.87 -> 4.02 M rays/s on
         # MI355X (profiles/). `side_stream = None` runs them back to back (the data-parallel path does: its proposal
@@ -437,16 +440,26 @@ class NerfactoTrainStep(TrainStepRunner):
         if branches:
             # The backward chains are independent (disjoint gradients, separate scratch): fork the proposal chains onto
             # their own streams so that these latency-bound kernels overlap with the main chain.
+            # The main chain is issued FIRST: inside a captured graph the fork's first-created child stays on its parent's
+            # hardware queue and every further child starts on another one, 8-11 us late. The main chain's 6 us compositing
+            # backward is the critical one; created second it hopped, and the field backward behind it started 19 instead
+            # of 11 us after the losses, into the proposal chains' first kernel (profiles/critical_chain_hops_ab.txt:
+            # -15 us per step on the long run). The dependencies are the same either way.
             main = N.current_stream()
             self._fork.record(main)
+            if self.main_chain_first:
+                self.backward_main()
+                if self.normals is not None:
+                    self.normals_backward()
             for stream, join, levels in branches:
                 stream.wait_event(self._fork)
                 with N.on_stream(stream):
                     self.backward_proposals(levels=levels)
                     join.record(stream)
-            self.backward_main()
-            if self.normals is not None:
-                self.normals_backward()
+            if not self.main_chain_first:
+                self.backward_main()
+                if self.normals is not None:
+                    self.normals_backward()
         else:
             self.backward_main()
             if self.normals is not None:
@@ -659,13 +672,23 @@ class NerfactoTrainStep(TrainStepRunner):
         """The camera indices the main field reads its appearance rows by (None: no appearance table, or `app_const`)."""
         return self.camera_indices if (self.model.field.embedding_appearance is not None and app_const is None) else None
 
-    def ray_terms_launch(self, fm: Optional[N.FieldMlp] = None, app_const: Optional[Tensor] = None) -> None:
+    def ray_terms_launch(self, fm: Optional[N.FieldMlp] = None, app_const: Optional[Tensor] = None, select=None) -> None:
         """nsamd_field_ray_terms for the batch in the static buffers: head layer 0's share of the 48 per-ray inputs. Needs the
         batch's (pose-corrected) directions and camera indices and the CURRENT head_W0 / head_b0 / appearance table — i.e. it
         runs after batch selection and after the main-field Adam of the previous iteration. On torch's current stream.
-        app_const: see forward_main (the per-ray inputs are then not kept: no backward reads them)."""
-        F.ray_terms_launch(self.directions, self._cams(app_const), app_const, self.n, fm if fm is not None else self._field_mlp(),
-                           self.ray_terms, self.ray_inputs if app_const is None else None)
+        app_const: see forward_main (the per-ray inputs are then not kept: no backward reads them). select: the `pending_select`
+        (slot pointer, slots, pool) the same iteration's `forward_proposals` fills the static buffers from — the terms are then
+        read out of the pool itself (the same rows, the same bits) and need not wait for that launch; only without a camera
+        optimiser, whose corrected directions exist nowhere but in the static buffers."""
+        fm = fm if fm is not None else self._field_mlp()
+        inputs = self.ray_inputs if app_const is None else None
+        if select is not None:
+            assert self.cam_opt is None
+            slot, slots, pool = select
+            F.ray_terms_launch(pool["directions"], None if self._cams(app_const) is None else pool["cameras"], app_const, self.n,
+                               fm, self.ray_terms, inputs, slot=slot, slots=slots)
+            return
+        F.ray_terms_launch(self.directions, self._cams(app_const), app_const, self.n, fm, self.ray_terms, inputs)
 
     @profiler.time_function
     def forward_main(self, terms_ready: bool = False, app_const: Optional[Tensor] = None) -> None:

@@ -172,6 +172,9 @@ class HipTrainer:
         self._capture_tried = False  # pipeline.TrainEngine: one capture attempt per trainer
         self.defer_scatter = False  # read by bench.py: the main table scatter is never deferred to the next iteration
         self.opt_parallel = True  # False: the deferred Adam runs on the main stream (per-kernel timing)
+        # the ray terms on the Adam branch read a batch the fused selection is still to copy out of the pool's own rows
+        # (nsamd_field_mlp.batch_slot): no edge from the bins launch to that branch; False: behind the bins, by an event
+        self.terms_from_pool = True
         # False: the jitter buffer of the runner is filled by the caller before every iteration (parity tests inject the
         # draws the CPU oracle uses; the default draws them on the device inside the iteration, graph-safe Philox)
         self.draw_jitter = True
@@ -347,7 +350,7 @@ class HipTrainer:
     def _body(self, updated, pending):
         """One N = 1 iteration over the runner, eager or captured as the graph ("all", updated, pending):
             in order:  select batch -> zero-fills -> proposal forward -> main forward, losses, backward chains -> Adam
-            deferred:  [Adam main k-1, zero-fills  ||  select batch, proposal forward k] -> main forward, losses,
+            deferred:  [Adam main k-1, zero-fills, ray terms k  ||  select batch, proposal forward k] -> main forward, losses,
                        backward chains k -> [Adam proposals k]                                          (update steps)
         Inside a captured hipGraph the two halves of the deferred first line are parallel branches. With the camera parts
         outside, batch selection and the pose corrections have already run (eagerly, `_cameras_before`)."""
@@ -360,6 +363,12 @@ class HipTrainer:
         # records once the batch is in place — off the critical path instead of a launch (and a dependent-launch gap) in
         # front of the hash forward.
         terms_beside = beside and r.ray_terms_on
+        # ... and where `forward_proposals` will select the batch out of the pool (`_select_batch` hands it over), they read
+        # the pool's rows themselves: behind the Adam and the zero-fills on that branch, no event, and the bins launch keeps
+        # the first proposal field as its only child — which a replayed graph leaves on the bins' hardware queue
+        # (profiles/critical_chain_hops_ab.txt)
+        select = self._pool_select() if (terms_beside and self.terms_from_pool and not r.cameras_outside) else None
+        terms_after_bins = terms_beside and select is None
 
         def terms_behind_batch():  # (runs inside forward_proposals, right behind the launch that selects the batch)
             self._batch_ready.record(main)
@@ -378,7 +387,9 @@ class HipTrainer:
                 # gradients, the proposal / camera groups were consumed at the end of their last update iteration, and
                 # nothing before the join below writes a gradient
                 self._zero(updated)
-                if not terms_beside:
+                if select is not None:
+                    r.ray_terms_launch(select=select)
+                if not terms_after_bins:
                     self._opt_join.record(self.opt_stream)
         elif pending:
             a.step(grad_scale=1.0, groups=["fields"], hyper_dev=self.hyper_views)
@@ -389,7 +400,7 @@ class HipTrainer:
             # the main table's gradient is written, not accumulated; the proposal group's gradients are neither produced nor
             # consumed on a step that does not update it (ray_samplers.py:590-599), so its 10 MB need no zero-fill then
             self._zero(updated)
-        r.forward_proposals(self.draw_jitter and not self.prologue, need_enc=updated, after_bins=terms_behind_batch if terms_beside else None)
+        r.forward_proposals(self.draw_jitter and not self.prologue, need_enc=updated, after_bins=terms_behind_batch if terms_after_bins else None)
         if beside:
             main.wait_event(self._opt_join)
         elif self.defer:
@@ -421,6 +432,14 @@ class HipTrainer:
             self.arena.all_reduce()
         self.arena.step(grad_scale=1.0 / self.world, groups=self._stepped(updated, pending=False), hyper_dev=self.hyper_views)
 
+    def _pool_select(self):
+        """(slot pointer, slots, pool) of the step's batch where the runner's `forward_proposals` selects it out of the pool
+        itself (no source, no camera optimiser: the kernels read what the selection copies), else None."""
+        r = self.runner
+        if self.source is not None or self.pool is None or r is None or r.cam_opt is not None or not r.fuse_select:
+            return None
+        return (N.ptr(self.hyper[_HYPER_SLOT:_HYPER_SLOT + 1]), self.slots, self.pool)
+
     def _select_batch(self):
         """This step's rays out of the HBM-resident pool (slot index in device memory: replayable) — the hand-over the
         reference's datamanager does each iteration (base_datamanager.py:506-515)."""
@@ -440,9 +459,10 @@ class HipTrainer:
         if self.runner is not None:
             r = self.runner
             co = r.cam_opt is not None  # the kernels read the pose-corrected copies
-            if not co and r.fuse_select:
+            select = self._pool_select()
+            if select is not None:
                 # the runner's next `forward_proposals` selects the batch in the launch that writes the initial bins
-                r.pending_select = (N.ptr(self.hyper[_HYPER_SLOT:_HYPER_SLOT + 1]), self.slots, p)
+                r.pending_select = select
                 return
             o, d = (r.raw_origins, r.raw_directions) if co else (r.origins, r.directions)
             c, t = r.camera_indices, r.target
