@@ -3,7 +3,7 @@
 Reference: `Model.get_outputs_for_camera_ray_bundle` (models/base_model.py:178-205) slices the camera's ray bundle into
 chunks of `eval_num_rays_per_chunk` rays in Python, runs `forward` on each — ~60 module calls and as many tensor
 allocations per chunk — and `torch.cat`s every output. Here one chunk is ONE explicit kernel schedule over static buffers
-(the forward half of train_step.NerfactoTrainStep in eval mode), captured once per chunk size in a hipGraph; a frame is
+(forward_step.NerfactoForward, the base of the training runner, in eval mode), captured once per chunk size in a hipGraph; a frame is
 
     for each chunk:  copy the chunk's rays into the static input buffers -> replay -> copy the outputs into their
                      rows of the preallocated image buffers
@@ -66,7 +66,7 @@ class EvalRenderer:
     def __init__(self, model, chunk: Optional[int] = None, use_graph: bool = True, normals: bool = False) -> None:
         """normals: also render `normals` and `pred_normals` (a `predict_normals` model; `supported(model, normals=True)`): three
         more stages behind the chunk's weights — see `_launch_normals`."""
-        from .train_step import NerfactoTrainStep
+        from .forward_step import NerfactoForward
 
         self.model = model
         self.normals = bool(normals)
@@ -75,7 +75,7 @@ class EvalRenderer:
         self.chunk = int(chunk or model.config.eval_num_rays_per_chunk)
         dev = next(model.parameters()).device
         N.require_cuda(next(model.parameters()))
-        self.step = NerfactoTrainStep(model, self.chunk, dev, compute_depths=True, forward_only=True)
+        self.step = NerfactoForward(model, self.chunk, dev, compute_depths=True)
         self.step.nears.zero_()  # NearFarCollider at inference (reset_near_plane)
         fld = model.field
         emb = fld.embedding_appearance.embedding.weight if fld.embedding_appearance is not None else None
@@ -116,10 +116,10 @@ class EvalRenderer:
                     self.app_const.zero_()
 
     def _launch_chunk(self) -> None:
-        """The kernel schedule of one chunk (all arguments are static buffers: capturable): the training runner's forward in
+        """The kernel schedule of one chunk (all arguments are static buffers: capturable): the forward schedule in
         eval mode, then weights + compositing with the clamp."""
         s = self.step
-        s.forward_proposals(need_enc=False, stratified=False)
+        s.forward_proposals(stratified=False)
         s.forward_main(app_const=self.app_const)
         L = s.n_prop
         F.weights_launch(s.t_bins[L], s.f_dens, s.weights[L])

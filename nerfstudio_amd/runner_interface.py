@@ -5,7 +5,8 @@ from __future__ import annotations
 
 class TrainStepRunner:
     """The runner of trainer.HipTrainer, dp_schedule.PipelinedExchange's segments and pipeline.TrainEngine
-    (train_step.NerfactoTrainStep; tests: cpu_runner.CpuRunner, a toy schedule).
+    (train_step.NerfactoTrainStep, which is forward_step.NerfactoForward plus this interface; tests: cpu_runner.CpuRunner, a
+    toy schedule).
 
     Every runner provides
       n, origins, directions, camera_indices, target     the static batch buffers (`raw_origins`, `raw_directions` as well when

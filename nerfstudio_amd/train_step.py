@@ -3,13 +3,15 @@
 What the reference does per step (engine/trainer.py:487-531 -> pipelines/base_pipeline.py:290-303 ->
 models/nerfacto.py:298-392): collider, ProposalNetworkSampler (3 levels), NerfactoField, weights, renderers, MSE +
 interlevel + distortion losses, `backward()`, optimiser. `NerfactoModel` (nerfacto.py) reproduces that through the
-module API with autograd; this runner issues THE SAME kernels in a fixed order over buffers allocated once:
+module API with autograd; `NerfactoTrainStep` issues THE SAME kernels in a fixed order over buffers allocated once:
 
-  forward : piecewise_bins -> [hash_fwd -> density_mlp_fwd -> weights_fwd -> pdf_resample] x 2 proposal levels
-            -> hash_fwd(main) -> field_mlp_fwd -> weights_fwd -> composite_fwd (+ median depths)
+  forward : forward_step.NerfactoForward, its base (the schedule an eval render runs on its own) -> weights_fwd -> composite_fwd
   backward: mse_loss, distortion_loss, interlevel_loss x 2 (value + gradient in one pass each)
             -> composite_bwd -> weights_bwd -> field_mlp_bwd -> hash_bwd(main)
             -> (only on proposal-update steps, ray_samplers.py:590) weights_bwd -> density_mlp_bwd -> hash_bwd x 2
+
+The base owns the rays, the sampler state and the fields' outputs; this class adds the target, the levels' kept features, every
+gradient and loss buffer, workspaces, gates, streams and events, the camera optimiser, the normals stage, depth supervision.
 
 ~25 launches, every one a libnsamd kernel (round 5: batch selection + initial bins are one launch, the main field's
 weight-gradient reduce rides the table scatter's apply pass; the fully merged forms of the per-ray stages were bit-identical and
@@ -19,8 +21,7 @@ device, the anneal exponent lives in device memory), so the whole iteration can 
 schedule variant and replayed. Numerically identical to the autograd path (tests/test_gpu_kernels.py compares them).
 
 The launches this schedule shares with the module path (or with trainer / eval_render) go through the helpers of functional.py
-— piecewise_bins_launch, density_forward, weights_launch, composite_launch, pdf_resample_launch, depth_loss_launch,
-field_normals_launch, nerf_encode_launch, linear_launch, normals_losses_launch, normals_composite_launch,
+— depth_loss_launch, field_normals_launch, nerf_encode_launch, linear_launch, normals_losses_launch, normals_composite_launch,
 distance_gradient_scale_launch, weights_backward_launch, camera_apply_launch, camera_backward_launch, select_batch_launch
 and the field helpers — with this runner's static buffers; the entry points only this schedule launches are called here.
 """
@@ -35,113 +36,63 @@ from torch import Tensor
 
 from . import _native as N
 from . import functional as F
+from .forward_step import NerfactoForward
 from .nerfacto import NerfactoModel
 from .runner_interface import TrainStepRunner
 from .utils import profiler
 
 
-class NerfactoTrainStep(TrainStepRunner):
-    def __init__(self, model: NerfactoModel, num_rays: int, device, compute_depths: bool = True,
-                 forward_only: bool = False) -> None:
-        """forward_only: no gradient / saved-activation buffers (eval_render.EvalRenderer: at 32 768 rays per chunk they
-        are ~1.5 GB an eval render never touches); `forward_backward` and the backward methods must not be called."""
-        self.model = model
-        self.forward_only = bool(forward_only)
-        cfg = model.config
-        self.cfg = cfg
-        self.n = n = int(num_rays)
-        self.counts = (*cfg.num_proposal_samples_per_ray, cfg.num_nerf_samples_per_ray)
-        self.n_prop = len(cfg.num_proposal_samples_per_ray)
-        self.compute_depths = compute_depths
-        if cfg.background_color not in ("last_sample", "black", "white", "random"):
-            raise ValueError(cfg.background_color)
-        # use_single_jitter=False (ray_samplers.py:104-107, 318-322): one draw per bin EDGE instead of one per ray — the
-        # per-level jitter buffers become [n, S+1] and the resampling goes through the unfused kernels
-        self.single_jitter = bool(getattr(cfg, "use_single_jitter", True))
+class NerfactoTrainStep(NerfactoForward, TrainStepRunner):
+    def __init__(self, model: NerfactoModel, num_rays: int, device, compute_depths: bool = True) -> None:
+        super().__init__(model, num_rays, device, compute_depths)
+        cfg, n, mm = self.cfg, self.n, self.m_main
         self.gradient_scaling = bool(getattr(cfg, "use_gradient_scaling", False))
-        # the normals stage of a `predict_normals` model whose field carries the modules (training runners only: the eval render
-        # has its own, eval_render.EvalRenderer)
-        want_normals = (not forward_only and bool(getattr(cfg, "predict_normals", False))
-                        and bool(getattr(model.field, "use_pred_normals", False)))
+        # the normals stage of a `predict_normals` model whose field carries the modules (the eval render has its own,
+        # eval_render.EvalRenderer)
+        want_normals = bool(getattr(cfg, "predict_normals", False)) and bool(getattr(model.field, "use_pred_normals", False))
         if want_normals and self.gradient_scaling:
             # the reference scales the predicted normals' gradient as well (models/nerfacto.py:321-322)
             raise NotImplementedError("explicit schedule: predict_normals together with use_gradient_scaling is only on the "
                                       "module path")
         f32 = dict(device=device, dtype=torch.float32)
         e = lambda *shape: torch.empty(shape, **f32)  # noqa: E731
-        # (training-only buffers: one element each in a forward-only runner)
-        t = (lambda *shape: torch.empty((1,) * len(shape), **f32)) if forward_only else e  # noqa: E731
         if cfg.background_color == "random":
             # the rendered colour carries no background; the loss blends `rand_like(pred) * (1 - accumulation)` into the
             # prediction (renderers.py:112-115, 194-196; models/nerfacto.py:377-381) — a per-ray colour the kernels read
             # (zero-initialised: callers that inject the jitter — `draw_jitter=False` — and no background of their own
             # composite against black, never against uninitialised memory; ADVICE r02)
-            self.bg_mode, self.bg_vals, self.bg_rays = 3, None, torch.zeros((n, 3), **f32)
-        else:
-            self.bg_mode, self.bg_vals = F._bg_args(cfg.background_color, device)
-            self.bg_rays = None
-        # ---- per-step inputs (static addresses; the caller fills them) ----
-        self.origins, self.directions = e(n, 3), e(n, 3)
-        self.camera_indices = torch.zeros((n,), device=device, dtype=torch.int64)
+            self.bg_rays = torch.zeros((n, 3), **f32)
         self.target = e(n, 3)
-        self.nears = torch.full((n,), float(cfg.near_plane), **f32)  # NearFarCollider, training mode
-        self.fars = torch.full((n,), float(cfg.far_plane), **f32)
-        self.jitter = e(self.n_prop + 1, n)  # single jitter: one draw per level and ray
-        self.jitter_edges = None if self.single_jitter else [e(n, s + 1) for s in self.counts]  # per edge: [n, S+1] per level
-        self.anneal_dev = torch.ones((1,), **f32)
-        # ---- sampler state ----
-        self.s_bins = [e(n, s + 1) for s in self.counts]
-        self.t_bins = [e(n, s + 1) for s in self.counts]
-        self.weights = [e(n, s) for s in self.counts]
-        # ---- fields ----
-        self.props = list(model.proposal_networks) if not cfg.use_same_proposal_network else \
-            [model.proposal_networks[0]] * self.n_prop
-        self.p_enc, self.p_sel, self.p_pre, self.p_dens = [], [], [], []
-        for lvl in range(self.n_prop):
-            m = n * self.counts[lvl]
-            self.p_enc.append(t(self.props[lvl].encoding.get_out_dim(), m))  # (forward-only: see `ensure_proposal_features`)
-            self.p_sel.append(t(m))
-            self.p_pre.append(t(m))
-            self.p_dens.append(e(m))
-        self.m_main = mm = n * self.counts[-1]
-        fld = model.field
-        self.f_enc, self.f_sel, self.f_dens, self.f_rgb = e(fld.mlp_base.encoding.get_out_dim(), mm), e(mm), e(mm), e(mm, 3)
-        # ---- outputs ----
-        self.rgb, self.acc, self.depth_exp = e(n, 3), e(n), e(n)
-        self.minmax_ws = e(2 + 2 * ((n + 3) // 4))
-        self.depth_med = [e(n) for _ in self.counts]
+        for lvl, m in enumerate(x.numel() for x in self.p_dens):  # what forward_proposals(need_enc=True) keeps of the levels
+            self.p_enc[lvl], self.p_sel[lvl], self.p_pre[lvl] = e(self.props[lvl].encoding.get_out_dim(), m), e(m), e(m)
         # ---- losses / gradients ----
         self.sq_err = e(n)  # per-ray sum of squared rgb errors
         self.dist_per_ray = e(n)
         self.inter_per_ray = [e(n) for _ in range(self.n_prop)]
         self.d_rgb_out = e(n, 3)
-        self.dw_dist = t(n, self.counts[-1])
-        self.dw_prop = [t(n, self.counts[lvl]) for lvl in range(self.n_prop)]
-        self.d_rgb_s, self.d_dens_main = t(mm, 3), t(mm)
+        self.dw_dist = e(n, self.counts[-1])
+        self.dw_prop = [e(n, self.counts[lvl]) for lvl in range(self.n_prop)]
+        self.d_rgb_s, self.d_dens_main = e(mm, 3), e(mm)
         # host arrays of device pointers for nsamd_proposal_losses (the buffers are static, so built once)
         self._pl_s_bins = N.ptr_array(self.s_bins[: self.n_prop])
         self._pl_weights = N.ptr_array(self.weights[: self.n_prop])
         self._pl_per_ray = N.ptr_array(self.inter_per_ray)
         self._pl_dw = N.ptr_array(self.dw_prop)
         self._pl_S = (C.c_int32 * self.n_prop)(*self.counts[: self.n_prop])
-        # Ray terms (include/nsamd.h, nsamd_field_mlp.ray_terms): head layer 0's share of the 48 per-ray inputs (SH of the view
-        # direction, appearance row) once per ray instead of once per sample (a 16-point tile must lie inside one ray).
-        self.ray_terms_on = F.ray_terms_apply(self.counts[-1], mm)
-        self.ray_terms = e(n, 64) if self.ray_terms_on else None
-        self.ray_inputs = e(n, 16 + (32 if fld.embedding_appearance is not None else 0)) \
-            if (self.ray_terms_on and not forward_only) else None  # (the backward's: weight gradient of the 48 per-ray columns)
+        if self.ray_terms_on:  # their inputs, kept for the backward: weight gradient of the 48 per-ray columns
+            self.ray_inputs = e(n, 16 + (32 if model.field.embedding_appearance is not None else 0))
         # Saved tile (include/nsamd.h, nsamd_field_mlp.saved_hb): the forward leaves head layer 1's output, as its wavefronts hold
         # it, for the backward of the same step, which reads it and `f_rgb` instead of recomputing head layers 1 and 2. Whole
         # 16-sample tiles, zeroed once: a partial last tile's absent samples are never written. A static address, so a captured
         # iteration stays valid. `_saved_fresh`: the tile is that of the last `forward_main`.
-        self.saved_hb = None if forward_only else torch.zeros(((mm + 15) // 16, 4, 64, 4), **f32)
+        self.saved_hb = torch.zeros(((mm + 15) // 16, 4, 64, 4), **f32)
         self._saved_fresh = False
-        self.f_denc = t(*self.f_enc.shape)
-        self.p_ddens = [t(*x.shape) for x in self.p_dens]
-        self.p_denc = [t(*x.shape) for x in self.p_enc]
-        self.field_ws = None if forward_only else F.field_bwd_workspace(device)[0]
+        self.f_denc = e(*self.f_enc.shape)
+        self.p_ddens = [e(*x.shape) for x in self.p_dens]
+        self.p_denc = [e(*x.shape) for x in self.p_enc]
+        self.field_ws = F.field_bwd_workspace(device)[0]
         # one scratch per proposal level: their backward chains may run concurrently on different streams
-        self.density_ws = [] if forward_only else [F.density_bwd_workspace(device, slot=lvl) for lvl in range(self.n_prop)]
+        self.density_ws = [F.density_bwd_workspace(device, slot=lvl) for lvl in range(self.n_prop)]
         # Zero-gradient gating of the proposal chains (include/nsamd.h): one device flag per level, raised by the level's
         # weights backward when any ray carries interlevel-loss gradient; while it is clear the rest of the chain
         # (density MLP backward, table scatter, ray gradients) returns at once — the zero-filled gradients are the result.
@@ -166,8 +117,7 @@ class NerfactoTrainStep(TrainStepRunner):
         # bins, nsamd_select_bins); NSAMD_FUSE_SELECT=0: the caller launches nsamd_select_batch itself (A/B)
         self.pending_select = None
         # depth supervision (set_depth_target): None = today's launches, nothing else
-        self.depth = None
-        self._depth_buffers = None
+        self.depth = self._depth_buffers = None
         self._slot0 = None  # a device zero: `set_batch` as a one-slot batch selection
         self._outputs = None
         self.fuse_select = os.environ.get("NSAMD_FUSE_SELECT", "1") == "1"
@@ -221,10 +171,6 @@ class NerfactoTrainStep(TrainStepRunner):
         self.cameras_outside = False
         self.grad_lookup = None  # {id(parameter): gradient buffer} of an arena that does not bind `param.grad`
         self.main_table_write_only = True  # the main table's gradient is written, not accumulated (written_params)
-        self.spacing = int(getattr(model.proposal_sampler.initial_sampler, "spacing", 0))
-        # host-evaluated tables (bit-identical to the reference's CPU linspace)
-        self.edges = F._linspace("edges", self.counts[0], device)
-        self.u_base = [None] + [F._linspace("u", s, device) for s in self.counts[1:]]
 
     # -------------------------------------------------------------------------------------------------------------
     def set_batch(self, origins: Tensor, directions: Tensor, camera_indices: Tensor,
@@ -265,8 +211,6 @@ class NerfactoTrainStep(TrainStepRunner):
         if loss_type != F.DEPTH_DS_NERF:
             raise NotImplementedError("explicit schedule: only the DS_NERF depth loss; URF and the depth ranking loss are "
                                       "on the module path")
-        if self.forward_only:
-            raise RuntimeError("a forward-only runner has no gradient buffers")
         if not is_euclidean and directions_norm is None:
             raise ValueError("a depth that is not Euclidean needs directions_norm")
         d = self._depth_buffers
@@ -390,15 +334,6 @@ class NerfactoTrainStep(TrainStepRunner):
                 if prm.requires_grad and prm.grad is None:
                     prm.grad = torch.empty_like(prm) if prm is table else torch.zeros_like(prm)
 
-    def ensure_proposal_features(self, lvl: int) -> None:
-        """A forward-only runner whose proposal network the fused density kernel does not take (the two-kernel pair needs the
-        level's encoded features and selector): allocate them on first use."""
-        m = self.n * self.counts[lvl]
-        if self.p_sel[lvl].numel() != m:
-            dev = self.p_dens[lvl].device
-            self.p_enc[lvl] = torch.empty((self.props[lvl].encoding.get_out_dim(), m), device=dev)
-            self.p_sel[lvl] = torch.empty((m,), device=dev)
-
     def _grad(self, p: Tensor) -> Tensor:
         if self.grad_lookup is not None:  # an arena that keeps `param.grad` unset (arena.ParamArena(bind_grads=False))
             g = self.grad_lookup.get(id(p))
@@ -407,15 +342,10 @@ class NerfactoTrainStep(TrainStepRunner):
         assert p.grad is not None and p.grad.is_contiguous(), "parameters need preallocated .grad (use arena.ParamArena)"
         return p.grad
 
-    def _points(self, lvl: int) -> N.Points:
-        return N.make_points(None, self.origins, self.directions, self.t_bins[lvl], self.counts[lvl])
-
     # -------------------------------------------------------------------------------------------------------------
     def forward_backward(self, updated: bool, draw_jitter: bool = True) -> None:
         """One iteration up to (not including) the optimiser. `updated`: proposal networks receive gradient this step
         (ProposalNetworkSampler.updated_this_step()). Gradients ACCUMULATE into param.grad (zero them first)."""
-        if self.forward_only:
-            raise RuntimeError("NerfactoTrainStep(forward_only=True) has no gradient buffers")
         self.forward_and_losses(updated, draw_jitter)
         self.backward_all(updated)
 
@@ -474,15 +404,6 @@ class NerfactoTrainStep(TrainStepRunner):
             main.wait_event(join)
         self._open_branches = []
         self.backward_cameras(updated)
-
-    def forward_backward_main(self, updated: bool, draw_jitter: bool = True) -> None:
-        """Forward of everything, the losses, and the backward of the MAIN field (87 % of the gradient bytes). With data
-        parallelism the all-reduce of the main-field gradients can start right after this while `backward_proposals`
-        (interlevel-loss gradients of the proposal networks) still runs."""
-        self.forward_and_losses(updated, draw_jitter)
-        self.backward_main()
-        if self.normals is not None:
-            self.normals_backward()
 
     def written_params(self):
         """Parameters whose gradient this runner WRITES (hash tables, nsamd_hashgrid_encode_bwd_set): callers need not
@@ -583,134 +504,35 @@ class NerfactoTrainStep(TrainStepRunner):
     @profiler.time_function
     def forward_proposals(self, draw_jitter: bool = True, need_enc: bool = True, after_bins=None,
                           stratified: bool = True) -> None:
-        """Initial bins and the proposal levels (density fields + resampling): reads only the proposal networks'
-        parameters, so with data parallelism it can run while the main-field gradients of the previous step are still
-        being all-reduced (bench.py). need_enc: keep the levels' encoded features / selector / pre-activation for
-        backward_proposals (False on the steps where the proposal networks get no gradient, ray_samplers.py:590: the
-        fused forward then writes nothing but the densities). after_bins: called right behind the launch that writes the
-        initial bins (and selects the batch), before the proposal levels. stratified=False: eval sampling (ray_samplers.py:
-        104-111, 323-327) — bin centres in the initial sampler, the fixed offset in the PDF resampling, nothing drawn."""
-        lib, st, n = N.load(), N.stream(), self.n
-        ck = N.check
-        per_edge = stratified and not self.single_jitter
-        if draw_jitter and stratified:
-            if per_edge:
-                for j in self.jitter_edges:
-                    j.uniform_()
-            else:
-                self.jitter.uniform_()  # torch.rand per level and ray (ray_samplers.py:105, :322), drawn on the device
-            if self.bg_rays is not None:
-                self.bg_rays.uniform_()  # rand_like(pred) of the loss blend (renderers.py:195)
-        S0 = self.counts[0]
-        jit0 = (self.jitter_edges[0] if per_edge else self.jitter[0]) if stratified else None
+        """NerfactoForward.forward_proposals for training: reads only the proposal networks' parameters, so with data parallelism
+        it can run while the main-field gradients of the previous step are still being all-reduced (bench.py). need_enc: keep
+        the levels' encoded features / selector / pre-activation for backward_proposals (False on the steps where the proposal
+        networks get no gradient, ray_samplers.py:590). after_bins: called right behind the launch that writes the initial
+        bins (and selects the batch), before the proposal levels."""
+        self._proposals(draw_jitter, need_enc, after_bins, stratified)
+
+    def _initial_bins(self, jit0: Optional[Tensor], per_edge: bool) -> None:
         sel, self.pending_select = self.pending_select, None
-        if sel is not None:
-            # the step's batch out of the caller's pool of batches AND the initial bins in one launch (trainer.HipTrainer hands
-            # the selection over instead of launching it: the bins need nears / fars / the draw, not the rays)
-            slot, slots, pool = sel
-            ck(lib.nsamd_select_bins(slot, slots, n, N.ptr(pool["origins"]), N.ptr(pool["directions"]), N.ptr(pool["cameras"]),
-                                     N.ptr(pool["target"]), N.ptr(self.origins), N.ptr(self.directions),
-                                     N.ptr(self.camera_indices), N.ptr(self.target), N.ptr(self.nears), N.ptr(self.fars),
-                                     N.ptr(self.edges), N.ptr(jit0), int(per_edge), S0, self.spacing, N.ptr(self.s_bins[0]),
-                                     N.ptr(self.t_bins[0]), st), "select_bins")
-        else:
-            F.piecewise_bins_launch(self.nears, self.fars, self.edges, jit0, int(per_edge), self.spacing, self.s_bins[0],
-                                    self.t_bins[0])
-        if after_bins is not None:  # (trainer.HipTrainer: the ray terms, behind the batch selection)
-            after_bins()
-        # ---- proposal levels ----
-        for lvl in range(self.n_prop):
-            net = self.props[lvl]
-            S, m = self.counts[lvl], n * self.counts[lvl]
-            dm = F.density_mlp(*net.mlp_base[1].param_tensors(), net.average_init_density)
-            # hash grid + MLP + trunc_exp in one launch, features in registers (nsamd_density_field_fwd); networks the
-            # fused kernel is not built for go through the two-kernel pair
-            fused = lib.nsamd_density_field_fwd(
-                self._points(lvl), m, net._transform, net._box, N.ptr(net.encoding.hash_table), net.encoding.spec.native(), dm,
-                N.ptr(self.p_enc[lvl]) if need_enc else None, N.ptr(self.p_sel[lvl]) if need_enc else None,
-                N.ptr(self.p_dens[lvl]), N.ptr(self.p_pre[lvl]) if need_enc else None, st)
-            if fused == N.ERR_UNSUPPORTED:
-                self.ensure_proposal_features(lvl)
-                F.hash_forward(self._points(lvl), m, net._transform, net._box, net.encoding.hash_table, net.encoding.spec,
-                               self.p_enc[lvl], 1, m, self.p_sel[lvl])
-                F.density_forward(self.p_enc[lvl], self.p_sel[lvl], m, dm, self.p_dens[lvl],
-                                  None if self.forward_only else self.p_pre[lvl])
-            else:
-                ck(fused, "density_field_fwd")
-            S2 = self.counts[lvl + 1]
-            if per_edge:
-                # one draw per new bin edge: the fused launch below draws per ray, so this (non-default) configuration takes
-                # its three constituents — same numbers (nsamd.h)
-                F.weights_launch(self.t_bins[lvl], self.p_dens[lvl], self.weights[lvl])
-                if self.compute_depths:
-                    F.composite_launch(None, self.weights[lvl], self.t_bins[lvl], N.BG_NONE, None, False, None, None, None,
-                                       self.depth_med[lvl], None, None)
-                F.pdf_resample_launch(self.s_bins[lvl], self.weights[lvl], self.u_base[lvl + 1], self.jitter_edges[lvl + 1],
-                                      self.nears, self.fars, 1.0, self.anneal_dev, 0.01, 1e-5, self.spacing, 1, False, S2,
-                                      self.s_bins[lvl + 1], self.t_bins[lvl + 1], None)
-                continue
-            # weights of this level, its median depth (prop_depth_i, models/nerfacto.py:346-347) and the PDF resampling
-            ck(lib.nsamd_proposal_resample(N.ptr(self.t_bins[lvl]), N.ptr(self.s_bins[lvl]), N.ptr(self.p_dens[lvl]), S,
-                                           N.ptr(self.u_base[lvl + 1]), N.ptr(self.jitter[lvl + 1]) if stratified else None,
-                                           N.ptr(self.nears),
-                                           N.ptr(self.fars), 1.0, N.ptr(self.anneal_dev), 0.01, 1e-5,
-                                           1.0 / (2 * (S2 + 1)), self.spacing, n, S2, N.ptr(self.weights[lvl]),
-                                           N.ptr(self.depth_med[lvl]) if self.compute_depths else None,
-                                           N.ptr(self.s_bins[lvl + 1]), N.ptr(self.t_bins[lvl + 1]), st),
-               "proposal_resample")
+        if sel is None:
+            return super()._initial_bins(jit0, per_edge)
+        # the step's batch out of the caller's pool of batches AND the initial bins in one launch (trainer.HipTrainer hands
+        # the selection over instead of launching it: the bins need nears / fars / the draw, not the rays)
+        slot, slots, pool = sel
+        N.check(N.load().nsamd_select_bins(
+            slot, slots, self.n, N.ptr(pool["origins"]), N.ptr(pool["directions"]), N.ptr(pool["cameras"]),
+            N.ptr(pool["target"]), N.ptr(self.origins), N.ptr(self.directions), N.ptr(self.camera_indices), N.ptr(self.target),
+            N.ptr(self.nears), N.ptr(self.fars), N.ptr(self.edges), N.ptr(jit0), int(per_edge), self.counts[0], self.spacing,
+            N.ptr(self.s_bins[0]), N.ptr(self.t_bins[0]), N.stream()), "select_bins")
 
     def forward_main_and_losses(self, updated: bool, terms_ready: bool = False) -> None:
         """Main field on the final samples, compositing, and the three losses with their gradients."""
         self.forward_main(terms_ready)
         self.losses(updated)
 
-    def _field_mlp(self) -> N.FieldMlp:
-        fld = self.model.field
-        return F.field_mlp(*F.field_params(fld), fld.average_init_density)
-
-    def _cams(self, app_const: Optional[Tensor]) -> Optional[Tensor]:
-        """The camera indices the main field reads its appearance rows by (None: no appearance table, or `app_const`)."""
-        return self.camera_indices if (self.model.field.embedding_appearance is not None and app_const is None) else None
-
-    def ray_terms_launch(self, fm: Optional[N.FieldMlp] = None, app_const: Optional[Tensor] = None, select=None) -> None:
-        """nsamd_field_ray_terms for the batch in the static buffers: head layer 0's share of the 48 per-ray inputs. Needs the
-        batch's (pose-corrected) directions and camera indices and the CURRENT head_W0 / head_b0 / appearance table — i.e. it
-        runs after batch selection and after the main-field Adam of the previous iteration. On torch's current stream.
-        app_const: see forward_main (the per-ray inputs are then not kept: no backward reads them). select: the `pending_select`
-        (slot pointer, slots, pool) the same iteration's `forward_proposals` fills the static buffers from — the terms are then
-        read out of the pool itself (the same rows, the same bits) and need not wait for that launch; only without a camera
-        optimiser, whose corrected directions exist nowhere but in the static buffers."""
-        fm = fm if fm is not None else self._field_mlp()
-        inputs = self.ray_inputs if app_const is None else None
-        if select is not None:
-            assert self.cam_opt is None
-            slot, slots, pool = select
-            F.ray_terms_launch(pool["directions"], None if self._cams(app_const) is None else pool["cameras"], app_const, self.n,
-                               fm, self.ray_terms, inputs, slot=slot, slots=slots)
-            return
-        F.ray_terms_launch(self.directions, self._cams(app_const), app_const, self.n, fm, self.ray_terms, inputs)
-
     @profiler.time_function
     def forward_main(self, terms_ready: bool = False, app_const: Optional[Tensor] = None) -> None:
-        """Hash grid + MLPs of the main field on the final samples -> per-sample density and rgb. terms_ready: the caller has
-        launched `ray_terms_launch` for this batch and these parameters itself (trainer.HipTrainer: off the critical path).
-        app_const: one appearance row for every sample instead of the rays' cameras' (eval mode, eval_render.EvalRenderer)."""
-        L = self.n_prop
-        fm = self._field_mlp()
-        if self.ray_terms_on:
-            if not terms_ready:
-                self.ray_terms_launch(fm, app_const)
-            fm.ray_terms = N.ptr(self.ray_terms)
-            fm.ray_inputs = N.ptr(self.ray_inputs if app_const is None else None)
-        # (an eval-mode forward has no backward: no tile is stored, and that of an earlier forward no longer matches f_rgb)
-        self._saved_fresh = self.saved_hb is not None and app_const is None
-        if self._saved_fresh:
-            fm.saved_hb = N.ptr(self.saved_hb)
-        fld = self.model.field
-        tbl = fld.mlp_base.encoding
-        F.field_forward(tbl.hash_table, tbl.spec, fld._transform, fld._box, self._points(L), self.m_main, self.f_enc, self.f_sel,
-                        self.directions, self._cams(app_const), app_const, self.counts[L], fm, self.f_dens, self.f_rgb)
-        self._normals_fresh = False
+        super().forward_main(terms_ready, app_const)
+        self._saved_fresh, self._normals_fresh = app_const is None, False  # (an eval-mode forward stores no tile)
 
     @profiler.time_function
     def losses(self, updated: bool) -> None:
@@ -824,7 +646,7 @@ class NerfactoTrainStep(TrainStepRunner):
     @profiler.time_function
     def backward_proposals(self, levels=None) -> None:
         """Backward of the proposal networks (interlevel loss only; main-level weights are detached, losses.py:119-120).
-        Needs the dw_prop written by forward_backward_main(updated=True). `levels`: subset of proposal levels (their
+        Needs the dw_prop written by losses(updated=True). `levels`: subset of proposal levels (their
         chains share nothing, so they may run on different streams)."""
         lib, st, n = N.load(), N.stream(), self.n
         ck = N.check

@@ -494,7 +494,7 @@ def test_set_depth_target_declines_everything_but_ds_nerf():
     from nerfstudio_amd.train_step import NerfactoTrainStep
 
     step = object.__new__(NerfactoTrainStep)
-    step.depth, step._depth_buffers, step.forward_only = None, None, False
+    step.depth, step._depth_buffers = None, None
     for kind in (2, 3):
         with pytest.raises(NotImplementedError, match="module path"):
             step.set_depth_target(torch.ones(4), torch.ones(4), loss_type=kind)

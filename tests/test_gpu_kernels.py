@@ -1177,31 +1177,39 @@ def test_train_step_runner_matches_autograd_path(F):
             assert float(p.grad.abs().max()) == 0.0, k
 
 
-@pytest.mark.parametrize("forward_only", [False, True])
-def test_runner_two_kernel_proposal_forward_reports_what_the_module_path_reports(F, forward_only):
+@pytest.mark.parametrize("eval_forward", [False, True])
+def test_runner_two_kernel_proposal_forward_reports_what_the_module_path_reports(F, eval_forward):
     """The two-kernel pair behind nsamd_density_field_fwd's NSAMD_ERR_UNSUPPORTED in NerfactoTrainStep.forward_proposals
-    (F.hash_forward + F.density_forward, train and forward-only form). The fused kernel is built for 5 / 8 levels x 16 / 64
-    hidden units and nsamd_density_mlp_fwd for the same four shapes (10 / 16 inputs), so a network that reaches the pair
+    (F.hash_forward + F.density_forward; the training runner, and forward_step.NerfactoForward in eval mode). The fused kernel
+    is built for 5 / 8 levels x 16 / 64 hidden units and nsamd_density_mlp_fwd for the same four shapes (10 / 16 inputs), so a network that reaches the pair
     (3 levels here) has no kernel: the runner must raise the module path's error, word for word, and never return densities."""
     from nerfstudio_amd.cameras.rays import RayBundle
+    from nerfstudio_amd.forward_step import NerfactoForward
     from nerfstudio_amd.train_step import NerfactoTrainStep
 
     cfg = orc.NerfactoCfg(main_grid=orc.HashGridCfg(16, 16, 2048, 12),
                           prop_grids=(orc.HashGridCfg(3, 16, 128, 10), orc.HashGridCfg(3, 16, 256, 10)), num_images=6)
-    model = _hip_model(cfg, orc.init_params(cfg, seed=7, table_std=0.4), training=not forward_only)
+    model = _hip_model(cfg, orc.init_params(cfg, seed=7, table_std=0.4), training=not eval_forward)
     n = 64
     o, d, cam, tgt = orc.synthetic_rays(n, cfg.num_images, seed=8)
     rb = RayBundle(origins=o.cuda(), directions=d.cuda(), pixel_area=torch.full((n, 1), 1e-6).cuda(),
                    camera_indices=cam.cuda()[:, None])
     with pytest.raises(RuntimeError, match=r"density_mlp_fwd failed with status -2") as module_error:
         model(rb)
-    step = NerfactoTrainStep(model, n, torch.device("cuda"), forward_only=forward_only)
-    step.set_batch(o.cuda(), d.cuda(), cam.cuda(), tgt.cuda())
+    step = (NerfactoForward if eval_forward else NerfactoTrainStep)(model, n, torch.device("cuda"))
+    if eval_forward:
+        step.origins.copy_(o.cuda())
+        step.directions.copy_(d.cuda())
+    else:
+        step.set_batch(o.cuda(), d.cuda(), cam.cuda(), tgt.cuda())
     step.jitter.fill_(0.5)
     with pytest.raises(RuntimeError) as runner_error:
-        step.forward_proposals(draw_jitter=False, need_enc=not forward_only, stratified=not forward_only)
+        if eval_forward:
+            step.forward_proposals(draw_jitter=False, stratified=False)
+        else:
+            step.forward_proposals(draw_jitter=False, need_enc=True)
     assert str(runner_error.value) == str(module_error.value)
-    m = n * step.counts[0]  # the pair's buffers exist at the level's size (forward-only: allocated on first use)
+    m = n * step.counts[0]  # the pair's buffers exist at the level's size (NerfactoForward: allocated on first use)
     assert step.p_enc[0].shape == (6, m) and step.p_sel[0].shape == (m,)
     torch.cuda.synchronize()
 
