@@ -93,6 +93,28 @@ void hc_normalise(float* xyz, int64_t n, int transform, const float* lo, const f
   for (int64_t p = 0; p < n; ++p) sel[p] = normalise_position(transform, box, xyz[3 * p], xyz[3 * p + 1], xyz[3 * p + 2]);
 }
 
+// the end of position_gradient (csrc/hashgrid.hip) on dL/d(grid input) g [n,3], in place: back through `positions * selector`,
+// the affine map and the contraction, from the RAW positions xyz
+void hc_position_gradient_tail(const float* xyz, float* g, int64_t n, int transform, const float* lo, const float* hi,
+                               const float* sel) {
+  for (int64_t p = 0; p < n; ++p) {
+    float gx = g[3 * p] * sel[p], gy = g[3 * p + 1] * sel[p], gz = g[3 * p + 2] * sel[p];
+    if (transform == NSAMD_XFORM_CONTRACT) {
+      gx /= 4.0f;
+      gy /= 4.0f;
+      gz /= 4.0f;
+      contract_linf_bwd(xyz[3 * p], xyz[3 * p + 1], xyz[3 * p + 2], gx, gy, gz);
+    } else if (transform == NSAMD_XFORM_AABB) {
+      gx /= (hi[0] - lo[0]);
+      gy /= (hi[1] - lo[1]);
+      gz /= (hi[2] - lo[2]);
+    }
+    g[3 * p] = gx;
+    g[3 * p + 1] = gy;
+    g[3 * p + 2] = gz;
+  }
+}
+
 void hc_sh4(const float* d, int64_t n, float* out /* [n,16] */) {
   for (int64_t p = 0; p < n; ++p) sh4_components(d[3 * p], d[3 * p + 1], d[3 * p + 2], out + 16 * p);
 }

@@ -36,6 +36,7 @@ import pytest
 import torch
 
 from oracle import nerfacto_oracle as orc
+from position_gradient_reference import _contract_bwd, _position_grad  # noqa: F401  (moved there; _position_grad uses the first)
 
 pytestmark = pytest.mark.gpu
 
@@ -694,52 +695,6 @@ def test_fused_producer_route_against_float64(F, init):
 
 
 # ---------------------------------------------------------------- position and ray gradients ---------------------------
-def _contract_bwd(x, gx, gy, gz):
-    """contract_linf_bwd (common.h) vectorised, in the dtype of its arguments."""
-    ax, ay, az = x[:, 0].abs(), x[:, 1].abs(), x[:, 2].abs()
-    mag = torch.maximum(ax, torch.maximum(ay, az))
-    a, inv = 2.0 - 1.0 / mag, 1.0 / mag
-    g_a = gx * (x[:, 0] * inv) + gy * (x[:, 1] * inv) + gz * (x[:, 2] * inv)
-    g_mag = g_a * (inv * inv) - a * (gx * x[:, 0] + gy * x[:, 1] + gz * x[:, 2]) * (inv * inv)
-    t = [(v == mag).to(x.dtype) for v in (ax, ay, az)]
-    cnt = t[0] + t[1] + t[2]
-    out = [g * a * inv + g_mag * torch.sign(x[:, i]) * t[i] / cnt for i, g in enumerate((gx, gy, gz))]
-    inside = mag < 1.0
-    return [torch.where(inside, g, o) for g, o in zip((gx, gy, gz), out)]
-
-
-def _position_grad(raw, table, scal, T, denc, dtype):
-    """dL/d(raw position) of the hash encoding as position_gradient (hashgrid.hip) writes it, evaluated in `dtype` from the
-    fp32 cells, weights and table values."""
-    x, sel = orc.normalise_positions(raw, True)
-    M, L = x.shape[0], len(scal)
-    g = denc.view(M, L, 2).to(dtype)
-    G = [torch.zeros(M, dtype=dtype) for _ in range(3)]
-    for l, s in enumerate(scal):
-        scaled = x * s
-        lo, hi = torch.floor(scaled), torch.ceil(scaled)
-        w = (scaled - lo).to(dtype)
-        lo_i, hi_i = lo.numpy().astype(np.int32), hi.numpy().astype(np.int32)
-        v = []
-        for k in range(8):
-            idx = orc.hash_corner_index((hi_i if k & 1 else lo_i)[:, 0], (hi_i if k & 2 else lo_i)[:, 1],
-                                        (hi_i if k & 4 else lo_i)[:, 2], l, T)
-            v.append(table[torch.from_numpy(idx)].to(dtype))
-        wx, wy, wz = w[:, 0:1], w[:, 1:2], w[:, 2:3]
-        ux, uy, uz = 1 - wx, 1 - wy, 1 - wz
-        yc_zc, yf_zc = v[7] * wx + v[6] * ux, v[5] * wx + v[4] * ux
-        yf_zf, yc_zf = v[1] * wx + v[0] * ux, v[3] * wx + v[2] * ux
-        zc, zf = yc_zc * wy + yf_zc * uy, yc_zf * wy + yf_zf * uy
-        gg = g[:, l]
-        lz = (gg * (zc - zf)).sum(1)
-        g_zc, g_zf = gg * wz, gg * uz
-        ly = (g_zc * (yc_zc - yf_zc) + g_zf * (yc_zf - yf_zf)).sum(1)
-        lx = (g_zc * wy * (v[7] - v[6]) + g_zc * uy * (v[5] - v[4]) + g_zf * uy * (v[1] - v[0]) + g_zf * wy * (v[3] - v[2])).sum(1)
-        G[0], G[1], G[2] = G[0] + lx * s, G[1] + ly * s, G[2] + lz * s
-    G = [gi * sel.to(dtype) / 4.0 for gi in G]
-    return torch.stack(_contract_bwd(raw.to(dtype), *G), dim=1)
-
-
 def _rel_l2(a, b):
     a, b = a.double(), b.double()
     return float((a - b).norm() / max(1e-300, float(b.norm())))
