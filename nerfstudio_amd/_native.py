@@ -62,6 +62,10 @@ class FieldMlpGrads(C.Structure):
                 ("head_W1", vp), ("head_b1", vp), ("head_W2", vp), ("head_b2", vp), ("appearance", vp)]
 
 
+class TsdfVolume(C.Structure):
+    _fields_ = [("origin", f32 * 3), ("voxel_size", f32 * 3), ("dims", i32 * 3), ("truncation", f32)]
+
+
 class ProposalLevelBwd(C.Structure):
     """nsamd_proposal_level_bwd: one proposal level's gated backward chain (nsamd_proposal_levels_bwd)."""
     _fields_ = [("num_rays", i64), ("samples_per_ray", i32),
@@ -158,6 +162,10 @@ _SIGNATURES = {
     "nsamd_probe_mfma16": [vp, vp, vp, vp],
     "nsamd_probe_mfma_bf16": [vp, vp, vp, vp],
 }
+# The same for include/nsamd_export.h, the mesh-export part of the ABI (tests/test_tsdf_cpu.py checks header, library and binding).
+_EXPORT_SIGNATURES = {
+    "nsamd_tsdf_integrate": [TsdfVolume, vp, vp, vp, vp, vp, i32, vp, vp, i32, i32, vp],
+}
 _RESTYPES = {"nsamd_version": C.c_char_p, "nsamd_status_string": C.c_char_p,
              "nsamd_hashgrid_encode_bwd_workspace": C.c_int64, "nsamd_hashgrid_encode_bwd_workspace_state": C.c_int64,
              "nsamd_field_mlp_bwd_scatter_workspace": C.c_int64,
@@ -222,7 +230,7 @@ def load():
     cdll = C.CDLL(path)
     lib = _Lib()
     lib.cdll = cdll
-    for name, argtypes in _SIGNATURES.items():
+    for name, argtypes in {**_SIGNATURES, **_EXPORT_SIGNATURES}.items():
         fn = getattr(cdll, name)  # AttributeError here = header / library mismatch
         fn.argtypes = argtypes
         fn.restype = _RESTYPES.get(name, C.c_int)

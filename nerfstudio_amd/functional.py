@@ -1719,3 +1719,21 @@ def packed_composite(rgb: Tensor, weights: Tensor, ray_indices: Tensor, packed_i
     """accumulate_along_rays compositing of packed samples -> (rgb `[N,3]`, accumulation `[N]`, depth `[N]` or None)."""
     mode, vals = _packed_bg(background)
     return _PackedCompositeFn.apply(rgb, weights, ray_indices, packed_info, t_starts, t_ends, mode, vals, bool(eval_mode))
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# mesh export: TSDF fusion (exporter/tsdf_utils.py:172-274)
+# ---------------------------------------------------------------------------------------------------------------
+def tsdf_integrate_launch(origin: Sequence[float], voxel_size: Sequence[float], truncation: float, values: Tensor, weights: Tensor,
+                          colors: Optional[Tensor], w2c: Tensor, K: Tensor, depth: Tensor, color: Optional[Tensor]) -> None:
+    """nsamd_tsdf_integrate (include/nsamd_export.h) on dense fp32 device tensors: values / weights `[X,Y,Z]` and colors `[X,Y,Z,3]` updated in place by
+    the B views w2c `[B,3,4]`, K `[B,2,3]`, depth `[B,H,W]`, color `[B,H,W,3]` (or None: colours untouched). origin, voxel_size:
+    three host floats each."""
+    N.require_cuda(values, weights, colors, w2c, K, depth, color)
+    vol = N.TsdfVolume()
+    for i in range(3):
+        vol.origin[i], vol.voxel_size[i], vol.dims[i] = float(origin[i]), float(voxel_size[i]), int(values.shape[i])
+    vol.truncation = float(truncation)
+    B, H, W = (int(s) for s in depth.shape)
+    N.check(N.load().nsamd_tsdf_integrate(vol, N.ptr(values), N.ptr(weights), N.ptr(colors), N.ptr(w2c), N.ptr(K), B,
+                                          N.ptr(depth), N.ptr(color), H, W, N.stream()), "tsdf_integrate")
