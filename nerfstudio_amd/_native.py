@@ -166,6 +166,11 @@ _SIGNATURES = {
 _EXPORT_SIGNATURES = {
     "nsamd_tsdf_integrate": [TsdfVolume, vp, vp, vp, vp, vp, i32, vp, vp, i32, i32, vp],
 }
+# And for include/nsamd_render.h, the eval render of the packed path (tests/test_ngp_eval_render_cpu.py checks the three).
+_RENDER_SIGNATURES = {
+    "nsamd_packed_render_fwd": [vp, vp, vp, vp, vp, i64, C.c_int, C.POINTER(f32), C.c_int, vp, vp, vp, vp, vp, vp],
+    "nsamd_packed_ray_points": [vp, vp, vp, vp, vp, i64, vp, vp, vp],
+}
 _RESTYPES = {"nsamd_version": C.c_char_p, "nsamd_status_string": C.c_char_p,
              "nsamd_hashgrid_encode_bwd_workspace": C.c_int64, "nsamd_hashgrid_encode_bwd_workspace_state": C.c_int64,
              "nsamd_field_mlp_bwd_scatter_workspace": C.c_int64,
@@ -230,7 +235,7 @@ def load():
     cdll = C.CDLL(path)
     lib = _Lib()
     lib.cdll = cdll
-    for name, argtypes in {**_SIGNATURES, **_EXPORT_SIGNATURES}.items():
+    for name, argtypes in {**_SIGNATURES, **_EXPORT_SIGNATURES, **_RENDER_SIGNATURES}.items():
         fn = getattr(cdll, name)  # AttributeError here = header / library mismatch
         fn.argtypes = argtypes
         fn.restype = _RESTYPES.get(name, C.c_int)

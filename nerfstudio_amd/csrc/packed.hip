@@ -11,6 +11,7 @@
 // carried running sum (double, like the dense scans of sampler.hip): the scan that gives the transmittance in front of
 // each sample is also what decides, in visibility order, where a ray stops contributing.
 #include "common.h"
+#include "../../include/nsamd_render.h"
 
 namespace nsamd {
 
@@ -24,6 +25,53 @@ __device__ __forceinline__ double pk_scan_inclusive(double v, int lane) {
     if (lane >= d) v += o;
   }
   return v;
+}
+
+// One 64-sample chunk of a ray's transmittance scan, shared by packed_weights_kernel and packed_render_kernel: dd = sigma dt of
+// this lane's sample (0 outside the ray), `carry` = the optical depth in front of the chunk (double, advanced to the next
+// chunk's) -> alpha = 1 - exp(-dd) and the transmittance in front of the sample, T = exp(-(float) exclusive prefix).
+__device__ __forceinline__ void pk_transmittance_chunk(float dd, int lane, double& carry, float& alpha, float& trans) {
+  const double incl = carry + pk_scan_inclusive((double)dd, lane);
+  double excl = __shfl_up(incl, 1);
+  if (lane == 0) excl = carry;
+  carry = __shfl(incl, 63);
+  alpha = 1.0f - expf(-dd);
+  trans = expf(-(float)excl);
+}
+
+// A lane's partial sums of the packed compositing (packed_composite_fwd_kernel, packed_render_kernel): one sample added per
+// call in the lane's own order, the xor butterfly over the wavefront, lane 0's epilogue.
+struct pk_sums {
+  float c0 = 0.f, c1 = 0.f, c2 = 0.f, a = 0.f, dsum = 0.f;
+};
+__device__ __forceinline__ void pk_add_sample(pk_sums& s, float w, float r0, float r1, float r2, int eval_mode) {
+  if (eval_mode) { r0 = nan_to_num(r0); r1 = nan_to_num(r1); r2 = nan_to_num(r2); }
+  s.c0 += w * r0; s.c1 += w * r1; s.c2 += w * r2;
+  s.a += w;
+}
+__device__ __forceinline__ void pk_add_depth(pk_sums& s, float w, float ts, float te) { s.dsum += w * ((ts + te) / 2.0f); }
+__device__ __forceinline__ void pk_reduce(pk_sums& s) {
+#pragma unroll
+  for (int m = 1; m < 64; m <<= 1) {
+    s.c0 += __shfl_xor(s.c0, m); s.c1 += __shfl_xor(s.c1, m); s.c2 += __shfl_xor(s.c2, m);
+    s.a += __shfl_xor(s.a, m); s.dsum += __shfl_xor(s.dsum, m);
+  }
+}
+// (lane 0) background, eval clamp, expected depth dsum / (acc + 1e-10)
+__device__ __forceinline__ void pk_write_ray(pk_sums s, int64_t ray, int bg_mode, float bg0, float bg1, float bg2, int eval_mode,
+                                             float* __restrict__ out_rgb, float* __restrict__ out_acc,
+                                             float* __restrict__ out_depth) {
+  float c0 = s.c0, c1 = s.c1, c2 = s.c2;
+  const float a = s.a;
+  if (bg_mode == 1) {  // a constant colour
+    c0 = c0 + bg0 * (1.0f - a); c1 = c1 + bg1 * (1.0f - a); c2 = c2 + bg2 * (1.0f - a);
+  }
+  if (eval_mode) {
+    c0 = fminf(fmaxf(c0, 0.0f), 1.0f); c1 = fminf(fmaxf(c1, 0.0f), 1.0f); c2 = fminf(fmaxf(c2, 0.0f), 1.0f);
+  }
+  out_rgb[3 * ray] = c0; out_rgb[3 * ray + 1] = c1; out_rgb[3 * ray + 2] = c2;
+  out_acc[ray] = a;
+  if (out_depth != nullptr) out_depth[ray] = s.dsum / (a + 1e-10f);
 }
 
 // ---- occupancy-grid marching ---------------------------------------------------------------------------------------
@@ -260,12 +308,8 @@ __global__ __launch_bounds__(kPackThreads) void packed_weights_kernel(
     const int64_t i = i0 + lane;
     const bool in = i < cnt;
     const float dd = in ? sigmas[s0 + i] * (t_ends[s0 + i] - t_starts[s0 + i]) : 0.0f;
-    const double incl = carry + pk_scan_inclusive((double)dd, lane);
-    double excl = __shfl_up(incl, 1);
-    if (lane == 0) excl = carry;
-    carry = __shfl(incl, 63);
-    const float alpha = 1.0f - expf(-dd);
-    const float trans = expf(-(float)excl);
+    float alpha, trans;
+    pk_transmittance_chunk(dd, lane, carry, alpha, trans);
     if (kVisibility) {
       const bool k = in && trans >= early_stop_eps && alpha >= alpha_thre;
       if (in) mask[s0 + i] = k ? 1 : 0;
@@ -370,30 +414,62 @@ __global__ __launch_bounds__(kPackThreads) void packed_composite_fwd_kernel(
   const int64_t ray = (int64_t)blockIdx.x * kPackWaves + (threadIdx.x >> 6);
   if (ray >= num_rays) return;
   const int64_t s0 = info[2 * ray], cnt = info[2 * ray + 1];
-  float c0 = 0.f, c1 = 0.f, c2 = 0.f, a = 0.f, dsum = 0.f;
+  pk_sums s;
   for (int64_t i = lane; i < cnt; i += 64) {
     const float w = weights[s0 + i];
-    float r0 = rgb[3 * (s0 + i)], r1 = rgb[3 * (s0 + i) + 1], r2 = rgb[3 * (s0 + i) + 2];
-    if (eval_mode) { r0 = nan_to_num(r0); r1 = nan_to_num(r1); r2 = nan_to_num(r2); }
-    c0 += w * r0; c1 += w * r1; c2 += w * r2;
-    a += w;
-    if (t_starts != nullptr) dsum += w * ((t_starts[s0 + i] + t_ends[s0 + i]) / 2.0f);
+    pk_add_sample(s, w, rgb[3 * (s0 + i)], rgb[3 * (s0 + i) + 1], rgb[3 * (s0 + i) + 2], eval_mode);
+    if (t_starts != nullptr) pk_add_depth(s, w, t_starts[s0 + i], t_ends[s0 + i]);
   }
+  pk_reduce(s);
+  if (lane == 0) pk_write_ray(s, ray, bg_mode, bg0, bg1, bg2, eval_mode, out_rgb, out_acc, out_depth);
+}
+
+// Weights, compositing and the ray's range of sample midpoints in one pass (the eval render's per-ray tail): the scan of
+// packed_weights_kernel<false> chunk by chunk, each lane adding its sample of the chunk to the sums of
+// packed_composite_fwd_kernel — the same operations in the same order as the two launches, hence the same bits, with the
+// weights never written: 24 B read per sample (interval, density, colour) instead of 40 B moved. No early exit once the
+// transmittance has underflowed: the two launches have none, and 0 * NaN must stay NaN without eval_mode.
+// mid_lo / mid_hi (nullable together): min / max of (t_start + t_end) / 2 over the ray's samples, +inf / -inf without any.
+__global__ __launch_bounds__(kPackThreads) void packed_render_kernel(
+    const float* __restrict__ t_starts, const float* __restrict__ t_ends, const float* __restrict__ sigmas,
+    const float* __restrict__ rgb, const int64_t* __restrict__ info, int64_t num_rays, int bg_mode, float bg0, float bg1,
+    float bg2, int eval_mode, float* __restrict__ out_rgb, float* __restrict__ out_acc, float* __restrict__ out_depth,
+    float* __restrict__ mid_lo, float* __restrict__ mid_hi) {
+  const int lane = threadIdx.x & 63;
+  const int64_t ray = (int64_t)blockIdx.x * kPackWaves + (threadIdx.x >> 6);
+  if (ray >= num_rays) return;  // wave-uniform
+  const int64_t s0 = info[2 * ray], cnt = info[2 * ray + 1];
+  double carry = 0.0;
+  pk_sums s;
+  float lo = __builtin_inff(), hi = -__builtin_inff();
+  for (int64_t i0 = 0; i0 < cnt; i0 += 64) {
+    const int64_t i = i0 + lane;
+    const bool in = i < cnt;
+    const float ts = in ? t_starts[s0 + i] : 0.0f, te = in ? t_ends[s0 + i] : 0.0f;
+    const float dd = in ? sigmas[s0 + i] * (te - ts) : 0.0f;
+    float alpha, trans;
+    pk_transmittance_chunk(dd, lane, carry, alpha, trans);
+    if (in) {
+      const float w = trans * alpha;
+      pk_add_sample(s, w, rgb[3 * (s0 + i)], rgb[3 * (s0 + i) + 1], rgb[3 * (s0 + i) + 2], eval_mode);
+      pk_add_depth(s, w, ts, te);
+      const float mid = (ts + te) / 2.0f;
+      lo = fminf(lo, mid);
+      hi = fmaxf(hi, mid);
+    }
+  }
+  pk_reduce(s);
 #pragma unroll
   for (int m = 1; m < 64; m <<= 1) {
-    c0 += __shfl_xor(c0, m); c1 += __shfl_xor(c1, m); c2 += __shfl_xor(c2, m);
-    a += __shfl_xor(a, m); dsum += __shfl_xor(dsum, m);
+    lo = fminf(lo, __shfl_xor(lo, m));
+    hi = fmaxf(hi, __shfl_xor(hi, m));
   }
   if (lane == 0) {
-    if (bg_mode == 1) {  // a constant colour
-      c0 = c0 + bg0 * (1.0f - a); c1 = c1 + bg1 * (1.0f - a); c2 = c2 + bg2 * (1.0f - a);
+    pk_write_ray(s, ray, bg_mode, bg0, bg1, bg2, eval_mode, out_rgb, out_acc, out_depth);
+    if (mid_lo != nullptr) {
+      mid_lo[ray] = lo;
+      mid_hi[ray] = hi;
     }
-    if (eval_mode) {
-      c0 = fminf(fmaxf(c0, 0.0f), 1.0f); c1 = fminf(fmaxf(c1, 0.0f), 1.0f); c2 = fminf(fmaxf(c2, 0.0f), 1.0f);
-    }
-    out_rgb[3 * ray] = c0; out_rgb[3 * ray + 1] = c1; out_rgb[3 * ray + 2] = c2;
-    out_acc[ray] = a;
-    if (out_depth != nullptr) out_depth[ray] = dsum / (a + 1e-10f);
   }
 }
 
@@ -421,15 +497,31 @@ __global__ void packed_composite_bwd_kernel(const float* __restrict__ rgb, const
 
 // positions of packed samples: o[ray] + d[ray] * (t_start + t_end) / 2  (the sigma_fn of VolumetricSampler,
 // ray_samplers.py:420-429, and Frustums.get_positions for the packed RaySamples)
+__device__ __forceinline__ void pk_position(const float* __restrict__ origins, const float* __restrict__ directions, int64_t ray,
+                                            float t_start, float t_end, float* __restrict__ out) {
+  const float span = t_start + t_end;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) out[k] = origins[3 * ray + k] + directions[3 * ray + k] * span / 2.0f;
+}
 __global__ void packed_positions_kernel(const float* __restrict__ origins, const float* __restrict__ directions,
                                         const int64_t* __restrict__ ray_indices, const float* __restrict__ t_starts,
                                         const float* __restrict__ t_ends, int64_t n, float* __restrict__ positions) {
   const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= n) return;
+  pk_position(origins, directions, ray_indices[s], t_starts[s], t_ends[s], positions + 3 * s);
+}
+// the same positions and, beside them, the direction row of each sample's ray (what the field takes per sample): one launch
+// for packed_positions_kernel + an index_select of the directions
+__global__ void packed_ray_points_kernel(const float* __restrict__ origins, const float* __restrict__ directions,
+                                         const int64_t* __restrict__ ray_indices, const float* __restrict__ t_starts,
+                                         const float* __restrict__ t_ends, int64_t n, float* __restrict__ positions,
+                                         float* __restrict__ sample_directions) {
+  const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= n) return;
   const int64_t ray = ray_indices[s];
-  const float span = t_starts[s] + t_ends[s];
+  pk_position(origins, directions, ray, t_starts[s], t_ends[s], positions + 3 * s);
 #pragma unroll
-  for (int k = 0; k < 3; ++k) positions[3 * s + k] = origins[3 * ray + k] + directions[3 * ray + k] * span / 2.0f;
+  for (int k = 0; k < 3; ++k) sample_directions[3 * s + k] = directions[3 * ray + k];
 }
 
 static unsigned pack_ray_blocks(int64_t rays) { return (unsigned)((rays + kPackWaves - 1) / kPackWaves); }
@@ -763,6 +855,40 @@ extern "C" int nsamd_packed_positions(const float* origins, const float* directi
   if (nb > 0x7fffffffLL) return NSAMD_ERR_UNSUPPORTED;
   packed_positions_kernel<<<(unsigned)nb, 256, 0, (hipStream_t)stream>>>(origins, directions, ray_indices, t_starts,
                                                                         t_ends, num_samples, positions);
+  NSAMD_CHECK_LAUNCH();
+  return NSAMD_OK;
+}
+
+extern "C" int nsamd_packed_render_fwd(const float* t_starts, const float* t_ends, const float* sigmas, const float* rgb,
+                                       const int64_t* packed_info, int64_t num_rays, int background_mode,
+                                       const float* background_rgb_host, int eval_mode, float* out_rgb, float* out_accumulation,
+                                       float* out_depth, float* out_mid_lo, float* out_mid_hi, nsamd_stream_t stream) {
+  NSAMD_REQUIRE(num_rays >= 0 && (background_mode == 0 || background_mode == 1));
+  NSAMD_REQUIRE((out_mid_lo == nullptr) == (out_mid_hi == nullptr));
+  if (num_rays == 0) return NSAMD_OK;
+  NSAMD_REQUIRE(t_starts && t_ends && sigmas && rgb && packed_info && out_rgb && out_accumulation && out_depth);
+  NSAMD_REQUIRE(background_mode == 0 || background_rgb_host != nullptr);
+  const int64_t nb = (num_rays + kPackWaves - 1) / kPackWaves;
+  if (nb > 0x7fffffffLL) return NSAMD_ERR_UNSUPPORTED;
+  const float b0 = background_mode ? background_rgb_host[0] : 0.f, b1 = background_mode ? background_rgb_host[1] : 0.f,
+              b2 = background_mode ? background_rgb_host[2] : 0.f;
+  packed_render_kernel<<<(unsigned)nb, kPackThreads, 0, (hipStream_t)stream>>>(
+      t_starts, t_ends, sigmas, rgb, packed_info, num_rays, background_mode, b0, b1, b2, eval_mode, out_rgb, out_accumulation,
+      out_depth, out_mid_lo, out_mid_hi);
+  NSAMD_CHECK_LAUNCH();
+  return NSAMD_OK;
+}
+
+extern "C" int nsamd_packed_ray_points(const float* origins, const float* directions, const int64_t* ray_indices,
+                                       const float* t_starts, const float* t_ends, int64_t num_samples, float* positions,
+                                       float* sample_directions, nsamd_stream_t stream) {
+  NSAMD_REQUIRE(num_samples >= 0);
+  if (num_samples == 0) return NSAMD_OK;
+  NSAMD_REQUIRE(origins && directions && ray_indices && t_starts && t_ends && positions && sample_directions);
+  const int64_t nb = (num_samples + 255) / 256;
+  if (nb > 0x7fffffffLL) return NSAMD_ERR_UNSUPPORTED;
+  packed_ray_points_kernel<<<(unsigned)nb, 256, 0, (hipStream_t)stream>>>(origins, directions, ray_indices, t_starts, t_ends,
+                                                                         num_samples, positions, sample_directions);
   NSAMD_CHECK_LAUNCH();
   return NSAMD_OK;
 }

@@ -235,22 +235,16 @@ class EvalRenderer:
         s, n = self.step, self.chunk
         dev = s.origins.device
         c2w = c2w.reshape(3, 4).to(device=dev, dtype=torch.float32).contiguous()
-        lib, st = N.load(), N.stream()
-        if lens is None:
-            def load_chunk(a, k):
-                N.check(lib.nsamd_raygen_pinhole_grid(N.ptr(c2w), float(fx), float(fy), float(cx), float(cy), int(width), a, k, n,
-                                                      N.ptr(s.origins), N.ptr(s.directions), None, st), "raygen_pinhole_grid")
-        else:
+        if lens is not None:
             camera_type, dist = int(lens[0]), lens[1]
             if camera_type not in F.LENS_TYPES:
                 raise ValueError(f"render_camera: camera type {camera_type} is not one of {sorted(F.LENS_TYPES)}")
             if dist is not None:
                 dist = torch.as_tensor(dist).reshape(6).to(device=dev, dtype=torch.float32).contiguous()
+            lens = (camera_type, dist)
 
-            def load_chunk(a, k):
-                N.check(lib.nsamd_raygen_lens_grid(N.ptr(c2w), float(fx), float(fy), float(cx), float(cy), camera_type,
-                                                   N.ptr(dist), int(width), a, k, n, N.ptr(s.origins), N.ptr(s.directions), None,
-                                                   st), "raygen_lens_grid")
+        def load_chunk(a, k):
+            F.raygen_grid_launch(c2w, fx, fy, cx, cy, lens, width, a, k, n, s.origins, s.directions)
 
         out = self._render_rays(int(height) * int(width), dev, load_chunk)
         return {k_: v.view(int(height), int(width), -1) for k_, v in out.items()}

@@ -32,6 +32,7 @@ from torch import Tensor
 from . import _native as N
 from . import eval_render
 from . import functional as F
+from . import ngp_eval_render
 
 PERSPECTIVE = 1  # CameraType.PERSPECTIVE (cameras/cameras.py:41-52)
 _CAMERA_TYPE_NAMES = {1: "PERSPECTIVE", 2: "FISHEYE", 3: "EQUIRECTANGULAR", 4: "OMNIDIRECTIONALSTEREO_L",
@@ -180,7 +181,8 @@ def fuse_views(model, cameras, volume: TSDFVolume, downscale_factor=2, views_per
     """Render every camera of `cameras` at 1 / downscale_factor of its resolution — pinhole, distortion disabled, as
     tsdf_utils.py:330-339 asks — and fuse the frames into `volume`, `views_per_launch` views per launch, in camera order.
     Returns the number of launches. render_fn(c2w, fx, fy, cx, cy, H, W) -> dict of `[H,W,C]` device tensors replaces the
-    model's EvalRenderer (required for a model `eval_render.supported` refuses)."""
+    model's own runner — NgpEvalRenderer for a model `ngp_eval_render.supported` accepts, else EvalRenderer — and is required for
+    a model both refuse."""
     views = scaled_pinhole_cameras(cameras, downscale_factor)
     V = int(views_per_launch)
     if V < 1:
@@ -189,12 +191,14 @@ def fuse_views(model, cameras, volume: TSDFVolume, downscale_factor=2, views_per
     launches = 0
     with _eval_mode(model):
         if render_fn is None:
-            normals = bool(getattr(model.config, "predict_normals", False))
-            reason = eval_render.supported(model, normals=normals)
-            if reason is not None:
-                raise ValueError(f"fuse_views: the eval renderer does not cover this model ({reason}); pass render_fn")
+            ngp = ngp_eval_render.supported(model) is None  # an instant-ngp model: its own runner (depth and rgb are all it takes)
+            if not ngp:
+                normals = bool(getattr(model.config, "predict_normals", False))
+                reason = eval_render.supported(model, normals=normals)
+                if reason is not None:
+                    raise ValueError(f"fuse_views: the eval renderer does not cover this model ({reason}); pass render_fn")
             N.require_cuda(volume.values)
-            runner = eval_render.runner_for(model, dev)
+            runner = (ngp_eval_render if ngp else eval_render).runner_for(model, dev)
             if runner is None:
                 raise RuntimeError("fuse_views: the device-side eval renderer is switched off (NSAMD_EVAL_RUNNER=0)")
             render_fn = lambda *view: runner.render_camera(*view, lens=None)  # noqa: E731

@@ -1377,6 +1377,22 @@ def raygen_pinhole(ray_indices: Tensor, c2w: Tensor, fx: Tensor, fy: Tensor, cx:
     return o, d, pa, dn
 
 
+def raygen_grid_launch(c2w: Tensor, fx: float, fy: float, cx: float, cy: float, lens, width: int, first: int, count: int, rows: int,
+                       origins: Tensor, directions: Tensor) -> None:
+    """nsamd_raygen_pinhole_grid (lens None) or nsamd_raygen_lens_grid (lens = (camera type 1 - 3, its six distortion parameters on
+    the device or None)) on the current stream: the rays of pixels first .. first + count - 1 of ONE camera's row-major grid of
+    width `width` into the first `rows` >= count rows of the eval loops' input buffers, rows count .. rows - 1 repeating the last
+    pixel. c2w `[3, 4]` on the device, intrinsics by value."""
+    lib = N.load()
+    if lens is None:
+        N.check(lib.nsamd_raygen_pinhole_grid(N.ptr(c2w), float(fx), float(fy), float(cx), float(cy), int(width), first, count, rows,
+                                              N.ptr(origins), N.ptr(directions), None, N.stream()), "raygen_pinhole_grid")
+    else:
+        N.check(lib.nsamd_raygen_lens_grid(N.ptr(c2w), float(fx), float(fy), float(cx), float(cy), int(lens[0]), N.ptr(lens[1]),
+                                           int(width), first, count, rows, N.ptr(origins), N.ptr(directions), None, N.stream()),
+                "raygen_lens_grid")
+
+
 LENS_TYPES = {1: "PERSPECTIVE", 2: "FISHEYE", 3: "EQUIRECTANGULAR"}  # CameraType values the lens generator covers
 _CAMERA_TYPE_NAMES = {**LENS_TYPES, 4: "OMNIDIRECTIONALSTEREO_L", 5: "OMNIDIRECTIONALSTEREO_R", 6: "VR180_L", 7: "VR180_R",
                       8: "ORTHOPHOTO", 9: "FISHEYE624"}  # cameras/cameras.py:41-52
@@ -1567,6 +1583,26 @@ def packed_composite_launch(rgb: Tensor, weights: Tensor, t_starts: Optional[Ten
     N.check(N.load().nsamd_packed_composite_fwd(N.ptr(rgb), N.ptr(weights), N.ptr(t_starts), N.ptr(t_ends), N.ptr(packed_info),
                                                 n, bg_mode, bg_vals, int(eval_mode), N.ptr(out_rgb),
                                                 N.ptr(acc), N.ptr(depth), N.stream()), "packed_composite_fwd")
+
+
+def packed_render_launch(t_starts: Tensor, t_ends: Tensor, sigmas: Tensor, rgb: Tensor, packed_info: Tensor, n: int, bg_mode: int,
+                         bg_vals, eval_mode: bool, out_rgb: Tensor, acc: Tensor, depth: Tensor, mid_lo: Optional[Tensor],
+                         mid_hi: Optional[Tensor]) -> None:
+    """nsamd_packed_render_fwd (include/nsamd_render.h) on the current stream: `packed_weights_launch` followed by
+    `packed_composite_launch` in one pass — the same bits, the weights never in memory — and (both or neither) the rays' minimum
+    / maximum sample midpoint `mid_lo` / `mid_hi` `[n]`."""
+    N.check(N.load().nsamd_packed_render_fwd(N.ptr(t_starts), N.ptr(t_ends), N.ptr(sigmas), N.ptr(rgb), N.ptr(packed_info), n,
+                                             bg_mode, bg_vals, int(eval_mode), N.ptr(out_rgb), N.ptr(acc), N.ptr(depth),
+                                             N.ptr(mid_lo), N.ptr(mid_hi), N.stream()), "packed_render_fwd")
+
+
+def packed_ray_points_launch(origins: Tensor, directions: Tensor, ray_indices: Tensor, t_starts: Tensor, t_ends: Tensor,
+                             count: int, positions: Tensor, sample_directions: Tensor) -> None:
+    """nsamd_packed_ray_points (include/nsamd_render.h) on the current stream: `packed_positions_launch` of the first `count`
+    packed samples and, beside the positions, each sample's row of `directions`."""
+    N.check(N.load().nsamd_packed_ray_points(N.ptr(origins), N.ptr(directions), N.ptr(ray_indices), N.ptr(t_starts),
+                                             N.ptr(t_ends), count, N.ptr(positions), N.ptr(sample_directions), N.stream()),
+            "packed_ray_points")
 
 
 def packed_composite_backward_launch(rgb: Tensor, weights: Tensor, ray_indices: Tensor, count: int, bg_mode: int, bg_vals,

@@ -170,8 +170,29 @@ class NGPModel(nn.Module):
         return {"rgb_loss": self.rgb_loss(image, pred_rgb)}
 
     @torch.no_grad()
+    def get_outputs_for_camera(self, camera, obb_box=None) -> Dict[str, Tensor]:
+        """models/base_model.py:166-175. Eval mode, one perspective camera (undistorted, or with OpenCV distortion parameters),
+        no crop box: the rays of each chunk are generated inside the device-side chunk loop
+        (ngp_eval_render.NgpEvalRenderer.render_camera); anything else generates the bundle — a crop box's nears / fars on it
+        reach the marcher through `render` — and takes the method below."""
+        from . import eval_render, ngp_eval_render
+
+        args = eval_render.in_loop_camera_args(camera) if obb_box is None else None
+        runner = ngp_eval_render.runner_for(self, next(self.parameters()).device) if args is not None else None
+        if runner is not None:
+            return runner.render_camera(*args[0], lens=args[1])
+        return self.get_outputs_for_camera_ray_bundle(camera.generate_rays(camera_indices=0, keep_shape=True, obb_box=obb_box))
+
+    @torch.no_grad()
     def get_outputs_for_camera_ray_bundle(self, camera_ray_bundle: RayBundle) -> Dict[str, Tensor]:
-        """Chunked full-image render (models/base_model.py:178-205)."""
+        """Chunked full-image render (models/base_model.py:178-205). In eval mode on the GPU the chunk loop is device-side
+        (ngp_eval_render.NgpEvalRenderer: static buffers, the per-ray tail in one launch, the next chunk counted while this one's
+        field runs); NSAMD_EVAL_RUNNER=0, training mode or an unsupported configuration take the Python loop over `forward`."""
+        from . import ngp_eval_render
+
+        runner = ngp_eval_render.runner_for(self, camera_ray_bundle.origins.device)
+        if runner is not None:
+            return runner.render(camera_ray_bundle)
         image_shape = camera_ray_bundle.origins.shape[:-1]
         num_rays = len(camera_ray_bundle)
         outs: Dict[str, List[Tensor]] = {}

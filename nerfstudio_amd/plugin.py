@@ -270,6 +270,45 @@ def install_hip_ngp_modules(model: Any) -> None:
     model.renderer_depth = DepthRenderer(method="expected")
 
 
+def _ngp_eval_runner(model: Any, device):
+    """HipNGPModel's device-side eval loop for rays on `device`, or None: the reference's own loop. The model's `_hip_flush` hook
+    (pipeline.EngineSeam.attach_optimizers installs one) first applies a pending parameter update. Model.forward puts a
+    collider's nears / fars on every chunk (models/base_model.py:140-141); instant-ngp has none (models/instant_ngp.py:48-51),
+    and only such a model takes the device-side loop."""
+    from . import ngp_eval_render
+
+    flush = getattr(model, "_hip_flush", None)
+    if flush is not None:
+        flush()
+    if getattr(model, "collider", None) is not None or torch.device(device) != torch.device(model.device):
+        return None
+    return ngp_eval_render.runner_for(model, device)
+
+
+def ngp_outputs_for_camera(model: Any, camera, obb_box, reference_path):
+    """HipNGPModel.get_outputs_for_camera. One perspective camera without a crop box, in eval mode on the model's GPU: the rays
+    of every chunk are generated inside the device-side chunk loop (ngp_eval_render.NgpEvalRenderer.render_camera). Anything
+    else is `reference_path`, the reference's own method: its bundle — with a crop box's nears / fars — comes back through
+    `ngp_outputs_for_camera_ray_bundle`."""
+    from . import eval_render
+
+    args = eval_render.in_loop_camera_args(camera) if obb_box is None else None
+    runner = _ngp_eval_runner(model, model.device)
+    if runner is not None and args is not None:
+        return runner.render_camera(*args[0], lens=args[1])
+    return reference_path(camera, obb_box=obb_box)
+
+
+def ngp_outputs_for_camera_ray_bundle(model: Any, camera_ray_bundle, reference_path):
+    """HipNGPModel.get_outputs_for_camera_ray_bundle. In eval mode, with the rays already on the model's GPU, the chunk loop is
+    the device-side one (ngp_eval_render.NgpEvalRenderer); anything else takes `reference_path`, the reference's own loop.
+    NSAMD_EVAL_RUNNER=0 switches it off."""
+    runner = _ngp_eval_runner(model, camera_ray_bundle.origins.device)
+    if runner is not None:
+        return runner.render(camera_ray_bundle)
+    return reference_path(camera_ray_bundle)
+
+
 def _ngp_model_classes():
     """(HipInstantNGPModelConfig, HipNGPModel), built ONCE against the installed nerfstudio (which imports nerfacc)."""
     if "HipNGPModel" in globals():
@@ -314,6 +353,14 @@ def _ngp_model_classes():
             if "ngp_step" in outputs:
                 return outputs["ngp_step"].get_loss_dict(outputs, batch)
             return super().get_loss_dict(outputs, batch, metrics_dict)
+
+        @torch.no_grad()
+        def get_outputs_for_camera(self, camera, obb_box=None):  # models/base_model.py:165-175 (viewer, ns-render)
+            return ngp_outputs_for_camera(self, camera, obb_box, super().get_outputs_for_camera)
+
+        @torch.no_grad()
+        def get_outputs_for_camera_ray_bundle(self, camera_ray_bundle):  # models/base_model.py:177-205
+            return ngp_outputs_for_camera_ray_bundle(self, camera_ray_bundle, super().get_outputs_for_camera_ray_bundle)
 
     @dataclass
     class HipInstantNGPModelConfig(InstantNGPModelConfig):
