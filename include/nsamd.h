@@ -671,12 +671,16 @@ int nsamd_occgrid_march_write_stashed(const float* origins, const float* directi
 /* Occupancy-grid maintenance — what nerfacc's OccGridEstimator.update_every_n_steps does around `occ_eval_fn` (call site
  * models/instant_ngp.py:151-156; nerfacc 0.5.2 restated, see above):
  *   _cell_positions   positions [M,3] inside the cells `cells` [M] (flat index over [levels, R, R, R]; NULL: cell i = i) at
- *                     the fractional offsets jitter [M,3] in [0,1) — the points the density is evaluated at;
+ *                     the fractional offsets jitter [M,3] in [0,1) — the points the density is evaluated at; clamped to
+ *                     the fp32 numbers inside the cell's closed box (the box in double from the fp32 region of interest);
  *   _update           occs[c] = max(occs[c] * ema_decay, the new estimates of cell c)  for the listed cells (repeats
- *                     allowed, the result does not depend on the thread order); scratch: total_cells floats;
- *   _binarise         binaries = occs > min(mean(occs), occ_thre) (mean in double, fixed summation order) and the coarse
- *                     bitfield of the result (nullable); scratch: 1024 doubles; threshold_out (nullable) [2] = (threshold,
- *                     mean) in device memory. */
+ *                     allowed, the result does not depend on the thread order); scratch: total_cells floats; an
+ *                     estimate counts as max(estimate, +0), a NaN estimate of either sign leaves the cell NaN;
+ *   _binarise         binaries = occs > min(mean, occ_thre), mean = the mean over the cells with occs >= 0 (nerfacc's cells
+ *                     "evaluated so far": a NaN or negative cell enters neither sum nor count; 0 when there is none; sum and
+ *                     count in double, fixed summation order), and the coarse bitfield of the result (nullable; a pointer
+ *                     for a shape without a bitfield, nsamd_occgrid_coarse_words == 0, is INVALID_ARG and nothing is
+ *                     launched); scratch: 1024 doubles; threshold_out (nullable) [2] = (threshold, mean) in device memory. */
 int64_t nsamd_occgrid_coarse_words(int32_t levels, int32_t resolution);
 int nsamd_occgrid_cell_positions(const int64_t* cells, int64_t M, nsamd_occgrid grid, const float* jitter, float* positions,
                                  nsamd_stream_t stream);

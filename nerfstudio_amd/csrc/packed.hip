@@ -528,7 +528,17 @@ static unsigned pack_ray_blocks(int64_t rays) { return (unsigned)((rays + kPackW
 
 // ---- occupancy-grid maintenance (nerfacc OccGridEstimator.update_every_n_steps / _update) ---------------------------
 // x[i] = position inside cell `cells[i]` (flat index over [levels, R, R, R]; nullptr: cell i) at the fractional offset
-// jitter[i] in [0,1)^3: level l covers the region of interest scaled by 2^l about its centre.
+// jitter[i] in [0,1)^3: level l covers the region of interest scaled by 2^l about its centre. The fp32 evaluation lands up
+// to an ulp or two outside the cell when the offset is 0 or next to 1 and the cell's edge is no fp32 number (R not a power
+// of two): the result is clamped to the fp32 numbers inside the cell's closed box, the box taken in double from the fp32
+// region of interest ((centre - half) + (ix / R) (2 half) and the same with ix + 1, in this order), so the density is
+// never evaluated in a neighbour of the cell it is stored for.
+__device__ __forceinline__ float occgrid_clamp_into(float x, double lo, double hi) {
+  float lof = (float)lo, hif = (float)hi;  // round to nearest, then step inside
+  if ((double)lof < lo) lof = nextafterf(lof, 3.4028234663852886e38f);
+  if ((double)hif > hi) hif = nextafterf(hif, -3.4028234663852886e38f);
+  return x < lof ? lof : (x > hif ? hif : x);  // (a NaN stays)
+}
 __global__ __launch_bounds__(256) void occgrid_cell_positions_kernel(const int64_t* __restrict__ cells, int64_t M,
                                                                      nsamd_occgrid grid, const float* __restrict__ jitter,
                                                                      float* __restrict__ x) {
@@ -544,14 +554,19 @@ __global__ __launch_bounds__(256) void occgrid_cell_positions_kernel(const int64
     const float u = ((float)ix[k] + jitter[3 * i + k]) / (float)R;  // in [0,1) of the level's box
     const float centre = (grid.aabb[k] + grid.aabb[3 + k]) / 2.0f;
     const float half = (grid.aabb[3 + k] - grid.aabb[k]) / 2.0f * grow;
-    x[3 * i + k] = (centre - half) + (u * 2.0f) * half;
+    const double cd = ((double)grid.aabb[k] + (double)grid.aabb[3 + k]) / 2.0;
+    const double hd = ((double)grid.aabb[3 + k] - (double)grid.aabb[k]) / 2.0 * (double)grow;
+    const double lo = (cd - hd) + ((double)ix[k] / (double)R) * (2.0 * hd);
+    const double hi = (cd - hd) + ((double)(ix[k] + 1) / (double)R) * (2.0 * hd);
+    x[3 * i + k] = occgrid_clamp_into((centre - half) + (u * 2.0f) * half, lo, hi);
   }
 }
 
 // occs[c] = max(old[c] * decay, every new estimate of c): `old` is a snapshot of occs taken before the call, so repeated
-// cells (the refresh draws random cells WITH replacement) all write the same decayed value, and the estimates — all
-// >= 0, so their float bits order like integers — are folded in with an integer atomicMax: the result does not depend
-// on the order of the threads. NaN estimates (a diverged field) compare above every number and stay.
+// cells (the refresh draws random cells WITH replacement) all write the same decayed value, and the estimates — clamped
+// to >= +0, so their float bits order like integers — are folded in with an integer atomicMax: the result does not depend
+// on the order of the threads. A NaN estimate (a diverged field) of either sign is folded in as the positive quiet NaN
+// 0x7FC00000, which as an integer is above every number's bits, +inf included: the cell stays NaN until it is decayed again.
 __global__ __launch_bounds__(256) void occgrid_decay_kernel(float* __restrict__ occs, const float* __restrict__ old,
                                                             const int64_t* __restrict__ cells, int64_t M, float decay) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -564,37 +579,61 @@ __global__ __launch_bounds__(256) void occgrid_max_kernel(float* __restrict__ oc
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= M) return;
   const int64_t c = cells != nullptr ? cells[i] : i;
-  const float v = fmaxf(occ_new[i], 0.0f);  // (NaN -> 0 under fmaxf; estimates are density x step >= 0)
-  atomicMax(reinterpret_cast<int*>(occs) + c, __float_as_int(occ_new[i] != occ_new[i] ? occ_new[i] : v));
+  const float e = occ_new[i];
+  // negative estimates and -0.0 count as +0 (estimates are density x step >= 0); a NaN's own bits may carry the sign bit,
+  // which would make it the SMALLEST integer
+  const int bits = e != e ? 0x7FC00000 : __float_as_int(e > 0.0f ? e : 0.0f);
+  atomicMax(reinterpret_cast<int*>(occs) + c, bits);
 }
 
-// mean(occs) in double with a fixed summation order (kSumBlocks contiguous ranges, a fixed tree inside each, the partials
-// added in index order), threshold = min(mean, occ_thre) rounded to fp32 once, binaries = occs > threshold, and the
-// coarse bitfield the marcher stages in LDS (one bit per 4x4x4 block of cells).
-constexpr int kSumBlocks = 1024;
+// The mean of nerfacc's rule runs over the cells evaluated so far, occs >= 0 (oracle/packed_oracle.py::occgrid_thresholds):
+// a NaN cell (a diverged field) or a negative one ("unseen") enters neither the sum nor the count, so one of them does not
+// decide the threshold of the whole grid. Sum and count in double with a fixed summation order (kSumBlocks contiguous
+// ranges, a fixed tree inside each, the partials added in index order; the counts are integers below 2^53, exact in any
+// order): partial[0 .. kSumBlocks) the sums, partial[kSumBlocks .. 2 kSumBlocks) the counts — the 1024 doubles of the
+// contract. mean = sum / count (0 when no cell counts), threshold = min(mean, occ_thre) rounded to fp32 once, binaries =
+// occs > threshold (false for a NaN cell), and the coarse bitfield the marcher stages in LDS (one bit per 4x4x4 block).
+constexpr int kSumBlocks = 512;
 __global__ __launch_bounds__(256) void occgrid_sum_kernel(const float* __restrict__ occs, int64_t total,
                                                           double* __restrict__ partial) {
   __shared__ double red[256];
+  __shared__ double cnt[256];
   const int64_t per = (total + kSumBlocks - 1) / kSumBlocks;
   const int64_t a = (int64_t)blockIdx.x * per, b = a + per < total ? a + per : total;
-  double s = 0.0;
-  for (int64_t i = a + threadIdx.x; i < b; i += 256) s += (double)occs[i];
+  double s = 0.0, n = 0.0;
+  for (int64_t i = a + threadIdx.x; i < b; i += 256) {
+    const float v = occs[i];
+    if (v >= 0.0f) {
+      s += (double)v;
+      n += 1.0;
+    }
+  }
   red[threadIdx.x] = s;
+  cnt[threadIdx.x] = n;
   __syncthreads();
   for (int w = 128; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+    if ((int)threadIdx.x < w) {
+      red[threadIdx.x] += red[threadIdx.x + w];
+      cnt[threadIdx.x] += cnt[threadIdx.x + w];
+    }
     __syncthreads();
   }
-  if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
+  if (threadIdx.x == 0) {
+    partial[blockIdx.x] = red[0];
+    partial[kSumBlocks + blockIdx.x] = cnt[0];
+  }
 }
 __global__ __launch_bounds__(256) void occgrid_binarise_kernel(const float* __restrict__ occs, int64_t total, float occ_thre,
                                                                const double* __restrict__ partial,
                                                                uint8_t* __restrict__ binaries, float* __restrict__ thre_out) {
   __shared__ float thre_s;
   if (threadIdx.x == 0) {
-    double s = 0.0;
-    for (int k = 0; k < kSumBlocks; ++k) s += partial[k];
-    const double mean = s / (double)total;
+    double s = 0.0, n = 0.0;
+    for (int k = 0; k < kSumBlocks; ++k) {
+      s += partial[k];
+      n += partial[kSumBlocks + k];
+    }
+    const double mean = n > 0.0 ? s / n : 0.0;
     thre_s = (float)(mean < (double)occ_thre ? mean : (double)occ_thre);
     if (blockIdx.x == 0 && thre_out != nullptr) {
       thre_out[0] = thre_s;
@@ -734,6 +773,9 @@ extern "C" int nsamd_occgrid_binarise(const float* occs, int32_t levels, int32_t
                                       nsamd_stream_t stream) {
   NSAMD_REQUIRE(occs && binaries && scratch && levels >= 1 && levels <= 8 && resolution >= 1 && resolution <= 1024);
   const int64_t total = (int64_t)levels * resolution * resolution * resolution;
+  // a coarse pointer for a shape that has no bitfield is refused before anything is launched
+  const int words = coarse != nullptr ? (int)nsamd_occgrid_coarse_words(levels, resolution) : 0;
+  NSAMD_REQUIRE(coarse == nullptr || words > 0);
   occgrid_sum_kernel<<<kSumBlocks, 256, 0, (hipStream_t)stream>>>(occs, total, scratch);
   NSAMD_CHECK_LAUNCH();
   const int64_t nb = (total + 255) / 256;
@@ -741,8 +783,6 @@ extern "C" int nsamd_occgrid_binarise(const float* occs, int32_t levels, int32_t
                                                                                               binaries, threshold_out);
   NSAMD_CHECK_LAUNCH();
   if (coarse != nullptr) {
-    const int words = (int)nsamd_occgrid_coarse_words(levels, resolution);
-    NSAMD_REQUIRE(words > 0);
     occgrid_coarse_kernel<<<(words + 255) / 256, 256, 0, (hipStream_t)stream>>>(binaries, levels, resolution, coarse, words);
     NSAMD_CHECK_LAUNCH();
   }

@@ -1500,8 +1500,8 @@ def occgrid_update(occs: Tensor, cells: Optional[Tensor], occ_new: Tensor, ema_d
 @torch.no_grad()
 def occgrid_binarise(occs: Tensor, binaries: Tensor, coarse: Optional[Tensor], occ_thre: float, scratch: Tensor,
                      threshold_out: Optional[Tensor] = None) -> None:
-    """binaries = occs > min(mean(occs), occ_thre) and its coarse bitfield (nsamd_occgrid_binarise). scratch: >= 1024
-    float64; threshold_out: optional `[2]` fp32 (threshold, mean)."""
+    """binaries = occs > min(mean over the cells with occs >= 0, occ_thre) and its coarse bitfield (nsamd_occgrid_binarise).
+    scratch: >= 1024 float64; threshold_out: optional `[2]` fp32 (threshold, mean)."""
     N.require_cuda(occs, binaries, scratch, coarse, threshold_out)
     assert scratch.dtype == torch.float64 and scratch.numel() >= 1024
     N.check(N.load().nsamd_occgrid_binarise(N.ptr(occs), int(binaries.shape[0]), int(binaries.shape[1]), float(occ_thre),

@@ -64,6 +64,13 @@ class OccGridEstimator(nn.Module):
             self._scratch[name] = t
         return t
 
+    def _seen_mean(self) -> Tensor:
+        """Mean of `occs` over the cells evaluated so far, occs >= 0 (nerfacc's rule, oracle/packed_oracle.py
+        `occgrid_thresholds`; what nsamd_occgrid_binarise computes): a NaN estimate of a diverged field or a negative cell is
+        left out, so it does not empty the grid. Double, 0 when no cell counts."""
+        seen = self.occs[self.occs >= 0]
+        return seen.double().mean() if seen.numel() else torch.zeros((), dtype=torch.float64, device=self.occs.device)
+
     def _refresh_derived(self, occ_thre: Optional[float] = None) -> None:
         """binaries (when `occ_thre` is given), the coarse bitfield and the cached mean from `occs`."""
         if self.occs.is_cuda:
@@ -72,7 +79,7 @@ class OccGridEstimator(nn.Module):
                 self._coarse = torch.zeros(words, device=self.occs.device, dtype=torch.int32)
             if occ_thre is None:  # binaries came from a checkpoint / were set by hand: derive the rest from them (rare)
                 self._rebuild_coarse_from_binaries()
-                self._occ_mean = float(self.occs.double().mean().float())
+                self._occ_mean = float(self._seen_mean().float())
                 return
             stats = self._buf("stats", 2, torch.float32)
             F.occgrid_binarise(self.occs, self.binaries, self._coarse if words else None, occ_thre,
@@ -80,9 +87,9 @@ class OccGridEstimator(nn.Module):
             self._coarse_version = self.binaries._version
             self._occ_mean = float(stats[1])  # one host read per refresh (every 16 steps), none on the sampling path
         else:
-            mean = self.occs.double().mean()
-            if occ_thre is not None:
-                thre = torch.clamp(mean, max=occ_thre).float()
+            mean = self._seen_mean()
+            if occ_thre is not None:  # (occ_thre as the fp32 the kernel is handed)
+                thre = torch.clamp(mean, max=float(torch.tensor(occ_thre, dtype=torch.float32))).float()
                 self.binaries.copy_((self.occs > thre).view_as(self.binaries).to(torch.uint8))
             self._occ_mean = float(mean.float())
             self._coarse = None
@@ -147,7 +154,17 @@ class OccGridEstimator(nn.Module):
         u = (ix + jitter) / r  # in [0,1]^3 of the level's box
         centre = (self.aabb[:3] + self.aabb[3:]) / 2
         half = (self.aabb[3:] - self.aabb[:3]) / 2 * (2.0 ** level_idx.float())[:, None]
-        return (centre - half) + (u * 2) * half
+        x = (centre - half) + (u * 2) * half
+        # clamped to the fp32 numbers inside the cell's closed box (taken in double), as the kernel does: an offset of 0 or
+        # next to 1 must not land in a neighbour of the cell when the cell's edge is no fp32 number
+        a = self.aabb.double()
+        cd, hd = (a[:3] + a[3:]) / 2, (a[3:] - a[:3]) / 2 * (2.0 ** level_idx.double())[:, None]
+        ixd = ix.double()
+        lo, hi = (cd - hd) + (ixd / r) * (2 * hd), (cd - hd) + ((ixd + 1) / r) * (2 * hd)
+        lof, hif = lo.float(), hi.float()
+        lof = torch.where(lof.double() < lo, torch.nextafter(lof, torch.full_like(lof, float("inf"))), lof)
+        hif = torch.where(hif.double() > hi, torch.nextafter(hif, torch.full_like(hif, float("-inf"))), hif)
+        return torch.minimum(torch.maximum(x, lof), hif)
 
     def refreshes_at(self, step: int, n: int = 16) -> bool:
         """`update_every_n_steps(step)` would refresh the grid (a caller that wants to time / account for the refreshes)."""
@@ -158,7 +175,7 @@ class OccGridEstimator(nn.Module):
                              warmup_steps: int = 256, n: int = 16) -> None:
         """Refresh the grid every n-th training step: all cells during warm-up, afterwards a quarter of the cells at random
         plus as many occupied ones; occs = max(occs * decay, occ_eval_fn(x)) — over every estimate of a cell when it was
-        drawn more than once —; binaries = occs > min(mean(occs), occ_thre)."""
+        drawn more than once —; binaries = occs > min(mean of the cells with occs >= 0, occ_thre)."""
         if not self.training or step % n != 0:
             return
         dev = self.occs.device
