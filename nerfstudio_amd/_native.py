@@ -66,6 +66,16 @@ class TsdfVolume(C.Structure):
     _fields_ = [("origin", f32 * 3), ("voxel_size", f32 * 3), ("dims", i32 * 3), ("truncation", f32)]
 
 
+class CropBox(C.Structure):
+    """nsamd_crop_box (include/nsamd_pointcloud.h): world2box = rows of the 3x4 inverse of [R T; 0 1], half_scale = S / 2."""
+    _fields_ = [("enabled", i32), ("world2box", f32 * 12), ("half_scale", f32 * 3)]
+
+
+class PointGrid(C.Structure):
+    """nsamd_point_grid: the uniform grid of the neighbour search."""
+    _fields_ = [("origin", f32 * 3), ("cell_size", f32), ("dims", i32 * 3)]
+
+
 class ProposalLevelBwd(C.Structure):
     """nsamd_proposal_level_bwd: one proposal level's gated backward chain (nsamd_proposal_levels_bwd)."""
     _fields_ = [("num_rays", i64), ("samples_per_ray", i32),
@@ -171,6 +181,16 @@ _RENDER_SIGNATURES = {
     "nsamd_packed_render_fwd": [vp, vp, vp, vp, vp, i64, C.c_int, C.POINTER(f32), C.c_int, vp, vp, vp, vp, vp, vp],
     "nsamd_packed_ray_points": [vp, vp, vp, vp, vp, i64, vp, vp, vp],
 }
+# And for include/nsamd_pointcloud.h, point-cloud export (tests/test_pointcloud_cpu.py checks the three).
+_POINTCLOUD_SIGNATURES = {
+    "nsamd_points_select": [vp, vp, vp, vp, vp, vp, i64, CropBox, vp, vp, vp, vp, i64, vp, vp, vp],
+    "nsamd_select_below": [vp, i64, vp, vp, vp, vp, vp],
+    "nsamd_point_cell_keys": [vp, i64, PointGrid, vp, vp],
+    "nsamd_knn_mean_distance": [vp, i64, vp, vp, PointGrid, i32, i32, vp, vp, vp],
+}
+SELECT_BLOCK = 256  # NSAMD_SELECT_BLOCK
+KNN_MAX_K = 32  # NSAMD_KNN_MAX_K
+KNN_MAX_CELLS = 1 << 24  # NSAMD_KNN_MAX_CELLS
 _RESTYPES = {"nsamd_version": C.c_char_p, "nsamd_status_string": C.c_char_p,
              "nsamd_hashgrid_encode_bwd_workspace": C.c_int64, "nsamd_hashgrid_encode_bwd_workspace_state": C.c_int64,
              "nsamd_field_mlp_bwd_scatter_workspace": C.c_int64,
@@ -235,7 +255,7 @@ def load():
     cdll = C.CDLL(path)
     lib = _Lib()
     lib.cdll = cdll
-    for name, argtypes in {**_SIGNATURES, **_EXPORT_SIGNATURES, **_RENDER_SIGNATURES}.items():
+    for name, argtypes in {**_SIGNATURES, **_EXPORT_SIGNATURES, **_RENDER_SIGNATURES, **_POINTCLOUD_SIGNATURES}.items():
         fn = getattr(cdll, name)  # AttributeError here = header / library mismatch
         fn.argtypes = argtypes
         fn.restype = _RESTYPES.get(name, C.c_int)
@@ -355,6 +375,31 @@ def make_aabb(aabb: Optional[torch.Tensor]) -> Aabb:
             a.lo[i] = vals[0][i]
             a.hi[i] = vals[1][i]
     return a
+
+
+def select_scratch_words(n: int) -> int:
+    """NSAMD_SELECT_SCRATCH_WORDS(n): int64 words of scratch the two selection entry points need for n entries."""
+    return 1 + ((n + SELECT_BLOCK - 1) // SELECT_BLOCK + 1) // 2
+
+
+def make_crop_box(world2box=None, half_scale=None) -> CropBox:
+    """world2box: 12 host floats (rows of the 3x4 matrix), half_scale: 3; None: the box is disabled."""
+    b = CropBox()
+    if world2box is not None:
+        b.enabled = 1
+        for i, v in enumerate(world2box):
+            b.world2box[i] = float(v)
+        for i, v in enumerate(half_scale):
+            b.half_scale[i] = float(v)
+    return b
+
+
+def make_point_grid(origin, cell_size: float, dims) -> PointGrid:
+    g = PointGrid()
+    for i in range(3):
+        g.origin[i], g.dims[i] = float(origin[i]), int(dims[i])
+    g.cell_size = float(cell_size)
+    return g
 
 
 def device_info() -> dict:

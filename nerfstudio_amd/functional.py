@@ -1773,3 +1773,61 @@ def tsdf_integrate_launch(origin: Sequence[float], voxel_size: Sequence[float], 
     B, H, W = (int(s) for s in depth.shape)
     N.check(N.load().nsamd_tsdf_integrate(vol, N.ptr(values), N.ptr(weights), N.ptr(colors), N.ptr(w2c), N.ptr(K), B,
                                           N.ptr(depth), N.ptr(color), H, W, N.stream()), "tsdf_integrate")
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# point-cloud export: ordered selection and the outlier rule's neighbour search (include/nsamd_pointcloud.h)
+# ---------------------------------------------------------------------------------------------------------------
+def points_select_launch(origins: Tensor, directions: Tensor, depth: Tensor, rgb: Tensor, alpha: Optional[Tensor],
+                         normals01: Optional[Tensor], box: "N.CropBox", out_points: Tensor, out_colors: Tensor,
+                         out_view_dirs: Tensor, out_normals: Optional[Tensor], cursor: Tensor, scratch: Tensor) -> None:
+    """nsamd_points_select on dense device tensors: the rays kept of origins / directions / rgb `[n,3]`, depth / alpha `[n]`
+    (alpha None: every ray passes the opacity test), normals01 `[n,3]` or None, appended in ray order at row cursor[0] of the
+    `[cap,3]` outputs; cursor `[2]` int64 (rows so far, overflow flag), scratch: int64, `N.select_scratch_words(n)` words."""
+    N.require_cuda(origins, directions, depth, rgb, alpha, normals01, out_points, out_colors, out_view_dirs, out_normals, cursor,
+                   scratch)
+    n = int(depth.numel())
+    assert origins.numel() == directions.numel() == rgb.numel() == 3 * n and (alpha is None or alpha.numel() == n)
+    assert (normals01 is None) == (out_normals is None) and (normals01 is None or normals01.numel() == 3 * n)
+    assert cursor.dtype == scratch.dtype == torch.int64 and cursor.numel() >= 2 and scratch.numel() >= N.select_scratch_words(n)
+    cap = int(out_points.shape[0])
+    assert tuple(out_colors.shape) == tuple(out_view_dirs.shape) == (cap, 3) and (out_normals is None or out_normals.shape[0] == cap)
+    N.check(N.load().nsamd_points_select(N.ptr(origins), N.ptr(directions), N.ptr(depth), N.ptr(rgb), N.ptr(alpha),
+                                         N.ptr(normals01), n, box, N.ptr(out_points), N.ptr(out_colors), N.ptr(out_view_dirs),
+                                         N.ptr(out_normals), cap, N.ptr(cursor), N.ptr(scratch), N.stream()), "points_select")
+
+
+def select_below_launch(avg: Tensor, threshold: Tensor, out_indices: Tensor, count: Tensor, scratch: Tensor) -> None:
+    """nsamd_select_below: out_indices `[n]` int64 receives, ascending, the i with 0 < avg[i] < threshold[0] (both float64 on the
+    device), count `[1]` int64 their number."""
+    N.require_cuda(avg, threshold, out_indices, count, scratch)
+    n = int(avg.numel())
+    assert avg.dtype == threshold.dtype == torch.float64 and out_indices.dtype == count.dtype == scratch.dtype == torch.int64
+    assert out_indices.numel() >= n and scratch.numel() >= N.select_scratch_words(n)
+    N.check(N.load().nsamd_select_below(N.ptr(avg), n, N.ptr(threshold), N.ptr(out_indices), N.ptr(count), N.ptr(scratch),
+                                        N.stream()), "select_below")
+
+
+def point_cell_keys_launch(points: Tensor, grid: "N.PointGrid", keys: Tensor) -> None:
+    """nsamd_point_cell_keys: keys `[n]` int64, the grid cell of every row of points `[n,3]` fp32."""
+    N.require_cuda(points, keys)
+    n = int(points.shape[0])
+    assert points.dtype == torch.float32 and keys.dtype == torch.int64 and keys.numel() >= n
+    N.check(N.load().nsamd_point_cell_keys(N.ptr(points), n, grid, N.ptr(keys), N.stream()), "point_cell_keys")
+
+
+def knn_mean_distance_launch(points: Tensor, order: Tensor, cell_start: Tensor, grid: "N.PointGrid", k: int, max_rings: int,
+                             avg: Tensor, unfinished: Tensor) -> None:
+    """nsamd_knn_mean_distance: avg `[n]` float64, the mean distance of every row of points `[n,3]` fp32 to its min(k, n) nearest
+    rows (itself included). order `[n]` int32: the rows sorted by cell key; cell_start `[cells + 1]` int32; unfinished `[1 + n]`
+    int32: word 0 receives the number of queries that fell to the brute-force phase."""
+    if k > N.KNN_MAX_K:
+        raise ValueError(f"knn_mean_distance: at most {N.KNN_MAX_K} neighbours are supported, got {k}")
+    N.require_cuda(points, order, cell_start, avg, unfinished)
+    n = int(points.shape[0])
+    cells = int(grid.dims[0]) * int(grid.dims[1]) * int(grid.dims[2])
+    assert points.dtype == torch.float32 and avg.dtype == torch.float64 and avg.numel() >= n
+    assert order.dtype == cell_start.dtype == unfinished.dtype == torch.int32
+    assert order.numel() == n and cell_start.numel() == cells + 1 and unfinished.numel() >= n + 1
+    N.check(N.load().nsamd_knn_mean_distance(N.ptr(points), n, N.ptr(order), N.ptr(cell_start), grid, int(k), int(max_rings),
+                                             N.ptr(avg), N.ptr(unfinished), N.stream()), "knn_mean_distance")
