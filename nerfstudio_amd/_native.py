@@ -76,6 +76,11 @@ class PointGrid(C.Structure):
     _fields_ = [("origin", f32 * 3), ("cell_size", f32), ("dims", i32 * 3)]
 
 
+class MeshVolume(C.Structure):
+    """nsamd_mesh_volume (include/nsamd_mesh.h): the volume the mesh is extracted from."""
+    _fields_ = [("origin", f32 * 3), ("voxel_size", f32 * 3), ("dims", i32 * 3)]
+
+
 class ProposalLevelBwd(C.Structure):
     """nsamd_proposal_level_bwd: one proposal level's gated backward chain (nsamd_proposal_levels_bwd)."""
     _fields_ = [("num_rays", i64), ("samples_per_ray", i32),
@@ -188,7 +193,13 @@ _POINTCLOUD_SIGNATURES = {
     "nsamd_point_cell_keys": [vp, i64, PointGrid, vp, vp],
     "nsamd_knn_mean_distance": [vp, i64, vp, vp, PointGrid, i32, i32, vp, vp, vp],
 }
+# And for include/nsamd_mesh.h, the mesh extraction of mesh export (tests/test_mesh_cpu.py checks the three).
+_MESH_SIGNATURES = {
+    "nsamd_mesh_count": [MeshVolume, vp, vp, vp, vp],
+    "nsamd_mesh_emit": [MeshVolume, vp, vp, vp, i64, i64, vp, vp, vp, vp, vp],
+}
 SELECT_BLOCK = 256  # NSAMD_SELECT_BLOCK
+MESH_BLOCK = 256  # NSAMD_MESH_BLOCK
 KNN_MAX_K = 32  # NSAMD_KNN_MAX_K
 KNN_MAX_CELLS = 1 << 24  # NSAMD_KNN_MAX_CELLS
 _RESTYPES = {"nsamd_version": C.c_char_p, "nsamd_status_string": C.c_char_p,
@@ -255,7 +266,8 @@ def load():
     cdll = C.CDLL(path)
     lib = _Lib()
     lib.cdll = cdll
-    for name, argtypes in {**_SIGNATURES, **_EXPORT_SIGNATURES, **_RENDER_SIGNATURES, **_POINTCLOUD_SIGNATURES}.items():
+    for name, argtypes in {**_SIGNATURES, **_EXPORT_SIGNATURES, **_RENDER_SIGNATURES, **_POINTCLOUD_SIGNATURES,
+                           **_MESH_SIGNATURES}.items():
         fn = getattr(cdll, name)  # AttributeError here = header / library mismatch
         fn.argtypes = argtypes
         fn.restype = _RESTYPES.get(name, C.c_int)
@@ -400,6 +412,18 @@ def make_point_grid(origin, cell_size: float, dims) -> PointGrid:
         g.origin[i], g.dims[i] = float(origin[i]), int(dims[i])
     g.cell_size = float(cell_size)
     return g
+
+
+def mesh_scratch_bytes(n: int) -> int:
+    """NSAMD_MESH_SCRATCH_BYTES(n): bytes of scratch the two mesh entry points need for a volume of n voxels."""
+    return 16 + 8 * ((n + MESH_BLOCK - 1) // MESH_BLOCK) + 4 * n
+
+
+def make_mesh_volume(origin, voxel_size, dims) -> MeshVolume:
+    v = MeshVolume()
+    for i in range(3):
+        v.origin[i], v.voxel_size[i], v.dims[i] = float(origin[i]), float(voxel_size[i]), int(dims[i])
+    return v
 
 
 def device_info() -> dict:

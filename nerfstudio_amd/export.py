@@ -11,11 +11,18 @@ in that function, to update 470 MB of state. Here
     fuse_views          renders the cameras with EvalRenderer.render_camera — rays generated inside the chunk loop — into two
                         static device buffers of `views_per_launch` frames and integrates each full buffer: no frame goes to
                         the host, memory is bounded by `views_per_launch`
-    export_tsdf_mesh    the reference's function, signature and defaults, over the two; marching cubes and the PLY writer
-                        stay the reference's (`TSDFVolume.to_reference`)
+    TSDFVolume.get_mesh marching cubes at level 0 on the device (csrc/mesh.hip through functional.mesh_count_launch and
+                        functional.mesh_emit_launch): an ordered compaction of the crossed edges and the cells' triangles into
+                        an indexed `Mesh`; the host reads two counts to size the outputs, nothing else leaves the device
+    write_mesh_ply      binary PLY of a `Mesh`: positions, normals, colours, faces
+    export_tsdf_mesh    the reference's function, signature and defaults, over the two; by default marching cubes and the PLY
+                        writer are the reference's (`TSDFVolume.to_reference`: skimage, pymeshlab)
+    export_tsdf_mesh_on_device   the same with `device_mesh` and `write_mesh_ply`: no reference installation needed
 
 Kept as the reference has them (csrc/tsdf.h): the weight clamp of :267, voxels behind a camera, voxel coordinates at the
-voxel's corner, the truncation from the x voxel size alone.
+voxel's corner, the truncation from the x voxel size alone. The device mesh (include/nsamd_mesh.h) restates marching cubes
+over a generated triangle table, since skimage was not available to compare with: same surface, its own vertex and triangle
+order; its normals are in world space where the reference's are in index space (they differ for anisotropic voxels only).
 
 This module imports nothing of nerfstudio at module level: `to_reference` and the default mesh / writer functions import it
 lazily. There is no torch fallback: a CPU tensor with the native launch raises RuntimeError.
@@ -23,9 +30,11 @@ lazily. There is no torch fallback: a CPU tensor with the native launch raises R
 from __future__ import annotations
 
 import contextlib
+from dataclasses import dataclass
 from pathlib import Path
 from typing import Callable, Dict, List, Optional, Sequence, Tuple, Union
 
+import numpy as np
 import torch
 from torch import Tensor
 
@@ -47,6 +56,17 @@ def _import_reference():
                           "(nerfstudio.exporter.tsdf_utils.TSDF.get_mesh / export_mesh: skimage marching cubes, pymeshlab); "
                           f"install nerfstudio with its export dependencies to use them ({e})") from e
     return tsdf_utils
+
+
+@dataclass
+class Mesh:
+    """The fields of the reference's exporter_utils.Mesh (:46-57) that TSDF.get_mesh fills: vertices `[V,3]` fp32, faces `[T,3]`
+    (int32 here: indices into vertices), normals `[V,3]` fp32, colors `[V,3]` fp32 in [0, 1]."""
+
+    vertices: Tensor
+    faces: Tensor
+    normals: Tensor
+    colors: Tensor
 
 
 class TSDFVolume:
@@ -128,6 +148,24 @@ class TSDFVolume:
         launch = F.tsdf_integrate_launch if launch_fn is None else launch_fn
         launch(self.origin.tolist(), self.voxel_size.tolist(), self.truncation, self.values, self.weights, self.colors, w2c, K,
                depth, color)
+
+    @torch.no_grad()
+    def get_mesh(self, launch_fns: Optional[Tuple[Callable, Callable]] = None) -> Mesh:
+        """TSDF.get_mesh (:115-136) on the volume's device: marching cubes at level 0 over clamp(values, -1, 1), no mask on the
+        weights. Two launches of csrc/mesh.hip — count, emit — with one read of the two totals between them to size the outputs:
+        the only synchronisation. launch_fns: a (count, emit) pair standing in for functional.mesh_count_launch and
+        functional.mesh_emit_launch (same arguments) in CPU tests. With the native launches a CPU volume raises RuntimeError."""
+        count, emit = (F.mesh_count_launch, F.mesh_emit_launch) if launch_fns is None else launch_fns
+        dev = self.device
+        vol = N.make_mesh_volume(self.origin.tolist(), self.voxel_size.tolist(), self.values.shape)
+        scratch = torch.empty(N.mesh_scratch_bytes(self.values.numel()), dtype=torch.uint8, device=dev)
+        totals = torch.zeros(2, dtype=torch.int64, device=dev)
+        count(vol, self.values, scratch, totals)
+        V, T = totals.tolist()
+        vertices, normals, colors = (torch.empty((V, 3), dtype=torch.float32, device=dev) for _ in range(3))
+        faces = torch.empty((T, 3), dtype=torch.int32, device=dev)
+        emit(vol, self.values, self.colors, scratch, vertices, normals, colors, faces)
+        return Mesh(vertices=vertices, faces=faces, normals=normals, colors=colors)
 
     def voxel_coords(self) -> Tensor:
         """`[3,X,Y,Z]` as the reference builds them (:100-104), on the volume's device. The kernel never materialises them."""
@@ -244,6 +282,38 @@ def _reference_write(mesh, filename: str) -> None:
     _import_reference().TSDF.export_mesh(mesh, filename=filename)
 
 
+def device_mesh(volume: TSDFVolume) -> Mesh:
+    """`mesh_fn` of export_tsdf_mesh: the volume's own marching cubes."""
+    return volume.get_mesh()
+
+
+def write_mesh_ply(mesh: Mesh, filename) -> None:
+    """`write_fn` of export_tsdf_mesh. Binary little-endian PLY in the style of pointcloud.PointCloud.write_ply: per vertex
+    x y z nx ny nz float32 and red green blue alpha uint8 — colors * 255 truncated, the product formed in float64 (a colour
+    outside [0, 1] saturates, NaN writes 0), alpha 255 — then per face `list uchar int vertex_indices`. An empty mesh writes a
+    valid file with no elements' rows."""
+    V, T = int(mesh.vertices.shape[0]), int(mesh.faces.shape[0])
+    vertex = np.empty(V, dtype=np.dtype([(k, "<f4") for k in ("x", "y", "z", "nx", "ny", "nz")]
+                                        + [(k, "u1") for k in ("red", "green", "blue", "alpha")]))
+    xyz = mesh.vertices.detach().float().cpu().numpy()
+    nrm = mesh.normals.detach().float().cpu().numpy()
+    rgb = torch.nan_to_num(mesh.colors.detach().double() * 255, nan=0.0).clamp(0, 255).to(torch.uint8).cpu().numpy()
+    for c, (a, b, k) in enumerate((("x", "nx", "red"), ("y", "ny", "green"), ("z", "nz", "blue"))):
+        vertex[a], vertex[b], vertex[k] = xyz[:, c], nrm[:, c], rgb[:, c]
+    vertex["alpha"] = 255
+    face = np.empty(T, dtype=np.dtype([("n", "u1"), ("i", "<i4", (3,))]))
+    face["n"] = 3
+    face["i"] = mesh.faces.detach().to(torch.int32).cpu().numpy()
+    header = ["ply", "format binary_little_endian 1.0", f"element vertex {V}"]
+    header += [f"property float {k}" for k in ("x", "y", "z", "nx", "ny", "nz")]
+    header += [f"property uchar {k}" for k in ("red", "green", "blue", "alpha")]
+    header += [f"element face {T}", "property list uchar int vertex_indices", "end_header"]
+    with open(filename, "wb") as f:
+        f.write(("\n".join(header) + "\n").encode("ascii"))
+        f.write(vertex.tobytes())
+        f.write(face.tobytes())
+
+
 def export_tsdf_mesh(pipeline, output_dir: Path, downscale_factor: int = 2, depth_output_name: str = "depth",
                      rgb_output_name: str = "rgb", resolution: Union[int, Sequence[int]] = (256, 256, 256), batch_size: int = 10,
                      use_bounding_box: bool = True, bounding_box_min: Tuple[float, float, float] = (-1.0, -1.0, -1.0),
@@ -284,3 +354,11 @@ def export_tsdf_mesh(pipeline, output_dir: Path, downscale_factor: int = 2, dept
         vertices_max = torch.max(mesh.vertices, dim=0).values + refinement_epsilon
         mesh = mesh_fn(fused(torch.stack([vertices_min, vertices_max]).cpu()))
     write_fn(mesh, str(Path(output_dir) / "tsdf_mesh.ply"))
+
+
+def export_tsdf_mesh_on_device(pipeline, output_dir: Path, **kwargs) -> None:
+    """export_tsdf_mesh with the mesh extracted on the device and written by `write_mesh_ply`: the whole of `ns-export tsdf`,
+    the refinement pass over the mesh's bounds included, with no reference installed. kwargs: export_tsdf_mesh's."""
+    kwargs.setdefault("mesh_fn", device_mesh)
+    kwargs.setdefault("write_fn", write_mesh_ply)
+    export_tsdf_mesh(pipeline, output_dir, **kwargs)

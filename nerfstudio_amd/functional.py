@@ -1831,3 +1831,30 @@ def knn_mean_distance_launch(points: Tensor, order: Tensor, cell_start: Tensor, 
     assert order.numel() == n and cell_start.numel() == cells + 1 and unfinished.numel() >= n + 1
     N.check(N.load().nsamd_knn_mean_distance(N.ptr(points), n, N.ptr(order), N.ptr(cell_start), grid, int(k), int(max_rings),
                                              N.ptr(avg), N.ptr(unfinished), N.stream()), "knn_mean_distance")
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# mesh export: marching cubes over the fused volume (include/nsamd_mesh.h)
+# ---------------------------------------------------------------------------------------------------------------
+def mesh_count_launch(vol: "N.MeshVolume", values: Tensor, scratch: Tensor, totals: Tensor) -> None:
+    """nsamd_mesh_count: totals `[2]` int64 on the device receives the number of vertices and of triangles of the mesh of
+    values `[X,Y,Z]` fp32; scratch: uint8, `N.mesh_scratch_bytes(values.numel())` bytes, kept for `mesh_emit_launch`."""
+    N.require_cuda(values, scratch, totals)
+    assert values.dtype == torch.float32 and tuple(values.shape) == tuple(vol.dims)
+    assert totals.dtype == torch.int64 and totals.numel() >= 2
+    assert scratch.dtype == torch.uint8 and scratch.numel() >= N.mesh_scratch_bytes(values.numel()) and scratch.data_ptr() % 8 == 0
+    N.check(N.load().nsamd_mesh_count(vol, N.ptr(values), N.ptr(scratch), N.ptr(totals), N.stream()), "mesh_count")
+
+
+def mesh_emit_launch(vol: "N.MeshVolume", values: Tensor, colors: Tensor, scratch: Tensor, vertices: Tensor, normals: Tensor,
+                     vertex_colors: Tensor, faces: Tensor) -> None:
+    """nsamd_mesh_emit after `mesh_count_launch` on the same volume and scratch: vertices, normals, vertex_colors `[V,3]` fp32
+    and faces `[T,3]` int32, V and T the totals the count gave; colors `[X,Y,Z,3]` fp32."""
+    N.require_cuda(values, colors, scratch, vertices, normals, vertex_colors, faces)
+    V, T = int(vertices.shape[0]), int(faces.shape[0])
+    assert values.dtype == colors.dtype == torch.float32 and tuple(colors.shape) == (*vol.dims, 3) == (*values.shape, 3)
+    assert vertices.dtype == normals.dtype == vertex_colors.dtype == torch.float32 and faces.dtype == torch.int32
+    assert tuple(vertices.shape) == tuple(normals.shape) == tuple(vertex_colors.shape) == (V, 3) and tuple(faces.shape) == (T, 3)
+    assert scratch.dtype == torch.uint8 and scratch.numel() >= N.mesh_scratch_bytes(values.numel())
+    N.check(N.load().nsamd_mesh_emit(vol, N.ptr(values), N.ptr(colors), N.ptr(scratch), V, T, N.ptr(vertices), N.ptr(normals),
+                                     N.ptr(vertex_colors), N.ptr(faces), N.stream()), "mesh_emit")
