@@ -1,13 +1,13 @@
 // Mesh extraction from a TSDF volume (include/nsamd_mesh.h): nsamd_mesh_count / nsamd_mesh_emit. What the reference does with
 // skimage's marching cubes on a host copy of the volume (exporter/tsdf_utils.py:115-136) is an ordered, data-dependent stream
-// compaction over the voxels here, in the three-launch pattern of nsamd_points_select (pointcloud.hip): per-workgroup counts,
-// a one-workgroup scan, writes — every placement a sum of counts, no atomics, no workgroup waiting for another. Both passes
+// compaction over the voxels here, in the three launches that block_scan.h describes and serves: per-workgroup counts, a
+// one-workgroup scan, writes — every placement a sum of counts, no atomics, no workgroup waiting for another. Both passes
 // are bandwidth-bound: the values are read once from memory per pass (the seven neighbour reads of a lane hit the lines its
 // own and the neighbouring wavefronts fetch), the per-voxel words are written by the count pass and read by the emit pass.
 // The per-voxel arithmetic is mesh.h.
+#include "block_scan.h"
 #include "launch.h"
 #include "mesh.h"
-#include "wave.h"
 
 using namespace nsamd;
 
@@ -36,12 +36,11 @@ __device__ __forceinline__ bool stage_table(bool surface, unsigned char* table) 
 }
 
 // One lane per voxel. Vertices (0-3) and triangles (0-5) of the lane as one packed 32-bit count — a workgroup's sums, 768 and
-// 1280 at most, stay inside their 16-bit halves — scanned over the wavefront on the DPP path and over the four wavefronts
-// through LDS. Lanes past the volume count nothing and stay active for the scan.
+// 1280 at most, stay inside their 16-bit halves — scanned over the workgroup in one call (block_scan.h). Lanes past the volume
+// count nothing and stay active for the scan.
 __global__ __launch_bounds__(kMeshThreads) void mesh_count_kernel(nsamd_mesh_volume vol, int64_t voxels,
                                                                   const float* __restrict__ values, void* scratch) {
   __shared__ __attribute__((aligned(16))) unsigned char table[kMeshTableBytes];
-  __shared__ uint32_t wave_total[kMeshWaves];
   const MeshScratch s = mesh_scratch(scratch, voxels);
   const int64_t lin = (int64_t)blockIdx.x * kMeshThreads + threadIdx.x;
   const bool active = lin < voxels;
@@ -57,15 +56,8 @@ __global__ __launch_bounds__(kMeshThreads) void mesh_count_kernel(nsamd_mesh_vol
   if (stage_table(surface, table) && surface) triangle_mask = mesh_triangle_mask(v, table + kMeshRow * code);
 
   const uint32_t mine = (uint32_t)__popc(edge_mask) | ((uint32_t)__popc(triangle_mask) << 16);
-  const uint32_t inclusive = wave_scan_inclusive_u32(mine);
-  if ((threadIdx.x & 63) == 63) wave_total[wave_index()] = inclusive;
-  __syncthreads();
-  uint32_t before = 0, sum = 0;
-  for (int w = 0; w < kMeshWaves; ++w) {
-    if (w < wave_index()) before += wave_total[w];
-    sum += wave_total[w];
-  }
-  const uint32_t exclusive = before + inclusive - mine;
+  uint32_t exclusive, sum;
+  block_scan_exclusive_u32<kMeshWaves>(&mine, &exclusive, &sum);
   if (active) s.words[lin] = mesh_word(exclusive & 0xffffu, edge_mask, exclusive >> 16);
   if (threadIdx.x == 0) {
     s.vertex_base[blockIdx.x] = sum & 0xffffu;
@@ -73,34 +65,17 @@ __global__ __launch_bounds__(kMeshThreads) void mesh_count_kernel(nsamd_mesh_vol
   }
 }
 
-// ONE workgroup: exclusive scan in place of the workgroups' vertex and triangle counts, 256 at a sweep, the carries in 64 bits;
+// ONE workgroup: exclusive scan in place of the workgroups' vertex and triangle counts (the two-channel sweep of block_scan.h);
 // the totals into scratch and into totals[2]. A base above 2^32 wraps: the emit entry point refuses such totals.
 __global__ __launch_bounds__(kMeshThreads) void mesh_scan_kernel(void* scratch, int64_t voxels, int64_t blocks,
                                                                  int64_t* __restrict__ totals) {
-  __shared__ uint32_t wave_total[2][kMeshWaves];
   const MeshScratch s = mesh_scratch(scratch, voxels);
-  uint64_t carry[2] = {0, 0};
-  for (int64_t base = 0; base < blocks; base += kMeshThreads) {  // uniform trip count: every lane stays active for the DPP scan
-    const int64_t b = base + threadIdx.x;
-    const uint32_t mine[2] = {b < blocks ? s.vertex_base[b] : 0u, b < blocks ? s.triangle_base[b] : 0u};
-    const uint32_t inclusive[2] = {wave_scan_inclusive_u32(mine[0]), wave_scan_inclusive_u32(mine[1])};
-    if ((threadIdx.x & 63) == 63) wave_total[0][wave_index()] = inclusive[0], wave_total[1][wave_index()] = inclusive[1];
-    __syncthreads();
-    for (int c = 0; c < 2; ++c) {
-      uint32_t before = 0, chunk = 0;
-      for (int w = 0; w < kMeshWaves; ++w) {
-        if (w < wave_index()) before += wave_total[c][w];
-        chunk += wave_total[c][w];
-      }
-      const uint32_t exclusive = (uint32_t)carry[c] + before + inclusive[c] - mine[c];
-      if (b < blocks) (c == 0 ? s.vertex_base : s.triangle_base)[b] = exclusive;
-      carry[c] += chunk;
-    }
-    __syncthreads();  // wave_total is rewritten by the next sweep
-  }
+  uint32_t* const counts[2] = {s.vertex_base, s.triangle_base};
+  uint64_t sum[2];
+  block_sweep_exclusive_u32<kMeshWaves, 2>(counts, blocks, sum);
   if (threadIdx.x != 0) return;
-  s.totals[0] = totals[0] = (int64_t)carry[0];
-  s.totals[1] = totals[1] = (int64_t)carry[1];
+  s.totals[0] = totals[0] = (int64_t)sum[0];
+  s.totals[1] = totals[1] = (int64_t)sum[1];
 }
 
 // One lane per voxel again: the lane writes the vertices it owns and the triangles of its cell, at its workgroup's base plus

@@ -3,9 +3,9 @@
 // nsamd_point_cell_keys / nsamd_knn_mean_distance. What the reference does with two boolean-index passes over four tensors
 // per batch plus a host k-d tree (exporter/exporter_utils.py:155-193) stays on the device. The per-element arithmetic is
 // pointcloud.h.
+#include "block_scan.h"
 #include "launch.h"
 #include "pointcloud.h"
-#include "wave.h"
 
 using namespace nsamd;
 
@@ -17,7 +17,7 @@ constexpr int kSelectWaves = kSelectThreads / 64;
 // ---- ordered compaction: counts, scan, writes ----------------------------------------------------------------------------------
 // scratch: word 0 = the row the launch's first kept entry goes to, or -1 (overflow: nothing is written); from word 1 on, one
 // int32 per workgroup: its number of kept entries, turned by the scan into the number kept by the workgroups before it.
-// Every placement is a sum of counts: no atomics, no workgroup waits for another inside a launch.
+// Every placement is a sum of counts: no atomics, no workgroup waits for another inside a launch. The scans are block_scan.h.
 struct RayPredicate {
   const float *origins, *directions, *depth, *alpha;
   nsamd_crop_box box;
@@ -29,22 +29,13 @@ struct BelowPredicate {
   __device__ bool operator()(int64_t i, float*) const { return below_threshold(avg[i], threshold[0]); }
 };
 
-__device__ __forceinline__ int32_t* select_counts(int64_t* scratch) { return reinterpret_cast<int32_t*>(scratch + 1); }
+__device__ __forceinline__ uint32_t* select_counts(int64_t* scratch) { return reinterpret_cast<uint32_t*>(scratch + 1); }
 
 // kept entries of this workgroup before the calling lane's, and in the whole workgroup. All threads of the block call it.
 __device__ __forceinline__ uint32_t block_rank(bool keep, uint32_t* total) {
-  __shared__ uint32_t wave_total[kSelectWaves];
-  const unsigned long long mask = __ballot(keep);
-  const int lane = (int)(threadIdx.x & 63);
-  const uint32_t before = (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
-  if (lane == 0) wave_total[wave_index()] = (uint32_t)__popcll(mask);
-  __syncthreads();
-  uint32_t rank = before, sum = 0;
-  for (int w = 0; w < kSelectWaves; ++w) {
-    if (w < wave_index()) rank += wave_total[w];
-    sum += wave_total[w];
-  }
-  *total = sum;
+  const uint32_t mine = keep ? 1u : 0u;
+  uint32_t rank;
+  block_scan_exclusive_u32<kSelectWaves>(&mine, &rank, total);
   return rank;
 }
 
@@ -55,7 +46,7 @@ __global__ __launch_bounds__(kSelectThreads) void select_count_kernel(Predicate 
   const bool keep = i < n && pred(i, p);
   uint32_t total;
   block_rank(keep, &total);
-  if (threadIdx.x == 0) select_counts(scratch)[blockIdx.x] = (int32_t)total;
+  if (threadIdx.x == 0) select_counts(scratch)[blockIdx.x] = total;
 }
 
 // ONE workgroup: exclusive scan of the counts in place (their sum is at most n < 2^31), then the decision. append: the first
@@ -63,26 +54,11 @@ __global__ __launch_bounds__(kSelectThreads) void select_count_kernel(Predicate 
 // (select_below) the first row is 0 and cursor[0] receives the total.
 __global__ __launch_bounds__(kSelectThreads) void select_scan_kernel(int64_t* __restrict__ scratch, int64_t blocks, int append,
                                                                       int64_t cap, int64_t* __restrict__ cursor) {
-  __shared__ uint32_t wave_total[kSelectWaves];
-  int32_t* counts = select_counts(scratch);
-  uint32_t carry = 0;
-  for (int64_t base = 0; base < blocks; base += kSelectThreads) {  // uniform trip count: every lane stays active for the DPP scan
-    const int64_t b = base + threadIdx.x;
-    const uint32_t mine = b < blocks ? (uint32_t)counts[b] : 0u;
-    const uint32_t inclusive = wave_scan_inclusive_u32(mine);
-    if ((threadIdx.x & 63) == 63) wave_total[wave_index()] = inclusive;
-    __syncthreads();
-    uint32_t before = carry, chunk = 0;
-    for (int w = 0; w < kSelectWaves; ++w) {
-      if (w < wave_index()) before += wave_total[w];
-      chunk += wave_total[w];
-    }
-    if (b < blocks) counts[b] = (int32_t)(before + inclusive - mine);
-    carry += chunk;
-    __syncthreads();  // wave_total is rewritten by the next chunk
-  }
+  uint32_t* const counts = select_counts(scratch);
+  uint64_t sum;
+  block_sweep_exclusive_u32<kSelectWaves, 1>(&counts, blocks, &sum);
   if (threadIdx.x != 0) return;
-  const int64_t total = (int64_t)carry;
+  const int64_t total = (int64_t)sum;
   if (!append) {
     scratch[0] = 0;
     cursor[0] = total;

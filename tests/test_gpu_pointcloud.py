@@ -23,6 +23,9 @@ import pointcloud_reference as pr
 pytestmark = pytest.mark.gpu
 T = torch.from_numpy
 SIZES = [1, 63, 64, 65, 255, 256, 257, 4097]
+# The one-workgroup scan of the workgroups' counts takes 256 of them at a sweep: 65536 entries are 256 workgroups, exactly one
+# full sweep; 65537 are 257, the smallest size at which a second sweep exists and the carry between the sweeps decides rows.
+SWEEP_SIZES = [65536, 65537]
 GUARD = 5
 
 
@@ -144,6 +147,32 @@ def test_points_select_is_the_torch_composition_bit_for_bit(dev, n):
                 assert m == 1
             if name == "all" and not use_alpha:
                 assert m == n
+
+
+@pytest.mark.parametrize("n", SWEEP_SIZES)
+def test_points_select_across_the_sweeps_of_the_count_scan(dev, n):
+    """box, alpha and normals on, two keep patterns. The kept count is above 256 and no multiple of 256, so a carry lost between
+    the sweeps shifts rows (and the total) and cannot cancel. The last ray sits inside the box: with the random alpha it is kept,
+    so at 65537 the one entry of the second sweep's workgroup writes a row whose place is the carry; with "alternating" entry
+    65536 is dropped and the carry shows in the total alone."""
+    base = rays(n, seed=n)
+    base["origins"][-1], base["depth"][-1] = 0.0, 0.05
+    box = crop_box()
+    for name in ("all", "alternating"):
+        r = pattern(base, name)
+        t = {k: T(v).to(dev) for k, v in r.items()}
+        sel = Select(n, dev, True)
+        sel.launch(t, True, True, box)
+        ref = torch_select(r, True, True, box, dev)
+        m = int(sel.cursor[0])
+        print(f"n = {n}, {name}: {len(ref[0])} kept by the torch composition, {m} by the kernels")
+        assert len(ref[0]) > 256 and len(ref[0]) % 256 != 0
+        if name == "all":  # the last ray is kept (the directions tell the rays apart)
+            assert torch.equal(ref[2][-1], t["directions"][-1])
+        assert m == len(ref[0]) and int(sel.cursor[1]) == 0, name
+        for got, want in zip(sel.rows(m), ref):
+            assert torch.equal(got.view(torch.int32), want.view(torch.int32)), name
+        assert sel.guards_intact(m)
 
 
 def test_points_select_appends_refuses_an_overflow_and_repeats_its_bits(dev):
@@ -278,24 +307,46 @@ def test_knn_is_exact_with_points_far_outside_the_grid_box(dev):
     assert not np.isin(np.arange(30), kept.cpu().numpy()).any()
 
 
-def test_select_below_at_the_workgroup_edges(dev):
+def select_below_case(n):
+    rs = np.random.RandomState(n)
+    avg = rs.uniform(0, 2, n)
+    avg[rs.uniform(size=n) < 0.2] = 0.0
+    if n > 2:
+        avg[1] = np.nan
+    return avg
+
+
+def check_select_below(avg, dev):
+    """the kept indices and their count against pointcloud_reference.kept_indices, the guard rows; returns the reference's"""
     from nerfstudio_amd import _native as N
     from nerfstudio_amd import functional as F
 
+    n = len(avg)
+    a = T(avg).to(dev)
+    kept = torch.full((n + GUARD,), -7, dtype=torch.int64, device=dev)
+    count = torch.full((1,), -1, dtype=torch.int64, device=dev)
+    F.select_below_launch(a, torch.tensor([1.0], dtype=torch.float64, device=dev), kept[:n], count,
+                          torch.empty(N.select_scratch_words(n), dtype=torch.int64, device=dev))
+    want = pr.kept_indices(avg, 1.0)
+    assert int(count) == len(want) and np.array_equal(kept[:len(want)].cpu().numpy(), want)
+    assert bool((kept[len(want):] == -7).all())
+    return want
+
+
+def test_select_below_at_the_workgroup_edges(dev):
     for n in SIZES:
-        rs = np.random.RandomState(n)
-        avg = rs.uniform(0, 2, n)
-        avg[rs.uniform(size=n) < 0.2] = 0.0
-        if n > 2:
-            avg[1] = np.nan
-        a = T(avg).to(dev)
-        kept = torch.full((n + GUARD,), -7, dtype=torch.int64, device=dev)
-        count = torch.full((1,), -1, dtype=torch.int64, device=dev)
-        F.select_below_launch(a, torch.tensor([1.0], dtype=torch.float64, device=dev), kept[:n], count,
-                              torch.empty(N.select_scratch_words(n), dtype=torch.int64, device=dev))
-        want = pr.kept_indices(avg, 1.0)
-        assert int(count) == len(want) and np.array_equal(kept[:len(want)].cpu().numpy(), want)
-        assert bool((kept[len(want):] == -7).all())
+        check_select_below(select_below_case(n), dev)
+
+
+@pytest.mark.parametrize("n", SWEEP_SIZES)
+def test_select_below_across_the_sweeps_of_the_count_scan(dev, n):
+    """the last entry is kept, so at 65537 the second sweep's workgroup writes an index at the row the carry gives; the kept
+    count is above 256 and no multiple of 256, so a lost carry cannot cancel"""
+    avg = select_below_case(n)
+    avg[-1] = 0.5
+    want = check_select_below(avg, dev)
+    print(f"n = {n}: {len(want)} kept")
+    assert len(want) > 256 and len(want) % 256 != 0 and want[-1] == n - 1
 
 
 # ---------------------------------------------------------------- the layers, on the device ---------------------------------------
