@@ -10,7 +10,7 @@
 namespace nsamd {
 
 
-__global__ __launch_bounds__(kLossThreads) void interlevel_kernel(
+__global__ __launch_bounds__(kRayThreads) void interlevel_kernel(
     const float* __restrict__ c_in, const float* __restrict__ w_in, int Sf, const float* __restrict__ cp_in,
     const float* __restrict__ wp_in, int Sp, int64_t num_rays, float grad_scale, float* __restrict__ per_ray,
     float* __restrict__ dwp) {
@@ -19,11 +19,11 @@ __global__ __launch_bounds__(kLossThreads) void interlevel_kernel(
                   grad_scale, per_ray, dwp);
 }
 
-__global__ __launch_bounds__(kLossThreads) void distortion_kernel(const float* __restrict__ s_bins,
-                                                                  const float* __restrict__ weights, int S,
-                                                                  int64_t num_rays, float grad_scale,
-                                                                  float* __restrict__ per_ray,
-                                                                  float* __restrict__ dw) {
+__global__ __launch_bounds__(kRayThreads) void distortion_kernel(const float* __restrict__ s_bins,
+                                                                 const float* __restrict__ weights, int S,
+                                                                 int64_t num_rays, float grad_scale,
+                                                                 float* __restrict__ per_ray,
+                                                                 float* __restrict__ dw) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   distortion_body(lds + (size_t)wave_index() * 2 * S, s_bins, weights, S, num_rays, grad_scale, per_ray, dw);
 }
@@ -40,7 +40,7 @@ struct PropLossArgs {
   int levels;
 };
 
-__global__ __launch_bounds__(kLossThreads) void proposal_losses_kernel(
+__global__ __launch_bounds__(kRayThreads) void proposal_losses_kernel(
     const float* __restrict__ s_fine, const float* __restrict__ w_fine, int Sf, PropLossArgs a, int64_t num_rays,
     float inter_scale, float dist_scale, float* __restrict__ dist_per_ray, float* __restrict__ dw_dist) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -68,12 +68,12 @@ struct DepthLossArgs {
   int levels;
 };
 
-__global__ __launch_bounds__(kLossThreads) void depth_loss_kernel(
+__global__ __launch_bounds__(kRayThreads) void depth_loss_kernel(
     DepthLossArgs a, int64_t num_rays, const float* __restrict__ termination_depth,
     const float* __restrict__ directions_norm, const float* __restrict__ predicted_depth, float sigma, float log_scale,
     int loss_type, float scale, int accumulate, float* __restrict__ per_ray, float* __restrict__ d_predicted) {
   const int lane = threadIdx.x & 63, wave = wave_index();
-  const int64_t ray = (int64_t)blockIdx.x * kLossRays + wave;
+  const int64_t ray = (int64_t)blockIdx.x * kRaysPerBlock + wave;
   if (ray >= num_rays) return;  // wave-uniform
   const int lvl = blockIdx.y;
   const int S = a.S[lvl];
@@ -134,7 +134,7 @@ extern "C" int nsamd_proposal_losses(const float* s_bins_fine, const float* w_fi
   if (S_fine > 2048) return NSAMD_ERR_UNSUPPORTED;
   PropLossArgs a{};
   a.levels = levels;
-  size_t lds = sizeof(float) * 2 * S_fine * kLossRays;
+  size_t lds = sizeof(float) * 2 * S_fine * kRaysPerBlock;
   for (int i = 0; i < levels; ++i) {
     NSAMD_REQUIRE(s_bins_prop[i] && w_prop[i] && interlevel_per_ray[i] && S_prop[i] > 0);
     a.s_bins[i] = s_bins_prop[i];
@@ -144,11 +144,11 @@ extern "C" int nsamd_proposal_losses(const float* s_bins_fine, const float* w_fi
     a.S[i] = S_prop[i];
     const size_t per_wave =
         sizeof(float) * ((2 * (S_fine + 2) + 2 * (S_prop[i] + 1) + (S_fine + 1) + 4 * S_fine + 1) & ~1);
-    if (per_wave * kLossRays > lds) lds = per_wave * kLossRays;
+    if (per_wave * kRaysPerBlock > lds) lds = per_wave * kRaysPerBlock;
   }
   if (lds > 64 * 1024) return NSAMD_ERR_UNSUPPORTED;
-  dim3 g((unsigned)((num_rays + kLossRays - 1) / kLossRays), (unsigned)(levels + 1));
-  proposal_losses_kernel<<<g, kLossThreads, lds, (hipStream_t)stream>>>(
+  dim3 g((unsigned)((num_rays + kRaysPerBlock - 1) / kRaysPerBlock), (unsigned)(levels + 1));
+  proposal_losses_kernel<<<g, kRayThreads, lds, (hipStream_t)stream>>>(
       s_bins_fine, w_fine, S_fine, a, num_rays, interlevel_grad_scale, distortion_grad_scale, distortion_per_ray,
       dw_distortion);
   NSAMD_CHECK_LAUNCH();
@@ -163,9 +163,9 @@ extern "C" int nsamd_interlevel_loss(const float* s_bins_fine, const float* w_fi
   if (num_rays == 0) return NSAMD_OK;
   NSAMD_REQUIRE(s_bins_fine && w_fine && s_bins_prop && w_prop && per_ray_loss);
   const size_t per_wave = sizeof(float) * ((2 * (S_fine + 2) + 2 * (S_prop + 1) + (S_fine + 1) + 4 * S_fine + 1) & ~1);
-  if (per_wave * kLossRays > 64 * 1024) return NSAMD_ERR_UNSUPPORTED;
-  const unsigned blocks = (unsigned)((num_rays + kLossRays - 1) / kLossRays);
-  interlevel_kernel<<<blocks, kLossThreads, per_wave * kLossRays, (hipStream_t)stream>>>(
+  if (per_wave * kRaysPerBlock > 64 * 1024) return NSAMD_ERR_UNSUPPORTED;
+  const unsigned blocks = (unsigned)((num_rays + kRaysPerBlock - 1) / kRaysPerBlock);
+  interlevel_kernel<<<blocks, kRayThreads, per_wave * kRaysPerBlock, (hipStream_t)stream>>>(
       s_bins_fine, w_fine, S_fine, s_bins_prop, w_prop, S_prop, num_rays, grad_scale, per_ray_loss, dw_prop);
   NSAMD_CHECK_LAUNCH();
   return NSAMD_OK;
@@ -178,8 +178,8 @@ extern "C" int nsamd_distortion_loss(const float* s_bins, const float* weights, 
   if (num_rays == 0) return NSAMD_OK;
   NSAMD_REQUIRE(s_bins && weights && per_ray_loss);
   if (S > 2048) return NSAMD_ERR_UNSUPPORTED;
-  const unsigned blocks = (unsigned)((num_rays + kLossRays - 1) / kLossRays);
-  distortion_kernel<<<blocks, kLossThreads, sizeof(float) * 2 * S * kLossRays, (hipStream_t)stream>>>(
+  const unsigned blocks = (unsigned)((num_rays + kRaysPerBlock - 1) / kRaysPerBlock);
+  distortion_kernel<<<blocks, kRayThreads, sizeof(float) * 2 * S * kRaysPerBlock, (hipStream_t)stream>>>(
       s_bins, weights, S, num_rays, grad_scale, per_ray_loss, dweights);
   NSAMD_CHECK_LAUNCH();
   return NSAMD_OK;
@@ -194,7 +194,7 @@ extern "C" int nsamd_depth_loss(int32_t levels, const float* const* t_bins, cons
   if (!depth_loss_type_supported(loss_type) || levels > kMaxDepthLevels) return NSAMD_ERR_UNSUPPORTED;
   for (int i = 0; i < levels; ++i)
     if (S[i] < 1 || S[i] > kMaxDepthSamples) return NSAMD_ERR_UNSUPPORTED;
-  if (num_rays > (int64_t)kLossRays * 0x7fffffff) return NSAMD_ERR_UNSUPPORTED;
+  if (num_rays > (int64_t)kRaysPerBlock * 0x7fffffff) return NSAMD_ERR_UNSUPPORTED;
   if (num_rays == 0) return NSAMD_OK;
   NSAMD_REQUIRE(termination_depth && (loss_type != kDepthLossUrf || predicted_depth));
   DepthLossArgs a{};
@@ -207,10 +207,10 @@ extern "C" int nsamd_depth_loss(int32_t levels, const float* const* t_bins, cons
     a.S[i] = S[i];
   }
   const float log_scale = loss_type == kDepthLossUrf ? urf_log_scale(sigma) : 0.0f;  // host, once per launch
-  dim3 g((unsigned)((num_rays + kLossRays - 1) / kLossRays), (unsigned)levels);
-  depth_loss_kernel<<<g, kLossThreads, 0, (hipStream_t)stream>>>(a, num_rays, termination_depth, directions_norm,
-                                                                 predicted_depth, sigma, log_scale, loss_type, scale, accumulate,
-                                                                 per_ray, d_predicted);
+  dim3 g((unsigned)((num_rays + kRaysPerBlock - 1) / kRaysPerBlock), (unsigned)levels);
+  depth_loss_kernel<<<g, kRayThreads, 0, (hipStream_t)stream>>>(a, num_rays, termination_depth, directions_norm,
+                                                                predicted_depth, sigma, log_scale, loss_type, scale, accumulate,
+                                                                per_ray, d_predicted);
   NSAMD_CHECK_LAUNCH();
   return NSAMD_OK;
 }

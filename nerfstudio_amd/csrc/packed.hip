@@ -8,36 +8,15 @@
 //
 // Layout: samples of a ray are contiguous, rays in increasing order ("packed"); packed_info[r] = (start, count) int64.
 // Variable-length rows, so every per-ray kernel is one WAVEFRONT per ray walking its segment in chunks of 64 with a
-// carried running sum (double, like the dense scans of sampler.hip): the scan that gives the transmittance in front of
-// each sample is also what decides, in visibility order, where a ray stops contributing.
-#include "common.h"
+// carried running sum (double): the dense rays' own scan step (wave_scan_carry_f64 of wave.h, sample_transmittance of
+// ray_bodies.h), so equal rays give equal bits on both paths. The scan that gives the transmittance in front of each sample is
+// also what decides, in visibility order, where a ray stops contributing. Workgroups are the dense kernels' too: kRayThreads
+// threads, a ray per wavefront. Every scan call below is reached by all 64 lanes: a ray's count, hence its chunk loops, its
+// early return and the visibility break are wave-uniform.
+#include "ray_bodies.h"
 #include "../../include/nsamd_render.h"
 
 namespace nsamd {
-
-constexpr int kPackThreads = 256;
-constexpr int kPackWaves = kPackThreads / 64;
-
-__device__ __forceinline__ double pk_scan_inclusive(double v, int lane) {
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const double o = __shfl_up(v, d);
-    if (lane >= d) v += o;
-  }
-  return v;
-}
-
-// One 64-sample chunk of a ray's transmittance scan, shared by packed_weights_kernel and packed_render_kernel: dd = sigma dt of
-// this lane's sample (0 outside the ray), `carry` = the optical depth in front of the chunk (double, advanced to the next
-// chunk's) -> alpha = 1 - exp(-dd) and the transmittance in front of the sample, T = exp(-(float) exclusive prefix).
-__device__ __forceinline__ void pk_transmittance_chunk(float dd, int lane, double& carry, float& alpha, float& trans) {
-  const double incl = carry + pk_scan_inclusive((double)dd, lane);
-  double excl = __shfl_up(incl, 1);
-  if (lane == 0) excl = carry;
-  carry = __shfl(incl, 63);
-  alpha = 1.0f - expf(-dd);
-  trans = expf(-(float)excl);
-}
 
 // A lane's partial sums of the packed compositing (packed_composite_fwd_kernel, packed_render_kernel): one sample added per
 // call in the lane's own order, the xor butterfly over the wavefront, lane 0's epilogue.
@@ -50,6 +29,7 @@ __device__ __forceinline__ void pk_add_sample(pk_sums& s, float w, float r0, flo
   s.a += w;
 }
 __device__ __forceinline__ void pk_add_depth(pk_sums& s, float w, float ts, float te) { s.dsum += w * ((ts + te) / 2.0f); }
+// (partners 1, 2, ..., 32: not wave_sum's association, see wave.h)
 __device__ __forceinline__ void pk_reduce(pk_sums& s) {
 #pragma unroll
   for (int m = 1; m < 64; m <<= 1) {
@@ -294,12 +274,12 @@ __global__ __launch_bounds__(1024) void packed_info_kernel(const int32_t* __rest
 // keep-mask T_i >= early_stop_eps && alpha_i >= alpha_thre and its per-ray count — T is non-increasing along the ray, so
 // the first sample behind the threshold ends the ray (visibility-ordered early termination).
 template <bool kVisibility>
-__global__ __launch_bounds__(kPackThreads) void packed_weights_kernel(
+__global__ __launch_bounds__(kRayThreads) void packed_weights_kernel(
     const float* __restrict__ t_starts, const float* __restrict__ t_ends, const float* __restrict__ sigmas,
     const int64_t* __restrict__ info, int64_t num_rays, float early_stop_eps, float alpha_thre,
     float* __restrict__ weights, float* __restrict__ trans_out, uint8_t* __restrict__ mask, int32_t* __restrict__ kept) {
   const int lane = threadIdx.x & 63;
-  const int64_t ray = (int64_t)blockIdx.x * kPackWaves + (threadIdx.x >> 6);
+  const int64_t ray = (int64_t)blockIdx.x * kRaysPerBlock + (threadIdx.x >> 6);
   if (ray >= num_rays) return;  // wave-uniform
   const int64_t s0 = info[2 * ray], cnt = info[2 * ray + 1];
   double carry = 0.0;
@@ -308,8 +288,8 @@ __global__ __launch_bounds__(kPackThreads) void packed_weights_kernel(
     const int64_t i = i0 + lane;
     const bool in = i < cnt;
     const float dd = in ? sigmas[s0 + i] * (t_ends[s0 + i] - t_starts[s0 + i]) : 0.0f;
-    float alpha, trans;
-    pk_transmittance_chunk(dd, lane, carry, alpha, trans);
+    const SampleTransmittance t = sample_transmittance(dd, wave_scan_carry_f64((double)dd, carry).excl);
+    const float alpha = 1.0f - t.ex, trans = t.trans;
     if (kVisibility) {
       const bool k = in && trans >= early_stop_eps && alpha >= alpha_thre;
       if (in) mask[s0 + i] = k ? 1 : 0;
@@ -335,11 +315,11 @@ __global__ __launch_bounds__(kPackThreads) void packed_weights_kernel(
 // which one opaque sample (dd 1e10) behind thin ones makes visible in every T in front of it, and Inf - Inf is NaN.
 // A ray longer than 64 chunks (4096 samples) is handled in blocks of 64 chunks, last block first; pass A runs again from
 // the ray's start for each block (same sums, same bits).
-__global__ __launch_bounds__(kPackThreads) void packed_weights_bwd_kernel(
+__global__ __launch_bounds__(kRayThreads) void packed_weights_bwd_kernel(
     const float* __restrict__ t_starts, const float* __restrict__ t_ends, const float* __restrict__ sigmas,
     const float* __restrict__ dweights, const int64_t* __restrict__ info, int64_t num_rays, float* __restrict__ dsigmas) {
   const int lane = threadIdx.x & 63;
-  const int64_t ray = (int64_t)blockIdx.x * kPackWaves + (threadIdx.x >> 6);
+  const int64_t ray = (int64_t)blockIdx.x * kRaysPerBlock + (threadIdx.x >> 6);
   if (ray >= num_rays) return;
   const int64_t s0 = info[2 * ray], cnt = info[2 * ray + 1];
   const int64_t chunks = (cnt + 63) >> 6;
@@ -351,40 +331,32 @@ __global__ __launch_bounds__(kPackThreads) void packed_weights_bwd_kernel(
       const int64_t i = c * 64 + lane;
       const float dd = i < cnt ? sigmas[s0 + i] * (t_ends[s0 + i] - t_starts[s0 + i]) : 0.0f;
       if (c - b0 == lane) held = carry;
-      carry = __shfl(carry + pk_scan_inclusive((double)dd, lane), 63);
+      wave_scan_carry_f64((double)dd, carry);
     }
     for (int64_t c = b1 - 1; c >= b0; --c) {
       const int64_t i = c * 64 + lane;
       const bool in = i < cnt;
       const float dt = in ? t_ends[s0 + i] - t_starts[s0 + i] : 0.0f;
       const float dd = in ? sigmas[s0 + i] * dt : 0.0f;
-      const double before = __shfl(held, (int)(c - b0));
-      const double incl = before + pk_scan_inclusive((double)dd, lane);
-      double excl = __shfl_up(incl, 1);
-      if (lane == 0) excl = before;
-      const float ex = expf(-dd);
-      const float trans = expf(-(float)excl);
+      double before = __shfl(held, (int)(c - b0));
+      const SampleTransmittance t = sample_transmittance(dd, wave_scan_carry_f64((double)dd, before).excl);
       const float g = in ? dweights[s0 + i] : 0.0f;
-      const float gw = in ? g * ((1.0f - ex) * trans) : 0.0f;
-      // suffix over the later samples: the lanes mirrored, scanned, mirrored back
-      const double incl_gw = suf_gw + pk_scan_inclusive(__shfl((double)gw, 63 - lane), lane);
-      double excl_gw = __shfl_up(incl_gw, 1);
-      if (lane == 0) excl_gw = suf_gw;
-      suf_gw = __shfl(incl_gw, 63);
-      excl_gw = __shfl(excl_gw, 63 - lane);
-      if (in) dsigmas[s0 + i] = dt * (g * trans * ex - (float)excl_gw);
+      const float gw = in ? g * ((1.0f - t.ex) * t.trans) : 0.0f;
+      // suffix over the later samples: the lanes mirrored (a lane reversal has no DPP form), scanned, mirrored back
+      const double excl_gw = __shfl(wave_scan_carry_f64(__shfl((double)gw, 63 - lane), suf_gw).excl, 63 - lane);
+      if (in) dsigmas[s0 + i] = dt * (g * t.trans * t.ex - (float)excl_gw);
     }
   }
 }
 
 // Keep the samples whose mask is set: new packed_info from the per-ray kept counts (packed_info_kernel), then one
 // wavefront per ray moves its survivors to their new place (order preserved).
-__global__ __launch_bounds__(kPackThreads) void packed_compact_kernel(
+__global__ __launch_bounds__(kRayThreads) void packed_compact_kernel(
     const uint8_t* __restrict__ mask, const int64_t* __restrict__ info_old, const int64_t* __restrict__ info_new,
     int64_t num_rays, const float* __restrict__ t_starts, const float* __restrict__ t_ends,
     int64_t* __restrict__ ray_indices_out, float* __restrict__ t_starts_out, float* __restrict__ t_ends_out) {
   const int lane = threadIdx.x & 63;
-  const int64_t ray = (int64_t)blockIdx.x * kPackWaves + (threadIdx.x >> 6);
+  const int64_t ray = (int64_t)blockIdx.x * kRaysPerBlock + (threadIdx.x >> 6);
   if (ray >= num_rays) return;
   const int64_t s0 = info_old[2 * ray], cnt = info_old[2 * ray + 1];
   int64_t dst = info_new[2 * ray];
@@ -405,13 +377,13 @@ __global__ __launch_bounds__(kPackThreads) void packed_compact_kernel(
 // ---- packed compositing (accumulate_along_rays; renderers.py:93-119, 310-317, 365-383) ------------------------------
 // rgb = sum w c (+ background (1 - acc) for "white" / "black" / a colour; "random": nothing), acc = sum w,
 // depth = sum w (t_start + t_end) / 2 / (acc + 1e-10). eval_mode: nan_to_num on the samples' colours, clamp to [0, 1].
-__global__ __launch_bounds__(kPackThreads) void packed_composite_fwd_kernel(
+__global__ __launch_bounds__(kRayThreads) void packed_composite_fwd_kernel(
     const float* __restrict__ rgb, const float* __restrict__ weights, const float* __restrict__ t_starts,
     const float* __restrict__ t_ends, const int64_t* __restrict__ info, int64_t num_rays, int bg_mode, float bg0,
     float bg1, float bg2, int eval_mode, float* __restrict__ out_rgb, float* __restrict__ out_acc,
     float* __restrict__ out_depth) {
   const int lane = threadIdx.x & 63;
-  const int64_t ray = (int64_t)blockIdx.x * kPackWaves + (threadIdx.x >> 6);
+  const int64_t ray = (int64_t)blockIdx.x * kRaysPerBlock + (threadIdx.x >> 6);
   if (ray >= num_rays) return;
   const int64_t s0 = info[2 * ray], cnt = info[2 * ray + 1];
   pk_sums s;
@@ -430,13 +402,13 @@ __global__ __launch_bounds__(kPackThreads) void packed_composite_fwd_kernel(
 // weights never written: 24 B read per sample (interval, density, colour) instead of 40 B moved. No early exit once the
 // transmittance has underflowed: the two launches have none, and 0 * NaN must stay NaN without eval_mode.
 // mid_lo / mid_hi (nullable together): min / max of (t_start + t_end) / 2 over the ray's samples, +inf / -inf without any.
-__global__ __launch_bounds__(kPackThreads) void packed_render_kernel(
+__global__ __launch_bounds__(kRayThreads) void packed_render_kernel(
     const float* __restrict__ t_starts, const float* __restrict__ t_ends, const float* __restrict__ sigmas,
     const float* __restrict__ rgb, const int64_t* __restrict__ info, int64_t num_rays, int bg_mode, float bg0, float bg1,
     float bg2, int eval_mode, float* __restrict__ out_rgb, float* __restrict__ out_acc, float* __restrict__ out_depth,
     float* __restrict__ mid_lo, float* __restrict__ mid_hi) {
   const int lane = threadIdx.x & 63;
-  const int64_t ray = (int64_t)blockIdx.x * kPackWaves + (threadIdx.x >> 6);
+  const int64_t ray = (int64_t)blockIdx.x * kRaysPerBlock + (threadIdx.x >> 6);
   if (ray >= num_rays) return;  // wave-uniform
   const int64_t s0 = info[2 * ray], cnt = info[2 * ray + 1];
   double carry = 0.0;
@@ -447,10 +419,9 @@ __global__ __launch_bounds__(kPackThreads) void packed_render_kernel(
     const bool in = i < cnt;
     const float ts = in ? t_starts[s0 + i] : 0.0f, te = in ? t_ends[s0 + i] : 0.0f;
     const float dd = in ? sigmas[s0 + i] * (te - ts) : 0.0f;
-    float alpha, trans;
-    pk_transmittance_chunk(dd, lane, carry, alpha, trans);
+    const SampleTransmittance t = sample_transmittance(dd, wave_scan_carry_f64((double)dd, carry).excl);
     if (in) {
-      const float w = trans * alpha;
+      const float w = t.trans * (1.0f - t.ex);
       pk_add_sample(s, w, rgb[3 * (s0 + i)], rgb[3 * (s0 + i) + 1], rgb[3 * (s0 + i) + 2], eval_mode);
       pk_add_depth(s, w, ts, te);
       const float mid = (ts + te) / 2.0f;
@@ -459,11 +430,8 @@ __global__ __launch_bounds__(kPackThreads) void packed_render_kernel(
     }
   }
   pk_reduce(s);
-#pragma unroll
-  for (int m = 1; m < 64; m <<= 1) {
-    lo = fminf(lo, __shfl_xor(lo, m));
-    hi = fmaxf(hi, __shfl_xor(hi, m));
-  }
+  lo = wave_min(lo);
+  hi = wave_max(hi);
   if (lane == 0) {
     pk_write_ray(s, ray, bg_mode, bg0, bg1, bg2, eval_mode, out_rgb, out_acc, out_depth);
     if (mid_lo != nullptr) {
@@ -524,7 +492,7 @@ __global__ void packed_ray_points_kernel(const float* __restrict__ origins, cons
   for (int k = 0; k < 3; ++k) sample_directions[3 * s + k] = directions[3 * ray + k];
 }
 
-static unsigned pack_ray_blocks(int64_t rays) { return (unsigned)((rays + kPackWaves - 1) / kPackWaves); }
+static unsigned pack_ray_blocks(int64_t rays) { return (unsigned)((rays + kRaysPerBlock - 1) / kRaysPerBlock); }
 
 // ---- occupancy-grid maintenance (nerfacc OccGridEstimator.update_every_n_steps / _update) ---------------------------
 // x[i] = position inside cell `cells[i]` (flat index over [levels, R, R, R]; nullptr: cell i) at the fractional offset
@@ -804,7 +772,7 @@ extern "C" int nsamd_packed_weights_fwd(const float* t_starts, const float* t_en
   NSAMD_REQUIRE(num_rays >= 0);
   if (num_rays == 0) return NSAMD_OK;
   NSAMD_REQUIRE(t_starts && t_ends && sigmas && packed_info && weights);
-  packed_weights_kernel<false><<<pack_ray_blocks(num_rays), kPackThreads, 0, (hipStream_t)stream>>>(
+  packed_weights_kernel<false><<<pack_ray_blocks(num_rays), kRayThreads, 0, (hipStream_t)stream>>>(
       t_starts, t_ends, sigmas, packed_info, num_rays, 0.0f, 0.0f, weights, transmittance, nullptr, nullptr);
   NSAMD_CHECK_LAUNCH();
   return NSAMD_OK;
@@ -816,7 +784,7 @@ extern "C" int nsamd_packed_weights_bwd(const float* t_starts, const float* t_en
   NSAMD_REQUIRE(num_rays >= 0);
   if (num_rays == 0) return NSAMD_OK;
   NSAMD_REQUIRE(t_starts && t_ends && sigmas && dweights && packed_info && dsigmas);
-  packed_weights_bwd_kernel<<<pack_ray_blocks(num_rays), kPackThreads, 0, (hipStream_t)stream>>>(
+  packed_weights_bwd_kernel<<<pack_ray_blocks(num_rays), kRayThreads, 0, (hipStream_t)stream>>>(
       t_starts, t_ends, sigmas, dweights, packed_info, num_rays, dsigmas);
   NSAMD_CHECK_LAUNCH();
   return NSAMD_OK;
@@ -828,7 +796,7 @@ extern "C" int nsamd_packed_visibility(const float* t_starts, const float* t_end
   NSAMD_REQUIRE(num_rays >= 0);
   if (num_rays == 0) return NSAMD_OK;
   NSAMD_REQUIRE(t_starts && t_ends && sigmas && packed_info && mask && kept_counts);
-  packed_weights_kernel<true><<<pack_ray_blocks(num_rays), kPackThreads, 0, (hipStream_t)stream>>>(
+  packed_weights_kernel<true><<<pack_ray_blocks(num_rays), kRayThreads, 0, (hipStream_t)stream>>>(
       t_starts, t_ends, sigmas, packed_info, num_rays, early_stop_eps, alpha_thre, nullptr, nullptr, mask, kept_counts);
   NSAMD_CHECK_LAUNCH();
   return NSAMD_OK;
@@ -841,7 +809,7 @@ extern "C" int nsamd_packed_compact(const uint8_t* mask, const int64_t* packed_i
   if (num_rays == 0) return NSAMD_OK;
   NSAMD_REQUIRE(mask && packed_info_old && packed_info_new && t_starts && t_ends && ray_indices_out && t_starts_out &&
                 t_ends_out);
-  packed_compact_kernel<<<pack_ray_blocks(num_rays), kPackThreads, 0, (hipStream_t)stream>>>(
+  packed_compact_kernel<<<pack_ray_blocks(num_rays), kRayThreads, 0, (hipStream_t)stream>>>(
       mask, packed_info_old, packed_info_new, num_rays, t_starts, t_ends, ray_indices_out, t_starts_out, t_ends_out);
   NSAMD_CHECK_LAUNCH();
   return NSAMD_OK;
@@ -859,7 +827,7 @@ extern "C" int nsamd_packed_composite_fwd(const float* rgb, const float* weights
   NSAMD_REQUIRE(out_depth == nullptr || (t_starts && t_ends));
   const float b0 = background_mode ? background_rgb_host[0] : 0.f, b1 = background_mode ? background_rgb_host[1] : 0.f,
               b2 = background_mode ? background_rgb_host[2] : 0.f;
-  packed_composite_fwd_kernel<<<pack_ray_blocks(num_rays), kPackThreads, 0, (hipStream_t)stream>>>(
+  packed_composite_fwd_kernel<<<pack_ray_blocks(num_rays), kRayThreads, 0, (hipStream_t)stream>>>(
       rgb, weights, out_depth ? t_starts : nullptr, t_ends, packed_info, num_rays, background_mode, b0, b1, b2, eval_mode,
       out_rgb, out_accumulation, out_depth);
   NSAMD_CHECK_LAUNCH();
@@ -908,11 +876,11 @@ extern "C" int nsamd_packed_render_fwd(const float* t_starts, const float* t_end
   if (num_rays == 0) return NSAMD_OK;
   NSAMD_REQUIRE(t_starts && t_ends && sigmas && rgb && packed_info && out_rgb && out_accumulation && out_depth);
   NSAMD_REQUIRE(background_mode == 0 || background_rgb_host != nullptr);
-  const int64_t nb = (num_rays + kPackWaves - 1) / kPackWaves;
+  const int64_t nb = (num_rays + kRaysPerBlock - 1) / kRaysPerBlock;
   if (nb > 0x7fffffffLL) return NSAMD_ERR_UNSUPPORTED;
   const float b0 = background_mode ? background_rgb_host[0] : 0.f, b1 = background_mode ? background_rgb_host[1] : 0.f,
               b2 = background_mode ? background_rgb_host[2] : 0.f;
-  packed_render_kernel<<<(unsigned)nb, kPackThreads, 0, (hipStream_t)stream>>>(
+  packed_render_kernel<<<(unsigned)nb, kRayThreads, 0, (hipStream_t)stream>>>(
       t_starts, t_ends, sigmas, rgb, packed_info, num_rays, background_mode, b0, b1, b2, eval_mode, out_rgb, out_accumulation,
       out_depth, out_mid_lo, out_mid_hi);
   NSAMD_CHECK_LAUNCH();

@@ -1,10 +1,17 @@
-// Per-ray device bodies (one wavefront per ray) shared by the stand-alone launches of render.hip / losses.hip / sampler.hip and
-// by the training step's fused per-ray launch (fused_rays.hip: compositing + depth + MSE + proposal losses + compositing backward
-// [+ the proposal levels' weights backward] in ONE launch). Each body is the code its kernel used to hold, moved here unchanged:
-// the fused launch concatenates them inside one wave, so its results are the stand-alone launches' bits by construction.
-// A body takes the wave's LDS row as a pointer (`lds_wave`); the caller lays the rows of a workgroup's waves out with ONE stride
-// (the largest any body of the launch needs), so that waves of a workgroup in different bodies never overlap.
-// Every body maps  ray = blockIdx.x * 4 + wave  (256-thread workgroups). Not part of the C ABI.
+// Per-ray device bodies (one wavefront per ray) of the launches of render.hip, losses.hip and sampler.hip, and the steps that
+// packed.hip's variable-length rays share with them. Which launch runs which body today:
+//   composite_fwd_body   composite_fwd_kernel (render.hip: nsamd_composite_fwd, nsamd_render_train)
+//   composite_bwd_body   composite_bwd_kernel (render.hip: nsamd_composite_bwd, nsamd_render_train_bwd)
+//   weights_bwd_body     weights_bwd_kernel and, two levels per launch, weights_bwd_pair_kernel (sampler.hip)
+//   piecewise_bins_body  piecewise_bins_kernel and select_bins_kernel (sampler.hip)
+//   pdf_resample_body    pdf_resample_kernel<false / true> (sampler.hip: nsamd_pdf_resample, nsamd_proposal_resample)
+//   interlevel_body, distortion_body   their own kernels and, one per blockIdx.y, proposal_losses_kernel (losses.hip)
+// and the steps below them: the carried scan of wave.h, sample_transmittance / sample_weight (also weights_fwd_kernel and the
+// packed weights, backward and render kernels), weights_bwd_passes (weights_bwd_body and composite_bwd_body's density tail),
+// median_index (composite_fwd_body, pdf_resample_body<true>). Shared code is what makes two launches' results the same bits.
+// A body takes the wave's LDS row as a pointer (`lds_wave`); a kernel that runs different bodies in the waves of one launch
+// lays the rows out with the largest stride any of them needs.
+// Every launch maps  ray = blockIdx.x * kRaysPerBlock + wave  (kRayThreads-thread workgroups). Not part of the C ABI.
 #pragma once
 
 #include "common.h"
@@ -12,8 +19,8 @@
 
 namespace nsamd {
 
-constexpr int kRenderThreads = 256;
-constexpr int kRaysPerBlock = kRenderThreads / 64;
+constexpr int kRayThreads = 256;
+constexpr int kRaysPerBlock = kRayThreads / 64;
 
 #if defined(__HIPCC__)
 // Host (render.hip): the finishing pass of the expected depth — re-reduces the per-workgroup min / max partials in `ws` and clips
@@ -21,33 +28,103 @@ constexpr int kRaysPerBlock = kRenderThreads / 64;
 int depth_clip_launch(float* depth, int64_t n, float* ws, int partials, hipStream_t stream);
 #endif
 
+// ---- steps shared by the bodies -------------------------------------------------------------------------------------------
+
+// number of entries of sorted a[0..n) that are <= v   (torch.searchsorted side="right")
+__device__ __forceinline__ int upper_bound(const float* a, int n, float v) {
+  int lo = 0, hi = n;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (a[mid] <= v) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// One sample of RaySamples.get_weights (cameras/rays.py:129-152): dd = density * delta of the sample, optical_depth = the sum of
+// dd over the samples in front of it — the `.excl` of wave_scan_carry_f64 over the ray's dd, a chunk of 64 samples per call —
+// -> ex = exp(-dd) (alpha = 1 - ex) and the transmittance in front of the sample, T = exp(-(float) optical_depth).
+// Per lane, no wave-level operation: a kernel calls it for the lanes that hold a sample.
+struct SampleTransmittance {
+  float ex, trans;
+};
+__device__ __forceinline__ SampleTransmittance sample_transmittance(float dd, double optical_depth) {
+  return {expf(-dd), expf(-(float)optical_depth)};
+}
+// ... and the sample's weight, nan_to_num as the dense reference has it (the packed kernels take alpha * T as it comes)
+__device__ __forceinline__ float sample_weight(float dd, double optical_depth) {
+  const SampleTransmittance t = sample_transmittance(dd, optical_depth);
+  return nan_to_num((1.0f - t.ex) * t.trans);
+}
+
+// searchsorted(cumsum(w), 0.5, side="left"), clamped to S - 1  (DepthRenderer "median", renderers.py:359-362). torch.cumsum (CPU)
+// accumulates in double and rounds each output to fp32: the carried wave scan in double (see sampler.hip on why that is the same
+// number). w: the ray's weight row, global or LDS. Wave-uniform result; all 64 lanes call it.
+__device__ __forceinline__ int median_index(const float* w, int S) {
+  const int lane = threadIdx.x & 63;
+  double carry = 0.0;
+  int idx = S;
+  for (int s0 = 0; s0 < S && idx == S; s0 += 64) {
+    const int s = s0 + lane;
+    const double incl = wave_scan_carry_f64(s < S ? (double)w[s] : 0.0, carry).incl;
+    const unsigned long long hit = __ballot(s < S && (float)incl >= 0.5f);
+    if (hit != 0ull) idx = s0 + __builtin_ctzll(hit);
+  }
+  return min(idx, S - 1);
+}
+
+// The two passes of RaySamples.get_weights' backward for one ray: d(weights)/d(density), dd_j gets
+//     gw_j * T_j * exp(-dd_j)  -  sum_{i>j} gw_i * w_i        (through delta_j),
+// where gw = the upstream gradient of the weights with nan_to_num's backward applied (0 where the forward product is not finite).
+// Pass 1 walks the ray forwards and leaves ex = exp(-dd) and T in LDS rows; pass 2 scans the REVERSED row: exclusive suffix sums
+// of gw * w (reverse cumsum, as autograd). lds_wave: 3 S floats of the wave. The upstream gradient comes in one of two ways:
+//   kGradientInLds false: dw[S] is in global memory; pass 1 masks it and leaves it in LDS: rows ex, T, gw (weights_bwd_body);
+//   kGradientInLds true:  the caller has just written it, unmasked, to the FIRST row: rows dw, ex, T (composite_bwd_body); pass 2
+//                         masks it as it reads, and `dw` is not used.
+// All 64 lanes call it; it fences the wave's LDS writes (the caller's included) before pass 2 reads them.
+template <bool kGradientInLds>
+__device__ __forceinline__ void weights_bwd_passes(float* lds_wave, const float* tb, const float* dn, const float* dw, int S,
+                                                   float* ddensity) {
+  const int lane = threadIdx.x & 63;
+  float* ex_row = kGradientInLds ? lds_wave + S : lds_wave;
+  float* tr_row = ex_row + S;
+  float* g_row = kGradientInLds ? lds_wave : tr_row + S;
+  const auto finite = [](float ex, float trans) {  // nan_to_num backward masks non-finite products
+    const float w = (1.0f - ex) * trans;
+    return (w == w) && (fabsf(w) <= 3.4028234663852886e38f);
+  };
+  double carry = 0.0;
+  for (int i0 = 0; i0 < S; i0 += 64) {
+    const int i = i0 + lane;
+    const float dd = i < S ? (tb[i + 1] - tb[i]) * dn[i] : 0.0f;
+    const double excl = wave_scan_carry_f64((double)dd, carry).excl;
+    if (i < S) {
+      const SampleTransmittance t = sample_transmittance(dd, excl);
+      const float g = !kGradientInLds && finite(t.ex, t.trans) ? dw[i] : 0.0f;
+      ex_row[i] = t.ex;
+      tr_row[i] = t.trans;
+      if (!kGradientInLds) g_row[i] = g;
+    }
+  }
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  carry = 0.0;
+  for (int r0 = 0; r0 < S; r0 += 64) {
+    const int r = r0 + lane;      // reversed position
+    const int i = S - 1 - r;      // element
+    float ex = 0.0f, trans = 0.0f, g = 0.0f;
+    if (r < S) {
+      ex = ex_row[i];
+      trans = tr_row[i];
+      g = !kGradientInLds || finite(ex, trans) ? g_row[i] : 0.0f;
+    }
+    const float gw = g * ((1.0f - ex) * trans);
+    const double excl = wave_scan_carry_f64((double)(r < S ? gw : 0.0f), carry).excl;
+    if (r < S) ddensity[i] = (tb[i + 1] - tb[i]) * (g * trans * ex - (float)excl);
+  }
+}
+
 // ---- compositing (render.hip) ---------------------------------------------------------------------------------------
-
-
-__device__ __forceinline__ uint32_t float_key(float f) {
-  const uint32_t b = __float_as_uint(f);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float key_float(uint32_t k) {
-  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-__device__ __forceinline__ float wave_min(float v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v = fminf(v, __shfl_xor(v, o));
-  return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-  return v;
-}
-
 
 __device__ __forceinline__ void composite_fwd_body(float* blk_min, float* blk_max,
     const float* __restrict__ rgb, const float* __restrict__ weights, const float* __restrict__ t_bins,
@@ -59,7 +136,7 @@ __device__ __forceinline__ void composite_fwd_body(float* blk_min, float* blk_ma
   // background == 3 ("random", training): rgb_out is the composite WITHOUT a background (renderers.py:112-115) and the loss
   // is taken on rgb_out + bg_rays[ray] * (1 - acc) (blend_background_for_loss_computation, renderers.py:194-196).
   // density != nullptr (training step, nsamd_render_train): the weights are computed here from the densities
-  // (RaySamples.get_weights, as sampler.hip) and written to weights_out; target != nullptr adds the per-ray squared
+  // (RaySamples.get_weights: sample_weight) and written to weights_out; target != nullptr adds the per-ray squared
   // error and the MSE gradient of the composited colour.
   const int lane = threadIdx.x & 63, wave = wave_index();
   const int64_t ray = (int64_t)blockIdx.x * kRaysPerBlock + wave;
@@ -81,14 +158,9 @@ __device__ __forceinline__ void composite_fwd_body(float* blk_min, float* blk_ma
     float w = 0.0f;
     if (density) {
       const float dd = s < S ? (tb[s + 1] - tb[s]) * density[ray * S + s] : 0.0f;
-      double incl = (double)dd;
-      incl = wave_scan_inclusive_f64(incl);
-      incl = incl + w_carry;
-      double excl = wave_shift_up1_f64(incl);
-      if (lane == 0) excl = w_carry;
-      w_carry = wave_read_f64<63>(incl);
+      const double excl = wave_scan_carry_f64((double)dd, w_carry).excl;
       if (s < S) {
-        w = nan_to_num((1.0f - expf(-dd)) * expf(-(float)excl));
+        w = sample_weight(dd, excl);
         weights_out[ray * S + s] = w;
       }
     } else if (s < S) {
@@ -180,20 +252,7 @@ __device__ __forceinline__ void composite_fwd_body(float* blk_min, float* blk_ma
   }
   if (density) __threadfence_block();  // the median pass re-reads the weights this wave has just written
   if (tb && (depth_med || med_idx)) {
-    // searchsorted(cumsum(w), 0.5, side="left"), clamped  (renderers.py:359-362). torch.cumsum (CPU) accumulates in
-    // double and rounds each output to fp32: wave scan in double (see sampler.hip on why that is the same number).
-    double carry = 0.0;
-    int idx = S;
-    for (int s0 = 0; s0 < S && idx == S; s0 += 64) {
-      const int s2 = s0 + lane;
-      double v = s2 < S ? (double)w_in[s2] : 0.0;
-      v = wave_scan_inclusive_f64(v);
-      v = v + carry;
-      carry = wave_read_f64<63>(v);
-      const unsigned long long hit = __ballot(s2 < S && (float)v >= 0.5f);
-      if (hit != 0ull) idx = s0 + __builtin_ctzll(hit);
-    }
-    idx = min(idx, S - 1);
+    const int idx = median_index(w_in, S);
     if (lane == 0) {
       if (med_idx) med_idx[ray] = idx;
       if (depth_med) depth_med[ray] = (tb[idx] + tb[idx + 1]) / 2.0f;
@@ -209,7 +268,7 @@ __device__ __forceinline__ void composite_bwd_body(float* lds_wave,
     float* __restrict__ d_weights, const float* __restrict__ density, float* __restrict__ d_density,
     const float* __restrict__ bg_rays) {
   // density != nullptr (nsamd_render_train_bwd): d_weights is not stored; the gradient goes on through
-  // RaySamples.get_weights to d_density (same formulas as weights_bwd_kernel in sampler.hip).
+  // RaySamples.get_weights to d_density (weights_bwd_passes, the code of weights_bwd_kernel).
   const int lane = threadIdx.x & 63, wave = wave_index();
   const int64_t ray = (int64_t)blockIdx.x * kRaysPerBlock + wave;
   if (ray >= num_rays) return;
@@ -263,55 +322,12 @@ __device__ __forceinline__ void composite_bwd_body(float* lds_wave,
     o[1] = gg * e;
     o[2] = gb * e;
   }
-  if (density) {
-    // d weights / d density: dd_j gets  gw_j T_j exp(-dd_j) - sum_{i>j} gw_i w_i, through delta_j
-    const float* tbw = t_bins + ray * (S + 1);
-    float* dwr = lds_wave;
-    float* ex_row = dwr + S;
-    float* tr_row = ex_row + S;
-    double carry = 0.0;
-    for (int i0 = 0; i0 < S; i0 += 64) {
-      const int i = i0 + lane;
-      const float dd = i < S ? (tbw[i + 1] - tbw[i]) * density[ray * S + i] : 0.0f;
-      double incl = (double)dd;
-      incl = wave_scan_inclusive_f64(incl);
-      incl = incl + carry;
-      double excl = wave_shift_up1_f64(incl);
-      if (lane == 0) excl = carry;
-      carry = wave_read_f64<63>(incl);
-      if (i < S) {
-        ex_row[i] = expf(-dd);
-        tr_row[i] = expf(-(float)excl);
-      }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    carry = 0.0;
-    for (int r0 = 0; r0 < S; r0 += 64) {  // reversed order: exclusive suffix sums of gw * w
-      const int r = r0 + lane;
-      const int i = S - 1 - r;
-      float ex = 0.f, trans = 0.f, g = 0.f;
-      if (r < S) {
-        ex = ex_row[i];
-        trans = tr_row[i];
-        const float w = (1.0f - ex) * trans;
-        const bool finite = (w == w) && (fabsf(w) <= 3.4028234663852886e38f);
-        g = finite ? dwr[i] : 0.0f;  // nan_to_num backward masks non-finite products
-      }
-      double incl = (double)(r < S ? g * ((1.0f - ex) * trans) : 0.0f);
-      incl = wave_scan_inclusive_f64(incl);
-      incl = incl + carry;
-      double excl = wave_shift_up1_f64(incl);
-      if (lane == 0) excl = carry;
-      carry = wave_read_f64<63>(incl);
-      if (r < S) d_density[ray * S + i] = (tbw[i + 1] - tbw[i]) * (g * trans * ex - (float)excl);
-    }
-  }
+  if (density)  // (LDS per wave: dw[S], written above, then ex[S], trans[S])
+    weights_bwd_passes<true>(lds_wave, t_bins + ray * (S + 1), density + ray * S, nullptr, S, d_density + ray * S);
 }
 
 // ---- RaySamples.get_weights backward (sampler.hip) ----------------------------------------------------------------------
-// d(weights)/d(density): dd_j gets  gw_j * T_j * exp(-dd_j)  -  sum_{i>j} gw_i * w_i
-// LDS: per wave  ex[S], trans[S], gw[S]  (the reverse pass needs the forward values again)
+// LDS: per wave  ex[S], trans[S], gw[S]  (weights_bwd_passes: the reverse pass needs the forward values again)
 __device__ __forceinline__ void weights_bwd_body(float* lds_wave, const float* __restrict__ t_bins,
                                                                const float* __restrict__ density,
                                                                const float* __restrict__ dweights,
@@ -323,9 +339,6 @@ __device__ __forceinline__ void weights_bwd_body(float* lds_wave, const float* _
   const int wave = wave_index();
   const int64_t ray = (int64_t)blockIdx.x * kRaysPerBlock + wave;
   if (ray >= num_rays) return;  // wave-uniform; no workgroup barrier below
-  float* ex_row = lds_wave;
-  float* tr_row = ex_row + S;
-  float* g_row = tr_row + S;
   const float* tb = t_bins + ray * (S + 1);
   const float* dn = density + ray * S;
   const float* dw = dweights + ray * S;
@@ -373,41 +386,7 @@ __device__ __forceinline__ void weights_bwd_body(float* lds_wave, const float* _
     if (gate_out != nullptr && lane == 0 && *reinterpret_cast<volatile uint32_t*>(gate_out) == 0u)
       *reinterpret_cast<volatile uint32_t*>(gate_out) = 1u;
   }
-  double carry = 0.0;
-  for (int i0 = 0; i0 < S; i0 += 64) {
-    const int i = i0 + lane;
-    const float dd = i < S ? (tb[i + 1] - tb[i]) * dn[i] : 0.0f;
-    const double incl = carry + wave_scan_inclusive_f64((double)dd);
-    double excl = wave_shift_up1_f64(incl);
-    if (lane == 0) excl = carry;
-    carry = wave_read_f64<63>(incl);
-    if (i < S) {
-      const float ex = expf(-dd);
-      const float trans = expf(-(float)excl);
-      const float w = (1.0f - ex) * trans;
-      const bool finite = (w == w) && (fabsf(w) <= 3.4028234663852886e38f);
-      const float g = finite ? dw[i] : 0.0f;  // nan_to_num backward masks non-finite products
-      ex_row[i] = ex;
-      tr_row[i] = trans;
-      g_row[i] = g;
-    }
-  }
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  // exclusive suffix sums  suf_j = sum_{i>j} g_i w_i  (reverse cumsum, as autograd): scan the reversed row
-  carry = 0.0;
-  for (int r0 = 0; r0 < S; r0 += 64) {
-    const int r = r0 + lane;      // reversed position
-    const int i = S - 1 - r;      // element
-    float ex = 0.0f, trans = 0.0f, g = 0.0f;
-    if (r < S) { ex = ex_row[i]; trans = tr_row[i]; g = g_row[i]; }
-    const float gw = g * ((1.0f - ex) * trans);
-    const double incl = carry + wave_scan_inclusive_f64((double)(r < S ? gw : 0.0f));
-    double excl = wave_shift_up1_f64(incl);
-    if (lane == 0) excl = carry;
-    carry = wave_read_f64<63>(incl);
-    if (r < S) ddensity[ray * S + i] = (tb[i + 1] - tb[i]) * (g * trans * ex - (float)excl);
-  }
+  weights_bwd_passes<false>(lds_wave, tb, dn, dw, S, ddensity + ray * S);
 }
 
 // ---- UniformLinDispPiecewiseSampler (sampler.hip; ray_samplers.py:78-128, 225-248): the bin edges of one ray ------------------
@@ -498,29 +477,15 @@ __device__ __forceinline__ void pdf_resample_body(float* lds_wave, int64_t ray,
       const int i = i0 + lane;
       const float dd = i0 == 0 ? dd_pre[0] : i0 == 64 ? dd_pre[1] : i0 == 128 ? dd_pre[2] : i0 == 192 ? dd_pre[3]
                        : (i < S_prev ? (tb[i + 1] - tb[i]) * dn[i] : 0.0f);  // (selects, not an indexed array: no scratch)
-      const double incl = carry0 + wave_scan_inclusive_f64((double)dd);
-      double excl = wave_shift_up1_f64(incl);
-      if (lane == 0) excl = carry0;
-      carry0 = wave_read_f64<63>(incl);
+      const double excl = wave_scan_carry_f64((double)dd, carry0).excl;
       if (i < S_prev) {
-        const float alpha = 1.0f - expf(-dd);
-        const float trans = expf(-(float)excl);
-        const float wv = nan_to_num(alpha * trans);
+        const float wv = sample_weight(dd, excl);
         weights_out[ray * S_prev + i] = wv;
         w[i] = wv;
       }
     }
-    if (depth_median != nullptr) {  // searchsorted(cumsum(w), 0.5, side="left"), clamped
-      double carry1 = 0.0;
-      int idx = S_prev;
-      for (int i0 = 0; i0 < S_prev && idx == S_prev; i0 += 64) {
-        const int i = i0 + lane;
-        const double incl = carry1 + wave_scan_inclusive_f64(i < S_prev ? (double)w[i] : 0.0);
-        carry1 = wave_read_f64<63>(incl);
-        const unsigned long long hit = __ballot(i < S_prev && (float)incl >= 0.5f);
-        if (hit != 0ull) idx = i0 + __builtin_ctzll(hit);
-      }
-      idx = min(idx, S_prev - 1);
+    if (depth_median != nullptr) {
+      const int idx = median_index(w, S_prev);
       if (lane == 0) depth_median[ray] = (tb[idx] + tb[idx + 1]) / 2.0f;
     }
   }
@@ -539,7 +504,7 @@ __device__ __forceinline__ void pdf_resample_body(float* lds_wave, int64_t ray,
       v = v + hist_pad;
       w[i] = v;
     }
-    total = total + wave_read_f64<63>(wave_scan_inclusive_f64((double)v));
+    wave_scan_carry_f64((double)v, total);
   }
   const float run = (float)total;  // double-accumulated sum, rounded once (= cumsum(w)[-1] of the oracle)
   const float pad = fmaxf(eps - run, 0.0f);
@@ -551,8 +516,7 @@ __device__ __forceinline__ void pdf_resample_body(float* lds_wave, int64_t ray,
   for (int i0 = 0; i0 < S_prev; i0 += 64) {
     const int i = i0 + lane;
     const float pdf = i < S_prev ? (w[i] + wpad) / wsum : 0.0f;
-    const double incl = carry + wave_scan_inclusive_f64((double)pdf);
-    carry = wave_read_f64<63>(incl);
+    const double incl = wave_scan_carry_f64((double)pdf, carry).incl;
     if (i < S_prev) cdf[i + 1] = fminf(1.0f, (float)incl);
   }
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -566,13 +530,7 @@ __device__ __forceinline__ void pdf_resample_body(float* lds_wave, int64_t ray,
     // rand / num_bins: one draw per ray (single_jitter) or per new edge   (ray_samplers.py:318-322)
     if (jitter != nullptr) u = u + (jitter_per_edge ? jitter[ray * nb + j] : jit_ray) / (float)nb;
     else u = u + u_offset;                                    // 1 / (2 num_bins)  (ray_samplers.py:327), host-rounded
-    // searchsorted(side="right"): number of cdf entries <= u
-    int lo = 0, hi = S_prev + 1;
-    while (lo < hi) {
-      const int mid = (lo + hi) >> 1;
-      if (cdf[mid] <= u) lo = mid + 1;
-      else hi = mid;
-    }
+    const int lo = upper_bound(cdf, S_prev + 1, u);  // searchsorted(side="right"): number of cdf entries <= u
     const int below = min(max(lo - 1, 0), S_prev);
     const int above = min(max(lo, 0), S_prev);
     const float c0 = cdf[below], c1 = cdf[above];
@@ -608,12 +566,7 @@ __device__ __forceinline__ void pdf_resample_body(float* lds_wave, int64_t ray,
     }
     for (int j = lane; j < nb; j += 64) {  // new edge j: existing edges at or below it
       const float v = fresh[j];
-      int lo = 0, hi = S_prev + 1;
-      while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (bprev[mid] <= v) lo = mid + 1;
-        else hi = mid;
-      }
+      const int lo = upper_bound(bprev, S_prev + 1, v);
       so[j + lo] = v;
       to[j + lo] = spacing_to_euclidean_mode(spacing, v, s_near, s_far);
     }
@@ -623,26 +576,7 @@ __device__ __forceinline__ void pdf_resample_body(float* lds_wave, int64_t ray,
 
 // ---- proposal losses (losses.hip) -----------------------------------------------------------------------------------------
 
-constexpr int kLossThreads = 256;
-constexpr int kLossRays = kLossThreads / 64;
 constexpr float kLossEps = 1.0e-7f;  // losses.py:35
-
-__device__ __forceinline__ float wave_sum_l(float v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
-// number of entries of sorted a[0..n) that are <= v   (torch.searchsorted side="right")
-__device__ __forceinline__ int upper_bound(const float* a, int n, float v) {
-  int lo = 0, hi = n;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (a[mid] <= v) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
 
 // first index in sorted int a[0..n) with a[i] >= v
 __device__ __forceinline__ int lower_bound_i(const int* a, int n, int v) {
@@ -674,8 +608,7 @@ __host__ __device__ constexpr int interlevel_row_floats(int Sf, int Sp) {
 __device__ __forceinline__ void interlevel_body(
     float* lds_wave, const float* __restrict__ c_in, const float* __restrict__ w_in, int Sf, const float* __restrict__ cp_in,
     const float* __restrict__ wp_in, int Sp, int64_t num_rays, float grad_scale, float* __restrict__ per_ray,
-    float* __restrict__ dwp, const float* __restrict__ dens_fine = nullptr,
-    const float* __restrict__ t_fine = nullptr) {
+    float* __restrict__ dwp) {
   const int lane = threadIdx.x & 63, wave = wave_index();
   const int64_t ray = (int64_t)blockIdx.x * kRaysPerBlock + wave;
   if (ray >= num_rays) return;
@@ -689,35 +622,13 @@ __device__ __forceinline__ void interlevel_body(
   int* hi_i = lo_i + Sf;
   for (int k = lane; k <= Sp; k += 64) cp[k] = cp_in[ray * (Sp + 1) + k];
   for (int i = lane; i <= Sf; i += 64) c[i] = c_in[ray * (Sf + 1) + i];
-  if (dens_fine != nullptr) {
-    // the fine level's weights from its densities (RaySamples.get_weights, cameras/rays.py:129-152): the same operations as
-    // composite_fwd_body, so the same bits — a launch that composites and takes the losses at once (round 5's merged launch: csrc/experiments)
-    // has no weight row in memory yet when this wave starts
-    const float* tbf = t_fine + ray * (Sf + 1);
-    double w_carry = 0.0;
-    for (int s0 = 0; s0 < Sf; s0 += 64) {
-      const int s = s0 + lane;
-      const float dd = s < Sf ? (tbf[s + 1] - tbf[s]) * dens_fine[ray * Sf + s] : 0.0f;
-      double incl = (double)dd;
-      incl = wave_scan_inclusive_f64(incl);
-      incl = incl + w_carry;
-      double excl = wave_shift_up1_f64(incl);
-      if (lane == 0) excl = w_carry;
-      w_carry = wave_read_f64<63>(incl);
-      if (s < Sf) w[s] = nan_to_num((1.0f - expf(-dd)) * expf(-(float)excl));
-    }
-  } else {
-    for (int i = lane; i < Sf; i += 64) w[i] = w_in[ray * Sf + i];
-  }
+  for (int i = lane; i < Sf; i += 64) w[i] = w_in[ray * Sf + i];
   {  // cy = [0, cumsum(wp)]   (losses.py:69); double-accumulated like torch's CPU cumsum, as a wave scan
     double carry = 0.0;
     if (lane == 0) cy[0] = 0.0f;
     for (int k0 = 0; k0 < Sp; k0 += 64) {
       const int k = k0 + lane;
-      double v = k < Sp ? (double)wp_in[ray * Sp + k] : 0.0;
-      v = wave_scan_inclusive_f64(v);
-      v = v + carry;
-      carry = wave_read_f64<63>(v);
+      const double v = wave_scan_carry_f64(k < Sp ? (double)wp_in[ray * Sp + k] : 0.0, carry).incl;
       if (k < Sp) cy[k + 1] = (float)v;
     }
   }
@@ -737,7 +648,7 @@ __device__ __forceinline__ void interlevel_body(
     lo_i[i] = lo;
     hi_i[i] = hi;
   }
-  loss = wave_sum_l(loss);
+  loss = wave_sum(loss);
   if (lane == 0) per_ray[ray] = loss;
   if (dwp != nullptr) {
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -753,10 +664,7 @@ __device__ __forceinline__ void interlevel_body(
       if (lane == 0) R[0] = 0.0;
       for (int i0 = 0; i0 < Sf; i0 += 64) {
         const int i = i0 + lane;
-        double v = i < Sf ? (double)rr[i] : 0.0;
-        v = wave_scan_inclusive_f64(v);
-        v = v + carry;
-        carry = wave_read_f64<63>(v);
+        const double v = wave_scan_carry_f64(i < Sf ? (double)rr[i] : 0.0, carry).incl;
         if (i < Sf) R[i + 1] = v;
       }
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -805,7 +713,7 @@ __device__ __forceinline__ void distortion_body(float* lds_wave, const float* __
     loss += wi * inner + wi * wi * delta / 3.0f;
     if (dw != nullptr) dw[ray * S + i] = (2.0f * inner + 2.0f * wi * delta / 3.0f) * grad_scale;
   }
-  loss = wave_sum_l(loss);
+  loss = wave_sum(loss);
   if (lane == 0) per_ray[ray] = loss;
 }
 

@@ -13,7 +13,7 @@
 
 namespace nsamd {
 
-__global__ __launch_bounds__(kRenderThreads) void composite_fwd_kernel(
+__global__ __launch_bounds__(kRayThreads) void composite_fwd_kernel(
     const float* __restrict__ rgb, const float* __restrict__ weights, const float* __restrict__ t_bins,
     int64_t num_rays, int S, int background, float bg_r, float bg_g, float bg_b, int eval_mode,
     float* __restrict__ rgb_out, float* __restrict__ acc_out, float* __restrict__ depth_exp,
@@ -51,7 +51,7 @@ __global__ void depth_clip_kernel(float* __restrict__ depth, int64_t n, float* _
   if (i < n) depth[i] = fminf(fmaxf(depth[i], lo), hi);  // torch.clip(depth, steps.min(), steps.max())
 }
 
-__global__ __launch_bounds__(kRenderThreads) void composite_bwd_kernel(
+__global__ __launch_bounds__(kRayThreads) void composite_bwd_kernel(
     const float* __restrict__ rgb, const float* __restrict__ weights, const float* __restrict__ t_bins,
     int64_t num_rays, int S, int background, float bg_r, float bg_g, float bg_b,
     const float* __restrict__ d_rgb_out, const float* __restrict__ d_acc, const float* __restrict__ d_depth,
@@ -140,7 +140,7 @@ extern "C" int nsamd_composite_fwd(const float* rgb, const float* weights, const
   const unsigned blocks = (unsigned)((num_rays + kRaysPerBlock - 1) / kRaysPerBlock);
   const float br = bg_rgb_host ? bg_rgb_host[0] : 0.f, bg = bg_rgb_host ? bg_rgb_host[1] : 0.f,
               bb = bg_rgb_host ? bg_rgb_host[2] : 0.f;
-  composite_fwd_kernel<<<blocks, kRenderThreads, 0, st>>>(
+  composite_fwd_kernel<<<blocks, kRayThreads, 0, st>>>(
       rgb, weights, need_t ? t_bins : nullptr, num_rays, S, background, br, bg, bb, eval_mode, rgb_out, acc,
       depth_expected, depth_median, median_idx, ws, nullptr, nullptr, nullptr, 0.0f, nullptr, nullptr, nullptr);
   NSAMD_CHECK_LAUNCH();
@@ -165,7 +165,7 @@ extern "C" int nsamd_composite_bwd(const float* rgb, const float* weights, const
   const unsigned blocks = (unsigned)((num_rays + kRaysPerBlock - 1) / kRaysPerBlock);
   const float br = bg_rgb_host ? bg_rgb_host[0] : 0.f, bg = bg_rgb_host ? bg_rgb_host[1] : 0.f,
               bb = bg_rgb_host ? bg_rgb_host[2] : 0.f;
-  composite_bwd_kernel<<<blocks, kRenderThreads, 0, (hipStream_t)stream>>>(
+  composite_bwd_kernel<<<blocks, kRayThreads, 0, (hipStream_t)stream>>>(
       rgb, weights, t_bins, num_rays, S, background, br, bg, bb, d_rgb_out, d_acc, d_depth, workspace, d_weights_add, d_rgb,
       d_weights, nullptr, nullptr, nullptr);
   NSAMD_CHECK_LAUNCH();
@@ -189,9 +189,9 @@ extern "C" int nsamd_render_train(const float* rgb, const float* density, const 
   const unsigned blocks = (unsigned)((num_rays + kRaysPerBlock - 1) / kRaysPerBlock);
   const float br = bg_rgb_host ? bg_rgb_host[0] : 0.f, bg = bg_rgb_host ? bg_rgb_host[1] : 0.f,
               bb = bg_rgb_host ? bg_rgb_host[2] : 0.f;
-  composite_fwd_kernel<<<blocks, kRenderThreads, 0, st>>>(rgb, nullptr, t_bins, num_rays, S, background, br, bg, bb, 0,
-                                                          rgb_out, acc, depth_expected, depth_median, nullptr, workspace,
-                                                          density, weights, target, grad_scale, sq_err, d_rgb_out, bg_rays);
+  composite_fwd_kernel<<<blocks, kRayThreads, 0, st>>>(rgb, nullptr, t_bins, num_rays, S, background, br, bg, bb, 0,
+                                                       rgb_out, acc, depth_expected, depth_median, nullptr, workspace,
+                                                       density, weights, target, grad_scale, sq_err, d_rgb_out, bg_rays);
   NSAMD_CHECK_LAUNCH();
   if (depth_expected) {
     depth_clip_kernel<<<(unsigned)((num_rays + 255) / 256), 256, 0, st>>>(depth_expected, num_rays, workspace,
@@ -215,7 +215,7 @@ extern "C" int nsamd_render_train_bwd(const float* rgb, const float* weights, co
   const unsigned blocks = (unsigned)((num_rays + kRaysPerBlock - 1) / kRaysPerBlock);
   const float br = bg_rgb_host ? bg_rgb_host[0] : 0.f, bg = bg_rgb_host ? bg_rgb_host[1] : 0.f,
               bb = bg_rgb_host ? bg_rgb_host[2] : 0.f;
-  composite_bwd_kernel<<<blocks, kRenderThreads, sizeof(float) * 3 * kRaysPerBlock * (size_t)S, (hipStream_t)stream>>>(
+  composite_bwd_kernel<<<blocks, kRayThreads, sizeof(float) * 3 * kRaysPerBlock * (size_t)S, (hipStream_t)stream>>>(
       rgb, weights, t_bins, num_rays, S, background, br, bg, bb, d_rgb_out, nullptr, nullptr, nullptr, d_weights_add,
       d_rgb, nullptr, density, d_density, bg_rays);
   NSAMD_CHECK_LAUNCH();

@@ -18,22 +18,20 @@ NSAMD_PROBE_DEFINE(sampler)
 
 namespace nsamd {
 
-constexpr int kThreads = 256;  // 4 wavefronts
-
 // ---------------------------------------------------------------------------------------------------------------
 // UniformLinDispPiecewiseSampler (ray_samplers.py:78-128, 225-248): pure elementwise.
 // ---------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kThreads) void piecewise_bins_kernel(const float* __restrict__ nears,
-                                                                  const float* __restrict__ fars,
-                                                                  const float* __restrict__ edges,
-                                                                  const float* __restrict__ jitter,
-                                                                  int jitter_per_edge, int64_t num_rays, int S,
-                                                                  int spacing, float* __restrict__ s_bins,
-                                                                  float* __restrict__ t_bins) {
+__global__ __launch_bounds__(kRayThreads) void piecewise_bins_kernel(const float* __restrict__ nears,
+                                                                     const float* __restrict__ fars,
+                                                                     const float* __restrict__ edges,
+                                                                     const float* __restrict__ jitter,
+                                                                     int jitter_per_edge, int64_t num_rays, int S,
+                                                                     int spacing, float* __restrict__ s_bins,
+                                                                     float* __restrict__ t_bins) {
   // one wavefront per ray (4 rays per workgroup): per-ray scalars are computed once, the edge index is a 32-bit loop
   // counter (the flat-index version spent its time in 64-bit divisions)
   const int lane = threadIdx.x & 63;
-  const int64_t ray = (int64_t)blockIdx.x * (kThreads / 64) + wave_index();
+  const int64_t ray = (int64_t)blockIdx.x * kRaysPerBlock + wave_index();
   if (ray >= num_rays) return;
   piecewise_bins_body(ray, lane, nears, fars, edges, jitter, jitter_per_edge, S, spacing, s_bins, t_bins);
 }
@@ -41,7 +39,7 @@ __global__ __launch_bounds__(kThreads) void piecewise_bins_kernel(const float* _
 // nsamd_select_batch + nsamd_piecewise_bins in one launch (the first two launches of a training iteration over a pool of ray
 // batches; neither depends on the other — the bins need nears / fars / the jitter draw, not the rays): the ray's wave copies
 // its origin, direction, target colour and camera index out of the pool slot, then writes its initial bins.
-__global__ __launch_bounds__(kThreads) void select_bins_kernel(
+__global__ __launch_bounds__(kRayThreads) void select_bins_kernel(
     const float* __restrict__ slot_dev, int32_t slots, int64_t num_rays, const float* __restrict__ origins_pool,
     const float* __restrict__ directions_pool, const int64_t* __restrict__ cameras_pool, const float* __restrict__ target_pool,
     float* __restrict__ origins, float* __restrict__ directions, int64_t* __restrict__ cameras, float* __restrict__ target,
@@ -49,7 +47,7 @@ __global__ __launch_bounds__(kThreads) void select_bins_kernel(
     const float* __restrict__ jitter, int jitter_per_edge, int S, int spacing, float* __restrict__ s_bins,
     float* __restrict__ t_bins) {
   const int lane = threadIdx.x & 63;
-  const int64_t ray = (int64_t)blockIdx.x * (kThreads / 64) + wave_index();
+  const int64_t ray = (int64_t)blockIdx.x * kRaysPerBlock + wave_index();
   if (ray >= num_rays) return;
   int32_t slot = (int32_t)slot_dev[0];
   slot = slot < 0 ? 0 : (slot >= slots ? slots - 1 : slot);
@@ -72,8 +70,6 @@ __global__ __launch_bounds__(kThreads) void select_bins_kernel(
 // accumulation except on a double-rounding tie (probability ~1e-9 per element; the parity tests pin indices
 // bit-exactly on their seeds). The previous one-lane-per-ray loop was 5x slower (profiles/).
 // ---------------------------------------------------------------------------------------------------------------
-constexpr int kWaves = 4;  // rays per 256-thread workgroup
-
 // nsamd_pdf_resample's accepted range (include/nsamd.h) and the LDS row of one wave of pdf_resample_kernel
 constexpr int kPdfMaxPrev = 1024;
 constexpr int kPdfMaxNew = 4096;
@@ -81,21 +77,18 @@ constexpr size_t pdf_row_floats(size_t S_prev, size_t S, bool include_original) 
   return 3 * S_prev + 2 + (include_original ? S + 1 : 0);
 }
 // the largest request, include_original at the limits: 114 736 B of gfx950's 160 KiB
-constexpr size_t kPdfLdsMax = sizeof(float) * kWaves * pdf_row_floats(kPdfMaxPrev, kPdfMaxNew, true);
+constexpr size_t kPdfLdsMax = sizeof(float) * kRaysPerBlock * pdf_row_floats(kPdfMaxPrev, kPdfMaxNew, true);
 static_assert(kPdfLdsMax <= 160 * 1024, "pdf_resample_kernel: the accepted range must fit the LDS of a workgroup");
-
-// (wave.h: DPP scans - the shuffle-based Hillis-Steele version spent ~1.5 k clocks per scan in ds_bpermute round trips)
-__device__ __forceinline__ double wave_scan_inclusive(double v, int /*lane*/) { return wave_scan_inclusive_f64(v); }
 
 // ---------------------------------------------------------------------------------------------------------------
 // RaySamples.get_weights (cameras/rays.py:129-152)
 // ---------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kThreads) void weights_fwd_kernel(const float* __restrict__ t_bins,
-                                                               const float* __restrict__ density,
-                                                               int64_t num_rays, int S,
-                                                               float* __restrict__ weights) {
+__global__ __launch_bounds__(kRayThreads) void weights_fwd_kernel(const float* __restrict__ t_bins,
+                                                                  const float* __restrict__ density,
+                                                                  int64_t num_rays, int S,
+                                                                  float* __restrict__ weights) {
   const int lane = threadIdx.x & 63;
-  const int64_t ray = (int64_t)blockIdx.x * kWaves + wave_index();
+  const int64_t ray = (int64_t)blockIdx.x * kRaysPerBlock + wave_index();
   if (ray >= num_rays) return;  // wave-uniform
   const float* tb = t_bins + ray * (S + 1);
   const float* dn = density + ray * S;
@@ -104,31 +97,24 @@ __global__ __launch_bounds__(kThreads) void weights_fwd_kernel(const float* __re
   for (int i0 = 0; i0 < S; i0 += 64) {
     const int i = i0 + lane;
     const float dd = i < S ? (tb[i + 1] - tb[i]) * dn[i] : 0.0f;
-    const double incl = carry + wave_scan_inclusive((double)dd, lane);
-    double excl = wave_shift_up1_f64(incl);
-    if (lane == 0) excl = carry;
-    carry = wave_read_f64<63>(incl);
-    if (i < S) {
-      const float alpha = 1.0f - expf(-dd);
-      const float trans = expf(-(float)excl);
-      out[i] = nan_to_num(alpha * trans);
-    }
+    const double excl = wave_scan_carry_f64((double)dd, carry).excl;
+    if (i < S) out[i] = sample_weight(dd, excl);
   }
 }
 
-__global__ __launch_bounds__(kThreads) void weights_bwd_kernel(const float* __restrict__ t_bins,
-                                                               const float* __restrict__ density,
-                                                               const float* __restrict__ dweights,
-                                                               int64_t num_rays, int S,
-                                                               float* __restrict__ ddensity,
-                                                               uint32_t* __restrict__ gate_out,
-                                                               uint8_t* __restrict__ ray_mask) {
+__global__ __launch_bounds__(kRayThreads) void weights_bwd_kernel(const float* __restrict__ t_bins,
+                                                                  const float* __restrict__ density,
+                                                                  const float* __restrict__ dweights,
+                                                                  int64_t num_rays, int S,
+                                                                  float* __restrict__ ddensity,
+                                                                  uint32_t* __restrict__ gate_out,
+                                                                  uint8_t* __restrict__ ray_mask) {
   extern __shared__ float lds[];  // (ray_bodies.h: weights_bwd_body — per wave ex[S], trans[S], gw[S])
   weights_bwd_body(lds + (size_t)wave_index() * 3 * S, t_bins, density, dweights, num_rays, S, ddensity, gate_out, ray_mask);
 }
 
 // two levels' weights backward in one launch (proposal_chain.h): blockIdx.y selects the call, each with its own sample count
-__global__ __launch_bounds__(kThreads) void weights_bwd_pair_kernel(WeightsBwdCall a, WeightsBwdCall b) {
+__global__ __launch_bounds__(kRayThreads) void weights_bwd_pair_kernel(WeightsBwdCall a, WeightsBwdCall b) {
   extern __shared__ float lds[];
   if (blockIdx.y == 0)
     weights_bwd_body(lds + (size_t)wave_index() * 3 * a.S, a.t_bins, a.density, a.dweights, a.num_rays, a.S, a.ddensity, a.gate,
@@ -146,7 +132,7 @@ __global__ __launch_bounds__(kThreads) void weights_bwd_pair_kernel(WeightsBwdCa
 // (DepthRenderer "median", renderers.py:354-364; models/nerfacto.py:346-347 renders one per proposal level) — the three
 // launches per proposal level of the training step in one, the weight row never leaves the wave.
 template <bool kFused>
-__global__ __launch_bounds__(kThreads) void pdf_resample_kernel(
+__global__ __launch_bounds__(kRayThreads) void pdf_resample_kernel(
     const float* __restrict__ s_bins_prev, const float* __restrict__ weights, int S_prev,
     const float* __restrict__ u_base, const float* __restrict__ jitter, const float* __restrict__ nears,
     const float* __restrict__ fars, float anneal_host, const float* __restrict__ anneal_dev, float hist_pad, float eps,
@@ -155,7 +141,7 @@ __global__ __launch_bounds__(kThreads) void pdf_resample_kernel(
     const float* __restrict__ t_bins_prev, const float* __restrict__ density, float* __restrict__ weights_out,
     float* __restrict__ depth_median, int jitter_per_edge, int include_original) {
   extern __shared__ float lds[];  // (ray_bodies.h: pdf_resample_body)
-  const int64_t ray = (int64_t)blockIdx.x * kWaves + wave_index();
+  const int64_t ray = (int64_t)blockIdx.x * kRaysPerBlock + wave_index();
   if (ray >= num_rays) return;  // wave-uniform; no workgroup barrier in the body
   const size_t row_floats = pdf_row_floats((size_t)S_prev, (size_t)S, include_original != 0);
   pdf_resample_body<kFused>(lds + (size_t)wave_index() * row_floats, ray, s_bins_prev, weights, S_prev, u_base, jitter, nears,
@@ -167,7 +153,7 @@ __global__ __launch_bounds__(kThreads) void pdf_resample_kernel(
 
 using namespace nsamd;
 
-static inline unsigned ray_blocks(int64_t num_rays) { return (unsigned)((num_rays + kWaves - 1) / kWaves); }
+static inline unsigned ray_blocks(int64_t num_rays) { return (unsigned)((num_rays + kRaysPerBlock - 1) / kRaysPerBlock); }
 
 extern "C" int nsamd_piecewise_bins(const float* nears, const float* fars, const float* edges, const float* jitter,
                                     int32_t jitter_per_edge, int64_t num_rays, int32_t S, int spacing, float* s_bins,
@@ -175,9 +161,9 @@ extern "C" int nsamd_piecewise_bins(const float* nears, const float* fars, const
   NSAMD_REQUIRE(num_rays >= 0 && S > 0 && (spacing == 0 || spacing == 1));
   if (num_rays == 0) return NSAMD_OK;
   NSAMD_REQUIRE(nears && fars && edges && s_bins && t_bins);
-  const int64_t blocks64 = (num_rays + (kThreads / 64) - 1) / (kThreads / 64);
+  const int64_t blocks64 = (num_rays + kRaysPerBlock - 1) / kRaysPerBlock;
   if (blocks64 > 0x7fffffffLL) return NSAMD_ERR_UNSUPPORTED;
-  piecewise_bins_kernel<<<(unsigned)blocks64, kThreads, 0, (hipStream_t)stream>>>(
+  piecewise_bins_kernel<<<(unsigned)blocks64, kRayThreads, 0, (hipStream_t)stream>>>(
       nears, fars, edges, jitter, jitter_per_edge != 0, num_rays, S, spacing, s_bins, t_bins);
   NSAMD_CHECK_LAUNCH();
   return NSAMD_OK;
@@ -192,9 +178,9 @@ extern "C" int nsamd_select_bins(const float* slot_dev, int32_t slots, int64_t n
   if (num_rays == 0) return NSAMD_OK;
   NSAMD_REQUIRE(slot_dev && origins_pool && directions_pool && cameras_pool && target_pool && origins && directions &&
                 cameras && target && nears && fars && edges && s_bins && t_bins);
-  const int64_t blocks64 = (num_rays + (kThreads / 64) - 1) / (kThreads / 64);
+  const int64_t blocks64 = (num_rays + kRaysPerBlock - 1) / kRaysPerBlock;
   if (blocks64 > 0x7fffffffLL) return NSAMD_ERR_UNSUPPORTED;
-  select_bins_kernel<<<(unsigned)blocks64, kThreads, 0, (hipStream_t)stream>>>(
+  select_bins_kernel<<<(unsigned)blocks64, kRayThreads, 0, (hipStream_t)stream>>>(
       slot_dev, slots, num_rays, origins_pool, directions_pool, cameras_pool, target_pool, origins, directions, cameras, target,
       nears, fars, edges, jitter, jitter_per_edge != 0, S, spacing, s_bins, t_bins);
   NSAMD_CHECK_LAUNCH();
@@ -206,8 +192,8 @@ extern "C" int nsamd_weights_fwd(const float* t_bins, const float* density, int6
   NSAMD_REQUIRE(num_rays >= 0 && S > 0);
   if (num_rays == 0) return NSAMD_OK;
   NSAMD_REQUIRE(t_bins && density && weights);
-  weights_fwd_kernel<<<ray_blocks(num_rays), kThreads, 0, (hipStream_t)stream>>>(t_bins, density, num_rays, S,
-                                                                                   weights);
+  weights_fwd_kernel<<<ray_blocks(num_rays), kRayThreads, 0, (hipStream_t)stream>>>(t_bins, density, num_rays, S,
+                                                                                      weights);
   NSAMD_CHECK_LAUNCH();
   return NSAMD_OK;
 }
@@ -224,7 +210,7 @@ namespace nsamd {
 // (the gates are cleared by the caller)
 int weights_bwd_launch(const WeightsBwdCall* c, int n, hipStream_t stream) {
   NSAMD_REQUIRE(c != nullptr && (n == 1 || n == 2));
-  const auto lds = [](int S) { return sizeof(float) * 3 * kWaves * (size_t)S; };
+  const auto lds = [](int S) { return sizeof(float) * 3 * kRaysPerBlock * (size_t)S; };
   if (n == 2) {
     const WeightsBwdCall &a = c[0], &b = c[1];
     if (a.num_rays <= 0 || b.num_rays <= 0 || weights_bwd_check(a) || weights_bwd_check(b)) {
@@ -232,11 +218,11 @@ int weights_bwd_launch(const WeightsBwdCall* c, int n, hipStream_t stream) {
       return rc ? rc : weights_bwd_launch(c + 1, 1, stream);
     }
     const int64_t rays = a.num_rays > b.num_rays ? a.num_rays : b.num_rays;
-    weights_bwd_pair_kernel<<<dim3(ray_blocks(rays), 2u), kThreads, lds(a.S > b.S ? a.S : b.S), stream>>>(a, b);
+    weights_bwd_pair_kernel<<<dim3(ray_blocks(rays), 2u), kRayThreads, lds(a.S > b.S ? a.S : b.S), stream>>>(a, b);
   } else {
     const int rc = weights_bwd_check(c[0]);
     if (rc || c[0].num_rays == 0) return rc;
-    weights_bwd_kernel<<<ray_blocks(c[0].num_rays), kThreads, lds(c[0].S), stream>>>(
+    weights_bwd_kernel<<<ray_blocks(c[0].num_rays), kRayThreads, lds(c[0].S), stream>>>(
         c[0].t_bins, c[0].density, c[0].dweights, c[0].num_rays, c[0].S, c[0].ddensity, c[0].gate, c[0].ray_mask);
   }
   NSAMD_CHECK_LAUNCH();
@@ -271,13 +257,13 @@ extern "C" int nsamd_pdf_resample(const float* s_bins_prev, const float* weights
   if (num_rays == 0) return NSAMD_OK;
   NSAMD_REQUIRE(s_bins_prev && weights && u_base && nears && fars && s_bins && t_bins);
   if (S_prev > kPdfMaxPrev || S > kPdfMaxNew) return NSAMD_ERR_UNSUPPORTED;
-  const size_t lds = sizeof(float) * kWaves * pdf_row_floats((size_t)S_prev, (size_t)S, include_original != 0);
+  const size_t lds = sizeof(float) * kRaysPerBlock * pdf_row_floats((size_t)S_prev, (size_t)S, include_original != 0);
   if (lds > 64 * 1024) {  // include_original with long rows: beyond the default dynamic-LDS limit (launch.h)
     static LdsOptIn opted_in;  // (once per device, for the largest accepted request)
     const int rc = lds_opt_in(opted_in, pdf_resample_kernel<false>, kPdfLdsMax);
     if (rc) return rc;
   }
-  pdf_resample_kernel<false><<<ray_blocks(num_rays), kThreads, lds, (hipStream_t)stream>>>(
+  pdf_resample_kernel<false><<<ray_blocks(num_rays), kRayThreads, lds, (hipStream_t)stream>>>(
       s_bins_prev, weights, S_prev, u_base, jitter, nears, fars, anneal, anneal_dev, histogram_padding, eps, u_offset,
       spacing, num_rays, S, s_bins, t_bins, inds, nullptr, nullptr, nullptr, nullptr, jitter_per_edge != 0,
       include_original != 0);
@@ -295,8 +281,8 @@ extern "C" int nsamd_proposal_resample(const float* t_bins_prev, const float* s_
   if (num_rays == 0) return NSAMD_OK;
   NSAMD_REQUIRE(t_bins_prev && s_bins_prev && density && u_base && nears && fars && weights && s_bins && t_bins);
   if (S_prev > kPdfMaxPrev) return NSAMD_ERR_UNSUPPORTED;
-  const size_t lds = sizeof(float) * kWaves * pdf_row_floats((size_t)S_prev, (size_t)S, false);
-  pdf_resample_kernel<true><<<ray_blocks(num_rays), kThreads, lds, (hipStream_t)stream>>>(
+  const size_t lds = sizeof(float) * kRaysPerBlock * pdf_row_floats((size_t)S_prev, (size_t)S, false);
+  pdf_resample_kernel<true><<<ray_blocks(num_rays), kRayThreads, lds, (hipStream_t)stream>>>(
       s_bins_prev, nullptr, S_prev, u_base, jitter, nears, fars, anneal, anneal_dev, histogram_padding, eps, u_offset,
       spacing, num_rays, S, s_bins, t_bins, nullptr, t_bins_prev, density, weights, depth_median, 0, 0);
   NSAMD_CHECK_LAUNCH();

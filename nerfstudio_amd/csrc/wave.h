@@ -1,5 +1,5 @@
 // Wave-level (64 lanes) scans and broadcasts of doubles on the DPP path of gfx9-family hardware.
-// The generic __shfl_up / __shfl of a double compile to two ds_bpermute_b32 each — an LDS-crossbar round trip of ~100 clocks
+// The generic shuffles of a double compile to two ds_bpermute_b32 each — an LDS-crossbar round trip of ~100 clocks
 // — and the per-ray kernels (one wavefront per ray) are chains of such scans: a 6-step Hillis-Steele scan was ~1.5 k clocks.
 // DPP moves run at VALU rate: row_shr 1/2/4/8 scan the four rows of 16 lanes, row_bcast:15 / row_bcast:31 carry the row
 // totals across (the sequence the AMDGPU backend itself emits for wave64 scans on GFX9).
@@ -49,6 +49,42 @@ __device__ __forceinline__ double wave_read_f64(double v) {
   const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(b & 0xffffffffull), LANE);
   const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(b >> 32), LANE);
   return __longlong_as_double((long long)(((unsigned long long)hi << 32) | (unsigned long long)lo));
+}
+
+// One 64-element chunk of a running prefix sum along a row that a wavefront walks 64 elements at a time (torch.cumsum on the
+// CPU: a double accumulator): v = this lane's element (0 past the row's end), `carry` = the sum of the chunks in front, advanced
+// to the next chunk's. incl / excl = the prefix sums with / without the lane's own element. All 64 lanes must be active: the
+// rays' early returns, chunk loops and breaks of every caller are wave-uniform. (carry + scan and scan + carry are the same
+// IEEE sum: addition commutes.) This is THE scan step of the per-ray kernels, dense (ray_bodies.h) and packed (packed.hip).
+struct CarryScan {
+  double incl, excl;
+};
+__device__ __forceinline__ CarryScan wave_scan_carry_f64(double v, double& carry) {
+  CarryScan s;
+  s.incl = carry + wave_scan_inclusive_f64(v);
+  s.excl = wave_shift_up1_f64(s.incl);
+  if ((threadIdx.x & 63) == 0) s.excl = carry;
+  carry = wave_read_f64<63>(s.incl);
+  return s;
+}
+
+// Sum / minimum / maximum of a float over the 64 lanes, in every lane: xor butterflies with the partners 32, 16, ..., 1. The sum's
+// association is this order's: pk_reduce (packed.hip) and the butterflies of loss_values.hip, field_reduce.h and hashgrid.hip
+// take the partners 1, 2, ..., 32 - other bits - and stay what they are. Minimum and maximum are order-free; fminf / fmaxf drop a NaN.
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+__device__ __forceinline__ float wave_min(float v) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v = fminf(v, __shfl_xor(v, o));
+  return v;
+}
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+  return v;
 }
 
 // inclusive prefix sum of a 32-bit count over the 64 lanes: the same six DPP steps as the double scan. All lanes active.

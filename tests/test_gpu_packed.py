@@ -102,12 +102,19 @@ def test_packed_weights_forward_backward_vs_oracle(F):
     np.testing.assert_allclose(s_gpu.grad.cpu().numpy(), ref_g, atol=1e-5 * np.abs(ref_g).max(), rtol=2e-3)
 
 
-def test_packed_weights_equal_the_dense_kernel_on_equal_counts(F):
-    """Anchor on the pinned dense path: with S samples on every ray the packed scan is RaySamples.get_weights."""
+@pytest.mark.parametrize("S", [48, 64, 65, 193, 257])
+def test_packed_weights_equal_the_dense_kernel_on_equal_counts(F, S):
+    """Anchor on the pinned dense path: with S samples on every ray the packed scan is RaySamples.get_weights — the same scan
+    step (csrc/wave.h: wave_scan_carry_f64) under both kernels. S: less than one 64-sample chunk, exactly one, the carry into a
+    chunk of one sample, four and five chunks; 5 rays: a tail workgroup of the dense kernel's four rays; one opaque sample
+    (density 1e10) in the middle of ray 1, whose optical depth every later prefix of that ray carries.
+    (nsamd_packed_render_fwd at the same chunk edges: test_gpu_ngp_eval_render.py, whose `edges` geometry has rays of every
+    count of 63 .. 65, 127 .. 129, 191 .. 193.)"""
     rs = np.random.RandomState(5)
-    n, S = 64, 48
+    n = 5
     t_bins = np.sort(rs.uniform(0.05, 5.0, (n, S + 1)), axis=1).astype(np.float32)
     dens = rs.lognormal(0, 1.2, (n, S)).astype(np.float32)
+    dens[1, S // 2] = 1e10
     dense = F.weights_from_density(dev(t_bins), dev(dens))
     info, _ = F.packed_info_from_counts(torch.full((n,), S, dtype=torch.int32, device="cuda"))
     packed = F.packed_weights(dev(dens.reshape(-1)), dev(np.ascontiguousarray(t_bins[:, :-1]).reshape(-1)),
