@@ -2,6 +2,10 @@
 // entry points of sampler.hip and density_mlp.hip). Each `*_launch` takes n = 1 or 2 calls: one call is the per-level launch;
 // two calls share ONE launch per kernel where they can, and otherwise run one after the other. The scatter stage is
 // scatter.h's scatter_launch, of the same shape. Not part of the C ABI.
+// The weights stage has ONE kernel for both cases (two calls as arguments, one slice of the grid per call; one call = one
+// slice, the second call zeroed and unread). The density and scatter stages keep a single-call kernel beside their two-call
+// kernel around the same body: launched with one slice, the two-call kernels cost the eager per-level entry points about
+// 1 us (1 - 3 %) at the benchmark's shapes (profiles/one_kernel_per_stage_ab.txt).
 #pragma once
 
 #include "common.h"

@@ -11,6 +11,8 @@
 // level, every workgroup runs the unchanged per-level body): twelve launches become six, and two latency chains run side
 // by side. Same bits as the per-level entry points, call by call. Whether two calls of a stage can share its launches is the
 // stage's own launcher's business (proposal_chain.h, scatter.h); where they cannot, it runs them one after the other.
+// (The weights stage runs one call through the same kernel, with one slice; the density and scatter stages have a
+// single-call kernel around the same body for that, proposal_chain.h says why.)
 #include "launch.h"
 #include "proposal_chain.h"
 #include "scatter.h"

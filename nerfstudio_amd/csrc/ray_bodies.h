@@ -2,7 +2,7 @@
 // packed.hip's variable-length rays share with them. Which launch runs which body today:
 //   composite_fwd_body   composite_fwd_kernel (render.hip: nsamd_composite_fwd, nsamd_render_train)
 //   composite_bwd_body   composite_bwd_kernel (render.hip: nsamd_composite_bwd, nsamd_render_train_bwd)
-//   weights_bwd_body     weights_bwd_kernel and, two levels per launch, weights_bwd_pair_kernel (sampler.hip)
+//   weights_bwd_body     weights_bwd_kernel: one level per launch, or two side by side (sampler.hip)
 //   piecewise_bins_body  piecewise_bins_kernel and select_bins_kernel (sampler.hip)
 //   pdf_resample_body    pdf_resample_kernel<false / true> (sampler.hip: nsamd_pdf_resample, nsamd_proposal_resample)
 //   interlevel_body, distortion_body   their own kernels and, one per blockIdx.y, proposal_losses_kernel (losses.hip)

@@ -102,20 +102,10 @@ __global__ __launch_bounds__(kRayThreads) void weights_fwd_kernel(const float* _
   }
 }
 
-__global__ __launch_bounds__(kRayThreads) void weights_bwd_kernel(const float* __restrict__ t_bins,
-                                                                  const float* __restrict__ density,
-                                                                  const float* __restrict__ dweights,
-                                                                  int64_t num_rays, int S,
-                                                                  float* __restrict__ ddensity,
-                                                                  uint32_t* __restrict__ gate_out,
-                                                                  uint8_t* __restrict__ ray_mask) {
+// one level's weights backward, or two levels' in one launch (proposal_chain.h): blockIdx.y selects the call, each with its
+// own sample count; a launch of one slice runs `a` alone
+__global__ __launch_bounds__(kRayThreads) void weights_bwd_kernel(WeightsBwdCall a, WeightsBwdCall b) {
   extern __shared__ float lds[];  // (ray_bodies.h: weights_bwd_body — per wave ex[S], trans[S], gw[S])
-  weights_bwd_body(lds + (size_t)wave_index() * 3 * S, t_bins, density, dweights, num_rays, S, ddensity, gate_out, ray_mask);
-}
-
-// two levels' weights backward in one launch (proposal_chain.h): blockIdx.y selects the call, each with its own sample count
-__global__ __launch_bounds__(kRayThreads) void weights_bwd_pair_kernel(WeightsBwdCall a, WeightsBwdCall b) {
-  extern __shared__ float lds[];
   if (blockIdx.y == 0)
     weights_bwd_body(lds + (size_t)wave_index() * 3 * a.S, a.t_bins, a.density, a.dweights, a.num_rays, a.S, a.ddensity, a.gate,
                      a.ray_mask);
@@ -210,21 +200,18 @@ namespace nsamd {
 // (the gates are cleared by the caller)
 int weights_bwd_launch(const WeightsBwdCall* c, int n, hipStream_t stream) {
   NSAMD_REQUIRE(c != nullptr && (n == 1 || n == 2));
-  const auto lds = [](int S) { return sizeof(float) * 3 * kRaysPerBlock * (size_t)S; };
-  if (n == 2) {
-    const WeightsBwdCall &a = c[0], &b = c[1];
-    if (a.num_rays <= 0 || b.num_rays <= 0 || weights_bwd_check(a) || weights_bwd_check(b)) {
-      const int rc = weights_bwd_launch(c, 1, stream);
-      return rc ? rc : weights_bwd_launch(c + 1, 1, stream);
-    }
-    const int64_t rays = a.num_rays > b.num_rays ? a.num_rays : b.num_rays;
-    weights_bwd_pair_kernel<<<dim3(ray_blocks(rays), 2u), kRayThreads, lds(a.S > b.S ? a.S : b.S), stream>>>(a, b);
-  } else {
-    const int rc = weights_bwd_check(c[0]);
-    if (rc || c[0].num_rays == 0) return rc;
-    weights_bwd_kernel<<<ray_blocks(c[0].num_rays), kRayThreads, lds(c[0].S), stream>>>(
-        c[0].t_bins, c[0].density, c[0].dweights, c[0].num_rays, c[0].S, c[0].ddensity, c[0].gate, c[0].ray_mask);
+  const WeightsBwdCall a = c[0], b = n == 2 ? c[1] : WeightsBwdCall{};
+  if (n == 2 && (a.num_rays <= 0 || b.num_rays <= 0 || weights_bwd_check(a) || weights_bwd_check(b))) {
+    const int rc = weights_bwd_launch(c, 1, stream);
+    return rc ? rc : weights_bwd_launch(c + 1, 1, stream);
   }
+  if (n == 1) {
+    const int rc = weights_bwd_check(a);
+    if (rc || a.num_rays == 0) return rc;
+  }
+  const int64_t rays = a.num_rays > b.num_rays ? a.num_rays : b.num_rays;
+  const size_t lds = sizeof(float) * 3 * kRaysPerBlock * (size_t)(a.S > b.S ? a.S : b.S);
+  weights_bwd_kernel<<<dim3(ray_blocks(rays), (unsigned)n), kRayThreads, lds, stream>>>(a, b);
   NSAMD_CHECK_LAUNCH();
   return NSAMD_OK;
 }

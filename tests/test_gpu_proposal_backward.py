@@ -676,6 +676,175 @@ def test_proposal_levels_pair_vs_float64(F):
     report("proposal levels pair", worst)
 
 
+# ---------------------------------------------------------------- merged chain == per-level chain, bit for bit ---------
+
+CHAIN_OUTPUTS = ("ddens", "denc", "mask", "dW0", "db0", "dW1", "db1", "dtable")
+DENC_PREFILL = 123.0  # (the chain does not write the rows of rays without gradient)
+
+
+def _chain_levels(F, shapes, one_network=False, zero_dw=()):
+    """nsamd_proposal_level_bwd structs for `shapes` = [(rays, samples)], set up as test_proposal_levels_pair_vs_float64 does:
+    grid (5, 16, 128, 12), IN, H = 10, 16, about a third of the rays carrying dweights (other rays per level; none on the
+    levels in `zero_dw`). one_network: every level has the same MLP gradients, table, dtable, MLP and scatter workspaces.
+    Returns (struct array, gates, per-level dicts of tensors and launch arguments)."""
+    N = _n()
+    IN, H = 10, 16
+    spec = F.HashGridSpec(5, 16, 128, 12)
+    levels, out = (N.ProposalLevelBwd * len(shapes))(), []
+    gates = torch.zeros(4 * len(shapes), dtype=torch.int32, device="cuda")
+    for i, (n, S) in enumerate(shapes):
+        M = n * S
+        t, dens, dw = _weights_case(n, S, 900 + i)
+        dens = dens.nan_to_num(0.0, 0.0, 0.0).clamp(min=0.0)
+        live = torch.rand(n, generator=torch.Generator().manual_seed(40 + i)) < 0.33
+        dw = dw.nan_to_num(0.0, 0.0, 0.0) * live[:, None]
+        if i in zero_dw:
+            dw = torch.zeros_like(dw)
+        enc, pre, _, sel = _mlp_inputs(IN, M, 950 + i, False)
+        g = torch.Generator().manual_seed(980 + i)
+        o = torch.randn(n, 3, generator=g) * 0.5
+        d = torch.nn.functional.normalize(torch.randn(n, 3, generator=g), dim=-1)
+        L = dict(n=n, S=S, M=M, spec=spec)
+        for k, x in zip(("t", "dens", "dw", "enc", "sel", "pre", "o", "d"), (t, dens, dw, enc.t(), sel, pre, o, d)):
+            L[k] = x.cuda().contiguous()
+        L["ddens"], L["denc"] = torch.empty(n, S, device="cuda"), torch.empty(IN, M, device="cuda")
+        L["mask"] = torch.empty(n, dtype=torch.uint8, device="cuda")
+        if one_network and i > 0:
+            for k in ("mlp", "dW0", "db0", "dW1", "db1", "mws", "table", "dtable"):
+                L[k] = out[0][k]
+        else:
+            L["mlp"] = _Mlp(F, *_mlp_params(IN, H, 990 + i, False), 0.01)
+            L["dW0"], L["db0"] = torch.empty(H, IN, device="cuda"), torch.empty(H, device="cuda")
+            L["dW1"], L["db1"] = torch.empty(H, device="cuda"), torch.empty(1, device="cuda")
+            L["mws"] = torch.empty(K_MAX_BLOCKS * ((H * IN + 2 * H + 1 + 3) & ~3), device="cuda")
+            L["table"] = torch.randn(5 * spec.table_size * 2, device="cuda") * 0.1
+            L["dtable"] = torch.empty_like(L["table"])
+        L["ws"], L["ws_n"] = F._scatter_workspace(spec, torch.device("cuda"), M)
+        assert L["ws"] is not None
+        L["gate"] = gates.data_ptr() + 16 * i
+        e = levels[i]
+        e.num_rays, e.samples_per_ray = n, S
+        e.t_bins, e.density, e.dweights = N.ptr(L["t"]), N.ptr(L["dens"]), N.ptr(L["dw"])
+        e.ddensity, e.gate, e.ray_mask = N.ptr(L["ddens"]), L["gate"], N.ptr(L["mask"])
+        e.enc, e.selector, e.pre = N.ptr(L["enc"]), N.ptr(L["sel"]), N.ptr(L["pre"])
+        e.mlp = L["mlp"].native
+        e.denc = N.ptr(L["denc"])
+        e.dW0, e.db0, e.dW1, e.db1 = (N.ptr(L[k]) for k in ("dW0", "db0", "dW1", "db1"))
+        e.mlp_workspace, e.mlp_workspace_floats = N.ptr(L["mws"]), L["mws"].numel()
+        e.origins, e.directions = N.ptr(L["o"]), N.ptr(L["d"])
+        e.transform, e.aabb = N.XFORM_CONTRACT, N.Aabb()
+        e.table, e.grid = N.ptr(L["table"]), spec.native()
+        e.dtable = N.ptr(L["dtable"])
+        e.scatter_workspace, e.scatter_workspace_floats = N.ptr(L["ws"]), L["ws_n"]
+        out.append(L)
+    return levels, gates, out
+
+
+def _chain_reset(gates, lv):
+    """Equal starting state for a run: zeroed gradients, `denc` and `ddensity` pre-filled, gates and masks set to junk."""
+    gates.fill_(5)
+    for L in lv:
+        for k in ("dW0", "db0", "dW1", "db1", "dtable"):
+            L[k].zero_()
+        L["ddens"].fill_(7.0)
+        L["denc"].fill_(DENC_PREFILL)
+        L["mask"].fill_(9)
+
+
+def _chain_results(gates, lv):
+    torch.cuda.synchronize()
+    return [gates[::4].clone().cpu()] + [{k: L[k].clone().cpu() for k in CHAIN_OUTPUTS} for L in lv]
+
+
+def _chain_per_level(lv, stage_major=False):
+    """The per-level gated entry points: level by level (each level's three stages, then the next level), or stage_major —
+    each stage over all levels before the next stage, the order nsamd_proposal_levels_bwd runs them in."""
+    N = _n()
+    lib, st = N.load(), N.stream()
+
+    def weights(L):
+        N.check(lib.nsamd_weights_bwd_gate(N.ptr(L["t"]), N.ptr(L["dens"]), N.ptr(L["dw"]), L["n"], L["S"], N.ptr(L["ddens"]),
+                                           L["gate"], N.ptr(L["mask"]), 0, st), "weights_bwd_gate")
+
+    def density(L):
+        grads = [N.ptr(L[k]) for k in ("dW0", "db0", "dW1", "db1")]
+        N.check(lib.nsamd_density_mlp_bwd_gated(N.ptr(L["enc"]), N.ptr(L["sel"]), N.ptr(L["pre"]), N.ptr(L["ddens"]), L["M"],
+                                                L["mlp"].native, N.ptr(L["denc"]), *grads, N.ptr(L["mws"]), L["mws"].numel(),
+                                                L["gate"], N.ptr(L["mask"]), L["S"], st), "density_mlp_bwd_gated")
+
+    def scatter(L):
+        pts = N.make_points(origins=L["o"], directions=L["d"], t_bins=L["t"], samples_per_ray=L["S"])
+        N.check(lib.nsamd_hashgrid_encode_bwd_gated(pts, L["M"], N.XFORM_CONTRACT, N.Aabb(), N.ptr(L["table"]),
+                                                    L["spec"].native(), N.ptr(L["denc"]), 1, L["M"], N.ptr(L["dtable"]),
+                                                    N.ptr(L["ws"]), L["ws_n"], L["gate"], N.ptr(L["mask"]), st),
+                "hashgrid_encode_bwd_gated")
+
+    stages = (weights, density, scatter)
+    for stage, L in ([(f, L) for f in stages for L in lv] if stage_major else [(f, L) for L in lv for f in stages]):
+        stage(L)
+
+
+def _assert_same_bits(tag, got, want):
+    assert torch.equal(got[0], want[0]), f"{tag}: gates {got[0].tolist()} != {want[0].tolist()}"
+    for i, (g, w) in enumerate(zip(got[1:], want[1:])):
+        for k in CHAIN_OUTPUTS:
+            a, b = (x.view(torch.int32) if x.dtype == torch.float32 else x for x in (g[k], w[k]))
+            diff = int((a != b).sum())
+            assert diff == 0, f"{tag}: level {i} {k}: {diff} of {a.numel()} entries differ from the per-level entry points"
+
+
+@pytest.mark.parametrize("zero_level0", [False, True])
+def test_proposal_levels_smaller_call_first_and_odd_level(F, zero_level0):
+    """nsamd_proposal_levels_bwd on THREE levels (37 x 96), (300 x 256), (50 x 48): levels 0 and 1 are all run-routed and share
+    every launch with the SMALLER call first — slice 0 has fewer workgroups than slice 1 in the weights, density-MLP and route
+    launches, so it takes the corner exits —; level 2 runs alone, through the fine route and the single-call launches. Against
+    the per-level gated entry points level by level, on equal inputs, zeroed gradients and the same workspaces: density
+    gradient, denc, gates, ray masks, the four MLP gradients and the table gradient bit for bit. The call runs twice (the
+    scatter workspace's self-cleaning header serves the second). zero_level0: level 0 carries no gradient — its gate stays
+    clear, its denc keeps the pre-filled value, its gradients stay zero; level 1 is as without."""
+    N = _n()
+    lib, st = N.load(), N.stream()
+    shapes = [(37, 96), (300, 256), (50, 48)]
+    levels, gates, lv = _chain_levels(F, shapes, zero_dw=(0,) if zero_level0 else ())
+    assert lv[0]["ws"].data_ptr() != lv[1]["ws"].data_ptr()  # (levels 0 and 1 may share launches)
+    _chain_reset(gates, lv)
+    _chain_per_level(lv)
+    want = _chain_results(gates, lv)
+    assert want[0].tolist() == [0 if zero_level0 else 1, 1, 1]
+    for i, L in enumerate(lv):
+        live = int(want[1 + i]["mask"].sum())
+        assert (live == 0) if (zero_level0 and i == 0) else (0 < live < L["n"])
+        assert bool((want[1 + i]["dtable"] != 0).any()) == (live > 0)
+    if zero_level0:
+        z = want[1]
+        assert bool((z["denc"] == DENC_PREFILL).all()) and float(z["ddens"].abs().max()) == 0.0
+        assert all(float(z[k].abs().max()) == 0.0 for k in ("dW0", "db0", "dW1", "db1", "dtable"))
+    for run in range(2):
+        _chain_reset(gates, lv)
+        N.check(lib.nsamd_proposal_levels_bwd(levels, 3, 0, st), "proposal_levels_bwd")
+        _assert_same_bits(f"run {run}", _chain_results(gates, lv), want)
+    for L in lv:
+        ev = F.scatter_events(L["ws"])
+        assert ev[1] == 0 and ev[2] == 0, ev
+
+
+def test_proposal_levels_one_network_runs_in_turn(F):
+    """Two levels (37 x 96), (64 x 256) with ONE network: the same MLP gradients, table, table gradient and scatter workspace.
+    The density and scatter stages must then run level after level (the weights stage may still pair), accumulating into the
+    same gradients: bit for bit what the per-level entry points give, called in the same order."""
+    N = _n()
+    lib, st = N.load(), N.stream()
+    levels, gates, lv = _chain_levels(F, [(37, 96), (64, 256)], one_network=True)
+    assert lv[0]["ws"].data_ptr() == lv[1]["ws"].data_ptr() and lv[0]["dtable"].data_ptr() == lv[1]["dtable"].data_ptr()
+    _chain_reset(gates, lv)
+    _chain_per_level(lv, stage_major=True)
+    want = _chain_results(gates, lv)
+    assert want[0].tolist() == [1, 1] and bool((want[1]["dtable"] != 0).any())
+    _chain_reset(gates, lv)
+    N.check(lib.nsamd_proposal_levels_bwd(levels, 2, 0, st), "proposal_levels_bwd")
+    _assert_same_bits("one network", _chain_results(gates, lv), want)
+
+
 # ---------------------------------------------------------------- identical inputs from the product ---------------------
 
 def test_bench_shape_proposal_chain_vs_float64(F):
