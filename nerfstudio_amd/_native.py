@@ -81,6 +81,11 @@ class MeshVolume(C.Structure):
     _fields_ = [("origin", f32 * 3), ("voxel_size", f32 * 3), ("dims", i32 * 3)]
 
 
+class TexelAtlasPod(C.Structure):
+    """nsamd_texel_atlas (include/nsamd_texture.h): the layout of the per-UV-triangle atlas."""
+    _fields_ = [("faces", i32), ("px", i32), ("squares_w", i32), ("squares_h", i32)]
+
+
 class ProposalLevelBwd(C.Structure):
     """nsamd_proposal_level_bwd: one proposal level's gated backward chain (nsamd_proposal_levels_bwd)."""
     _fields_ = [("num_rays", i64), ("samples_per_ray", i32),
@@ -198,8 +203,15 @@ _MESH_SIGNATURES = {
     "nsamd_mesh_count": [MeshVolume, vp, vp, vp, vp],
     "nsamd_mesh_emit": [MeshVolume, vp, vp, vp, i64, i64, vp, vp, vp, vp, vp],
 }
+# And for include/nsamd_texture.h, the texturing of an exported mesh (tests/test_texture_cpu.py checks the three).
+_TEXTURE_SIGNATURES = {
+    "nsamd_texel_rays": [TexelAtlasPod, vp, vp, vp, i64, vp, i64, i64, i64, vp, vp, vp, vp, vp],
+    "nsamd_mesh_raylen": [vp, i64, vp, i64, vp, vp, vp],
+    "nsamd_texture_store": [vp, i64, i64, vp, vp],
+}
 SELECT_BLOCK = 256  # NSAMD_SELECT_BLOCK
 MESH_BLOCK = 256  # NSAMD_MESH_BLOCK
+RAYLEN_SCRATCH_BYTES = 8 * 1024  # NSAMD_RAYLEN_SCRATCH_BYTES
 KNN_MAX_K = 32  # NSAMD_KNN_MAX_K
 KNN_MAX_CELLS = 1 << 24  # NSAMD_KNN_MAX_CELLS
 _RESTYPES = {"nsamd_version": C.c_char_p, "nsamd_status_string": C.c_char_p,
@@ -267,7 +279,7 @@ def load():
     lib = _Lib()
     lib.cdll = cdll
     for name, argtypes in {**_SIGNATURES, **_EXPORT_SIGNATURES, **_RENDER_SIGNATURES, **_POINTCLOUD_SIGNATURES,
-                           **_MESH_SIGNATURES}.items():
+                           **_MESH_SIGNATURES, **_TEXTURE_SIGNATURES}.items():
         fn = getattr(cdll, name)  # AttributeError here = header / library mismatch
         fn.argtypes = argtypes
         fn.restype = _RESTYPES.get(name, C.c_int)
@@ -424,6 +436,12 @@ def make_mesh_volume(origin, voxel_size, dims) -> MeshVolume:
     for i in range(3):
         v.origin[i], v.voxel_size[i], v.dims[i] = float(origin[i]), float(voxel_size[i]), int(dims[i])
     return v
+
+
+def make_texel_atlas(faces: int, px: int, squares_w: int, squares_h: int) -> TexelAtlasPod:
+    a = TexelAtlasPod()
+    a.faces, a.px, a.squares_w, a.squares_h = int(faces), int(px), int(squares_w), int(squares_h)
+    return a
 
 
 def device_info() -> dict:

@@ -18,6 +18,9 @@ of its last ray (which leaves that min / max untouched) and only its valid rows 
 Same kernels, same order as the module path, launched through the same helpers (functional.weights_launch, composite_launch,
 field_normals_launch, nerf_encode_launch, linear_launch, normals_composite_launch): the outputs are equal bit for bit
 (tests/test_gpu_kernels.py).
+A bundle that carries its own nears AND fars keeps them, as the collider leaves such a bundle alone (scene_colliders.py:40-44),
+and `render_texels` generates the texel rays of a textured mesh export — bounds included — inside the loop
+(tests/test_gpu_texture.py); either way the schedule's bounds are back at 0 / far_plane when the call returns.
 """
 from __future__ import annotations
 
@@ -218,8 +221,58 @@ class EvalRenderer:
                 s.origins[k:].copy_(o[b - 1:b].expand(n - k, 3))
                 s.directions[k:].copy_(d[b - 1:b].expand(n - k, 3))
 
-        out = self._render_rays(o.shape[0], o.device, load_chunk)
+        nears, fars = getattr(camera_ray_bundle, "nears", None), getattr(camera_ray_bundle, "fars", None)
+        if nears is None or fars is None:  # the collider's planes (scene_colliders.py:40-44 sets them when either is missing)
+            out = self._render_rays(o.shape[0], o.device, load_chunk)
+            return {k_: v.view(*image_shape, -1) for k_, v in out.items()}
+        # A bundle that carries its own bounds (the texel rays of exporter/texture_utils.py:386-400) keeps them, as the collider
+        # leaves it alone: they ride into the schedule with the rays, and the runner — cached on the model — gets its planes back.
+        nr, fr = nears.reshape(-1).to(torch.float32), fars.reshape(-1).to(torch.float32)
+
+        def load_bounded_chunk(a, k):
+            b = a + k
+            load_chunk(a, k)
+            s.nears[:k].copy_(nr[a:b])
+            s.fars[:k].copy_(fr[a:b])
+            if k < n:
+                s.nears[k:].copy_(nr[b - 1:b].expand(n - k))
+                s.fars[k:].copy_(fr[b - 1:b].expand(n - k))
+
+        try:
+            out = self._render_rays(o.shape[0], o.device, load_bounded_chunk)
+        finally:
+            self._restore_bounds()
         return {k_: v.view(*image_shape, -1) for k_, v in out.items()}
+
+    def _restore_bounds(self) -> None:
+        """The schedule's per-ray bounds back to what every camera frame renders with: near 0, far `far_plane`."""
+        self.step.nears.zero_()
+        self.step.fars.fill_(float(self.model.config.far_plane))
+
+    @profiler.time_function
+    @torch.no_grad()
+    def render_texels(self, atlas, mesh, raylen_dev: Tensor, out_u8: Tensor, out_f32: Optional[Tensor] = None) -> None:
+        """The texture of `mesh` (vertices, normals `[V,3]` fp32, faces `[F,3]` int32 on the device) over `atlas`
+        (texture.TexelAtlas): one ray per texel, from half of raylen_dev[0] outside the surface along the negated normal, near 0,
+        far raylen (exporter/texture_utils.py:374-400). Per chunk ONE nsamd_texel_rays launch writes the rays and their bounds
+        straight into the schedule's static input buffers, the chunk runs as for any frame, and nsamd_texture_store writes its
+        rgb rows as 8-bit levels into out_u8 `[H W, 3]` (or `[H, W, 3]`) uint8: no `[H, W]` bundle, no `[total, C]` output —
+        only rgb leaves a chunk. out_f32 `[H W, 3]` fp32 receives the unquantised rgb as well (tests)."""
+        s, n = self.step, self.chunk
+        total = int(atlas.width) * int(atlas.height)
+        pod = atlas.native()
+        self._refresh_constants()
+        try:
+            for a in range(0, total, n):
+                k = min(a + n, total) - a
+                F.texel_rays_launch(pod, mesh.vertices, mesh.normals, mesh.faces, raylen_dev, a, k, n, s.origins, s.directions,
+                                    s.nears, s.fars)
+                self._run_chunk()
+                F.texture_store_launch(s.rgb, k, a, out_u8)
+                if out_f32 is not None:
+                    out_f32[a:a + k].copy_(s.rgb[:k])
+        finally:
+            self._restore_bounds()
 
     @profiler.time_function
     @torch.no_grad()

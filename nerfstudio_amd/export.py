@@ -18,6 +18,8 @@ in that function, to update 470 MB of state. Here
     export_tsdf_mesh    the reference's function, signature and defaults, over the two; by default marching cubes and the PLY
                         writer are the reference's (`TSDFVolume.to_reference`: skimage, pymeshlab)
     export_tsdf_mesh_on_device   the same with `device_mesh` and `write_mesh_ply`: no reference installation needed
+    export_textured_tsdf_mesh_on_device   that, then the mesh textured through the model (texture.py): `mesh.obj`,
+                        `material_0.mtl`, `material_0.png` — `ns-export tsdf` with its default texture_method="nerf"
 
 Kept as the reference has them (csrc/tsdf.h): the weight clamp of :267, voxels behind a camera, voxel coordinates at the
 voxel's corner, the truncation from the x voxel size alone. The device mesh (include/nsamd_mesh.h) restates marching cubes
@@ -362,3 +364,25 @@ def export_tsdf_mesh_on_device(pipeline, output_dir: Path, **kwargs) -> None:
     kwargs.setdefault("mesh_fn", device_mesh)
     kwargs.setdefault("write_fn", write_mesh_ply)
     export_tsdf_mesh(pipeline, output_dir, **kwargs)
+
+
+def export_textured_tsdf_mesh_on_device(pipeline, output_dir: Path, px_per_uv_triangle: int = 4, **kwargs) -> Mesh:
+    """`ns-export tsdf` with its default texture_method="nerf" (scripts/exporter.py:211, 253-266) and no reference installed:
+    export_tsdf_mesh_on_device — `tsdf_mesh.ply` — then the mesh, which never left the device, textured by
+    texture.export_textured_mesh(unwrap_method="custom"): `mesh.obj`, `material_0.mtl`, `material_0.png`. Returns the mesh.
+    There is NO decimation (the reference's target_num_faces goes through pymeshlab): the atlas holds (P + 3) P / 2 texels per
+    face, so the volume's `resolution` is the lever on the number of faces and with it on the atlas size, which is logged.
+    kwargs: export_tsdf_mesh's."""
+    from . import texture
+
+    meshes: List[Mesh] = []
+    mesh_fn = kwargs.pop("mesh_fn", device_mesh)
+
+    def keeping_mesh(volume: TSDFVolume) -> Mesh:
+        meshes.append(mesh_fn(volume))
+        return meshes[-1]
+
+    export_tsdf_mesh_on_device(pipeline, output_dir, mesh_fn=keeping_mesh, **kwargs)
+    mesh = meshes[-1]  # (after a refinement pass: the second volume's)
+    texture.export_textured_mesh(mesh, pipeline, Path(output_dir), px_per_uv_triangle, unwrap_method="custom")
+    return mesh

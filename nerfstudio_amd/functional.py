@@ -1858,3 +1858,41 @@ def mesh_emit_launch(vol: "N.MeshVolume", values: Tensor, colors: Tensor, scratc
     assert scratch.dtype == torch.uint8 and scratch.numel() >= N.mesh_scratch_bytes(values.numel())
     N.check(N.load().nsamd_mesh_emit(vol, N.ptr(values), N.ptr(colors), N.ptr(scratch), V, T, N.ptr(vertices), N.ptr(normals),
                                      N.ptr(vertex_colors), N.ptr(faces), N.stream()), "mesh_emit")
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# mesh export: one ray per texel of the texture atlas, the ray length, the 8-bit image (include/nsamd_texture.h)
+# ---------------------------------------------------------------------------------------------------------------
+def texel_rays_launch(atlas: "N.TexelAtlasPod", vertices: Tensor, normals: Tensor, faces: Tensor, raylen_dev: Tensor, first: int,
+                      count: int, rows: int, origins: Tensor, directions: Tensor, nears: Tensor, fars: Tensor) -> None:
+    """nsamd_texel_rays on the current stream: the rays of texels first .. first + count - 1 of the atlas' row-major grid into the
+    first `rows` >= count rows of the eval loop's input buffers (origins, directions `[n,3]`, nears, fars `[n]`), rows count ..
+    rows - 1 repeating the last texel. vertices, normals `[V,3]` fp32, faces `[F,3]` int32, raylen_dev `[1]` fp32."""
+    N.require_cuda(vertices, normals, faces, raylen_dev, origins, directions, nears, fars)
+    V = int(vertices.shape[0])
+    assert vertices.dtype == normals.dtype == raylen_dev.dtype == torch.float32 and faces.dtype == torch.int32
+    assert tuple(normals.shape) == (V, 3) == tuple(vertices.shape) and tuple(faces.shape) == (atlas.faces, 3) and raylen_dev.numel() >= 1
+    assert origins.dtype == directions.dtype == nears.dtype == fars.dtype == torch.float32
+    assert origins.shape[0] >= rows and directions.shape[0] >= rows and nears.numel() >= rows and fars.numel() >= rows
+    N.check(N.load().nsamd_texel_rays(atlas, N.ptr(vertices), N.ptr(normals), N.ptr(faces), V, N.ptr(raylen_dev), int(first),
+                                      int(count), int(rows), N.ptr(origins), N.ptr(directions), N.ptr(nears), N.ptr(fars),
+                                      N.stream()), "texel_rays")
+
+
+def mesh_raylen_launch(vertices: Tensor, faces: Tensor, scratch: Tensor, raylen_dev: Tensor) -> None:
+    """nsamd_mesh_raylen: raylen_dev `[1]` fp32 receives twice the mean length of the faces' first edge (vertices `[V,3]` fp32, faces
+    `[T,3]` int32, T >= 1); scratch: uint8, `N.RAYLEN_SCRATCH_BYTES` bytes."""
+    N.require_cuda(vertices, faces, scratch, raylen_dev)
+    assert vertices.dtype == raylen_dev.dtype == torch.float32 and faces.dtype == torch.int32 and faces.dim() == 2 and faces.shape[1] == 3
+    assert scratch.dtype == torch.uint8 and scratch.numel() >= N.RAYLEN_SCRATCH_BYTES and scratch.data_ptr() % 8 == 0
+    N.check(N.load().nsamd_mesh_raylen(N.ptr(vertices), int(vertices.shape[0]), N.ptr(faces), int(faces.shape[0]), N.ptr(scratch),
+                                       N.ptr(raylen_dev), N.stream()), "mesh_raylen")
+
+
+def texture_store_launch(rgb: Tensor, count: int, first: int, atlas_u8: Tensor) -> None:
+    """nsamd_texture_store: the first `count` rows of rgb `[n,3]` fp32 as 8-bit levels into rows first .. first + count - 1 of the
+    `[H W, 3]` (or `[H, W, 3]`) uint8 atlas."""
+    N.require_cuda(rgb, atlas_u8)
+    assert rgb.dtype == torch.float32 and atlas_u8.dtype == torch.uint8 and rgb.shape[0] >= count >= 0
+    assert first >= 0 and 3 * (first + count) <= atlas_u8.numel()
+    N.check(N.load().nsamd_texture_store(N.ptr(rgb), int(count), int(first), N.ptr(atlas_u8), N.stream()), "texture_store")
