@@ -24,14 +24,15 @@ and `render_texels` generates the texel rays of a textured mesh export — bound
 """
 from __future__ import annotations
 
-import os
 from typing import Dict, Optional
 
 import torch
 from torch import Tensor
 
 from . import _native as N
+from . import eval_frame
 from . import functional as F
+from .eval_frame import in_loop_camera_args, lens_camera_args, pinhole_camera_args  # noqa: F401  (imported from here too)
 from .utils import profiler
 
 
@@ -109,14 +110,7 @@ class EvalRenderer:
         and the appearance row of eval mode."""
         m, s = self.model, self.step
         s.anneal_dev.fill_(float(m.proposal_sampler._anneal))
-        fld = m.field
-        if self.app_const is not None:
-            emb = fld.embedding_appearance.embedding.weight
-            with torch.no_grad():
-                if fld.use_average_appearance_embedding:
-                    torch.mean(emb, dim=0, out=self.app_const)
-                else:
-                    self.app_const.zero_()
+        eval_frame.eval_appearance_row(m.field, self.app_const)
 
     def _launch_chunk(self) -> None:
         """The kernel schedule of one chunk (all arguments are static buffers: capturable): the forward schedule in
@@ -180,12 +174,10 @@ class EvalRenderer:
         """The frame's chunk loop over `total` rays: `load_chunk(a, k)` puts rays a .. a + k - 1 into the schedule's input
         buffers, the chunk runs, and its k valid rows are copied into the preallocated `[total, C]` outputs."""
         s, n = self.step, self.chunk
-        out = {"rgb": torch.empty((total, 3), device=dev), "accumulation": torch.empty((total, 1), device=dev),
-               "depth": torch.empty((total, 1), device=dev), "expected_depth": torch.empty((total, 1), device=dev)}
-        for i in range(s.n_prop):
-            out[f"prop_depth_{i}"] = torch.empty((total, 1), device=dev)
-        if self.normals:
-            out["normals"], out["pred_normals"] = torch.empty((total, 3), device=dev), torch.empty((total, 3), device=dev)
+        one, three = (1, None), (3, None)  # (channels, the default dtype)
+        out = eval_frame.frame_outputs(total, dev, {
+            "rgb": three, "accumulation": one, "depth": one, "expected_depth": one, **{f"prop_depth_{i}": one for i in range(s.n_prop)},
+            **({"normals": three, "pred_normals": three} if self.normals else {})})
         self._refresh_constants()
         for a in range(0, total, n):
             k = min(a + n, total) - a
@@ -212,37 +204,18 @@ class EvalRenderer:
         image_shape = camera_ray_bundle.origins.shape[:-1]
         o = camera_ray_bundle.origins.reshape(-1, 3)
         d = camera_ray_bundle.directions.reshape(-1, 3)
-
-        def load_chunk(a, k):
-            b = a + k
-            s.origins[:k].copy_(o[a:b])
-            s.directions[:k].copy_(d[a:b])
-            if k < n:  # pad with copies of the last ray: the chunk's depth clip range is unchanged
-                s.origins[k:].copy_(o[b - 1:b].expand(n - k, 3))
-                s.directions[k:].copy_(d[b - 1:b].expand(n - k, 3))
-
         nears, fars = getattr(camera_ray_bundle, "nears", None), getattr(camera_ray_bundle, "fars", None)
         if nears is None or fars is None:  # the collider's planes (scene_colliders.py:40-44 sets them when either is missing)
-            out = self._render_rays(o.shape[0], o.device, load_chunk)
-            return {k_: v.view(*image_shape, -1) for k_, v in out.items()}
+            load_chunk = eval_frame.padded_loader((s.origins, s.directions), (o, d), n)
+            return eval_frame.as_image(self._render_rays(o.shape[0], o.device, load_chunk), image_shape)
         # A bundle that carries its own bounds (the texel rays of exporter/texture_utils.py:386-400) keeps them, as the collider
         # leaves it alone: they ride into the schedule with the rays, and the runner — cached on the model — gets its planes back.
         nr, fr = nears.reshape(-1).to(torch.float32), fars.reshape(-1).to(torch.float32)
-
-        def load_bounded_chunk(a, k):
-            b = a + k
-            load_chunk(a, k)
-            s.nears[:k].copy_(nr[a:b])
-            s.fars[:k].copy_(fr[a:b])
-            if k < n:
-                s.nears[k:].copy_(nr[b - 1:b].expand(n - k))
-                s.fars[k:].copy_(fr[b - 1:b].expand(n - k))
-
+        load_chunk = eval_frame.padded_loader((s.origins, s.directions, s.nears, s.fars), (o, d, nr, fr), n)
         try:
-            out = self._render_rays(o.shape[0], o.device, load_bounded_chunk)
+            return eval_frame.as_image(self._render_rays(o.shape[0], o.device, load_chunk), image_shape)
         finally:
             self._restore_bounds()
-        return {k_: v.view(*image_shape, -1) for k_, v in out.items()}
 
     def _restore_bounds(self) -> None:
         """The schedule's per-ray bounds back to what every camera frame renders with: near 0, far `far_plane`."""
@@ -287,87 +260,12 @@ class EvalRenderer:
         distortion parameters or None, and its chunks come from nsamd_raygen_lens_grid (the bits of functional.raygen_lens)."""
         s, n = self.step, self.chunk
         dev = s.origins.device
-        c2w = c2w.reshape(3, 4).to(device=dev, dtype=torch.float32).contiguous()
-        if lens is not None:
-            camera_type, dist = int(lens[0]), lens[1]
-            if camera_type not in F.LENS_TYPES:
-                raise ValueError(f"render_camera: camera type {camera_type} is not one of {sorted(F.LENS_TYPES)}")
-            if dist is not None:
-                dist = torch.as_tensor(dist).reshape(6).to(device=dev, dtype=torch.float32).contiguous()
-            lens = (camera_type, dist)
+        c2w, lens = eval_frame.prepare_view(c2w, lens, dev)
 
         def load_chunk(a, k):
             F.raygen_grid_launch(c2w, fx, fy, cx, cy, lens, width, a, k, n, s.origins, s.directions)
 
-        out = self._render_rays(int(height) * int(width), dev, load_chunk)
-        return {k_: v.view(int(height), int(width), -1) for k_, v in out.items()}
-
-
-def pinhole_camera_args(camera):
-    """(c2w [3,4], fx, fy, cx, cy, H, W) of a single undistorted perspective `Cameras` object (cameras/cameras.py), or None when the
-    camera needs the general ray generator (fisheye / equirectangular / orthographic types, distortion parameters, several
-    cameras, per-camera metadata the field consumes)."""
-    try:
-        c2w = camera.camera_to_worlds
-        if c2w.dim() == 3:
-            if c2w.shape[0] != 1:
-                return None
-            c2w = c2w[0]
-        ctype = getattr(camera, "camera_type", None)
-        if ctype is not None and int(torch.as_tensor(ctype).reshape(-1)[0]) != 1:  # CameraType.PERSPECTIVE
-            return None
-        dist = getattr(camera, "distortion_params", None)
-        if dist is not None and bool(torch.any(torch.as_tensor(dist) != 0)):
-            return None
-        one = lambda t: float(torch.as_tensor(t).reshape(-1)[0])  # noqa: E731
-        h, w = int(one(camera.height)), int(one(camera.width))
-        if h <= 0 or w <= 0 or torch.as_tensor(camera.fx).numel() != 1:
-            return None
-        return c2w[:3, :4], one(camera.fx), one(camera.fy), one(camera.cx), one(camera.cy), h, w
-    except (AttributeError, TypeError, ValueError, IndexError):
-        return None
-
-
-def lens_camera_args(camera):
-    """`pinhole_camera_args`' tuple plus (camera_type, distortion) for a single `Cameras` object of type PERSPECTIVE, FISHEYE or
-    EQUIRECTANGULAR (1 - 3): distortion is the camera's six parameters `[6]`, or None when it has none. None for several
-    cameras, missing intrinsics and the lens types the generator does not cover."""
-    try:
-        c2w = camera.camera_to_worlds
-        if c2w.dim() == 3:
-            if c2w.shape[0] != 1:
-                return None
-            c2w = c2w[0]
-        ctype = getattr(camera, "camera_type", None)
-        ctype = 1 if ctype is None else int(torch.as_tensor(ctype).reshape(-1)[0])
-        if ctype not in F.LENS_TYPES:
-            return None
-        dist = getattr(camera, "distortion_params", None)
-        if dist is not None:
-            dist = torch.as_tensor(dist).float().reshape(-1)
-            if dist.numel() != 6:
-                return None
-        one = lambda t: float(torch.as_tensor(t).reshape(-1)[0])  # noqa: E731
-        h, w = int(one(camera.height)), int(one(camera.width))
-        if h <= 0 or w <= 0 or torch.as_tensor(camera.fx).numel() != 1:
-            return None
-        return c2w[:3, :4], one(camera.fx), one(camera.fy), one(camera.cx), one(camera.cy), h, w, ctype, dist
-    except (AttributeError, TypeError, ValueError, IndexError):
-        return None
-
-
-def in_loop_camera_args(camera):
-    """(render_camera's positional arguments, its `lens`) for the cameras Model.get_outputs_for_camera renders without a ray
-    bundle: one undistorted pinhole camera (lens None), or one perspective camera with non-zero distortion. None otherwise —
-    fisheye and equirectangular cameras still take `camera.generate_rays` there; `render_camera(lens=...)` and RayGenerator
-    cover them."""
-    args = pinhole_camera_args(camera)
-    if args is not None:
-        return args, None
-    args = lens_camera_args(camera)
-    if args is not None and args[7] == 1:  # CameraType.PERSPECTIVE
-        return args[:7], (args[7], args[8])
-    return None
+        return eval_frame.as_image(self._render_rays(int(height) * int(width), dev, load_chunk), (int(height), int(width)))
 
 
 def supported(model, normals: bool = False) -> Optional[str]:
@@ -390,9 +288,9 @@ def supported(model, normals: bool = False) -> Optional[str]:
 def runner_for(model, device) -> Optional[EvalRenderer]:
     """The model's cached EvalRenderer (rebuilt when the chunk size changed) for an eval render of rays on `device`, or None:
     the module path (training mode, not a GPU, NSAMD_EVAL_RUNNER=0, or a configuration `supported` refuses)."""
-    if model.training or torch.device(device).type != "cuda" or os.environ.get("NSAMD_EVAL_RUNNER", "1") != "1":
+    if not eval_frame.runner_enabled(model, device):
         return None
-    normals = bool(getattr(model.config, "predict_normals", False))  # such a model renders through the normals runner
+    normals = eval_frame.predicts_normals(model)
     if supported(model, normals=normals) is not None:
         return None
     runner = getattr(model, "_eval_runner", None)

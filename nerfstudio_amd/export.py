@@ -31,23 +31,17 @@ lazily. There is no torch fallback: a CPU tensor with the native launch raises R
 """
 from __future__ import annotations
 
-import contextlib
 from dataclasses import dataclass
 from pathlib import Path
 from typing import Callable, Dict, List, Optional, Sequence, Tuple, Union
 
-import numpy as np
 import torch
 from torch import Tensor
 
 from . import _native as N
-from . import eval_render
+from . import _ply
+from . import eval_frame
 from . import functional as F
-from . import ngp_eval_render
-
-PERSPECTIVE = 1  # CameraType.PERSPECTIVE (cameras/cameras.py:41-52)
-_CAMERA_TYPE_NAMES = {1: "PERSPECTIVE", 2: "FISHEYE", 3: "EQUIRECTANGULAR", 4: "OMNIDIRECTIONALSTEREO_L",
-                      5: "OMNIDIRECTIONALSTEREO_R", 6: "VR180_L", 7: "VR180_R", 8: "ORTHOPHOTO", 9: "FISHEYE624"}
 
 
 def _import_reference():
@@ -185,16 +179,6 @@ class TSDFVolume:
                                self.origin.to(dev), self.truncation_margin)
 
 
-@contextlib.contextmanager
-def _eval_mode(model):
-    was_training = model.training
-    model.eval()
-    try:
-        yield
-    finally:
-        model.train(was_training)
-
-
 def scaled_pinhole_cameras(cameras, downscale_factor) -> List[Tuple[Tensor, float, float, float, float, int, int]]:
     """(c2w [3,4], fx, fy, cx, cy, H, W) per camera at 1 / downscale_factor of its resolution — the numbers
     Cameras.rescale_output_resolution (cameras/cameras.py:987-1020) would leave in the object: fp32 products, H and W truncated
@@ -205,8 +189,8 @@ def scaled_pinhole_cameras(cameras, downscale_factor) -> List[Tuple[Tensor, floa
     ctype = getattr(cameras, "camera_type", None)
     if ctype is not None:
         for i, t in enumerate(torch.as_tensor(ctype).reshape(-1).tolist()):
-            if int(t) != PERSPECTIVE:
-                raise ValueError(f"fuse_views: camera {i} is of type {_CAMERA_TYPE_NAMES.get(int(t), int(t))}; the TSDF "
+            if int(t) != eval_frame.PERSPECTIVE:
+                raise ValueError(f"fuse_views: camera {i} is of type {F._CAMERA_TYPE_NAMES.get(int(t), int(t))}; the TSDF "
                                  "projects voxels through a pinhole, only CameraType.PERSPECTIVE cameras can be fused")
     scale = torch.tensor([1.0 / downscale_factor], dtype=torch.float32)
     col = lambda t: torch.as_tensor(t).detach().reshape(-1).cpu()  # noqa: E731
@@ -229,18 +213,14 @@ def fuse_views(model, cameras, volume: TSDFVolume, downscale_factor=2, views_per
         raise ValueError(f"views_per_launch must be at least 1, got {views_per_launch}")
     dev = volume.device
     launches = 0
-    with _eval_mode(model):
+    with eval_frame.eval_mode(model):
         if render_fn is None:
-            ngp = ngp_eval_render.supported(model) is None  # an instant-ngp model: its own runner (depth and rgb are all it takes)
-            if not ngp:
-                normals = bool(getattr(model.config, "predict_normals", False))
-                reason = eval_render.supported(model, normals=normals)
-                if reason is not None:
-                    raise ValueError(f"fuse_views: the eval renderer does not cover this model ({reason}); pass render_fn")
-            N.require_cuda(volume.values)
-            runner = (ngp_eval_render if ngp else eval_render).runner_for(model, dev)
-            if runner is None:
-                raise RuntimeError("fuse_views: the device-side eval renderer is switched off (NSAMD_EVAL_RUNNER=0)")
+            runner, reason = eval_frame.export_runner_for(model, dev)
+            if reason == eval_frame.RUNNER_OFF:
+                N.require_cuda(volume.values)  # (a volume on the host has no runner either: that is the error to give)
+                raise RuntimeError(f"fuse_views: {reason}")
+            if reason is not None:
+                raise ValueError(f"fuse_views: {reason}; pass render_fn")
             render_fn = lambda *view: runner.render_camera(*view, lens=None)  # noqa: E731
         depth_buf = color_buf = None
         poses: List[Tensor] = []
@@ -290,30 +270,11 @@ def device_mesh(volume: TSDFVolume) -> Mesh:
 
 
 def write_mesh_ply(mesh: Mesh, filename) -> None:
-    """`write_fn` of export_tsdf_mesh. Binary little-endian PLY in the style of pointcloud.PointCloud.write_ply: per vertex
-    x y z nx ny nz float32 and red green blue alpha uint8 — colors * 255 truncated, the product formed in float64 (a colour
-    outside [0, 1] saturates, NaN writes 0), alpha 255 — then per face `list uchar int vertex_indices`. An empty mesh writes a
-    valid file with no elements' rows."""
-    V, T = int(mesh.vertices.shape[0]), int(mesh.faces.shape[0])
-    vertex = np.empty(V, dtype=np.dtype([(k, "<f4") for k in ("x", "y", "z", "nx", "ny", "nz")]
-                                        + [(k, "u1") for k in ("red", "green", "blue", "alpha")]))
-    xyz = mesh.vertices.detach().float().cpu().numpy()
-    nrm = mesh.normals.detach().float().cpu().numpy()
-    rgb = torch.nan_to_num(mesh.colors.detach().double() * 255, nan=0.0).clamp(0, 255).to(torch.uint8).cpu().numpy()
-    for c, (a, b, k) in enumerate((("x", "nx", "red"), ("y", "ny", "green"), ("z", "nz", "blue"))):
-        vertex[a], vertex[b], vertex[k] = xyz[:, c], nrm[:, c], rgb[:, c]
-    vertex["alpha"] = 255
-    face = np.empty(T, dtype=np.dtype([("n", "u1"), ("i", "<i4", (3,))]))
-    face["n"] = 3
-    face["i"] = mesh.faces.detach().to(torch.int32).cpu().numpy()
-    header = ["ply", "format binary_little_endian 1.0", f"element vertex {V}"]
-    header += [f"property float {k}" for k in ("x", "y", "z", "nx", "ny", "nz")]
-    header += [f"property uchar {k}" for k in ("red", "green", "blue", "alpha")]
-    header += [f"element face {T}", "property list uchar int vertex_indices", "end_header"]
-    with open(filename, "wb") as f:
-        f.write(("\n".join(header) + "\n").encode("ascii"))
-        f.write(vertex.tobytes())
-        f.write(face.tobytes())
+    """`write_fn` of export_tsdf_mesh. Binary little-endian PLY (_ply.write, as pointcloud.PointCloud.write_ply): per vertex
+    x y z nx ny nz float32 and red green blue alpha uint8 — _ply.colors, alpha 255 — then per face
+    `list uchar int vertex_indices`. An empty mesh writes a valid file with no elements' rows."""
+    props = _ply.floats("xyz", mesh.vertices) + _ply.floats(("nx", "ny", "nz"), mesh.normals) + _ply.colors(mesh.colors)
+    _ply.write(filename, props + [("alpha", "u1", 255)], mesh.faces.detach().to(torch.int32).cpu().numpy())
 
 
 def export_tsdf_mesh(pipeline, output_dir: Path, downscale_factor: int = 2, depth_output_name: str = "depth",

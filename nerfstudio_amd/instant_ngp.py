@@ -14,6 +14,7 @@ import torch
 from torch import Tensor, nn
 from torch.nn import Parameter
 
+from . import eval_frame, ngp_eval_render
 from . import functional as F
 from .cameras.rays import RayBundle
 from .field_components.field_heads import FieldHeadNames
@@ -175,33 +176,14 @@ class NGPModel(nn.Module):
         no crop box: the rays of each chunk are generated inside the device-side chunk loop
         (ngp_eval_render.NgpEvalRenderer.render_camera); anything else generates the bundle — a crop box's nears / fars on it
         reach the marcher through `render` — and takes the method below."""
-        from . import eval_render, ngp_eval_render
-
-        args = eval_render.in_loop_camera_args(camera) if obb_box is None else None
-        runner = ngp_eval_render.runner_for(self, next(self.parameters()).device) if args is not None else None
-        if runner is not None:
-            return runner.render_camera(*args[0], lens=args[1])
-        return self.get_outputs_for_camera_ray_bundle(camera.generate_rays(camera_indices=0, keep_shape=True, obb_box=obb_box))
+        return eval_frame.outputs_for_camera(self, camera, obb_box, ngp_eval_render.runner_for)
 
     @torch.no_grad()
     def get_outputs_for_camera_ray_bundle(self, camera_ray_bundle: RayBundle) -> Dict[str, Tensor]:
         """Chunked full-image render (models/base_model.py:178-205). In eval mode on the GPU the chunk loop is device-side
         (ngp_eval_render.NgpEvalRenderer: static buffers, the per-ray tail in one launch, the next chunk counted while this one's
         field runs); NSAMD_EVAL_RUNNER=0, training mode or an unsupported configuration take the Python loop over `forward`."""
-        from . import ngp_eval_render
-
-        runner = ngp_eval_render.runner_for(self, camera_ray_bundle.origins.device)
-        if runner is not None:
-            return runner.render(camera_ray_bundle)
-        image_shape = camera_ray_bundle.origins.shape[:-1]
-        num_rays = len(camera_ray_bundle)
-        outs: Dict[str, List[Tensor]] = {}
-        for i in range(0, num_rays, self.config.eval_num_rays_per_chunk):
-            rb = camera_ray_bundle.get_row_major_sliced_ray_bundle(i, i + self.config.eval_num_rays_per_chunk)
-            for k, v in self.forward(rb).items():
-                if torch.is_tensor(v):
-                    outs.setdefault(k, []).append(v)
-        return {k: torch.cat(v).view(*image_shape, -1) for k, v in outs.items()}
+        return eval_frame.outputs_for_bundle(self, camera_ray_bundle, ngp_eval_render.runner_for)
 
 
 class DynamicBatch:

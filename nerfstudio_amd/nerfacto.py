@@ -16,6 +16,7 @@ import torch
 from torch import Tensor, nn
 from torch.nn import Parameter
 
+from . import eval_frame, eval_render
 from .cameras.rays import RayBundle, RaySamples
 from .field_components.field_heads import FieldHeadNames
 from .field_components.spatial_distortions import SceneContraction
@@ -300,13 +301,7 @@ class NerfactoModel(nn.Module):
         (eval_render.EvalRenderer.render_camera) — no [H, W] bundle in HBM; anything else generates the bundle
         (`camera.generate_rays(camera_indices=0, keep_shape=True)`) and takes the loop below. Fisheye and equirectangular
         cameras are among "anything else" here; `render_camera(lens=...)` and RayGenerator generate their rays."""
-        from . import eval_render
-
-        args = eval_render.in_loop_camera_args(camera) if obb_box is None else None
-        runner = eval_render.runner_for(self, next(self.parameters()).device) if args is not None else None
-        if runner is not None:
-            return runner.render_camera(*args[0], lens=args[1])
-        return self.get_outputs_for_camera_ray_bundle(camera.generate_rays(camera_indices=0, keep_shape=True, obb_box=obb_box))
+        return eval_frame.outputs_for_camera(self, camera, obb_box, eval_render.runner_for)
 
     @torch.no_grad()
     def get_outputs_for_camera_ray_bundle(self, camera_ray_bundle: RayBundle) -> Dict[str, Tensor]:
@@ -314,18 +309,4 @@ class NerfactoModel(nn.Module):
         (eval_render.EvalRenderer: one captured kernel schedule per chunk over static buffers, outputs copied into
         preallocated image buffers — no per-chunk module graph, no torch.cat); NSAMD_EVAL_RUNNER=0, training mode or an
         unsupported configuration take the reference's Python loop over `forward`."""
-        from . import eval_render
-
-        runner = eval_render.runner_for(self, camera_ray_bundle.origins.device)
-        if runner is not None:
-            return runner.render(camera_ray_bundle)
-        image_shape = camera_ray_bundle.origins.shape[:-1]
-        num_rays = len(camera_ray_bundle)
-        chunk = self.config.eval_num_rays_per_chunk
-        outs: Dict[str, List[Tensor]] = {}
-        for i in range(0, num_rays, chunk):
-            rb = camera_ray_bundle.get_row_major_sliced_ray_bundle(i, i + chunk)
-            for k, v in self.forward(rb).items():
-                if torch.is_tensor(v):
-                    outs.setdefault(k, []).append(v)
-        return {k: torch.cat(v).view(*image_shape, -1) for k, v in outs.items()}
+        return eval_frame.outputs_for_bundle(self, camera_ray_bundle, eval_render.runner_for)

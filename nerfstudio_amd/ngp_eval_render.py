@@ -24,13 +24,13 @@ expression), as for ngp_step.NgpTrainStep.
 """
 from __future__ import annotations
 
-import os
 from typing import Dict, Optional
 
 import torch
 from torch import Tensor
 
 from . import _native as N
+from . import eval_frame
 from . import functional as F
 from .ngp_step import STASH_CAP
 from .utils import profiler
@@ -150,12 +150,7 @@ class NgpEvalRenderer:
         """Once per frame: the eval appearance row (fields/nerfacto_field.py:253-261: the embedding's mean, or zeros) into its
         static buffer, the background of the eval compositing, the grid's derived state."""
         m = self.model
-        fld = m.field
-        if self.app_const is not None:
-            if fld.use_average_appearance_embedding:
-                torch.mean(fld.embedding_appearance.embedding.weight.detach(), dim=0, out=self.app_const)
-            else:
-                self.app_const.zero_()
+        eval_frame.eval_appearance_row(m.field, self.app_const)
         self.bg_mode, self.bg_vals = F._packed_bg(m.renderer_rgb.background_color)
         m.occupancy_grid.ensure_derived()
 
@@ -164,9 +159,8 @@ class NgpEvalRenderer:
         slot's origins / directions (and t_min / t_max with `has_bounds`)."""
         dev, n, L = self.dev, self.chunk, self.launches
         cfg = self.model.config
-        out = {"rgb": torch.empty((total, 3), device=dev), "accumulation": torch.empty((total, 1), device=dev),
-               "depth": torch.empty((total, 1), device=dev),
-               "num_samples_per_ray": torch.empty((total, 1), device=dev, dtype=torch.int64)}
+        out = eval_frame.frame_outputs(total, dev, {"rgb": (3, None), "accumulation": (1, None), "depth": (1, None),
+                                                    "num_samples_per_ray": (1, torch.int64)})
         self._refresh_constants()
         grid = self.model.occupancy_grid
         march = (float(cfg.near_plane), min(float(cfg.far_plane), 3.0e38), grid, float(cfg.render_step_size), float(cfg.cone_angle))
@@ -243,8 +237,7 @@ class NgpEvalRenderer:
                 s.t_min[:k].copy_(nears[a:a + k])
                 s.t_max[:k].copy_(fars[a:a + k])
 
-        out = self._render_rays(o.shape[0], load_chunk, has_bounds)
-        return {k_: v.view(*image_shape, -1) for k_, v in out.items()}
+        return eval_frame.as_image(self._render_rays(o.shape[0], load_chunk, has_bounds), image_shape)
 
     @profiler.time_function
     @torch.no_grad()
@@ -253,21 +246,13 @@ class NgpEvalRenderer:
         """`render` for ONE camera without a ray bundle, as EvalRenderer.render_camera: each chunk's rays are generated straight
         into its slot's buffers (nsamd_raygen_pinhole_grid; lens = (camera_type, distortion): nsamd_raygen_lens_grid). Same bits
         as `render` on the bundle `camera.generate_rays(camera_indices=0, keep_shape=True)` gives."""
-        c2w = c2w.reshape(3, 4).to(device=self.dev, dtype=torch.float32).contiguous()
-        if lens is not None:
-            camera_type, dist = int(lens[0]), lens[1]
-            if camera_type not in F.LENS_TYPES:
-                raise ValueError(f"render_camera: camera type {camera_type} is not one of {sorted(F.LENS_TYPES)}")
-            if dist is not None:
-                dist = torch.as_tensor(dist).reshape(6).to(device=self.dev, dtype=torch.float32).contiguous()
-            lens = (camera_type, dist)
+        c2w, lens = eval_frame.prepare_view(c2w, lens, self.dev)
         view = (float(fx), float(fy), float(cx), float(cy), lens, int(width))
 
         def load_chunk(s: _Slot, a: int, k: int) -> None:
             self.launches.raygen(c2w, *view, a, k, s.origins, s.directions)
 
-        out = self._render_rays(int(height) * int(width), load_chunk, False)
-        return {k_: v.view(int(height), int(width), -1) for k_, v in out.items()}
+        return eval_frame.as_image(self._render_rays(int(height) * int(width), load_chunk, False), (int(height), int(width)))
 
 
 def supported(model) -> Optional[str]:
@@ -286,9 +271,7 @@ def supported(model) -> Optional[str]:
 def runner_for(model, device) -> Optional[NgpEvalRenderer]:
     """The model's cached NgpEvalRenderer (rebuilt when the chunk size changed) for an eval render of rays on `device`, or None:
     the module path (training mode, not a GPU, NSAMD_EVAL_RUNNER=0, or a configuration `supported` refuses)."""
-    if model.training or torch.device(device).type != "cuda" or os.environ.get("NSAMD_EVAL_RUNNER", "1") != "1":
-        return None
-    if supported(model) is not None:
+    if not eval_frame.runner_enabled(model, device) or supported(model) is not None:
         return None
     runner = getattr(model, "_ngp_eval_runner", None)
     if runner is None or runner.chunk != model.config.eval_num_rays_per_chunk:

@@ -103,6 +103,47 @@ def _publish(*classes):
     return classes
 
 
+def _flush_pending(model: Any) -> None:
+    """A pending (deferred / pipelined) main-field update of the pipeline's captured schedule is applied before the
+    parameters are read (pipeline.EngineSeam.attach_optimizers installs the `_hip_flush` hook)."""
+    getattr(model, "_hip_flush", lambda: None)()
+
+
+def _nerfacto_eval_runner(model: Any, device):
+    """HipNerfactoModel's device-side eval loop for rays on `device`, or None: the reference's own loop. The loop samples between
+    the config's near / far planes: only a model whose collider does too takes it, for rays on the model's device."""
+    from . import eval_render
+
+    col, cfg = getattr(model, "collider", None), model.config
+    planes = (getattr(col, "near_plane", None), getattr(col, "far_plane", None)) == (cfg.near_plane, cfg.far_plane)
+    return eval_render.runner_for(model, device) if planes and torch.device(device) == torch.device(model.device) else None
+
+
+def nerfacto_outputs_for_camera(model: Any, camera, obb_box, reference_path):
+    """HipNerfactoModel.get_outputs_for_camera. One perspective camera (undistorted, or with OpenCV distortion parameters) without
+    a crop box, in eval mode on the model's GPU: the rays of every chunk are generated inside the device-side chunk loop
+    (EvalRenderer.render_camera over nsamd_raygen_pinhole_grid / nsamd_raygen_lens_grid: the arithmetic of
+    `camera.generate_rays(camera_indices=0, keep_shape=True)`, cameras/cameras.py:321-503) — no [H, W] ray bundle is built.
+    Anything else — fisheye and equirectangular cameras included, which `render_camera(lens=...)` covers — is
+    `reference_path`, the reference's own method."""
+    from . import eval_frame
+
+    _flush_pending(model)
+    return eval_frame.outputs_for_camera(model, camera, obb_box, _nerfacto_eval_runner, reference_path)
+
+
+def nerfacto_outputs_for_camera_ray_bundle(model: Any, camera_ray_bundle, reference_path):
+    """HipNerfactoModel.get_outputs_for_camera_ray_bundle. In eval mode, with the rays already on the model's GPU, the chunk loop
+    is the device-side one (eval_render.EvalRenderer: one captured kernel schedule per chunk over static buffers, no
+    per-chunk module graph, no torch.cat — 30.5 against 23.3 M rays/s, profiles/r03_final2_bench_render_*.json; same
+    outputs bit for bit, tests/test_gpu_kernels.py); anything else takes `reference_path`, the reference's own loop.
+    NSAMD_EVAL_RUNNER=0 switches it off."""
+    from . import eval_frame
+
+    _flush_pending(model)
+    return eval_frame.outputs_for_bundle(model, camera_ray_bundle, _nerfacto_eval_runner, reference_path)
+
+
 def _model_classes():
     """(HipNerfactoModelConfig, HipNerfactoModel), built ONCE against the installed nerfstudio."""
     if "HipNerfactoModel" in globals():
@@ -138,55 +179,18 @@ def _model_classes():
             fused = self._fused_step()
             return fused.get_outputs(ray_bundle) if fused is not None else super().get_outputs(ray_bundle)
 
-        def _flush_pending(self):
-            """A pending (deferred / pipelined) main-field update of the pipeline's captured schedule is applied before the
-            parameters are read (pipeline.EngineSeam.attach_optimizers installs the hook)."""
-            flush = getattr(self, "_hip_flush", None)
-            if flush is not None:
-                flush()
-
         def train(self, mode: bool = True):  # the viewer and the evaluation entry points switch the MODEL to eval
             if not mode:
-                self._flush_pending()
+                _flush_pending(self)
             return super().train(mode)
 
         @torch.no_grad()
         def get_outputs_for_camera(self, camera, obb_box=None):  # models/base_model.py:162-176 (viewer, ns-render)
-            """One perspective camera (undistorted, or with OpenCV distortion parameters) without a crop box, in eval mode on the
-            model's GPU: the rays of every chunk are generated inside the device-side chunk loop (EvalRenderer.render_camera over
-            nsamd_raygen_pinhole_grid / nsamd_raygen_lens_grid: the arithmetic of `camera.generate_rays(camera_indices=0,
-            keep_shape=True)`, cameras/cameras.py:321-503) — no [H, W] ray bundle is built. Anything else — fisheye and
-            equirectangular cameras included, which `render_camera(lens=...)` covers — is the reference's own path."""
-            from . import eval_render
-
-            self._flush_pending()
-            args = eval_render.in_loop_camera_args(camera) if obb_box is None else None
-            runner = eval_render.runner_for(self, self.device) if (args is not None and self._collider_is_configs()) else None
-            if runner is not None:
-                return runner.render_camera(*args[0], lens=args[1])
-            return super().get_outputs_for_camera(camera, obb_box=obb_box)
+            return nerfacto_outputs_for_camera(self, camera, obb_box, super().get_outputs_for_camera)
 
         @torch.no_grad()
-        def get_outputs_for_camera_ray_bundle(self, camera_ray_bundle):
-            """models/base_model.py:178-205. In eval mode, with the rays already on the model's GPU, the chunk loop is the
-            device-side one (eval_render.EvalRenderer: one captured kernel schedule per chunk over static buffers, no
-            per-chunk module graph, no torch.cat — 30.5 against 23.3 M rays/s, profiles/r03_final2_bench_render_*.json; same
-            outputs bit for bit, tests/test_gpu_kernels.py); anything else takes the reference's own loop.
-            NSAMD_EVAL_RUNNER=0 switches it off."""
-            from . import eval_render
-
-            self._flush_pending()
-            dev = camera_ray_bundle.origins.device
-            runner = eval_render.runner_for(self, dev) if (dev == self.device and self._collider_is_configs()) else None
-            if runner is not None:
-                return runner.render(camera_ray_bundle)
-            return super().get_outputs_for_camera_ray_bundle(camera_ray_bundle)
-
-        def _collider_is_configs(self):
-            """The device-side chunk loop samples between the config's near / far planes: only a model whose collider does too."""
-            col = getattr(self, "collider", None)
-            return (getattr(col, "near_plane", None) == self.config.near_plane
-                    and getattr(col, "far_plane", None) == self.config.far_plane)
+        def get_outputs_for_camera_ray_bundle(self, camera_ray_bundle):  # models/base_model.py:178-205
+            return nerfacto_outputs_for_camera_ray_bundle(self, camera_ray_bundle, super().get_outputs_for_camera_ray_bundle)
 
         def get_loss_dict(self, outputs, batch, metrics_dict=None):
             """models/nerfacto.py:363-392 with the proposal losses on the fused HIP kernels (the reference's torch
@@ -271,42 +275,34 @@ def install_hip_ngp_modules(model: Any) -> None:
 
 
 def _ngp_eval_runner(model: Any, device):
-    """HipNGPModel's device-side eval loop for rays on `device`, or None: the reference's own loop. The model's `_hip_flush` hook
-    (pipeline.EngineSeam.attach_optimizers installs one) first applies a pending parameter update. Model.forward puts a
+    """HipNGPModel's device-side eval loop for rays on `device`, or None: the reference's own loop. Model.forward puts a
     collider's nears / fars on every chunk (models/base_model.py:140-141); instant-ngp has none (models/instant_ngp.py:48-51),
-    and only such a model takes the device-side loop."""
+    and only such a model takes the device-side loop, for rays on the model's device."""
     from . import ngp_eval_render
 
-    flush = getattr(model, "_hip_flush", None)
-    if flush is not None:
-        flush()
-    if getattr(model, "collider", None) is not None or torch.device(device) != torch.device(model.device):
-        return None
-    return ngp_eval_render.runner_for(model, device)
+    own = getattr(model, "collider", None) is None and torch.device(device) == torch.device(model.device)
+    return ngp_eval_render.runner_for(model, device) if own else None
 
 
 def ngp_outputs_for_camera(model: Any, camera, obb_box, reference_path):
     """HipNGPModel.get_outputs_for_camera. One perspective camera without a crop box, in eval mode on the model's GPU: the rays
     of every chunk are generated inside the device-side chunk loop (ngp_eval_render.NgpEvalRenderer.render_camera). Anything
     else is `reference_path`, the reference's own method: its bundle — with a crop box's nears / fars — comes back through
-    `ngp_outputs_for_camera_ray_bundle`."""
-    from . import eval_render
+    `ngp_outputs_for_camera_ray_bundle`. A pending parameter update is applied first, as for HipNerfactoModel."""
+    from . import eval_frame
 
-    args = eval_render.in_loop_camera_args(camera) if obb_box is None else None
-    runner = _ngp_eval_runner(model, model.device)
-    if runner is not None and args is not None:
-        return runner.render_camera(*args[0], lens=args[1])
-    return reference_path(camera, obb_box=obb_box)
+    _flush_pending(model)
+    return eval_frame.outputs_for_camera(model, camera, obb_box, _ngp_eval_runner, reference_path)
 
 
 def ngp_outputs_for_camera_ray_bundle(model: Any, camera_ray_bundle, reference_path):
     """HipNGPModel.get_outputs_for_camera_ray_bundle. In eval mode, with the rays already on the model's GPU, the chunk loop is
     the device-side one (ngp_eval_render.NgpEvalRenderer); anything else takes `reference_path`, the reference's own loop.
     NSAMD_EVAL_RUNNER=0 switches it off."""
-    runner = _ngp_eval_runner(model, camera_ray_bundle.origins.device)
-    if runner is not None:
-        return runner.render(camera_ray_bundle)
-    return reference_path(camera_ray_bundle)
+    from . import eval_frame
+
+    _flush_pending(model)
+    return eval_frame.outputs_for_bundle(model, camera_ray_bundle, _ngp_eval_runner, reference_path)
 
 
 def _ngp_model_classes():

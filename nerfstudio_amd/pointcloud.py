@@ -27,11 +27,11 @@ import math
 from pathlib import Path
 from typing import Callable, Dict, Optional, Sequence, Tuple
 
-import numpy as np
 import torch
 from torch import Tensor
 
 from . import _native as N
+from . import _ply
 from . import functional as F
 
 NB_NEIGHBORS = 20  # exporter_utils.py:193
@@ -69,30 +69,10 @@ class PointCloud:
                           None if self.normals is None else self.normals[ind])
 
     def write_ply(self, path) -> None:
-        """Binary little-endian PLY: x y z float32, red green blue uint8 = colors * 255 truncated, the product formed in float64
-        as the reference forms it from its float64 colours (scripts/exporter.py:183; a colour outside [0, 1] saturates, NaN
-        writes 0), nx ny nz float32 when there are normals."""
-        fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")]
-        if self.normals is not None:
-            fields += [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
-        n = len(self)
-        rows = np.empty(n, dtype=np.dtype(fields))
-        xyz = self.points.detach().float().cpu().numpy()
-        rgb = torch.nan_to_num(self.colors.detach().double() * 255, nan=0.0).clamp(0, 255).to(torch.uint8).cpu().numpy()
-        for c, name in enumerate(("x", "y", "z")):
-            rows[name] = xyz[:, c]
-        for c, name in enumerate(("red", "green", "blue")):
-            rows[name] = rgb[:, c]
-        if self.normals is not None:
-            nrm = self.normals.detach().float().cpu().numpy()
-            for c, name in enumerate(("nx", "ny", "nz")):
-                rows[name] = nrm[:, c]
-        names = {"<f4": "float", "u1": "uchar"}
-        header = ["ply", "format binary_little_endian 1.0", f"element vertex {n}"]
-        header += [f"property {names[t]} {name}" for name, t in fields] + ["end_header"]
-        with open(path, "wb") as f:
-            f.write(("\n".join(header) + "\n").encode("ascii"))
-            f.write(rows.tobytes())
+        """Binary little-endian PLY (_ply.write): x y z float32, red green blue uint8 (_ply.colors: colors * 255 truncated), then
+        nx ny nz float32 when there are normals."""
+        normals = [] if self.normals is None else _ply.floats(("nx", "ny", "nz"), self.normals)
+        _ply.write(path, _ply.floats("xyz", self.points) + _ply.colors(self.colors) + normals)
 
     def to_open3d(self):
         """open3d.geometry.PointCloud with float64 arrays, as the reference builds it (:186-188, :214)."""

@@ -36,7 +36,7 @@ import torch
 from torch import Tensor
 
 from . import _native as N
-from . import eval_render
+from . import eval_frame
 from . import functional as F
 
 MTL_LINES = ("# Generated with nerfstudio", "newmtl material_0", "Ka 1.000 1.000 1.000", "Kd 1.000 1.000 1.000",
@@ -96,9 +96,7 @@ def refusal(model) -> Optional[str]:
     """None, or why `render_texture` cannot render this model's texels."""
     if hasattr(model, "occupancy_grid"):
         return "an instant-ngp model: its ray marcher takes no per-ray near and far"
-    normals = bool(getattr(model.config, "predict_normals", False))
-    reason = eval_render.supported(model, normals=normals)
-    return None if reason is None else f"the eval renderer does not cover this model ({reason})"
+    return eval_frame.export_support(model)[1]
 
 
 @torch.no_grad()
@@ -122,21 +120,17 @@ def render_texture(model, mesh, px_per_uv_triangle: int, raylen_method: str = "e
     if lo < 0 or hi >= V:
         raise ValueError(f"render_texture: the faces index vertices {lo} .. {hi}, the mesh has {V}")
     dev = vertices.device
-    was_training = model.training
-    model.eval()
-    try:
-        runner = eval_render.runner_for(model, dev)
+    with eval_frame.eval_mode(model):
+        runner, reason = eval_frame.export_runner_for(model, dev)
         if runner is None:
             N.require_cuda(vertices)
-            raise RuntimeError("render_texture: the device-side eval renderer is switched off (NSAMD_EVAL_RUNNER=0)")
+            raise RuntimeError(f"render_texture: {reason}")
         raylen_dev = torch.zeros(1, dtype=torch.float32, device=dev)
         if raylen_method == "edge":
             scratch = torch.empty(N.RAYLEN_SCRATCH_BYTES, dtype=torch.uint8, device=dev)
             F.mesh_raylen_launch(vertices, faces, scratch, raylen_dev)
         image = torch.empty((atlas.height, atlas.width, 3), dtype=torch.uint8, device=dev)
         runner.render_texels(atlas, SimpleNamespace(vertices=vertices, normals=normals, faces=faces), raylen_dev, image, out_f32)
-    finally:
-        model.train(was_training)
     return image
 
 
@@ -213,12 +207,8 @@ def _render_bundle_texture(model, vertices: Tensor, faces: Tensor, origins: Tens
     one = torch.ones_like(origins[..., 0:1])
     bundle = RayBundle(origins=origins, directions=directions, pixel_area=one, camera_indices=torch.zeros_like(one),
                        nears=torch.zeros_like(one), fars=one * raylen, metadata={"directions_norm": one})
-    was_training = model.training
-    model.eval()
-    try:
+    with eval_frame.eval_mode(model):
         rgb = model.get_outputs_for_camera_ray_bundle(bundle)["rgb"][..., :3]
-    finally:
-        model.train(was_training)
     H, W = int(rgb.shape[0]), int(rgb.shape[1])
     image = torch.empty((H, W, 3), dtype=torch.uint8, device=dev)
     F.texture_store_launch(rgb.reshape(-1, 3).to(torch.float32).contiguous(), H * W, 0, image)
