@@ -86,6 +86,12 @@ class TexelAtlasPod(C.Structure):
     _fields_ = [("faces", i32), ("px", i32), ("squares_w", i32), ("squares_h", i32)]
 
 
+class ColormapParams(C.Structure):
+    """nsamd_colormap_params (include/nsamd_image.h): mode, options and fixed planes of one colormap launch."""
+    _fields_ = [("mode", i32), ("normalize", i32), ("invert", i32), ("fixed", i32), ("colormap_min", C.c_double),
+                ("colormap_max", C.c_double), ("near_plane", C.c_double), ("far_plane", C.c_double)]
+
+
 class ProposalLevelBwd(C.Structure):
     """nsamd_proposal_level_bwd: one proposal level's gated backward chain (nsamd_proposal_levels_bwd)."""
     _fields_ = [("num_rays", i64), ("samples_per_ray", i32),
@@ -209,15 +215,26 @@ _TEXTURE_SIGNATURES = {
     "nsamd_mesh_raylen": [vp, i64, vp, i64, vp, vp, vp],
     "nsamd_texture_store": [vp, i64, i64, vp, vp],
 }
+# And for include/nsamd_image.h, the eval image metrics and colormaps (tests/test_image_metrics_cpu.py checks the three).
+_IMAGE_SIGNATURES = {
+    "nsamd_image_range": [vp, i64, vp, vp, vp],
+    "nsamd_image_metrics_scratch_bytes": [i64, i64, i32],
+    "nsamd_image_metrics": [vp, vp, i64, i64, i32, vp, vp, f32, f32, vp, vp, vp, vp],
+    "nsamd_colormap": [vp, i64, vp, vp, vp, ColormapParams, vp, vp, vp],
+}
 SELECT_BLOCK = 256  # NSAMD_SELECT_BLOCK
 MESH_BLOCK = 256  # NSAMD_MESH_BLOCK
 RAYLEN_SCRATCH_BYTES = 8 * 1024  # NSAMD_RAYLEN_SCRATCH_BYTES
+RANGE_SCRATCH_BYTES = 8 * 1024  # NSAMD_RANGE_SCRATCH_BYTES
+SSIM_TILE = 32  # NSAMD_SSIM_TILE
+SSIM_WINDOW = 11  # NSAMD_SSIM_WINDOW
+COLORMAP_PLAIN, COLORMAP_DEPTH = 0, 1  # NSAMD_COLORMAP_PLAIN, NSAMD_COLORMAP_DEPTH
 KNN_MAX_K = 32  # NSAMD_KNN_MAX_K
 KNN_MAX_CELLS = 1 << 24  # NSAMD_KNN_MAX_CELLS
 _RESTYPES = {"nsamd_version": C.c_char_p, "nsamd_status_string": C.c_char_p,
              "nsamd_hashgrid_encode_bwd_workspace": C.c_int64, "nsamd_hashgrid_encode_bwd_workspace_state": C.c_int64,
              "nsamd_field_mlp_bwd_scatter_workspace": C.c_int64,
-             "nsamd_occgrid_coarse_words": C.c_int64}
+             "nsamd_occgrid_coarse_words": C.c_int64, "nsamd_image_metrics_scratch_bytes": C.c_int64}
 
 _lib = None
 ERR_UNSUPPORTED = -2  # nsamd_status NSAMD_ERR_UNSUPPORTED
@@ -279,7 +296,7 @@ def load():
     lib = _Lib()
     lib.cdll = cdll
     for name, argtypes in {**_SIGNATURES, **_EXPORT_SIGNATURES, **_RENDER_SIGNATURES, **_POINTCLOUD_SIGNATURES,
-                           **_MESH_SIGNATURES, **_TEXTURE_SIGNATURES}.items():
+                           **_MESH_SIGNATURES, **_TEXTURE_SIGNATURES, **_IMAGE_SIGNATURES}.items():
         fn = getattr(cdll, name)  # AttributeError here = header / library mismatch
         fn.argtypes = argtypes
         fn.restype = _RESTYPES.get(name, C.c_int)
@@ -442,6 +459,16 @@ def make_texel_atlas(faces: int, px: int, squares_w: int, squares_h: int) -> Tex
     a = TexelAtlasPod()
     a.faces, a.px, a.squares_w, a.squares_h = int(faces), int(px), int(squares_w), int(squares_h)
     return a
+
+
+def make_colormap_params(depth: bool = False, normalize: bool = False, colormap_min: float = 0.0, colormap_max: float = 1.0,
+                         invert: bool = False, near_plane: Optional[float] = None, far_plane: Optional[float] = None) -> ColormapParams:
+    p = ColormapParams()
+    p.mode, p.normalize, p.invert = (COLORMAP_DEPTH if depth else COLORMAP_PLAIN), int(bool(normalize)), int(bool(invert))
+    p.fixed = (1 if near_plane is not None else 0) | (2 if far_plane is not None else 0)
+    p.colormap_min, p.colormap_max = float(colormap_min), float(colormap_max)
+    p.near_plane, p.far_plane = float(near_plane or 0.0), float(far_plane or 0.0)
+    return p
 
 
 def device_info() -> dict:

@@ -5,6 +5,7 @@
 // the cache (the texels of a square share two faces). The per-texel arithmetic is texture.h.
 #include "launch.h"
 #include "texture.h"
+#include "wave.h"
 
 using namespace nsamd;
 
@@ -43,18 +44,6 @@ __global__ __launch_bounds__(kTexThreads) void texel_rays_kernel(nsamd_texel_atl
   }
 }
 
-// sum over the block in a fixed order: a butterfly per wavefront (every lane ends with the same bits), the wavefronts in index
-// order. Every thread of the block calls it; the result is valid in thread 0.
-__device__ __forceinline__ double block_sum_f64(double v) {
-  __shared__ double wave_sum[kTexWaves];
-  for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m);
-  if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double total = 0.0;
-  for (int w = 0; w < kTexWaves; ++w) total += wave_sum[w];
-  return total;
-}
-
 // workgroup b: faces b * 256 + lane, then every gridDim.x * 256 further, per lane in ascending order
 __global__ __launch_bounds__(kTexThreads) void raylen_partial_kernel(const float* __restrict__ vertices, int64_t V,
                                                                      const int32_t* __restrict__ faces, int64_t T,
@@ -62,7 +51,7 @@ __global__ __launch_bounds__(kTexThreads) void raylen_partial_kernel(const float
   double acc = 0.0;
   for (int64_t t = (int64_t)blockIdx.x * kTexThreads + threadIdx.x; t < T; t += (int64_t)gridDim.x * kTexThreads)
     acc += raylen_edge(vertices, V, faces, t);
-  const double total = block_sum_f64(acc);
+  const double total = block_sum_f64<kTexWaves>(acc);
   if (threadIdx.x == 0) partials[blockIdx.x] = total;
 }
 
@@ -71,7 +60,7 @@ __global__ __launch_bounds__(kTexThreads) void raylen_finish_kernel(const double
                                                                     float* __restrict__ raylen_dev) {
   double acc = 0.0;
   for (int b = threadIdx.x; b < blocks; b += kTexThreads) acc += partials[b];
-  const double total = block_sum_f64(acc);
+  const double total = block_sum_f64<kTexWaves>(acc);
   if (threadIdx.x == 0) raylen_dev[0] = raylen_finish(total, T);
 }
 

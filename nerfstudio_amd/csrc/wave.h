@@ -87,6 +87,22 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
+// Sum of a double over a workgroup of WAVES wavefronts in a fixed order: a butterfly per wavefront (every lane ends with the same
+// bits), the wavefronts in index order. Every thread of the workgroup calls it; the result is valid in thread 0 (in every thread,
+// in fact). The finishing scheme of the fp64 sums that are rounded once (nsamd_mesh_raylen, nsamd_image_metrics): no atomics, the
+// same bits run to run. The leading barrier lets a kernel call it more than once.
+template <int WAVES>
+__device__ __forceinline__ double block_sum_f64(double v) {
+  __shared__ double wave_sum[WAVES];
+  for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double total = 0.0;
+  for (int w = 0; w < WAVES; ++w) total += wave_sum[w];
+  return total;
+}
+
 // inclusive prefix sum of a 32-bit count over the 64 lanes: the same six DPP steps as the double scan. All lanes active.
 template <int CTRL, int ROW_MASK>
 __device__ __forceinline__ uint32_t dpp_move_u32(uint32_t v) {  // lanes without a source read 0

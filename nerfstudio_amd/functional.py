@@ -1896,3 +1896,96 @@ def texture_store_launch(rgb: Tensor, count: int, first: int, atlas_u8: Tensor) 
     assert rgb.dtype == torch.float32 and atlas_u8.dtype == torch.uint8 and rgb.shape[0] >= count >= 0
     assert first >= 0 and 3 * (first + count) <= atlas_u8.numel()
     N.check(N.load().nsamd_texture_store(N.ptr(rgb), int(count), int(first), N.ptr(atlas_u8), N.stream()), "texture_store")
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# eval frames: minimum / maximum, PSNR and SSIM, colormaps (include/nsamd_image.h)
+# ---------------------------------------------------------------------------------------------------------------
+def image_range_launch(x: Tensor, scratch: Tensor, range2: Tensor) -> None:
+    """nsamd_image_range on the current stream: range2 `[2]` fp32 receives {min, max} of the fp32 values of x (a NaN makes both
+    NaN); scratch: uint8, `N.RANGE_SCRATCH_BYTES` bytes."""
+    N.require_cuda(x, scratch, range2)
+    assert x.dtype == range2.dtype == torch.float32 and range2.numel() >= 2
+    assert scratch.dtype == torch.uint8 and scratch.numel() >= N.RANGE_SCRATCH_BYTES and scratch.data_ptr() % 8 == 0
+    N.check(N.load().nsamd_image_range(N.ptr(x), int(x.numel()), N.ptr(scratch), N.ptr(range2), N.stream()), "image_range")
+
+
+def image_metrics_scratch_bytes(H: int, W: int, C: int) -> int:
+    """nsamd_image_metrics_scratch_bytes: two fp64 partial sums per tile of NSAMD_SSIM_TILE^2 windows (host arithmetic only; 0 for
+    a size the entry point refuses)."""
+    return int(N.load().nsamd_image_metrics_scratch_bytes(int(H), int(W), int(C)))
+
+
+def image_metrics_launch(pred: Tensor, target: Tensor, range_pred: Optional[Tensor], range_target: Optional[Tensor],
+                         data_range: float, psnr_range: float, scratch: Tensor, out4: Tensor, ssim_map: Optional[Tensor]) -> None:
+    """nsamd_image_metrics: out4 `[4]` fp32 receives {mse, psnr, ssim, R} of pred against target, both `[H,W,C]` fp32; R from the
+    two `[2]` ranges on the device, or data_range when both are None. ssim_map: `[H-10,W-10,C]` fp32 or None."""
+    N.require_cuda(pred, target, range_pred, range_target, scratch, out4, ssim_map)
+    H, W, C = (int(s) for s in pred.shape)
+    assert pred.dtype == target.dtype == out4.dtype == torch.float32 and tuple(target.shape) == (H, W, C) and out4.numel() >= 4
+    assert (range_pred is None) == (range_target is None)
+    assert range_pred is None or (range_pred.dtype == range_target.dtype == torch.float32 and min(range_pred.numel(), range_target.numel()) >= 2)
+    assert scratch.dtype == torch.uint8 and scratch.numel() >= image_metrics_scratch_bytes(H, W, C) and scratch.data_ptr() % 8 == 0
+    assert ssim_map is None or (ssim_map.dtype == torch.float32 and tuple(ssim_map.shape) == (H - 10, W - 10, C))
+    N.check(N.load().nsamd_image_metrics(N.ptr(pred), N.ptr(target), H, W, C, N.ptr(range_pred), N.ptr(range_target), float(data_range),
+                                         float(psnr_range), N.ptr(scratch), N.ptr(out4), N.ptr(ssim_map), N.stream()), "image_metrics")
+
+
+def colormap_launch(values: Tensor, lut: Optional[Tensor], range2: Optional[Tensor], accumulation: Optional[Tensor],
+                    params: "N.ColormapParams", out_rgb: Optional[Tensor], out_u8: Optional[Tensor]) -> None:
+    """nsamd_colormap: the colours of the n fp32 values into out_rgb `[n,3]` fp32 and / or out_u8 `[n,3]` uint8. lut `[256,3]`
+    fp32 (None: "gray"), range2 `[2]` fp32 = {min, max} of the values where the parameters need them, accumulation `[n]` fp32."""
+    N.require_cuda(values, lut, range2, accumulation, out_rgb, out_u8)
+    n = int(values.numel())
+    assert values.dtype == torch.float32 and (lut is None or (lut.dtype == torch.float32 and tuple(lut.shape) == (256, 3)))
+    assert range2 is None or (range2.dtype == torch.float32 and range2.numel() >= 2)
+    assert accumulation is None or (accumulation.dtype == torch.float32 and accumulation.numel() == n)
+    assert out_rgb is None or (out_rgb.dtype == torch.float32 and out_rgb.numel() == 3 * n)
+    assert out_u8 is None or (out_u8.dtype == torch.uint8 and out_u8.numel() == 3 * n)
+    N.check(N.load().nsamd_colormap(N.ptr(values), n, N.ptr(lut), N.ptr(range2), N.ptr(accumulation), params, N.ptr(out_rgb),
+                                    N.ptr(out_u8), N.stream()), "colormap")
+
+
+def image_range(x: Tensor, scratch: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
+    """{min, max} of x as a `[2]` fp32 tensor on x's device; no host read."""
+    x = x.contiguous()
+    scratch = torch.empty(N.RANGE_SCRATCH_BYTES, dtype=torch.uint8, device=x.device) if scratch is None else scratch
+    out = torch.empty(2, dtype=torch.float32, device=x.device) if out is None else out
+    image_range_launch(x, scratch, out)
+    return out
+
+
+def image_metrics(pred: Tensor, target: Tensor, data_range: Optional[float] = None, psnr_range: float = 1.0, return_map: bool = False,
+                  scratch: Optional[Tensor] = None, out: Optional[Tensor] = None):
+    """{mse, psnr, ssim, R} of pred against target (`[H,W,C]` fp32) as a `[4]` fp32 tensor on their device, with the per-window
+    SSIM map `[H-10,W-10,C]` when asked for. data_range None: R is the larger of the two images' max - min, formed on the device."""
+    pred, target = pred.contiguous(), target.contiguous()
+    H, W, C = (int(s) for s in pred.shape)
+    nbytes = max(image_metrics_scratch_bytes(H, W, C), 2 * N.RANGE_SCRATCH_BYTES)
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=pred.device) if scratch is None else scratch
+    out = torch.empty(4, dtype=torch.float32, device=pred.device) if out is None else out
+    ranges = None
+    if data_range is None:
+        ranges = torch.empty(2, 2, dtype=torch.float32, device=pred.device)
+        image_range_launch(pred, scratch, ranges[0])
+        image_range_launch(target, scratch[N.RANGE_SCRATCH_BYTES:], ranges[1])
+    ssim_map = torch.empty(H - 10, W - 10, C, dtype=torch.float32, device=pred.device) if return_map else None
+    image_metrics_launch(pred, target, None if ranges is None else ranges[0], None if ranges is None else ranges[1],
+                         0.0 if data_range is None else data_range, psnr_range, scratch, out, ssim_map)
+    return (out, ssim_map) if return_map else out
+
+
+def colormap(values: Tensor, lut: Optional[Tensor], params: "N.ColormapParams", accumulation: Optional[Tensor] = None,
+             range2: Optional[Tensor] = None, rgb: bool = True, u8: bool = False):
+    """The colours of a one-channel image `[..., 1]` (or `[...]`): `[..., 3]` fp32, uint8, or both as a pair. range2 None: the
+    minimum and maximum the parameters need come from image_range of the values."""
+    values = values.contiguous()
+    shape = tuple(values.shape[:-1]) if values.dim() > 1 and values.shape[-1] == 1 else tuple(values.shape)
+    needs = bool(params.normalize) or (params.mode == N.COLORMAP_DEPTH and params.fixed != 3)
+    if needs and range2 is None:
+        range2 = image_range(values)
+    acc = None if accumulation is None else accumulation.contiguous()
+    out_rgb = torch.empty(*shape, 3, dtype=torch.float32, device=values.device) if rgb else None
+    out_u8 = torch.empty(*shape, 3, dtype=torch.uint8, device=values.device) if u8 else None
+    colormap_launch(values, lut, range2 if needs else None, acc, params, out_rgb, out_u8)
+    return (out_rgb, out_u8) if rgb and u8 else (out_rgb if rgb else out_u8)

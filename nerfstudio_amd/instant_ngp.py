@@ -98,6 +98,8 @@ def ngp_outputs(model, ray_bundle: RayBundle, jitter: Optional[Tensor] = None) -
 class NGPModel(nn.Module):
     """Instant NGP model (models/instant_ngp.py:83-262). `forward(ray_bundle)` = get_outputs (no collider)."""
 
+    lpips = None  # a callable (gt [1,C,H,W], pred) -> scalar adds "lpips" to the image metrics; its weights are not part of this package
+
     def __init__(self, config: InstantNGPModelConfig, aabb: Tensor, num_train_data: int) -> None:
         super().__init__()
         self.config = config
@@ -169,6 +171,13 @@ class NGPModel(nn.Module):
         pred_rgb, image = self.renderer_rgb.blend_background_for_loss_computation(
             pred_image=outputs["rgb"], pred_accumulation=outputs["accumulation"], gt_image=image)
         return {"rgb_loss": self.rgb_loss(image, pred_rgb)}
+
+    def get_image_metrics_and_images(self, outputs: Dict[str, Tensor], batch: Dict[str, Tensor]):
+        """models/instant_ngp.py:239-273: PSNR and SSIM of the frame on the device, read once as Python floats, and the
+        reference's images_dict (eval.image_metrics_and_images). "lpips" only with a callable `self.lpips`."""
+        from . import eval as eval_images
+
+        return eval_images.image_metrics_and_images(self, outputs, batch)
 
     @torch.no_grad()
     def get_outputs_for_camera(self, camera, obb_box=None) -> Dict[str, Tensor]:

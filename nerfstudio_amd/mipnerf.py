@@ -34,6 +34,7 @@ class MipNerfModel(NeRFModel):
     """models/mipnerf.py:38-161; `forward`, `get_outputs`, `get_loss_dict` and what is declined are NeRFModel's."""
 
     config: MipNerfModelConfig
+    clip_rgb_for_metrics = True  # models/mipnerf.py:196-197: the image metrics take the predictions clipped to [0, 1]
 
     def populate_modules(self) -> None:
         position_encoding = NeRFEncoding(in_dim=3, num_frequencies=16, min_freq_exp=0.0, max_freq_exp=16.0, include_input=True)

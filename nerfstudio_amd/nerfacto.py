@@ -93,6 +93,8 @@ class NerfactoModel(nn.Module):
     """The nerfacto graph on the MI355X kernels. `forward(ray_bundle)` = collider -> get_outputs
     (models/base_model.py:132-143)."""
 
+    lpips = None  # a callable (gt [1,C,H,W], pred) -> scalar adds "lpips" to the image metrics; its weights are not part of this package
+
     def __init__(self, config: NerfactoModelConfig, aabb: Tensor, num_train_data: int) -> None:
         super().__init__()
         self.config = config
@@ -293,6 +295,13 @@ class NerfactoModel(nn.Module):
                     outputs["rendered_pred_normal_loss"])
             self.camera_optimizer.get_loss_dict(loss_dict)  # L2 regulariser on the pose corrections
         return loss_dict
+
+    def get_image_metrics_and_images(self, outputs: Dict[str, Tensor], batch: Dict[str, Tensor]):
+        """models/nerfacto.py:393-431: PSNR and SSIM of the frame on the device, read once as Python floats, and the
+        reference's images_dict (eval.image_metrics_and_images). "lpips" only with a callable `self.lpips`."""
+        from . import eval as eval_images
+
+        return eval_images.image_metrics_and_images(self, outputs, batch)
 
     @torch.no_grad()
     def get_outputs_for_camera(self, camera, obb_box=None) -> Dict[str, Tensor]:

@@ -11,6 +11,7 @@ import torch
 from torch import Tensor, nn
 from torch.nn import Parameter
 
+from . import eval_frame
 from .cameras.rays import RayBundle
 from .field_components.encodings import NeRFEncoding
 from .field_components.field_heads import FieldHeadNames
@@ -34,10 +35,13 @@ class VanillaModelConfig:
     far_plane: float = 6.0
     rgb_loss_coarse_mult: float = 1.0
     rgb_loss_fine_mult: float = 1.0
+    eval_num_rays_per_chunk: int = 4096  # the base ModelConfig's (base_model.py:38-53)
 
 
 class NeRFModel(nn.Module):
     """models/vanilla_nerf.py:60-217. `forward(ray_bundle)` = collider + get_outputs (base_model.py:139-150)."""
+
+    lpips = None  # a callable (gt [1,C,H,W], pred) -> scalar adds "fine_lpips" to the image metrics; its weights are not part of this package
 
     def __init__(self, config: VanillaModelConfig) -> None:
         super().__init__()
@@ -96,6 +100,24 @@ class NeRFModel(nn.Module):
 
     def forward(self, ray_bundle: RayBundle, jitters=None) -> Dict[str, Tensor]:
         return self.get_outputs(self.collider(ray_bundle), jitters=jitters)
+
+    @torch.no_grad()
+    def get_outputs_for_camera(self, camera, obb_box=None) -> Dict[str, Tensor]:
+        """models/base_model.py:166-175: the camera's `[H, W]` bundle through the method below (no device-side runner covers the
+        dense-MLP methods)."""
+        return eval_frame.outputs_for_camera(self, camera, obb_box, lambda model, device: None)
+
+    @torch.no_grad()
+    def get_outputs_for_camera_ray_bundle(self, camera_ray_bundle: RayBundle) -> Dict[str, Tensor]:
+        """models/base_model.py:178-205: the Python chunk loop over `forward`, config.eval_num_rays_per_chunk rays at a time."""
+        return eval_frame.module_chunk_loop(self, camera_ray_bundle)
+
+    def get_image_metrics_and_images(self, outputs: Dict[str, Tensor], batch: Dict[str, Tensor]):
+        """models/vanilla_nerf.py:218-264 (mip-NeRF: models/mipnerf.py:163-213): PSNR and SSIM of the frame on the device, read once as Python floats, and the
+        reference's images_dict (eval.image_metrics_and_images). "fine_lpips" only with a callable `self.lpips`."""
+        from . import eval as eval_images
+
+        return eval_images.image_metrics_and_images(self, outputs, batch)
 
     def get_loss_dict(self, outputs, batch, metrics_dict=None) -> Dict[str, Tensor]:
         image = batch["image"].to(outputs["rgb_coarse"].device)
